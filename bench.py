@@ -17,6 +17,12 @@ ranks' edge blocks, so every rank holds the whole neighbour graph.
     python bench.py --gpus 1 --steps 20 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline alone: set-up, settle and warm-up passes, exactly K
+timed steps, the JSON line.  --full adds the other measurements after the timed steps
+(the contract's sequence without settle passes, the clustering call end to end, the
+other BASELINE configs, the CPU baselines; the --no-* switches drop single ones).
+--dump-outputs DIR writes the neighbour graph of the last timed step (dump_outputs()).
 """
 import argparse
 import json
@@ -309,19 +315,57 @@ def other_configs(M, dev, stream):
     return out
 
 
+DUMP_SAMPLE_SEED = 20240611
+DUMP_SAMPLE_ROWS = 1024
+DUMP_SAMPLE_EDGES = 1 << 20
+
+
+def dump_outputs(out_dir, edges, n):
+    """The neighbour graph one step hands its caller (packed edges, hammock_hip.h HMK_EDGE_*), as float64 .npy files in out_dir
+    that do not depend on the order in which the kernel stores its edges:
+        degree.npy        [n]     neighbours of every peptide
+        score_counts.npy  [k, 2]  (score, number of edges with it), by score
+        edges_sample.npy  [e, 3]  (a, b, score) with a < b of every edge that touches one of DUMP_SAMPLE_ROWS peptides drawn with
+                                  a fixed seed (fewer when the graph is dense: about DUMP_SAMPLE_EDGES edges at most), sorted
+    About 7 MB at the default workload."""
+    from hammock_amd import edge_fields
+    os.makedirs(out_dir, exist_ok=True)
+    x, m, s = edge_fields(edges.cpu().numpy())
+    a, b = np.minimum(x, m), np.maximum(x, m)
+    degree = np.bincount(a, minlength=n) + np.bincount(b, minlength=n)
+    scores, counts = np.unique(s, return_counts=True)
+    rows = max(1, min(n, DUMP_SAMPLE_ROWS, int(DUMP_SAMPLE_EDGES * n / max(1, 2 * len(s)))))
+    pick = np.zeros(n, dtype=bool)
+    pick[np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, rows, replace=False)] = True
+    sel = pick[a] | pick[b]
+    sample = np.stack([a[sel], b[sel], s[sel]], 1).astype(np.float64)
+    sample = sample[np.lexsort((sample[:, 2], sample[:, 1], sample[:, 0]))]
+    np.save(os.path.join(out_dir, "degree.npy"), degree.astype(np.float64))
+    np.save(os.path.join(out_dir, "score_counts.npy"), np.stack([scores, counts], 1).astype(np.float64))
+    np.save(os.path.join(out_dir, "edges_sample.npy"), sample)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--n", type=int, default=N_SEQ, help="number of synthetic peptides (default: the BASELINE workload)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure ms_per_step_no_settle, the clustering call end to end, the other "
+                         "BASELINE configs and the CPU baselines (a plain run measures the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the neighbour graph of the last timed step to DIR/<name>.npy (float64, see dump_outputs())")
     ap.add_argument("--cpu-sample", type=int, default=100000,
-                    help="peptides in the CPU baseline sample (default: the whole workload, about 4 s on 16 threads; "
-                         "bounded: the default run stays within a few minutes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-greedy", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the block with the other BASELINE configs (2, 4a, 4b, a shard of 5)")
+                    help="--full: peptides in the CPU baseline sample (default: the whole workload, about 4 s on 16 threads; "
+                         "bounded: the full run stays within a few minutes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-greedy", action="store_true", help="--full without the clustering call end to end")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="--full without the block with the other BASELINE configs (2, 4a, 4b, a shard of 5)")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -397,28 +441,30 @@ def main():
     # An idle MI355X needs about 25 ms of load to reach its clocks (profiles/round3_bench_warmup.log: 20 timed steps after 3 / 5 / 10 / 20
     # untimed ones take 2.60 / 2.58 / 2.53 / 2.53 ms each): SETTLE_STEPS untimed passes first, then the W warm-up steps the
     # contract asks for, then exactly K timed steps.  Reported in the line as "settle_steps".
-    # First the contract's sequence taken literally -- W warm-up steps from an idle GPU, then K timed steps -- reported beside
+    # --full: first the contract's sequence taken literally -- W warm-up steps from an idle GPU, then K timed steps -- reported beside
     # the settled figure as "ms_per_step_no_settle" (it measures the clock ramp as much as the kernel).
-    for _ in range(args.warmup):
-        step()
-    if px is not None:
-        px.finish()
-    torch.cuda.synchronize(dev)
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for k in range(args.steps):
-        step()
-    if px is not None:
-        px.finish()
-    torch.cuda.synchronize(dev)
-    if world > 1:
-        dist.barrier()
-    no_settle = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
-    if world > 1:
-        dist.all_reduce(no_settle, op=dist.ReduceOp.MAX)
-    ms_per_step_no_settle = float(no_settle.item()) / args.steps * 1e3
+    ms_per_step_no_settle = None
+    if args.full:
+        for _ in range(args.warmup):
+            step()
+        if px is not None:
+            px.finish()
+        torch.cuda.synchronize(dev)
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for k in range(args.steps):
+            step()
+        if px is not None:
+            px.finish()
+        torch.cuda.synchronize(dev)
+        if world > 1:
+            dist.barrier()
+        no_settle = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
+        if world > 1:
+            dist.all_reduce(no_settle, op=dist.ReduceOp.MAX)
+        ms_per_step_no_settle = float(no_settle.item()) / args.steps * 1e3
     for _ in range(SETTLE_STEPS):   # (this rank's scoring pass alone: the clocks are what settles, the exchange of N > 1 has no part in it)
         score_pass()
     torch.cuda.synchronize(dev)
@@ -464,6 +510,8 @@ def main():
     elapsed = float(elapsed.item())
     kern_ms = float(kern_ms.item())
     assert int(tot_pairs.item()) == pairs_total, (int(tot_pairs.item()), pairs_total)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, hd.compact_shards(d_edges, d_counts) if px is None else px.last_result(), n)
 
     e2e = None
     if rank == 0:
@@ -481,7 +529,7 @@ def main():
             "metric": "pairwise BLOSUM62 ShiftedScorer scores/sec (all-vs-all, thresholded neighbour list)",
             "value": value, "unit": "pair scores/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "settle_steps": SETTLE_STEPS, "ms_per_step_no_settle": ms_per_step_no_settle,
-            "passes_before_the_timed_region": args.warmup + args.steps + SETTLE_STEPS + args.warmup,
+            "passes_before_the_timed_region": (args.warmup + args.steps if args.full else 0) + SETTLE_STEPS + args.warmup,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "u8 (8-bit SWAR lanes, host-proven ranges with 16-bit / literal fallbacks; scores are int32-exact)",
             "data": "synthetic",
@@ -519,7 +567,7 @@ def main():
             line["exchange"] = {"format": px.fmt, "gathered_bytes_per_rank_per_step": px.bytes_per_step,
                                 "collectives_per_step": 1}
         maxc = int(np.floor(n * 0.025 + 0.5))
-        if world == 1:
+        if world == 1 and args.full:
             if not args.no_greedy:
                 # the sequences in the reference's default order (-R size: count descending, then the sequence string
                 # descending, UniqueSequence.java:238-248; all counts are 1 here), in a context of their own
@@ -590,8 +638,8 @@ def main():
                 line["cpu_baseline_1_thread"] = cpu_baseline(M, res, off, min(20000, n), 1)
     else:
         line = None
-    if world > 1 and not args.no_greedy:
-        # end to end on N GPUs, AFTER the measurement is complete: one more scored + exchanged pass, then the merge on rank 0
+    if world > 1 and args.full and not args.no_greedy:
+        # --full: end to end on N GPUs, AFTER the measurement is complete: one more scored + exchanged pass, then the merge on rank 0
         # from the gathered graph (hmk_greedy_from_edges_dev) and the broadcast of the cluster ids.  The throughput line must
         # not depend on this extra: a watchdog prints it without the end-to-end figures if the section does not finish.
         import threading

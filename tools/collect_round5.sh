@@ -32,7 +32,7 @@ if [ "$PART" = bench ]; then
     stats_of "$O/trace_local" "$O/round5_neighbors_local_kernel_stats.csv"
     cp "$O/round5_pmc_summary.json" profiles/round5_pmc_summary.json            # bench.py reads roofline.traffic from here
     [ -f "$O/round5_neighbors_local_pmc.json" ] && cp "$O/round5_neighbors_local_pmc.json" profiles/
-    timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > "$O/round5_bench_n1.json"; echo bench $?
+    timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 --full > "$O/round5_bench_n1.json"; echo bench $?
     rm -rf "$O/trace" "$O/trace_local" "$O"/pmc_*/
 elif [ "$PART" = passes ]; then
     cd "$R"
