@@ -59,6 +59,7 @@ struct Switches {
     bool greedy_timing = false;   // HMK_GREEDY_TIMING: a clustering call's timeline, the plan's and the merge's phases on stderr
     bool no_band = false;         // HMK_NO_BAND: no band hand-over, phase 1 waits for the whole pass
     bool no_rows_kernel = false;  // HMK_NO_ROWS_KERNEL: the shift-packed tier (k_neighbors.hip) for every class
+    int key_sort = 2;             // HMK_NO_KEY_SORT: 0, caller order and no key body; HMK_KEY_SORT_KEYS=1: the first key only (A/B runs)
     bool adj_8byte = false;       // HMK_ADJ_8BYTE: 8-byte adjacency entries even where 4 bytes hold every score
     bool local_literal = false;   // HMK_LOCAL_LITERAL: LocalAlignmentScorer through the literal DP
     bool local_signed = false;    // HMK_LOCAL_SIGNED: the signed tagged-max form (what gap_open = 0 runs) for every penalty
@@ -87,6 +88,9 @@ struct Plan {
     bool exact = false;       // the shift-packed length-12 kernel (k_neighbors_swar; only with HMK_NO_ROWS_KERNEL)
     bool rows_exact = false;  // one length for all and a row-packed instantiation for exactly that length
     bool no_rows_kernel = false;   // the switch this plan was built under (part of the cache key)
+    int key_sort = 2;              // ... and this one: keys the plan sorts by (0: none; else rows_keyed shapes only)
+    uint32_t *d_keyrun = nullptr;  // NeighborParams::keyrun / keytab (null: the plan is not key-sorted)
+    uint32_t *d_keytab = nullptr;
     uint32_t cols_per_tile = 16384;
     uint8_t *d_res_sorted = nullptr;
     uint32_t *d_perm = nullptr;
@@ -275,7 +279,8 @@ int grow_edge_buffer(hmk_ctx *ctx, uint64_t cap);
 void free_plan(Plan &pl);
 void classify(const hmk_ctx *ctx, int la, int lb, int X, int p, int thr, TileClass *out, long long row_bound = -1,
               long long *u8_row_limit = nullptr);
-int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_parts, int64_t band_rows = -1);
+// key_sort_ok: a plain single-part pass (no band, no degree counters) that may take the key-sorted order
+int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_parts, int64_t band_rows = -1, bool key_sort_ok = false);
 void free_plan_local(PlanLocal &pl);
 int build_plan_local(hmk_ctx *ctx, uint32_t part, uint32_t n_parts);
 // ---- hmk_pass.cpp

@@ -59,7 +59,20 @@ struct NeighborParams {
     // scoring of a clustering call) with fire-and-forget atomics.  Zeroed by the caller.
     uint32_t *deg;       // total degrees -- or, with deg_m_offset = n, upper counts (the edge's smaller end) in deg[0, n) and lower counts in deg[n, 2n)
     uint32_t deg_m_offset;   // the larger end m of a symmetric edge counts into deg[deg_m_offset + m] (0: one counter per row)
+    // optional (null: no key sort): a key-sorted one-length plan (hmk_plan.cpp, rows_keyed).  keyrun[2 s], keyrun[2 s + 1]: run id << 5 |
+    // residue of sorted position s at key position 0 / of the key pair; keytab: KEYTAB_DWORDS per (row group, key, residue)
+    const uint32_t *keyrun;
+    const uint32_t *keytab;
 };
+
+// Key-sorted one-length sets: the positions are ordered by the residues at two middle positions; a 64-column window
+// whose columns share a key residue adds that position's cells by scalar loads (keytab) instead of table reads.
+// keytab entry of (row group g, key q, residue c): dwords 2u, 2u + 1 = the 8-byte LDS entry of plane u at the key position, zero padded
+constexpr int KEYTAB_DWORDS = 16;
+// the shapes that run it: one length, one row group per tile, hits cut out in the loop -- only the BASELINE shape for now
+constexpr bool rows_keyed(int x, int d, int cap, bool exact, int g) { return exact && d == 0 && g == 1 && x == 3 && cap == 12; }
+// the two key positions of length l at max shift x: middle positions (paired with every row position by all 2x + 1 planes)
+constexpr int rows_key_pos(int x, int l, int q) { return l / 2 - 1 + q < x ? x : l / 2 - 1 + q; }
 
 // one directed neighbour: sequenceScore(seq1 = m, seq2 = x) = s for the row x it is stored under
 struct Nbr {

@@ -55,7 +55,7 @@ int neighbors_dev_locked(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uin
     if (st) return st;
     if (!d_edges || !d_counts || capacity < HMK_EDGE_SHARDS)
         return fail(ctx, HMK_ERR_BAD_ARG, "d_edges/d_counts must be device buffers, capacity >= HMK_EDGE_SHARDS");
-    st = build_plan(ctx, X, p, thr, part, n_parts, band_rows);
+    st = build_plan(ctx, X, p, thr, part, n_parts, band_rows, n_parts == 1 && which == LAUNCH_ALL && !d_deg);
     if (st) return st;
     Plan &pl = ctx->plan;
     if (which != LAUNCH_REST) HIPCHK(ctx, hipMemsetAsync(d_counts, 0, HMK_EDGE_SHARDS * sizeof(unsigned long long), stream));
@@ -74,6 +74,8 @@ int neighbors_dev_locked(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uin
     P.symmetric = ctx->symmetric ? 1u : 0u;
     P.deg = d_deg;
     P.deg_m_offset = (d_deg && d_deg_lo) ? (uint32_t)(d_deg_lo - d_deg) : 0u;   // split counters: upper counts, then lower counts
+    P.keyrun = pl.d_keyrun;
+    P.keytab = pl.d_keytab;
     // one launch per (lane path, entry width, column capacity) group.  A mixed-length plan has two dozen of them: fork them
     // round-robin onto three side streams so that one group's tail overlaps the next group's start, and join back into `stream`,
     // which itself only records the fork event and waits for the joins.

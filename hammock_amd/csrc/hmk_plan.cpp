@@ -44,6 +44,8 @@ void free_plan(Plan &pl) {
     if (pl.d_mb) (void)hipFree(pl.d_mb);
     if (pl.d_classes) (void)hipFree(pl.d_classes);
     if (pl.d_tiles) (void)hipFree(pl.d_tiles);
+    if (pl.d_keyrun) (void)hipFree(pl.d_keyrun);
+    if (pl.d_keytab) (void)hipFree(pl.d_keytab);
     pl = Plan();
 }
 
@@ -103,10 +105,11 @@ void classify(const hmk_ctx *ctx, int la, int lb, int X, int p, int thr, TileCla
 // band_rows: tiles that touch a sequence with caller index < band_rows are put first in every launch group, so that a
 // first launch of only those tiles completes the adjacency rows phase 1 of the greedy merge reads first
 // (hmk_greedy_cluster); -1 = the caller does not care (any cached plan with the other parameters will do).
-int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_parts, int64_t band_rows) {
+int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_parts, int64_t band_rows, bool key_sort_ok) {
     Plan &pl = ctx->plan;
+    const int want_keys = key_sort_ok ? ctx->sw.key_sort : 0;
     if (pl.valid && pl.X == X && pl.p == p && pl.thr == thr && pl.part == part && pl.n_parts == n_parts &&
-        (band_rows < 0 || pl.band_req == band_rows) && pl.no_rows_kernel == ctx->sw.no_rows_kernel)
+        (band_rows < 0 || pl.band_req == band_rows) && pl.no_rows_kernel == ctx->sw.no_rows_kernel && pl.key_sort == want_keys)
         return HMK_OK;
     free_plan(pl);
     if (band_rows < 0) band_rows = 0;
@@ -241,6 +244,39 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
         TileClass t12;
         classify(ctx, 12, 12, X, p, thr, &t12);
         pl.exact = t12.path == PATH_U8 && t12.nw == 2;
+    }
+    // Key sort: a one-length set whose bucket keeps the caller's order and runs a rows_keyed shape is ordered by the
+    // residues at the two key positions -- all but a band prefix, which keeps the caller's order (band_end stays what it is) -- with
+    // a stable counting sort.  Run ids over the whole order: equal at a window's two ends <=> the window shares the key.  Plain
+    // single-part passes only (key_sort_ok): a clustering call's scoring counts degrees per row group and its CSR build reads the
+    // edges in row order (both slower on the sorted order: 10^5 call 4.04 -> 4.44 ms), and shards keep their caller-order rows.
+    pl.key_sort = want_keys;
+    std::vector<uint32_t> keyrun;
+    const int L1 = ctx->min_len;
+    const bool key_sorted = pl.key_sort > 0 && pl.rows_exact && !(refine && !all_rows_fit) &&
+                            rows_keyed(X, 0, L1, true, rows_per_tile_rows(X, 0, L1, true) / 8) && n >= 2;
+    if (key_sorted) {
+        const int k0 = rows_key_pos(X, L1, 0), k1 = rows_key_pos(X, L1, 1);
+        auto key_of = [&](uint32_t k) { return (uint32_t)ctx->res[ctx->off[k] + k0] * HMK_ALPHABET + ctx->res[ctx->off[k] + k1]; };
+        const uint32_t b0 = band_end[L1], b1 = bucket[L1 + 1];
+        std::vector<uint32_t> cnt(HMK_ALPHABET * HMK_ALPHABET + 1, 0u), sorted(perm.begin() + b0, perm.begin() + b1);
+        for (uint32_t q = b0; q < b1; q++) cnt[key_of(perm[q]) + 1]++;
+        for (int v = 0; v < HMK_ALPHABET * HMK_ALPHABET; v++) cnt[v + 1] += cnt[v];
+        for (uint32_t q = b0; q < b1; q++) sorted[cnt[key_of(perm[q])]++] = perm[q];
+        std::copy(sorted.begin(), sorted.end(), perm.begin() + b0);
+        keyrun.resize(2 * (size_t)n);
+        uint32_t r0 = 0, r01 = 0;
+        for (uint32_t q = 0; q < n; q++) {
+            const uint32_t k = perm[q], c0 = ctx->res[ctx->off[k] + k0], c1 = ctx->res[ctx->off[k] + k1];
+            if (q > 0) {
+                const uint32_t kp = perm[q - 1];
+                const bool same0 = ctx->res[ctx->off[kp] + k0] == c0;
+                r0 += same0 ? 0u : 1u;
+                r01 += (pl.key_sort == 2 && same0 && ctx->res[ctx->off[kp] + k1] == c1) ? 0u : 1u;   // (one key: no window shares both)
+            }
+            keyrun[2 * (size_t)q] = r0 << 5 | c0;
+            keyrun[2 * (size_t)q + 1] = r01 << 5 | c1;
+        }
     }
     // Column runs: long runs amortise the table build (65,536 columns: 3.55 ms for the whole 10^5 pass against
     // 3.60 ms with 16,384), short ones keep the tail of a small launch short (a 1/8 shard: 0.478 ms with 16,384,
@@ -424,6 +460,15 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
     HIPCHK(ctx, hipMalloc((void **)&pl.d_tiles, std::max<size_t>(1, tiles.size()) * sizeof(Tile)));
     if (!tiles.empty())
         HIPCHK(ctx, hipMemcpy(pl.d_tiles, tiles.data(), tiles.size() * sizeof(Tile), hipMemcpyHostToDevice));
+    if (key_sorted) {   // run ids, and the key table built on the device from the sorted residues (hipMemcpy above: they are there)
+        const uint32_t n_groups = (n + 7) / 8;
+        const size_t tab_dwords = (size_t)n_groups * 2 * HMK_ALPHABET * KEYTAB_DWORDS;
+        HIPCHK(ctx, hipMalloc((void **)&pl.d_keyrun, keyrun.size() * 4));
+        HIPCHK(ctx, hipMemcpy(pl.d_keyrun, keyrun.data(), keyrun.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMalloc((void **)&pl.d_keytab, tab_dwords * 4));
+        HIPCHK(ctx, launch_rows_keytab(pl.d_res_sorted, (uint32_t)pl.lpad, n, pl.d_mb, classes.at(0).case_b, X, L1, pl.d_keytab, n_groups));
+        HIPCHK(ctx, hipStreamSynchronize(nullptr));
+    }
     pl.X = X; pl.p = p; pl.thr = thr; pl.part = part; pl.n_parts = n_parts;
     pl.valid = true;
     plan_lap("device copies");

@@ -192,23 +192,41 @@ struct RowsShape {
         offsets_of(words, tw, base, tbase, off, toff);
     }
 
-    // All shift sums of (8 rows of group GI) x (this lane's column): W0 / W1[u] = the 8 byte lanes of plane u.
-    template <int GI>
+    // key positions (rows_keyed shapes): a set bit q of SKIP leaves column position key_pos(q) out of every plane -- its cells
+    // are in the start values (the window's columns all have the same residue there, rows_tile)
+    static constexpr int key_pos(int q) { return rows_key_pos(X, CAP, q); }
+    static constexpr bool skipped(int skip, int j) { return ((skip & 1) && j == key_pos(0)) || ((skip & 2) && j == key_pos(1)); }
+    // EXACT_LB: plane u reads the column positions [plane_j0(u), plane_j1(u)) but the skipped ones; the k-th of them
+    static constexpr int plane_j0(int u) { return X - u > 0 ? X - u : 0; }
+    static constexpr int plane_j1(int u) { return NI + X - u < CAP ? NI + X - u : CAP; }   // (row position j + u - X < NI)
+    static constexpr int plane_reads(int u, int skip) {
+        int n = 0;
+        for (int j = plane_j0(u); j < plane_j1(u); j++) n += skipped(skip, j) ? 0 : 1;
+        return n;
+    }
+    static constexpr int plane_pos(int u, int skip, int k) {
+        for (int j = plane_j0(u); j < plane_j1(u); j++)
+            if (!skipped(skip, j) && k-- == 0) return j;
+        return -1;
+    }
+
+    // All shift sums of (8 rows of group GI) x (this lane's column): W0 / W1[u] = the 8 byte lanes of plane u, started at
+    // c0 / c1[u] (rows 0-3 / 4-7).  SKIP (EXACT_LB only): key positions left out, see key_pos.
+    template <int GI, int SKIP = 0>
     static __device__ __forceinline__ void accumulate(const uint32_t (&off)[CAP], const uint32_t (&toff)[NT], int lbs,
-                                                      const uint32_t (&ci)[ND], uint32_t (&W0)[ND], uint32_t (&W1)[ND]) {
+                                                      const uint32_t (&c0)[ND], const uint32_t (&c1)[ND], uint32_t (&W0)[ND], uint32_t (&W1)[ND]) {
+        static_assert(SKIP == 0 || EXACT_LB, "key positions are skipped by the one-length forms only");
+        const uint32_t (&ci)[ND] = c0;
         if constexpr (EXACT_LB) {
             // everything is known at compile time: plane by plane, the plane's reads summed two at a time (one v_add3 per
             // dword and pair; an odd count starts with a plain add): ceil(reads / 2) VALU instructions per dword, the minimum
 #pragma unroll
             for (int u = 0; u < ND; u++) {
-                constexpr int NMAIN = CAP - X;
-                const int j0 = X - u > 0 ? X - u : 0;                 // main positions j0 .. NMAIN - 1
-                const int nt = ND - 2 - u >= X ? X : (ND - 2 - u < 0 ? 0 : ND - 1 - u);   // tail positions q = 0 .. nt - 1 (u <= ND - 2 - q)
-                const int n = NMAIN - j0 + nt;
-                uint32_t a0 = ci[u], a1 = ci[u];
-                // read k of the plane: k < NMAIN - j0: main position j0 + k; else tail position k - (NMAIN - j0)
+                const int n = plane_reads(u, SKIP);
+                uint32_t a0 = c0[u], a1 = c1[u];
+                // read k of the plane: column position plane_pos (the tail positions' offsets are the main ones: toff = off)
                 auto rd = [&](int k) {
-                    const int j = k < NMAIN - j0 ? j0 + k : NMAIN + (k - (NMAIN - j0));   // column position (tail q = j - NMAIN)
+                    const int j = plane_pos(u, SKIP, k);
                     return rows_table_read<u32x2>(off[j] + (uint32_t)pos_addr(GI, j + u - X));
                 };
                 int k = 0;
@@ -642,11 +660,51 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
     uint32_t acc[G];
 #pragma unroll
     for (int g = 0; g < G; g++) acc[g] = 0;
+    // Key-sorted sets (rows_keyed, P.keyrun set): the wave's 64 columns are a window of the sorted order.  When its first and last
+    // live column lie in one run of the key residue, so do all of them: the key position's cells are the same for the whole
+    // wave, their 8-byte entries come from keytab by scalar loads and are summed into the planes' start values on the SALU,
+    // and the body that skips the position runs.  kmode: 0 none, 1 key 0, 3 both keys (wave-uniform).
+    constexpr bool KEYED = rows_keyed(X, D, CAP, EXACT_LB, G);
+    const bool keyed = KEYED && P.keyrun != nullptr;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     for (uint32_t bt = 0; bt < n_batches; bt++) {
         const uint32_t colrel = bt * 256 + tid;
         const uint32_t col = T.col0 + colrel;
+        // (the column's words are asked for first: the key's scalar loads below are two dependent round trips)
+        uint32_t words[S::LPADW], tw[S::TWN];
+        S::load_words(res_sorted + (size_t)col * lpad_s, col < col_end, lbs, words, tw);
+        int kmode = 0;
+        uint32_t ks0[ND], ks1[ND];   // start values of the planes, rows 0-3 / 4-7
+#pragma unroll
+        for (int u = 0; u < ND; u++) { ks0[u] = ci[u]; ks1[u] = ci[u]; }
+        if constexpr (KEYED) {
+            const uint32_t wc0 = T.col0 + bt * 256 + wave * 64;   // the wave's first column
+            if (keyed && wc0 < col_end) {
+                const uint32_t wc1 = min(wc0 + 63u, col_end - 1u);    // ... and its last live one
+                const u32x2 ra = rows_const_load<u32x2>(P.keyrun + 2 * (size_t)wc0), rb = rows_const_load<u32x2>(P.keyrun + 2 * (size_t)wc1);
+                if (ra.x == rb.x) {
+                    kmode = ra.y == rb.y ? 3 : 1;
+                    // both entries are loaded whole (the second one is valid memory whatever kmode is) and the second is masked
+                    static_assert(2 * ND <= KEYTAB_DWORDS, "key table entry");
+                    const uint32_t *kt = P.keytab + (size_t)(T.row0 >> 3) * (2 * 24 * KEYTAB_DWORDS);
+                    const uint32_t *e0 = kt + (ra.x & 31u) * KEYTAB_DWORDS;
+                    const uint32_t *e1 = kt + (24 + (ra.y & 31u)) * KEYTAB_DWORDS;
+                    const uint32_t m1 = kmode == 3 ? ~0u : 0u;
+#pragma unroll
+                    for (int u = 0; u + 1 < ND; u += 2) {   // byte lanes: every partial sum is <= the plane's final lane <= 255, no carry
+                        const u32x4 a = rows_const_load<u32x4>(e0 + 2 * u), b = rows_const_load<u32x4>(e1 + 2 * u);
+                        ks0[u] += a.x + (b.x & m1); ks1[u] += a.y + (b.y & m1);
+                        ks0[u + 1] += a.z + (b.z & m1); ks1[u + 1] += a.w + (b.w & m1);
+                    }
+                    if constexpr (ND & 1) {
+                        const u32x2 a = rows_const_load<u32x2>(e0 + 2 * (ND - 1)), b = rows_const_load<u32x2>(e1 + 2 * (ND - 1));
+                        ks0[ND - 1] += a.x + (b.x & m1); ks1[ND - 1] += a.y + (b.y & m1);
+                    }
+                }
+            }
+        }
         uint32_t off[CAP], toff[S::NT];
-        S::offsets(res_sorted + (size_t)col * lpad_s, col < col_end, lbs, tab_addr, tab_addr, off, toff);
+        S::offsets_of(words, tw, tab_addr, tab_addr, off, toff);
         const bool look = !DEFER || (bt & 3u) == 3u || bt + 1 == n_batches;   // wave-uniform
 
         auto one_group = [&](auto gt) {
@@ -654,7 +712,13 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
             if ((uint32_t)(8 * g) >= T.nrows) return;   // wave-uniform
             uint32_t W0[ND], W1[ND];
             read_phase_begin(prio);
-            S::template accumulate<g>(off, toff, lbs, ci, W0, W1);
+            if constexpr (KEYED) {
+                if (kmode == 3) S::template accumulate<g, 3>(off, toff, lbs, ks0, ks1, W0, W1);
+                else if (kmode == 1) S::template accumulate<g, 1>(off, toff, lbs, ks0, ks1, W0, W1);
+                else S::template accumulate<g>(off, toff, lbs, ks0, ks1, W0, W1);
+            } else {
+                S::template accumulate<g>(off, toff, lbs, ci, ci, W0, W1);
+            }
             read_phase_end(prio);
 
             // ---- threshold test: some (row, shift) lane has its top bit set <=> score >= threshold ----

@@ -1,5 +1,5 @@
 // k_neighbors_rows.hip -- which row-packed instantiation (k_neighbors_rows.h) a (max shift, lengths) class runs, and the
-// dispatch to the part (k_rows_part.hip) that holds it.  Host code only.
+// dispatch to the part (k_rows_part.hip) that holds it; the key table of a key-sorted plan.
 #include "k_rows_shapes.h"
 
 namespace hmk {
@@ -46,5 +46,37 @@ hipError_t launch_neighbors_rows(int X, int d, int cap, bool exact, const Neighb
 }
 
 hipError_t warm_neighbors_rows_module() { return warm_rows_part_0(); }
+
+// One thread per keytab dword: entry (row group g, key q, residue c), dword 2u + h = byte t: cell(row 8g + 4h + t, key position + u - X, c)
+// + bias, as the tile's table build (rows_tile) writes it -- zero for a row at or past n; dwords past the 2X + 1 planes zero.
+__global__ void __launch_bounds__(256) k_rows_keytab(const uint8_t *__restrict__ res_sorted, uint32_t lpad, uint32_t n,
+                                                     const uint8_t *__restrict__ mb, int case_b, int X, int L, uint32_t *__restrict__ keytab,
+                                                     uint32_t n_groups) {
+    const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (uint64_t)n_groups * 2 * HMK_ALPHABET * KEYTAB_DWORDS) return;
+    const int d = (int)(e % KEYTAB_DWORDS), c = (int)(e / KEYTAB_DWORDS % HMK_ALPHABET), q = (int)(e / (KEYTAB_DWORDS * HMK_ALPHABET) % 2);
+    const uint32_t g = (uint32_t)(e / (2 * HMK_ALPHABET * KEYTAB_DWORDS));
+    const int u = d >> 1, h = d & 1, i = rows_key_pos(X, L, q) + u - X;
+    uint32_t v = 0;
+    if (u <= 2 * X && i >= 0 && i < L) {
+        for (int t = 0; t < 4; t++) {
+            const uint32_t r = 8 * g + 4 * h + t;
+            if (r < n) {
+                const int a = res_sorted[(size_t)r * lpad + i];
+                v |= (uint32_t)(case_b ? mb[c * HMK_ALPHABET + a] : mb[a * HMK_ALPHABET + c]) << (8 * t);
+            }
+        }
+    }
+    keytab[e] = v;
+}
+
+hipError_t launch_rows_keytab(const uint8_t *res_sorted, uint32_t lpad, uint32_t n, const uint8_t *mb, int case_b, int X, int L,
+                              uint32_t *keytab, uint32_t n_groups) {
+    const uint64_t total = (uint64_t)n_groups * 2 * HMK_ALPHABET * KEYTAB_DWORDS;
+    if (total == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rows_keytab, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, res_sorted, lpad, n, mb, case_b, X, L, keytab,
+                       n_groups);
+    return hipGetLastError();
+}
 
 }  // namespace hmk
