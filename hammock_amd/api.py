@@ -240,6 +240,55 @@ class Context:
                 self._raise(st)
             return buf[:n_edges.value].copy(), stats
 
+    # -- query-vs-reference search ------------------------------------------------------
+    # Upload queries and references together once -- set_sequences(queries + references) -- and search the two index ranges:
+    # only the Q x R pairs are scored (an all-vs-all pass over the union would score (Q + R)^2 / 2).  score(q, r) is
+    # sequenceScore(seq1 = query, seq2 = reference); every edge comes out m = query, x = reference (edge_fields).
+    def _search(self, fn, q0, q1, r0, r1, a, b, threshold, capacity):
+        stats = N.NeighborStats()
+        n_edges = C.c_uint64(0)
+        cap = int(capacity) if capacity is not None else 1 << 20
+        while True:
+            buf = np.empty(max(cap, 1), dtype=np.uint64)
+            st = fn(self._h, int(q0), int(q1), int(r0), int(r1), int(a), int(b), int(threshold), _ptr(buf, C.c_uint64), cap,
+                    C.byref(n_edges), C.byref(stats))
+            if st == N.HMK_ERR_CAPACITY and capacity is None and int(n_edges.value) > cap:
+                cap = int(n_edges.value)
+                continue
+            if st:
+                self._raise(st)
+            return buf[:n_edges.value].copy(), stats
+
+    def search_shifted(self, q0, q1, r0, r1, max_shift, shift_penalty, threshold, capacity=None):
+        """Queries [q0, q1) against references [r0, r1) (disjoint ranges of the uploaded set), ShiftedScorer:
+        -> (edges uint64[n_edges] with m = query, NeighborStats).  Typical use:
+            ctx.set_sequences(queries + references)
+            edges, stats = ctx.search_shifted(0, len(queries), len(queries), len(queries) + len(references), 3, 0, 20)"""
+        return self._search(N.lib.hmk_search_shifted, q0, q1, r0, r1, max_shift, shift_penalty, threshold, capacity)
+
+    def search_local(self, q0, q1, r0, r1, gap_open, gap_extend, threshold, capacity=None):
+        """The same with LocalAlignmentScorer(seq1 = query, seq2 = reference) -> (edges uint64[n_edges], NeighborStats)"""
+        return self._search(N.lib.hmk_search_local, q0, q1, r0, r1, gap_open, gap_extend, threshold, capacity)
+
+    def search_best_shifted(self, q0, q1, r0, r1, max_shift, shift_penalty, threshold, k):
+        """The best k (1..32) references of every query with score >= threshold, by score descending, then reference
+        index ascending, selected on the device -> (index int64[nq, k] padded with -1, score int32[nq, k]); a padded
+        slot's score is INT32_MIN.  The selection's device time is in last_search_stats.kernel_ms."""
+        nq = max(int(q1) - int(q0), 0)
+        idx = np.empty((nq, max(int(k), 1)), dtype=np.uint32)
+        score = np.empty((nq, max(int(k), 1)), dtype=np.int32)
+        nh = np.empty(max(nq, 1), dtype=np.uint32)
+        stats = N.NeighborStats()
+        st = N.lib.hmk_search_best_shifted(self._h, int(q0), int(q1), int(r0), int(r1), int(max_shift), int(shift_penalty),
+                                           int(threshold), int(k), _ptr(idx, C.c_uint32), _ptr(score, C.c_int32),
+                                           _ptr(nh, C.c_uint32), C.byref(stats))
+        if st:
+            self._raise(st)
+        self.last_search_stats = stats
+        out = idx.astype(np.int64)
+        out[idx == np.uint32(0xFFFFFFFF)] = -1
+        return out, score
+
     def neighbors_shifted_dev(self, max_shift, shift_penalty, threshold, part, n_parts, d_edges_ptr, capacity,
                               d_counts_ptr, stream=0):
         st = N.lib.hmk_neighbors_shifted_dev(self._h, int(max_shift), int(shift_penalty), int(threshold), part, n_parts,

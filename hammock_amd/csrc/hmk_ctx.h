@@ -49,6 +49,8 @@ enum {
     SB_PEER, SB_PEERCNT, SB_PEERBAND, SB_PEERDEG,   // multi-device calls: the inbox of edge blocks from the other devices + their counts, band blocks (peers: compacted; root: gathered), degree slices
     SB_ROUTE, SB_ROUTECNT,                          // ... this device's edges dealt into one block per owning device; counts / offsets / cursors
     SB_REPL,                                        // ... (in a peer's context, on the ROOT's device) the peer's piece copied to the root: no peer access, or HMK_MULTI_REPLICATE
+    SB_SEARCH_OUT, SB_SEARCH_CNT, SB_SEARCH_START, SB_SEARCH_SCAN, SB_SEARCH_HITS,   // query-vs-reference search (hmk_search.cpp): edges / keys,
+                                                                                     // per-query counts + cursors, run starts, scan scratch, best-k
     SB_N
 };
 
@@ -101,6 +103,7 @@ struct Plan {
     std::vector<Group> groups;
     hmk_neighbor_stats stats{};
     uint64_t band_pairs = 0;   // pairs inside the band tiles (of stats.pairs_scored)
+    uint32_t q0 = 0, q1 = 0, r0 = 0, r1 = 0;   // a search plan (build_plan_search): its query and reference ranges
 };
 
 struct PlanLocal {
@@ -113,6 +116,7 @@ struct PlanLocal {
     Tile *d_tiles = nullptr;
     uint32_t n_tiles = 0;
     uint64_t pairs = 0;
+    uint32_t q0 = 0, q1 = 0, r0 = 0, r1 = 0;   // a search plan (build_plan_local_search): its query and reference ranges
 };
 
 } }  // namespace hmk::impl
@@ -141,6 +145,8 @@ struct hmk_ctx {
 
     Plan plan;
     PlanLocal plan_local;
+    Plan plan_search;              // the query-vs-reference searches' plans: cached apart from the all-vs-all ones, so that
+    PlanLocal plan_local_search;   // searches and clustering calls on one context do not rebuild each other's
     uint64_t *d_edges = nullptr;  // internal buffer of the host-buffer entry points
     uint64_t d_edges_cap = 0;
     unsigned long long *d_counts = nullptr;
@@ -283,11 +289,21 @@ void classify(const hmk_ctx *ctx, int la, int lb, int X, int p, int thr, TileCla
 int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_parts, int64_t band_rows = -1, bool key_sort_ok = false);
 void free_plan_local(PlanLocal &pl);
 int build_plan_local(hmk_ctx *ctx, uint32_t part, uint32_t n_parts);
+// ---- hmk_search.cpp
+// the rectangle queries [q0, q1) x references [r0, r1) (disjoint, non-empty): ctx->plan_search / ctx->plan_local_search
+int build_plan_search(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
+int build_plan_local_search(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
 // ---- hmk_pass.cpp
 int neighbors_dev_locked(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_parts, void *d_edges,
                          uint64_t capacity, void *d_counts, hipStream_t stream, int which = LAUNCH_ALL,
                          int64_t band_rows = -1, uint32_t *d_deg = nullptr, uint32_t *d_deg_lo = nullptr);
+int launch_plan(hmk_ctx *ctx, const Plan &pl, int X, int p, int thr, void *d_edges, uint64_t capacity, void *d_counts,
+                hipStream_t stream, int which = LAUNCH_ALL, uint32_t *d_deg = nullptr, uint32_t *d_deg_lo = nullptr);
 bool local_enc(const hmk_ctx *ctx, int gap_open, int gap_extend);
+bool local_literal(const hmk_ctx *ctx, int gap_open, int gap_extend);
+int check_local_fits(hmk_ctx *ctx, int gap_open, int gap_extend, int thr);
+int launch_plan_local(hmk_ctx *ctx, const PlanLocal &pl, int gap_open, int gap_extend, int thr, uint64_t *d_edges, uint64_t capacity,
+                      unsigned long long *d_counts, hipStream_t stream);
 int neighbors_internal(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_parts, uint64_t want_cap,
                        unsigned long long counts[HMK_EDGE_SHARDS], double *kernel_ms);
 int neighbors_local_dev_locked(hmk_ctx *ctx, int gap_open, int gap_extend, int thr, uint32_t part, uint32_t n_parts,

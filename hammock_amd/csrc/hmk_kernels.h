@@ -138,6 +138,18 @@ hipError_t launch_local_block(int lbmax, bool enc, bool force_signed, bool force
                               uint32_t r1, uint32_t c0, uint32_t c1, int gap_open, int gap_extend, int32_t *out,
                               hipStream_t s);
 
+// query-vs-reference searches (k_search.hip).  The segments of a search pass over the queries [q0, q0 + nq) and references disjoint
+// from them, every edge oriented m = query: packed into out[0 .. total) (the caller knows the total from the counts) ...
+// (max_count: the largest segment count, which sizes the grids)
+hipError_t launch_search_compact(const uint64_t *edges, uint64_t cap_per_shard, const unsigned long long *counts, uint64_t max_count,
+                                 uint32_t q0, uint32_t nq, uint64_t *out, uint64_t out_capacity, hipStream_t s);
+// ... or reduced to the k best references of every query (score descending, then reference index ascending): hit_index / hit_score
+// [nq * k], n_hits[nq], unused slots 0xFFFFFFFF / INT32_MIN.  cnt_cursor: uint32[2 nq], start: uint32[nq + 1], scan_scratch:
+// scan_scratch_bytes(nq), keys: uint64[total edges]
+hipError_t launch_search_best(const uint64_t *edges, uint64_t cap_per_shard, const unsigned long long *counts, uint64_t max_count,
+                              uint32_t q0, uint32_t nq, uint32_t k, uint32_t *cnt_cursor, uint32_t *start, uint64_t *scan_scratch, uint64_t *keys, uint64_t keys_capacity,
+                              uint32_t *hit_index, int32_t *hit_score, uint32_t *n_hits, hipStream_t s);
+
 // force the deferred load of the code objects a clustering call launches from (hmk_create)
 hipError_t warm_neighbors_module();
 hipError_t warm_edges_module();

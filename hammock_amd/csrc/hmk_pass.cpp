@@ -57,7 +57,12 @@ int neighbors_dev_locked(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uin
         return fail(ctx, HMK_ERR_BAD_ARG, "d_edges/d_counts must be device buffers, capacity >= HMK_EDGE_SHARDS");
     st = build_plan(ctx, X, p, thr, part, n_parts, band_rows, n_parts == 1 && which == LAUNCH_ALL && !d_deg);
     if (st) return st;
-    Plan &pl = ctx->plan;
+    return launch_plan(ctx, ctx->plan, X, p, thr, d_edges, capacity, d_counts, stream, which, d_deg, d_deg_lo);
+}
+
+// the launches of a built plan (the all-vs-all plan or a search plan, hmk_search.cpp)
+int launch_plan(hmk_ctx *ctx, const Plan &pl, int X, int p, int thr, void *d_edges, uint64_t capacity, void *d_counts,
+                hipStream_t stream, int which, uint32_t *d_deg, uint32_t *d_deg_lo) {
     if (which != LAUNCH_REST) HIPCHK(ctx, hipMemsetAsync(d_counts, 0, HMK_EDGE_SHARDS * sizeof(unsigned long long), stream));
     NeighborParams P{};
     P.res_sorted = pl.d_res_sorted;
@@ -137,19 +142,32 @@ int neighbors_local_dev_locked(hmk_ctx *ctx, int gap_open, int gap_extend, int t
                                uint64_t *d_edges, uint64_t capacity, unsigned long long *d_counts, hipStream_t stream) {
     int st = need_device(ctx);
     if (st) return st;
-    // the striped register kernels take gap penalties <= 0 and int8 matrix entries; anything else (the reference imposes
-    // neither, LocalAlignmentScorer.java:43-55) runs the literal DP on the same tiles
-    const bool literal = gap_open > 0 || gap_extend > 0 || ctx->min_m < -127 || ctx->max_m > 127 || ctx->sw.local_literal;
-    {   // edge scores travel as int16
-        const long long top = (long long)ctx->max_len * std::max(0, ctx->max_m) +
-                              2LL * ctx->max_len * (long long)std::max(0, std::max(gap_open, gap_extend));
-        if (top > 32767 || thr < -30000 || thr > 30000)
-            return fail(ctx, HMK_ERR_BAD_ARG, "scores up to " + std::to_string(top) + " are possible with this matrix / these gap penalties "
-                                               "(or the threshold is outside [-30000, 30000]): they do not fit the int16 score of a packed edge");
-    }
+    st = check_local_fits(ctx, gap_open, gap_extend, thr);
+    if (st) return st;
     st = build_plan_local(ctx, part, n_parts);
     if (st) return st;
-    PlanLocal &pl = ctx->plan_local;
+    return launch_plan_local(ctx, ctx->plan_local, gap_open, gap_extend, thr, d_edges, capacity, d_counts, stream);
+}
+
+// the striped register kernels take gap penalties <= 0 and int8 matrix entries; anything else (the reference imposes
+// neither, LocalAlignmentScorer.java:43-55) runs the literal DP on the same tiles
+bool local_literal(const hmk_ctx *ctx, int gap_open, int gap_extend) {
+    return gap_open > 0 || gap_extend > 0 || ctx->min_m < -127 || ctx->max_m > 127 || ctx->sw.local_literal;
+}
+
+// the edge scores of a LocalAlignmentScorer pass travel as int16
+int check_local_fits(hmk_ctx *ctx, int gap_open, int gap_extend, int thr) {
+    const long long top = (long long)ctx->max_len * std::max(0, ctx->max_m) +
+                          2LL * ctx->max_len * (long long)std::max(0, std::max(gap_open, gap_extend));
+    if (top > 32767 || thr < -30000 || thr > 30000)
+        return fail(ctx, HMK_ERR_BAD_ARG, "scores up to " + std::to_string(top) + " are possible with this matrix / these gap penalties "
+                                           "(or the threshold is outside [-30000, 30000]): they do not fit the int16 score of a packed edge");
+    return HMK_OK;
+}
+
+int launch_plan_local(hmk_ctx *ctx, const PlanLocal &pl, int gap_open, int gap_extend, int thr, uint64_t *d_edges, uint64_t capacity,
+                      unsigned long long *d_counts, hipStream_t stream) {
+    const bool literal = local_literal(ctx, gap_open, gap_extend);
     HIPCHK(ctx, hipMemsetAsync(d_counts, 0, HMK_EDGE_SHARDS * sizeof(unsigned long long), stream));
     NeighborParams P{};
     P.res_sorted = pl.d_res_sorted;

@@ -6,6 +6,7 @@
 //
 // Extra flags that the reference does not have: --device <k> (HIP ordinal, default 0) and --devices a,b,.. (several
 // GPUs of the node behind one context, the first is the root: hmk_create_multi).
+// Extra mode that the reference does not have: `hammock-hip search` (runSearch), queries against a reference set.
 #include <future>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -119,7 +120,9 @@ void parseClinkageArgs(const std::vector<std::string> &args, Options &o) {  // H
 
 void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
     std::cerr << "\nhammock-hip: MI355X-native greedy and clinkage modes of Hammock version " << VERSION << "\n\n"
-              << "Synopsis: hammock-hip <greedy|clinkage> <param1> <param2> ...\n\n"
+              << "Synopsis: hammock-hip <greedy|clinkage> <param1> <param2> ...\n"
+              << "          hammock-hip search -i <queries> --database <references> -d <directory> [-f fasta|tab] [-m <file>] [-x <int>]\n"
+              << "                      [-p <int>] [-g <int>] [--best <int>] [--device <int>]\n\n"
               << "-i, --input <file>\n\tA path to an input file\n\n"
               << "-d, --output_directory <directory>\n\tA directory to store all output files in\n\n"
               << "-t, --threads <int>\n\tAccepted for compatibility (the GPU path ignores it)\n\n"
@@ -135,6 +138,8 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "-L, --cache_size_limit <int>\n\t(clinkage) accepted and logged; has no effect, as in the reference\n\n"
               << "--device <int>\n\tHIP device ordinal (default 0)\n\n"
               << "--devices <int,int,...>\n\tShard the pair space over several GPUs of the node (the first one runs the merge)\n\n"
+              << "--database <file>\n\t(search) the reference sequences every query (-i) is scored against\n\n"
+              << "--best <int>\n\t(search) keep only the best 1..32 hits of each query\n\n"
               << "--java_hashset <8|7|6>\n\t(clinkage) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
 }
 
@@ -363,6 +368,173 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
     }
 }
 
+// `hammock-hip search -i queries --database references -d dir ...`: every query against every reference with ShiftedScorer
+// (sequenceScore(seq1 = query, seq2 = reference)), the hits at or above the threshold to <dir>/search_hits.tsv
+// (query, target, score, shift): queries in load order, each one's hits by score descending, then by the reference's load
+// order.  Each file is loaded and deduplicated on its own (FileIOManager.loadUniqueSequencesFrom*), so one peptide may be on
+// both sides.  Defaults: -x as greedy's over the union of both files (Hammock.java:803-811,1421-1434), -g = round(1.7 x the mean
+// query length) (:394-397), -p 0.  --best K: only the best K hits of each query (hmk_search_best_shifted).
+int runSearch(const std::vector<std::string> &args) {
+    Options o;
+    const std::string PARENT_DIR = parentDir();
+    o.matrixFile = PARENT_DIR + "/matrices/blosum62.txt";  // Hammock.java:45
+    parseCommonArgs(args, o);
+    parseGreedyArgs(args, o);
+    std::string database;
+    bool haveDatabase = false, havePenalty = false;
+    int best = 0;
+    for (size_t i = 1; i < args.size(); i++) {
+        const bool more = args.size() > i + 1;
+        if (args[i] == "--database" && more) { database = args[++i]; haveDatabase = true; }
+        else if (args[i] == "--best" && more) {
+            best = javaIntegerDecode(args[++i]);
+            if (best < 1 || best > 32) throw CLIException("Error. --best may be 1 to 32.");
+        } else if ((args[i] == "-p" || args[i] == "--gap_penalty") && more) havePenalty = true;
+    }
+    if (!o.devices.empty()) throw CLIException("Error. --devices is not available in mode search (a search runs on one device, --device).");
+    if (!o.haveInput) throw CLIException("Error. Parameter input file (-i or --input) missing with no default.");
+    if (!haveDatabase) throw CLIException("Error. Parameter reference file (--database) missing with no default.");
+    if (!(o.inputType == "fasta" || o.inputType == "tab"))
+        throw CLIException("Error. Parameter -f value may be either \"fasta\" or \"tab\" in mode search.");
+    if (o.haveDir) {
+        if (exists(o.workingDirectory)) throw CLIException("Error. Output directory exists. Exiting to prevent data loss.");
+        mkdir(o.workingDirectory.c_str(), 0777);
+    } else {
+        std::string name;
+        mkdir((PARENT_DIR + "/dist").c_str(), 0777);
+        for (int i = 1; i < 9999; i++) {
+            name = PARENT_DIR + "/dist/Hammock_result_" + std::to_string(i);
+            if (!exists(name)) { mkdir(name.c_str(), 0777); break; }
+        }
+        o.workingDirectory = name;
+        std::cerr << "Creating default output directory: " << name << std::endl;
+    }
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        logger.logAndStderr(std::string("\nHammock version ") + VERSION +
+                            " Run with --help for a brief description of command line parameters.\n");
+        const std::vector<std::vector<int>> scoringMatrix = FileIOManager::loadScoringMatrix(o.matrixFile);
+        std::shared_future<std::shared_ptr<NativeContext>> contextReady = std::async(std::launch::async, [&scoringMatrix, &o]() {
+            return std::make_shared<NativeContext>(scoringMatrix, o.device);
+        });
+        logger.logWithTime("Program started in mode \"search\".");
+        std::string argsString;
+        for (auto &a : args) argsString += " " + a;
+        logger.logWithoutTime("Command-line arguments: \n" + argsString + "\n");
+        auto load = [&](const std::string &file) {
+            return o.inputType == "fasta" ? FileIOManager::loadUniqueSequencesFromFasta(file) : FileIOManager::loadUniqueSequencesFromTable(file);
+        };
+        logger.logAndStderr("Loading query sequences...");
+        const std::vector<UniqueSequencePtr> queries = load(o.inputFileName);
+        logger.logAndStderr(std::to_string(queries.size()) + " unique query sequences loaded.");
+        logger.logAndStderr("Loading reference sequences...");
+        const std::vector<UniqueSequencePtr> references = load(database);
+        logger.logAndStderr(std::to_string(references.size()) + " unique reference sequences loaded.");
+        if (queries.empty() || references.empty()) throw FileFormatException("Error. No sequences to search.");
+        std::vector<UniqueSequencePtr> all(queries);
+        all.insert(all.end(), references.begin(), references.end());
+        const SequenceListSummary summary = summariseSequences(all), querySummary = summariseSequences(queries);
+        if (summary.maxLength > HMK_MAX_LEN)
+            throw HammockException("Error. The longest sequence has " + std::to_string(summary.maxLength) + " amino acids; the GPU kernels of hammock-hip "
+                                   "take sequences of up to " + std::to_string(HMK_MAX_LEN) + " (Hammock's domain is 7-20).");
+        if (!o.haveMaxShift) {
+            o.maxShift = checkMaxShift(summary, (int)javaRound(summary.meanLength() / 4));
+            logger.logAndStderr("Max shift not set. Setting automatically to: " + std::to_string(o.maxShift));
+        } else {
+            const int correct = checkMaxShift(summary, o.maxShift);
+            if (o.maxShift != correct) {
+                o.maxShift = correct;
+                logger.logAndStderr("Setting max shift to " + std::to_string(correct) +
+                                    " as the length of the shortest sequence is only " + std::to_string(correct + 1));
+            }
+        }
+        if (!o.haveThreshold) {
+            o.sequenceClusteringThreshold = (int)javaRound(querySummary.meanLength() * 1.7);
+            logger.logAndStderr("Search threshold not set. Setting automatically to: " + std::to_string(o.sequenceClusteringThreshold));
+        }
+        if (!havePenalty) logger.logAndStderr("Gap penalty not set. Setting automatically to: " + std::to_string(o.shiftPenalty));
+
+        const std::shared_ptr<NativeContext> nc = contextReady.get();
+        hmk_ctx *c = nc->get();
+        nc->setSequences(all, false);
+        const uint32_t nq = (uint32_t)queries.size(), n = (uint32_t)all.size();
+        logger.logAndStderr("Searching...");
+        const auto time0 = std::chrono::steady_clock::now();
+        // hits[q] = (score, reference index in load order)
+        std::vector<std::vector<std::pair<int, uint32_t>>> hits(nq);
+        hmk_neighbor_stats stats{};
+        if (best) {
+            std::vector<uint32_t> index((size_t)nq * best), count(nq);
+            std::vector<int32_t> score((size_t)nq * best);
+            const int st = hmk_search_best_shifted(c, 0, nq, nq, n, o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold, (uint32_t)best,
+                                                   index.data(), score.data(), count.data(), &stats);
+            if (st) nc->raise(st, nullptr);
+            for (uint32_t q = 0; q < nq; q++)
+                for (uint32_t t = 0; t < count[q]; t++) hits[q].push_back({score[(size_t)q * best + t], index[(size_t)q * best + t] - nq});
+        } else {
+            std::vector<uint64_t> edges(1 << 20);
+            uint64_t n_edges = 0;
+            int st = hmk_search_shifted(c, 0, nq, nq, n, o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold, edges.data(), edges.size(),
+                                        &n_edges, &stats);
+            if (st == HMK_ERR_CAPACITY) {
+                edges.resize(n_edges);
+                st = hmk_search_shifted(c, 0, nq, nq, n, o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold, edges.data(), edges.size(),
+                                        &n_edges, &stats);
+            }
+            if (st) nc->raise(st, nullptr);
+            for (uint64_t k = 0; k < n_edges; k++)
+                hits[HMK_EDGE_M(edges[k])].push_back({HMK_EDGE_SCORE(edges[k]), HMK_EDGE_X(edges[k]) - nq});
+            for (auto &h : hits)
+                std::sort(h.begin(), h.end(), [](const std::pair<int, uint32_t> &a, const std::pair<int, uint32_t> &b) {
+                    return a.first != b.first ? a.first > b.first : a.second < b.second;
+                });
+        }
+        // AligningScorerResult.getShift() of scoreWithShift(seq1 = query, seq2 = target), for the hits only
+        std::vector<uint32_t> pi, pj;
+        for (uint32_t q = 0; q < nq; q++)
+            for (auto &h : hits[q]) { pi.push_back(q); pj.push_back(nq + h.second); }
+        std::vector<int32_t> sc(pi.size()), shift(pi.size());
+        if (!pi.empty()) {
+            const int st = hmk_score_with_shift(c, pi.data(), pj.data(), pi.size(), o.maxShift, o.shiftPenalty, sc.data(), shift.data());
+            if (st) nc->raise(st, nullptr);
+        }
+        const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - time0).count();
+        logger.logAndStderr("Ready. Search time: " + std::to_string(ms));
+        logger.logAndStderr("Pairs scored: " + std::to_string(stats.pairs_scored) + ", hits reported: " + std::to_string(pi.size()) +
+                            ", GPU kernels: " + std::to_string(stats.kernel_ms) + " ms");
+        const std::string hitsFile = o.workingDirectory + "/search_hits.tsv";
+        {
+            std::ofstream out(hitsFile);
+            if (!out) throw HammockException("cannot write " + hitsFile);
+            out << "query\ttarget\tscore\tshift\n";
+            size_t k = 0;
+            for (uint32_t q = 0; q < nq; q++)
+                for (auto &h : hits[q]) {
+                    out << queries[q]->getSequenceString() << '\t' << references[h.second]->getSequenceString() << '\t' << h.first << '\t'
+                        << shift[k] << '\n';
+                    k++;
+                }
+        }
+        logger.logAndStderr("Search results in: " + hitsFile);
+        logger.logWithTime("Program successfully ended.");
+        return 0;
+    } catch (const CLIException &) {
+        throw;
+    } catch (const FileFormatException &e) {
+        logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
+        return 3;
+    } catch (const DataException &e) {
+        logger.logAndStderr("Error. Maybe wrong input file format or wrong set of labels? Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(std::string("cz.krejciadam.hammock.DataException: ") + e.what());
+        return 5;
+    } catch (const std::exception &e) {
+        logger.logAndStderr("Error. Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(e.what());
+        return 6;
+    }
+}
+
 // `hammock-hip io-selftest ...`: exposes the loaders / orderings to the CPU test-suite (no GPU involved)
 int ioSelftest(const std::vector<std::string> &args) {
     if (args.size() >= 3 && args[1] == "matrix") {
@@ -473,6 +645,7 @@ int main(int argc, char **argv) {
     try {
         if (args[0] == "greedy") return runSequenceClustering(args, false);
         if (args[0] == "clinkage") return runSequenceClustering(args, true);
+        if (args[0] == "search") return runSearch(args);
         if (args[0] == "io-selftest") return ioSelftest(args);
         if (args[0] == "dump-matrix") {   // the default matrix in the text format FileIOManager.loadScoringMatrix reads
             std::cout << "# BLOSUM62 substitution matrix (public NCBI table), 24 x 24, order " << AMINO_ACIDS << "\n"

@@ -184,6 +184,42 @@ int hmk_unpack_rows_dev(hmk_ctx *ctx, const void *d_row_start, const void *d_adj
 /* pairs / tiles of the plan the last hmk_neighbors_shifted[_dev] call used */
 int hmk_neighbors_last_plan(hmk_ctx *ctx, hmk_neighbor_stats *stats);
 
+/* ---- query-vs-reference search ---------------------------------------------- */
+
+/* Queries [q0, q1) against references [r0, r1) of the hmk_set_sequences set: the pairs (q, r) with
+ * score(q, r) >= threshold, where score(q, r) = ShiftedScorer(matrix, shift_penalty, max_shift).sequenceScore(seq1 = q,
+ * seq2 = r) (ShiftedScorer.java:48-100) -- the argument order ClinkageClusterScorer.clusterScore uses when a new sequence's
+ * cluster is scored against an existing one (ClinkageClusterScorer.java:36-38).  Upload queries and references together
+ * once (hmk_set_sequences), then search the two ranges; only the Q x R pairs are scored.
+ *   ranges     disjoint, within [0, n); HMK_ERR_BAD_ARG otherwise (checked before the device is: a host-only context
+ *              answers it).  An empty range: HMK_OK, 0 edges.
+ *   edges      packed as HMK_EDGE_*, ALWAYS m = query and x = reference, whatever the matrix's symmetry (unlike the
+ *              (min, max) edges of hmk_neighbors_shifted); order unspecified.  HMK_ERR_CAPACITY and *n_edges = the
+ *              number needed if `capacity` is too small.
+ *   checks     HMK_ERR_SHIFT_TOO_BIG when max_shift >= the shortest length within the two ranges (the check of
+ *              hmk_score_block_shifted; ShiftedScorer.java:59-62); the int16 score fit and threshold limits of
+ *              hmk_neighbors_shifted.
+ *   stats      pairs_scored = (q1 - q0)(r1 - r0), the class counters, n_tiles, kernel_ms.
+ * On a hmk_create_multi context the search runs on the root device. */
+int hmk_search_shifted(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1,
+                       int max_shift, int shift_penalty, int threshold,
+                       uint64_t *edges, uint64_t capacity, uint64_t *n_edges, hmk_neighbor_stats *stats);
+/* The same for LocalAlignmentScorer(matrix, gap_open, gap_extend).sequenceScore(seq1 = q = lines, seq2 = r = columns)
+ * (LocalAlignmentScorer.java:27-86): the striped kernels under hmk_neighbors_local's preconditions, the literal DP
+ * otherwise.  stats: n_edges, pairs_scored, n_tiles, kernel_ms. */
+int hmk_search_local(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1,
+                     int gap_open, int gap_extend, int threshold,
+                     uint64_t *edges, uint64_t capacity, uint64_t *n_edges, hmk_neighbor_stats *stats);
+/* The best k (1 <= k <= 32) references of every query among those with score(q, r) >= threshold (scores as in
+ * hmk_search_shifted), by score descending, then reference index ascending, selected on the device (the edge list never
+ * travels to the host): hit_index[(q - q0) * k + t], hit_score[(q - q0) * k + t], n_hits[q - q0] = how many are valid;
+ * unused slots hold UINT32_MAX / INT32_MIN.  Never HMK_ERR_CAPACITY (the call grows its own scratch).  stats->kernel_ms
+ * includes the selection; stats->n_edges = all hits above the threshold. */
+int hmk_search_best_shifted(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1,
+                            int max_shift, int shift_penalty, int threshold, uint32_t k,
+                            uint32_t *hit_index, int32_t *hit_score, uint32_t *n_hits,
+                            hmk_neighbor_stats *stats);
+
 /* ---- greedy clustering -------------------------------------------------- */
 
 typedef struct {
