@@ -29,6 +29,7 @@ SYMBOLS = [
     "hmk_score_pairs_shifted", "hmk_score_with_shift", "hmk_score_pairs_local", "hmk_score_block_shifted", "hmk_score_block_local",
     "hmk_neighbors_shifted", "hmk_neighbors_local", "hmk_neighbors_shifted_dev", "hmk_compact_edges_dev", "hmk_pack_rows_dev", "hmk_unpack_rows_dev",
     "hmk_neighbors_last_plan", "hmk_search_shifted", "hmk_search_local", "hmk_search_best_shifted",
+    "hmk_assign_shifted", "hmk_assign_local",
     "hmk_greedy_cluster", "hmk_greedy_from_edges", "hmk_greedy_from_edges_dev", "hmk_greedy_last_phases",
     "hmk_clinkage_cluster", "hmk_clinkage_from_edges", "hmk_set_java_hashset", "hmk_reserve",
 ]
@@ -109,6 +110,10 @@ def _load():
     L.hmk_search_shifted.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, p_u64, u64, p_u64, C.POINTER(NeighborStats)]
     L.hmk_search_local.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, p_u64, u64, p_u64, C.POINTER(NeighborStats)]
     L.hmk_search_best_shifted.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, u32, p_u32, p_i32, p_u32, C.POINTER(NeighborStats)]
+    L.hmk_assign_shifted.argtypes = [vp, u32, u32, u32, u32, p_u32, p_i32, u32, i32, i32, i32, u32, p_u32, p_i32, p_u32,
+                                     C.POINTER(NeighborStats)]
+    L.hmk_assign_local.argtypes = [vp, u32, u32, u32, u32, p_u32, p_i32, u32, i32, i32, i32, u32, p_u32, p_i32, p_u32,
+                                   C.POINTER(NeighborStats)]
     L.hmk_greedy_cluster.argtypes = [vp, i32, i32, i32, i32, p_i32, p_i32, p_i32, C.POINTER(GreedyStats)]
     L.hmk_greedy_from_edges_dev.argtypes = [vp, vp, u64, i32, i32, p_i32, p_i32, p_i32, C.POINTER(GreedyStats)]
     L.hmk_greedy_from_edges.argtypes = [vp, p_u64, u64, i32, i32, i32, p_i32, p_i32, p_i32, C.POINTER(GreedyStats)]

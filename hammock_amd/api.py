@@ -289,6 +289,47 @@ class Context:
         out[idx == np.uint32(0xFFFFFFFF)] = -1
         return out, score
 
+    # -- assignment of new sequences to existing clusters ----------------------------------
+    # Upload members and new sequences together once -- set_sequences(members + new, sizes=...) -- and classify every new
+    # sequence against the frozen clusters (NearestClusterRunner / findNearestClusterParallel, ClinkageSequenceClusterer.java
+    # :137-177, 243-294): score(m, x) = sequenceScore(seq1 = member, seq2 = new), the opposite of the search's orientation.
+    # New sequences never see each other: two of them given the same cluster are not checked against each other.
+    def _assign(self, fn, q0, q1, r0, r1, member_cluster, cluster_id, a, b, threshold, k):
+        nq = max(int(q1) - int(q0), 0)
+        mc = np.ascontiguousarray(np.asarray(member_cluster, dtype=np.int64).ravel())
+        cid = np.ascontiguousarray(np.asarray(cluster_id, dtype=np.int64).ravel())
+        if mc.size != max(int(r1) - int(r0), 0):
+            raise ValueError(f"member_cluster has {mc.size} entries for the {int(r1) - int(r0)} members [r0, r1)")
+        if (mc < 0).any() or (mc > 0xFFFFFFFF).any():
+            raise ValueError("member_cluster holds values outside uint32")
+        if (cid < -2 ** 31).any() or (cid >= 2 ** 31).any():
+            raise ValueError("cluster_id holds values outside int32")
+        mc = mc.astype(np.uint32)
+        cid = cid.astype(np.int32)
+        kk = max(int(k), 1)
+        best = np.empty((nq, kk), dtype=np.uint32)
+        score = np.empty((nq, kk), dtype=np.int32)
+        nf = np.empty(max(nq, 1), dtype=np.uint32)
+        stats = N.NeighborStats()
+        st = fn(self._h, int(q0), int(q1), int(r0), int(r1), _ptr(mc, C.c_uint32), _ptr(cid, C.c_int32), int(cid.size), int(a), int(b),
+                int(threshold), int(k), _ptr(best, C.c_uint32), _ptr(score, C.c_int32), _ptr(nf, C.c_uint32), C.byref(stats))
+        if st:
+            self._raise(st)
+        self.last_assign_stats = stats
+        return best, score, nf[:nq].copy()
+
+    def assign_shifted(self, q0, q1, r0, r1, member_cluster, cluster_id, max_shift, shift_penalty, threshold, k=1):
+        """New sequences [q0, q1) against the clusters of the members [r0, r1) (member r in slot member_cluster[r - r0],
+        slot c with Java id cluster_id[c]), ShiftedScorer, complete linkage -> (best_cluster uint32[nq, k] = slots,
+        best_score int32[nq, k], n_feasible uint32[nq]).  Feasible clusters rank by score descending, size() descending,
+        cluster_id ascending; unused slots hold 0xFFFFFFFF / INT32_MIN; n_feasible counts all feasible clusters (0 =
+        unassigned).  kernel_ms of last_assign_stats includes the aggregation and selection."""
+        return self._assign(N.lib.hmk_assign_shifted, q0, q1, r0, r1, member_cluster, cluster_id, max_shift, shift_penalty, threshold, k)
+
+    def assign_local(self, q0, q1, r0, r1, member_cluster, cluster_id, gap_open, gap_extend, threshold, k=1):
+        """The same with LocalAlignmentScorer(seq1 = member, seq2 = new)."""
+        return self._assign(N.lib.hmk_assign_local, q0, q1, r0, r1, member_cluster, cluster_id, gap_open, gap_extend, threshold, k)
+
     def neighbors_shifted_dev(self, max_shift, shift_penalty, threshold, part, n_parts, d_edges_ptr, capacity,
                               d_counts_ptr, stream=0):
         st = N.lib.hmk_neighbors_shifted_dev(self._h, int(max_shift), int(shift_penalty), int(threshold), part, n_parts,

@@ -51,6 +51,8 @@ enum {
     SB_REPL,                                        // ... (in a peer's context, on the ROOT's device) the peer's piece copied to the root: no peer access, or HMK_MULTI_REPLICATE
     SB_SEARCH_OUT, SB_SEARCH_CNT, SB_SEARCH_START, SB_SEARCH_SCAN, SB_SEARCH_HITS,   // query-vs-reference search (hmk_search.cpp): edges / keys,
                                                                                      // per-query counts + cursors, run starts, scan scratch, best-k
+                                                                                     // (the assignment, hmk_assign.cpp, uses them too)
+    SB_ASSIGN_CL,                                   // the assignment's clusters: member -> rank, members per rank, slot of each rank
     SB_N
 };
 
@@ -147,6 +149,8 @@ struct hmk_ctx {
     PlanLocal plan_local;
     Plan plan_search;              // the query-vs-reference searches' plans: cached apart from the all-vs-all ones, so that
     PlanLocal plan_local_search;   // searches and clustering calls on one context do not rebuild each other's
+    Plan plan_assign;              // the assignments' plans (hmk_assign.cpp: members = the search's queries): cached apart too
+    PlanLocal plan_local_assign;
     uint64_t *d_edges = nullptr;  // internal buffer of the host-buffer entry points
     uint64_t d_edges_cap = 0;
     unsigned long long *d_counts = nullptr;
@@ -293,6 +297,11 @@ int build_plan_local(hmk_ctx *ctx, uint32_t part, uint32_t n_parts);
 // the rectangle queries [q0, q1) x references [r0, r1) (disjoint, non-empty): ctx->plan_search / ctx->plan_local_search
 int build_plan_search(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
 int build_plan_local_search(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
+// ... into the plan slot `pl` (the assignment's own, hmk_assign.cpp)
+int build_plan_search(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
+int build_plan_local_search(hmk_ctx *ctx, PlanLocal &pl, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
+// the search's parameter checks of a shifted rectangle (the shift against both ranges, threshold and int16 limits)
+int check_shifted(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
 // ---- hmk_pass.cpp
 int neighbors_dev_locked(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_parts, void *d_edges,
                          uint64_t capacity, void *d_counts, hipStream_t stream, int which = LAUNCH_ALL,

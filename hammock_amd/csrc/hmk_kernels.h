@@ -150,6 +150,17 @@ hipError_t launch_search_best(const uint64_t *edges, uint64_t cap_per_shard, con
                               uint32_t q0, uint32_t nq, uint32_t k, uint32_t *cnt_cursor, uint32_t *start, uint64_t *scan_scratch, uint64_t *keys, uint64_t keys_capacity,
                               uint32_t *hit_index, int32_t *hit_score, uint32_t *n_hits, hipStream_t s);
 
+// assignment of new sequences to existing clusters (k_assign.hip).  The segments of a pass over the new sequences [q0, q0 + nq) and
+// the members [r0, r0 + nm) (disjoint), `total` edges in all: per new sequence its clusters' hits and minimum score, the clusters
+// whose hits equal their member count (feasible), the best k of them by (score, size, ~id) -- the ranks of the host's order.
+// member_rank[m - r0]: the rank of member m's cluster; members_of_rank / slot_of_rank[rank]: its member count / the caller's slot.
+// Outputs best_cluster / best_score [nq * k] (unused slots 0xFFFFFFFF / INT32_MIN), n_feasible[nq].  scratch: uint32[3 nq + 1],
+// start: uint32[nq + 1], scan_scratch: scan_scratch_bytes(nq), rec: uint64[total]
+hipError_t launch_assign(const uint64_t *edges, uint64_t cap_per_shard, const unsigned long long *counts, uint64_t max_count, uint64_t total,
+                         uint32_t q0, uint32_t nq, uint32_t r0, uint32_t nm, uint32_t k, const uint32_t *member_rank, const uint32_t *members_of_rank,
+                         const uint32_t *slot_of_rank, uint32_t *scratch, uint32_t *start, uint64_t *scan_scratch, uint64_t *rec,
+                         uint64_t rec_capacity, uint32_t *best_cluster, int32_t *best_score, uint32_t *n_feasible, hipStream_t s);
+
 // force the deferred load of the code objects a clustering call launches from (hmk_create)
 hipError_t warm_neighbors_module();
 hipError_t warm_edges_module();

@@ -46,7 +46,10 @@ bool is_identity_from(const std::vector<uint32_t> &perm) {
 // No score-bound refinement (hmk_plan.cpp's `refine`): a class whose 8-bit lanes do not fit every pair runs on 16-bit lanes.
 // No key sort.
 int build_plan_search(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1) {
-    Plan &pl = ctx->plan_search;
+    return build_plan_search(ctx, ctx->plan_search, X, p, thr, q0, q1, r0, r1);
+}
+
+int build_plan_search(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1) {
     if (pl.valid && pl.X == X && pl.p == p && pl.thr == thr && pl.q0 == q0 && pl.q1 == q1 && pl.r0 == r0 && pl.r1 == r1 &&
         pl.no_rows_kernel == ctx->sw.no_rows_kernel)
         return HMK_OK;
@@ -185,7 +188,10 @@ int build_plan_search(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t
 // The rectangle of a LocalAlignmentScorer search: rows = queries (seq1, lines), columns = references (seq2), one class per
 // (query length, reference length); the tiles' edges come out m = row = query (row_is_m, k_local.hip).
 int build_plan_local_search(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1) {
-    PlanLocal &pl = ctx->plan_local_search;
+    return build_plan_local_search(ctx, ctx->plan_local_search, q0, q1, r0, r1);
+}
+
+int build_plan_local_search(hmk_ctx *ctx, PlanLocal &pl, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1) {
     if (pl.valid && pl.q0 == q0 && pl.q1 == q1 && pl.r0 == r0 && pl.r1 == r1) return HMK_OK;
     free_plan_local(pl);
     const uint32_t N = (q1 - q0) + (r1 - r0);
@@ -242,18 +248,6 @@ int build_plan_local_search(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0,
     return HMK_OK;
 }
 
-namespace {
-
-enum { SEARCH_SHIFTED = 0, SEARCH_LOCAL = 1 };
-
-// the argument checks every search makes before it looks at the device (a host-only context answers them too)
-int check_ranges(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1) {
-    if (q0 > q1 || r0 > r1 || q1 > ctx->n || r1 > ctx->n)
-        return fail(ctx, HMK_ERR_BAD_ARG, "search ranges must lie within [0, n) with q0 <= q1 and r0 <= r1 (n = " + std::to_string(ctx->n) + ")");
-    if (q0 < q1 && r0 < r1 && q0 < r1 && r0 < q1) return fail(ctx, HMK_ERR_BAD_ARG, "the query and reference ranges overlap");
-    return HMK_OK;
-}
-
 // what the shifted search checks on its parameters (the all-vs-all pass's checks, build_plan; the shift against the two ranges'
 // shortest sequence, as hmk_score_block_shifted does)
 int check_shifted(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1) {
@@ -270,6 +264,18 @@ int check_shifted(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t q1,
     if (top > 32767)
         return fail(ctx, HMK_ERR_BAD_ARG, "scores up to " + std::to_string(top) + " are possible with this matrix / shift penalty: "
                                            "they do not fit the int16 score of a packed edge");
+    return HMK_OK;
+}
+
+namespace {
+
+enum { SEARCH_SHIFTED = 0, SEARCH_LOCAL = 1 };
+
+// the argument checks every search makes before it looks at the device (a host-only context answers them too)
+int check_ranges(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1) {
+    if (q0 > q1 || r0 > r1 || q1 > ctx->n || r1 > ctx->n)
+        return fail(ctx, HMK_ERR_BAD_ARG, "search ranges must lie within [0, n) with q0 <= q1 and r0 <= r1 (n = " + std::to_string(ctx->n) + ")");
+    if (q0 < q1 && r0 < r1 && q0 < r1 && r0 < q1) return fail(ctx, HMK_ERR_BAD_ARG, "the query and reference ranges overlap");
     return HMK_OK;
 }
 

@@ -1313,6 +1313,60 @@ inline void saveInputStatistics(const std::vector<UniqueSequencePtr> &sequences,
     for (size_t k = 0; k < L; k++) w << CSV_SEPARATOR << all[L + k];
 }
 
+// FileIOManager.loadClustersFromCsv / loadClusterDetailsFromCsv without alignments (FileIOManager.java:300-365): a cluster file
+// (initial_clusters_sequences.tsv and its kin) back into clusters.  The header's `alignment` and then `sum` columns are dropped;
+// the columns after cluster_id and sequence are labels, and each line's counts make its UniqueSequence (lineToUniqueSequence,
+// :246-255; size() = the sum of the counts).  Every line is a sequence of its own, duplicates included.  The ids go through
+// Integer.decode: an `NA` id (a sequence outside every cluster) is a format error, as a malformed line is.  Clusters come in the
+// order of their first line (the reference's come in HashMap order; nothing here depends on it).
+inline std::vector<ClusterPtr> loadClustersFromCsv(const std::string &fileName) {
+    auto wrong = [&](const std::string &why) {
+        return FileFormatException("Error in cluster file: " + fileName + " - wrong format. Original message: " + why);
+    };
+    auto decode = [&](const std::string &text) {
+        try { return javaIntegerDecode(text); } catch (const HammockException &e) { throw wrong(e.what()); }
+    };
+    const std::vector<std::string> lines = readLines(fileName);
+    if (lines.empty()) throw wrong("java.lang.NullPointerException (no header line)");
+    std::vector<std::string> header = splitChar(lines[0], CSV_SEPARATOR, true);
+    const auto alignmentAt = std::find(header.begin(), header.end(), "alignment");
+    const long alignmentIndex = alignmentAt == header.end() ? -1 : (long)(alignmentAt - header.begin());
+    if (alignmentIndex != -1) header.erase(header.begin() + alignmentIndex);
+    const auto sumAt = std::find(header.begin(), header.end(), "sum");
+    const long sumIndex = sumAt == header.end() ? -1 : (long)(sumAt - header.begin());
+    if (sumIndex != -1) header.erase(header.begin() + sumIndex);
+    if (header.size() < 2) throw wrong("java.lang.IndexOutOfBoundsException (the header has no cluster_id and sequence columns)");
+    const std::vector<std::string> labels(header.begin() + 2, header.end());
+    std::vector<int> ids;
+    std::unordered_map<int, std::vector<UniqueSequencePtr>> members;
+    for (size_t k = 1; k < lines.size(); k++) {
+        std::vector<std::string> f = splitChar(lines[k], CSV_SEPARATOR, true);
+        const int id = decode(f[0]);
+        if (alignmentIndex != -1) {
+            if ((long)f.size() <= alignmentIndex) throw wrong("java.lang.IndexOutOfBoundsException (line " + std::to_string(k + 1) + ")");
+            f.erase(f.begin() + alignmentIndex);
+        }
+        if (sumIndex != -1) {
+            if ((long)f.size() <= sumIndex) throw wrong("java.lang.IndexOutOfBoundsException (line " + std::to_string(k + 1) + ")");
+            f.erase(f.begin() + sumIndex);
+        }
+        if (f.size() < 2) throw wrong("java.lang.IndexOutOfBoundsException (line " + std::to_string(k + 1) + ")");
+        std::vector<std::pair<std::string, int>> lm;
+        for (size_t i = 2; i < f.size(); i++) {
+            const int value = decode(f[i]);
+            if (value == 0) continue;
+            if (i - 2 >= labels.size()) throw wrong("java.lang.IndexOutOfBoundsException (more columns than labels, line " + std::to_string(k + 1) + ")");
+            lm.push_back({labels[i - 2], value});
+        }
+        auto it = members.find(id);
+        if (it == members.end()) { ids.push_back(id); it = members.emplace(id, std::vector<UniqueSequencePtr>{}).first; }
+        it->second.push_back(std::make_shared<UniqueSequence>(f[1], lm));
+    }
+    std::vector<ClusterPtr> result;
+    for (int id : ids) result.push_back(std::make_shared<Cluster>(members[id], id));
+    return result;
+}
+
 }  // namespace FileIOManager
 }  // namespace hammock
 

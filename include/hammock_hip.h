@@ -220,6 +220,46 @@ int hmk_search_best_shifted(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0,
                             uint32_t *hit_index, int32_t *hit_score, uint32_t *n_hits,
                             hmk_neighbor_stats *stats);
 
+/* ---- assignment of new sequences to existing clusters ----------------------------- */
+
+/* Which existing cluster does each new sequence join?  The decision of NearestClusterRunner /
+ * findNearestClusterParallel (ClinkageSequenceClusterer.java:137-177, 243-294) with ClinkageClusterScorer
+ * (ClinkageClusterScorer.java:30-49), accepted when getScore() >= threshold (LimitedGreedySequenceClusterer.java:59-66),
+ * for every new sequence at once.  One uploaded set (hmk_set_sequences) holds both sides:
+ *   members    [r0, r1): member r belongs to cluster slot member_cluster[r - r0] in [0, n_clusters); slot c carries the
+ *              Java id cluster_id[c] (distinct).  Cluster.size() of slot c is the sum of its members' `sizes` as
+ *              uploaded (Cluster.java:156-158; 1 each when sizes was NULL) -- the library sums them.
+ *   new        [q0, q1), disjoint from the members.
+ * score(m, x) = ShiftedScorer(matrix, shift_penalty, max_shift).sequenceScore(seq1 = member m, seq2 = new x): the call
+ * ClinkageSequenceClusterer.java:263 makes (scorer.clusterScore(existing cluster, new sequence's cluster)) -- the
+ * OPPOSITE orientation of hmk_search_* (seq1 = query).  Cluster c is feasible for x iff every member m of c has
+ * score(m, x) >= threshold; its complete-linkage score is then min over m of score(m, x) (ClinkageClusterScorer's value;
+ * its early exit only matters for infeasible clusters).  Feasible clusters rank by score descending, then size()
+ * descending, then cluster_id ascending; rank 1 is the cluster findNearestClusterParallel returns.
+ * The clusters are frozen: every new sequence is classified on its own, a new sequence never sees another new one, and
+ * two new sequences given the same cluster are not checked against each other (classification, not clustering).
+ *   outputs    best_cluster[(x - q0) * k + t] = the slot of rank t + 1, best_score[...] its complete-linkage score;
+ *              unused slots UINT32_MAX / INT32_MIN.  n_feasible[x - q0] = ALL feasible clusters (not capped at k); 0 =
+ *              unassigned.  Selected on the device (the edge list never travels to the host).
+ *   checks     HMK_ERR_BAD_ARG (before the device is looked at: a host-only context answers them): ranges overlapping or
+ *              outside [0, n); k outside 1..32; a member_cluster value >= n_clusters; a slot without a member; two equal
+ *              cluster_ids.  Then the checks of hmk_search_shifted (the shift against both ranges, the threshold and
+ *              int16 limits).  Never HMK_ERR_CAPACITY (the call grows its own scratch).
+ *   stats      as hmk_search_shifted's; kernel_ms includes the aggregation and selection.
+ * On a hmk_create_multi context the assignment runs on the root device. */
+int hmk_assign_shifted(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1,
+                       const uint32_t *member_cluster, const int32_t *cluster_id, uint32_t n_clusters,
+                       int max_shift, int shift_penalty, int threshold, uint32_t k,
+                       uint32_t *best_cluster, int32_t *best_score, uint32_t *n_feasible,
+                       hmk_neighbor_stats *stats);
+/* The same with LocalAlignmentScorer(matrix, gap_open, gap_extend).sequenceScore(seq1 = member = lines, seq2 = new =
+ * columns) (LocalAlignmentScorer.java:27-86), under the preconditions of hmk_search_local. */
+int hmk_assign_local(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1,
+                     const uint32_t *member_cluster, const int32_t *cluster_id, uint32_t n_clusters,
+                     int gap_open, int gap_extend, int threshold, uint32_t k,
+                     uint32_t *best_cluster, int32_t *best_score, uint32_t *n_feasible,
+                     hmk_neighbor_stats *stats);
+
 /* ---- greedy clustering -------------------------------------------------- */
 
 typedef struct {
