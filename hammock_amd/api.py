@@ -330,6 +330,36 @@ class Context:
         """The same with LocalAlignmentScorer(seq1 = member, seq2 = new)."""
         return self._assign(N.lib.hmk_assign_local, q0, q1, r0, r1, member_cluster, cluster_id, gap_open, gap_extend, threshold, k)
 
+    # -- continuing a greedy clustering with new sequences --------------------------------------
+    # Upload members and new sequences together once -- set_sequences(members + new, sizes=...) -- and run the greedy's second loop
+    # (LimitedGreedySequenceClusterer.java:59-67) over the new sequences in index order, seeded with the given clusters: a new
+    # sequence that joins a cluster is a member for every later one.  New sequences never seed clusters (phase 1 does not run).
+    def greedy_continue(self, q0, q1, r0, r1, member_cluster, cluster_id, max_shift, shift_penalty, threshold):
+        """New sequences [q0, q1) into the clusters of the members [r0, r1) (member r in slot member_cluster[r - r0], slot c
+        with Java id cluster_id[c]), ShiftedScorer, complete linkage, symmetric matrices only -> (joined int32[nq] = the slot or
+        -1, member_rank int32[nq] = the position in Cluster.getSequences() or -1).  Statistics: last_continue_stats."""
+        nq = max(int(q1) - int(q0), 0)
+        mc = np.ascontiguousarray(np.asarray(member_cluster, dtype=np.int64).ravel())
+        cid = np.ascontiguousarray(np.asarray(cluster_id, dtype=np.int64).ravel())
+        if mc.size != max(int(r1) - int(r0), 0):
+            raise ValueError(f"member_cluster has {mc.size} entries for the {int(r1) - int(r0)} members [r0, r1)")
+        if (mc < 0).any() or (mc > 0xFFFFFFFF).any():
+            raise ValueError("member_cluster holds values outside uint32")
+        if (cid < -2 ** 31).any() or (cid >= 2 ** 31).any():
+            raise ValueError("cluster_id holds values outside int32")
+        mc = mc.astype(np.uint32)
+        cid = cid.astype(np.int32)
+        joined = np.empty(max(nq, 1), dtype=np.int32)
+        rank = np.empty(max(nq, 1), dtype=np.int32)
+        stats = N.ContinueStats()
+        st = N.lib.hmk_greedy_continue(self._h, int(q0), int(q1), int(r0), int(r1), _ptr(mc, C.c_uint32), _ptr(cid, C.c_int32),
+                                       int(cid.size), int(max_shift), int(shift_penalty), int(threshold), _ptr(joined, C.c_int32),
+                                       _ptr(rank, C.c_int32), C.byref(stats))
+        if st:
+            self._raise(st)
+        self.last_continue_stats = stats
+        return joined[:nq].copy(), rank[:nq].copy()
+
     def neighbors_shifted_dev(self, max_shift, shift_penalty, threshold, part, n_parts, d_edges_ptr, capacity,
                               d_counts_ptr, stream=0):
         st = N.lib.hmk_neighbors_shifted_dev(self._h, int(max_shift), int(shift_penalty), int(threshold), part, n_parts,

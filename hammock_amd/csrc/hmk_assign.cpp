@@ -17,18 +17,20 @@ struct ClusterOrder {
     std::vector<uint32_t> rank_of, slot_of_rank, members_of_rank;
 };
 
-// the argument checks before the device is looked at (a host-only context answers them too); fills `order`
-int check_assign(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, const uint32_t *member_cluster, const int32_t *cluster_id,
-                 uint32_t n_clusters, uint32_t k, ClusterOrder *order) {
-    if (k < 1 || k > 32) return fail(ctx, HMK_ERR_BAD_ARG, "k must be 1..32");
+}  // namespace
+
+// the checks of the clusters' description that the assignment and hmk_greedy_continue (hmk_continue.cpp) make before the device is
+// looked at (a host-only context answers them too): members[c] = slot c's members, size[c] = its Cluster.size()
+int check_clusters(hmk_ctx *ctx, const char *what, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, const uint32_t *member_cluster,
+                   const int32_t *cluster_id, uint32_t n_clusters, std::vector<uint32_t> &members, std::vector<int64_t> &size) {
     if (q0 > q1 || r0 > r1 || q1 > ctx->n || r1 > ctx->n)
-        return fail(ctx, HMK_ERR_BAD_ARG, "assignment ranges must lie within [0, n) with q0 <= q1 and r0 <= r1 (n = " + std::to_string(ctx->n) + ")");
+        return fail(ctx, HMK_ERR_BAD_ARG, std::string(what) + " ranges must lie within [0, n) with q0 <= q1 and r0 <= r1 (n = " + std::to_string(ctx->n) + ")");
     if (q0 < q1 && r0 < r1 && q0 < r1 && r0 < q1) return fail(ctx, HMK_ERR_BAD_ARG, "the new-sequence and member ranges overlap");
     const uint32_t nm = r1 - r0;
     if (nm && !member_cluster) return fail(ctx, HMK_ERR_BAD_ARG, "null member_cluster");
     if (n_clusters && !cluster_id) return fail(ctx, HMK_ERR_BAD_ARG, "null cluster_id");
-    std::vector<uint32_t> members(n_clusters, 0);
-    std::vector<int64_t> size(n_clusters, 0);
+    members.assign(n_clusters, 0);
+    size.assign(n_clusters, 0);
     for (uint32_t i = 0; i < nm; i++) {
         const uint32_t c = member_cluster[i];
         if (c >= n_clusters)
@@ -45,6 +47,19 @@ int check_assign(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r
         for (uint32_t c = 1; c < n_clusters; c++)
             if (ids[c] == ids[c - 1]) return fail(ctx, HMK_ERR_BAD_ARG, "cluster_id " + std::to_string(ids[c]) + " is given to two slots");
     }
+    return HMK_OK;
+}
+
+namespace {
+
+// the argument checks before the device is looked at (a host-only context answers them too); fills `order`
+int check_assign(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, const uint32_t *member_cluster, const int32_t *cluster_id,
+                 uint32_t n_clusters, uint32_t k, ClusterOrder *order) {
+    if (k < 1 || k > 32) return fail(ctx, HMK_ERR_BAD_ARG, "k must be 1..32");
+    std::vector<uint32_t> members;
+    std::vector<int64_t> size;
+    const int st = check_clusters(ctx, "assignment", q0, q1, r0, r1, member_cluster, cluster_id, n_clusters, members, size);
+    if (st) return st;
     order->slot_of_rank.resize(n_clusters);
     for (uint32_t c = 0; c < n_clusters; c++) order->slot_of_rank[c] = c;
     std::sort(order->slot_of_rank.begin(), order->slot_of_rank.end(), [&](uint32_t a, uint32_t b) {

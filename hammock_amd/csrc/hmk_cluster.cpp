@@ -99,6 +99,170 @@ int piece_precheck(hmk_ctx *c, const PreIn &in, uint32_t r0, uint32_t r1, uint32
     return fits ? 0 : 1;
 }
 
+// The device-side second loop (k_loop_*) on stream S over the pre-check's candidate lists (SB_CAND / SB_CSTART / SB_CNT, either
+// layout) and the uploaded SB_LEFT; what hmk_greedy_cluster's device_loop hook and hmk_greedy_continue (hmk_continue.cpp) run.
+bool device_second_loop(hmk_ctx *ctx, hipStream_t S, const LoopIn &in, std::vector<int32_t> &join_slot, uint32_t *rounds_out,
+                        std::string *stall_err) {
+    auto ms_since = [&](std::chrono::steady_clock::time_point a) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
+    };
+    const Switches &sw = ctx->sw;
+    const uint32_t n = in.n, nl = in.nl, ncl = in.ncl, pre_total_c = in.cand_total;
+    const bool packed = in.packed;
+    const size_t esz = packed ? sizeof(NbrPacked) : sizeof(Nbr);
+    const std::vector<EdgeSource::Piece> &pieces = *in.pieces;
+    const bool multi = pieces.size() > 1;
+    const std::vector<int64_t> &csize = *in.csize;
+    const std::vector<int32_t> &cids = *in.cids;
+    hipError_t r = ensure_buf(ctx, SB_JOINED, std::max<size_t>(ncl, 1) * 16);   // {joined, id, size} per cluster
+    if (r == hipSuccess) r = ensure_buf(ctx, SB_SUBSTART, ((size_t)ncl + 1) * 4);
+    if (r == hipSuccess) r = ensure_buf(ctx, SB_SUBS, std::max<size_t>(pre_total_c, 1) * 8);
+    if (r == hipSuccess) r = ensure_buf(ctx, SB_SUBS2, std::max<size_t>(pre_total_c, 1) * 8);   // merge scratch of the subscriber sort
+    if (r == hipSuccess) r = ensure_buf(ctx, SB_SCAN2, scan_scratch_bytes(std::max<uint32_t>({nl, n, ncl})));
+    if (r == hipSuccess) r = ensure_buf(ctx, SB_CSIZE, std::max<size_t>(ncl, 1) * 8);
+    if (r == hipSuccess) r = ensure_buf(ctx, SB_CID, std::max<size_t>(ncl, 1) * 4);
+    if (r == hipSuccess) r = ensure_buf(ctx, SB_FIRST, std::max<size_t>(ncl, 1) * 12);   // first[], taken[], list cursor[] per cluster
+    if (r == hipSuccess) r = ensure_buf(ctx, SB_STATUS, std::max<size_t>(nl, 1));
+    if (r == hipSuccess) r = ensure_buf(ctx, SB_ACTIVE, std::max<size_t>(nl, 1) * 8);   // two eval lists
+    if (r == hipSuccess) r = ensure_buf(ctx, SB_DIRTY, std::max<size_t>(nl, 1) * 4);
+    if (r == hipSuccess) r = ensure_buf(ctx, SB_CHOICE, std::max<size_t>(nl, 1) * 4);
+    if (r == hipSuccess) r = ensure_buf(ctx, SB_ACCEPTED, std::max<size_t>(nl, 1) * 4);
+    // which cluster a leftover joins: the kernels STORE it into the host's pinned block (a handful of writes per round; nothing on the
+    // device reads it) -- no copy and no second synchronise when the loop is over
+    int32_t *d_jslot = nullptr;
+    if (r == hipSuccess) r = ensure_pinned(&ctx->h_stage, &ctx->h_stage_cap, (size_t)std::max<size_t>(nl, 1) * 4 + 64, 0);
+    if (r == hipSuccess) r = hipHostGetDevicePointer((void **)&d_jslot, ctx->h_stage, 0);
+    if (r == hipSuccess) r = ensure_buf(ctx, SB_LCOUNT, 64);
+    if (r == hipSuccess && ctx->has_sizes) r = ensure_buf(ctx, SB_SEQSZ, (size_t)n * 4);
+    if (r != hipSuccess) return false;
+    // subscriber lists (count into FIRST as scratch, scan, fill, sort by leftover)
+    r = hipMemsetAsync(buf<void>(ctx, SB_FIRST), 0, (size_t)ncl * 4, S);
+    if (r == hipSuccess) r = launch_loop_subscribers(false, nl, buf<uint32_t>(ctx, SB_CSTART), buf<uint32_t>(ctx, SB_CNT), buf<GreedyCand>(ctx, SB_CAND),
+                                                     buf<uint32_t>(ctx, SB_FIRST), nullptr, nullptr, S);
+    if (r == hipSuccess) r = launch_scan_u32(buf<uint32_t>(ctx, SB_FIRST), buf<uint32_t>(ctx, SB_SUBSTART), ncl, buf<uint64_t>(ctx, SB_SCAN2), S);
+    if (r == hipSuccess) r = hipMemsetAsync(buf<void>(ctx, SB_FIRST), 0, (size_t)ncl * 4, S);
+    if (r == hipSuccess) r = launch_loop_subscribers(true, nl, buf<uint32_t>(ctx, SB_CSTART), buf<uint32_t>(ctx, SB_CNT), buf<GreedyCand>(ctx, SB_CAND),
+                                                     buf<uint32_t>(ctx, SB_FIRST), buf<uint32_t>(ctx, SB_SUBSTART), buf<uint64_t>(ctx, SB_SUBS), S);
+    if (r == hipSuccess) r = launch_loop_sort_subscribers(ncl, buf<uint32_t>(ctx, SB_SUBSTART), buf<uint64_t>(ctx, SB_SUBS), buf<uint64_t>(ctx, SB_SUBS2), S);
+    uint32_t *d_first = buf<uint32_t>(ctx, SB_FIRST), *d_taken = d_first + ncl, *d_clcursor = d_first + 2 * (size_t)ncl;
+    // (taken[], the statuses, the join slots and the counters are set by k_loop_init)
+    if (r == hipSuccess) r = hipMemcpyAsync(buf<void>(ctx, SB_CSIZE), csize.data(), (size_t)ncl * 8, hipMemcpyHostToDevice, S);
+    if (r == hipSuccess) r = hipMemcpyAsync(buf<void>(ctx, SB_CID), cids.data(), (size_t)ncl * 4, hipMemcpyHostToDevice, S);
+    if (r == hipSuccess) r = launch_loop_init(ncl, buf<long long>(ctx, SB_CSIZE), buf<int32_t>(ctx, SB_CID), buf<void>(ctx, SB_JOINED),
+                                              buf<uint32_t>(ctx, SB_SUBSTART), d_clcursor, nl, buf<uint32_t>(ctx, SB_ACTIVE),
+                                              buf<uint32_t>(ctx, SB_DIRTY), buf<uint32_t>(ctx, SB_LCOUNT), d_taken,
+                                              buf<uint8_t>(ctx, SB_STATUS), d_jslot, S);
+    if (r == hipSuccess && ctx->has_sizes)
+        r = hipMemcpyAsync(buf<void>(ctx, SB_SEQSZ), ctx->sizes.data(), (size_t)n * 4, hipMemcpyHostToDevice, S);
+    uint32_t rounds = 0;
+    bool done = false;
+    // a second first/accept pass per round saves a third of the rounds; it pays once a round's apply and eval are big enough
+    // first/accept passes per round: an accepted leftover stops blocking the other clusters it lists, so a second pass lets more joins into
+    // the round -- fewer, longer rounds.  Measured (loop ms, generator / default order): 10,000 clusters 3.46 / 4.58 with two passes, 3.66 / 4.72
+    // with three; 15,000: 6.93 / 9.59 against 7.04 / 9.68; 25,000 (10^6 sequences): 19.3 / 29.6 against 19.0 / 27.9 (one pass: 36.8 in the default order)
+    const int accept_passes = sw.loop_passes > 0 ? sw.loop_passes : ncl >= 20000 ? 3 : ncl >= 8192 ? 2 : 1;
+    // Every round accepts at least the earliest open leftover that has a feasible cluster, so nl + 1 rounds always suffice
+    // and a round without a join is the end.  The host keeps enqueuing rounds while it watches the progress word that
+    // k_loop_apply stores into pinned host memory (round << 32 | joins of that round), at most LOOKAHEAD rounds ahead of
+    // the device; rounds enqueued after the end find nothing to do.
+    // where the joiners' rows are read: this device's CSR, or (multi-device) every piece where it lives -- in the peers' memory, or in
+    // the copies the root made of their pieces (no peer access to that device; HMK_MULTI_REPLICATE)
+    RowPieces rowp{};
+    rowp.rows_per = multi ? in.rows_per : 0;
+    for (size_t d = 0; d < pieces.size() && r == hipSuccess; d++) {
+        hmk_ctx *pc = pieces[d].c;
+        rowp.start[d] = buf<uint64_t>(pc, SB_START);
+        rowp.up[d] = buf<uint32_t>(pc, SB_CURSOR);
+        rowp.adj[d] = buf<void>(pc, SB_ADJ);
+        if (multi && d > 0 && (!pc->peer_loads_ok || sw.multi_replicate)) {
+            const uint64_t entries = pc->h_counts[HC_TOTAL];
+            const size_t o_start = 0, o_up = ((size_t)n + 1) * 8, o_adj = (o_up + (size_t)n * 4 + 63) / 64 * 64, bytes = o_adj + std::max<uint64_t>(entries, 1) * esz;
+            DevBuf &rb = pc->sb[SB_REPL];   // (allocated on the ROOT's device, kept in the peer's context)
+            if (rb.cap < bytes) {
+                if (rb.p) (void)hipFree(rb.p);
+                rb.p = nullptr; rb.cap = 0;
+                r = hipMalloc(&rb.p, bytes + bytes / 8);
+                if (r == hipSuccess) rb.cap = bytes + bytes / 8;
+            }
+            char *rp = (char *)rb.p;
+            if (r == hipSuccess) r = hipMemcpyPeerAsync(rp + o_start, ctx->device, rowp.start[d], pc->device, ((size_t)n + 1) * 8, S);
+            if (r == hipSuccess) r = hipMemcpyPeerAsync(rp + o_up, ctx->device, rowp.up[d], pc->device, (size_t)n * 4, S);
+            if (r == hipSuccess && entries) r = hipMemcpyPeerAsync(rp + o_adj, ctx->device, rowp.adj[d], pc->device, entries * esz, S);
+            rowp.start[d] = (const uint64_t *)(rp + o_start);
+            rowp.up[d] = (const uint32_t *)(rp + o_up);
+            rowp.adj[d] = rp + o_adj;
+        }
+    }
+    if (r != hipSuccess) return false;
+    auto one_round = [&]() {
+        r = launch_loop_round(packed, rowp,
+                              buf<uint32_t>(ctx, SB_LEFT), nl, buf<uint32_t>(ctx, SB_CSTART), buf<uint32_t>(ctx, SB_CNT),
+                              buf<GreedyCand>(ctx, SB_CAND), buf<uint8_t>(ctx, SB_STATUS), buf<uint32_t>(ctx, SB_CHOICE),
+                              buf<uint32_t>(ctx, SB_ACTIVE), buf<uint32_t>(ctx, SB_DIRTY), rounds, d_first, d_taken, d_clcursor,
+                              ncl, accept_passes, buf<uint32_t>(ctx, SB_ACCEPTED), d_jslot,
+                              buf<uint32_t>(ctx, SB_SUBSTART), buf<uint64_t>(ctx, SB_SUBS), buf<void>(ctx, SB_JOINED),
+                              ctx->has_sizes ? buf<int32_t>(ctx, SB_SEQSZ) : nullptr, buf<uint32_t>(ctx, SB_LCOUNT), ctx->h_loop, sw.loop_chain, S);
+        rounds++;
+    };
+    if (nl == 0 || ncl == 0) {
+        done = true;
+    } else {
+        const uint32_t LOOKAHEAD = 2;   // a round is 3-5 small dependent kernels; one round in the queue beside the running one keeps the device busy
+                                        // (1 / 4 rounds in flight measured the same, 3.62 / 3.64 ms on the antibodies example) -- and every round enqueued
+                                        // past the last one is 25 us the call waits for at its end
+        volatile unsigned long long *word = ctx->h_loop;
+        *word = 0;
+        // never spin forever: the deadline runs from the last round the device was SEEN to finish (a long loop is fine, a
+        // stalled device is not) and is looked at on every poll (a few thousand spins apart)
+        auto t_progress = std::chrono::steady_clock::now();
+        uint32_t last_seen = 0;
+        bool stalled = false;
+        while (r == hipSuccess && !done && rounds <= nl + 8) {
+            one_round();
+            for (uint32_t spins = 0;; spins++) {
+                const unsigned long long w = *word;
+                const uint32_t seen = (uint32_t)(w >> 32);      // rounds the device has finished
+                if (seen && (uint32_t)w == 0) { done = true; break; }
+                if (rounds - seen < LOOKAHEAD) break;
+                if (seen != last_seen) {
+                    last_seen = seen;
+                    t_progress = std::chrono::steady_clock::now();
+                }
+                else if ((spins & 1023u) == 1023u && ms_since(t_progress) > 60e3) { stalled = true; break; }
+                std::this_thread::yield();
+            }
+            if (stalled) break;
+        }
+        if (stalled) {
+            // No k_loop_* kernel may still be writing cand[] or the progress word when the host path takes over -- but a
+            // device that made no progress for a minute may never drain, and a blocking synchronise would spin forever
+            // after all: poll for ten more seconds, then give the call up (HMK_ERR_DEVICE) instead of falling back.
+            const auto t_drain = std::chrono::steady_clock::now();
+            hipError_t q = hipStreamQuery(S);
+            while (q == hipErrorNotReady && ms_since(t_drain) < 10e3) {
+                std::this_thread::sleep_for(std::chrono::milliseconds(5));
+                q = hipStreamQuery(S);
+            }
+            if (q == hipErrorNotReady) {
+                ctx->wedged = true;
+                *stall_err = "the device made no progress for 70 s inside the second loop: call given up (the context is unusable)";
+            }
+            r = hipErrorNotReady;
+        }
+        if (r == hipSuccess && !done) {                         // (only when nl + 8 rounds were not enough: impossible)
+            r = hipStreamSynchronize(S);
+            done = r == hipSuccess && (uint32_t)*word == 0;
+        }
+        // (the round enqueued past the last one changes nothing -- a round without a join is the end -- and is not waited for here:
+        // every join's slot was stored by a kernel that ended before the final round's began; the caller drains S before it returns)
+    }
+    if (r != hipSuccess || !done) return false;
+    join_slot.resize(nl);
+    if (nl) std::memcpy(join_slot.data(), ctx->h_stage, (size_t)nl * 4);   // (the stream is drained: every store has landed)
+    *rounds_out = rounds;
+    return true;
+}
+
 // Builds the CSR adjacency on the device, hands rows to the host merge on demand, runs the merge.
 int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int32_t *cluster_id, int32_t *result_order,
                       int32_t *member_rank, hmk_greedy_stats *stats, std::chrono::steady_clock::time_point t0) {
@@ -597,155 +761,14 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
         // (measured: the device-side loop beats the host loop over device-built lists at every size -- 1e5 uniform 12-mers
         // 7.5 against 9.5 ms end to end, the antibodies example 14 against 18 ms; the lists stay as the second path)
         const auto tl = std::chrono::steady_clock::now();
-        const uint32_t nl = (uint32_t)leftover.size();
-        const uint32_t ncl = (uint32_t)usize.size();
-        hipError_t r = ensure_buf(ctx, SB_JOINED, std::max<size_t>(ncl, 1) * 16);   // {joined, id, size} per cluster
-        if (r == hipSuccess) r = ensure_buf(ctx, SB_SUBSTART, ((size_t)ncl + 1) * 4);
-        if (r == hipSuccess) r = ensure_buf(ctx, SB_SUBS, std::max<size_t>(pre_total_c, 1) * 8);
-        if (r == hipSuccess) r = ensure_buf(ctx, SB_SUBS2, std::max<size_t>(pre_total_c, 1) * 8);   // merge scratch of the subscriber sort
-        if (r == hipSuccess) r = ensure_buf(ctx, SB_SCAN2, scan_scratch_bytes(std::max<uint32_t>({nl, n, ncl})));
-        if (r == hipSuccess) r = ensure_buf(ctx, SB_CSIZE, std::max<size_t>(ncl, 1) * 8);
-        if (r == hipSuccess) r = ensure_buf(ctx, SB_CID, std::max<size_t>(ncl, 1) * 4);
-        if (r == hipSuccess) r = ensure_buf(ctx, SB_FIRST, std::max<size_t>(ncl, 1) * 12);   // first[], taken[], list cursor[] per cluster
-        if (r == hipSuccess) r = ensure_buf(ctx, SB_STATUS, std::max<size_t>(nl, 1));
-        if (r == hipSuccess) r = ensure_buf(ctx, SB_ACTIVE, std::max<size_t>(nl, 1) * 8);   // two eval lists
-        if (r == hipSuccess) r = ensure_buf(ctx, SB_DIRTY, std::max<size_t>(nl, 1) * 4);
-        if (r == hipSuccess) r = ensure_buf(ctx, SB_CHOICE, std::max<size_t>(nl, 1) * 4);
-        if (r == hipSuccess) r = ensure_buf(ctx, SB_ACCEPTED, std::max<size_t>(nl, 1) * 4);
-        // which cluster a leftover joins: the kernels STORE it into the host's pinned block (a handful of writes per round; nothing on the
-        // device reads it) -- no copy and no second synchronise when the loop is over
-        int32_t *d_jslot = nullptr;
-        if (r == hipSuccess) r = ensure_pinned(&ctx->h_stage, &ctx->h_stage_cap, (size_t)std::max<size_t>(nl, 1) * 4 + 64, 0);
-        if (r == hipSuccess) r = hipHostGetDevicePointer((void **)&d_jslot, ctx->h_stage, 0);
-        if (r == hipSuccess) r = ensure_buf(ctx, SB_LCOUNT, 64);
-        if (r == hipSuccess && ctx->has_sizes) r = ensure_buf(ctx, SB_SEQSZ, (size_t)n * 4);
-        if (r != hipSuccess) return false;
-        // subscriber lists (count into FIRST as scratch, scan, fill, sort by leftover)
-        r = hipMemsetAsync(buf<void>(ctx, SB_FIRST), 0, (size_t)ncl * 4, S);
-        if (r == hipSuccess) r = launch_loop_subscribers(false, nl, buf<uint32_t>(ctx, SB_CSTART), buf<uint32_t>(ctx, SB_CNT), buf<GreedyCand>(ctx, SB_CAND),
-                                                         buf<uint32_t>(ctx, SB_FIRST), nullptr, nullptr, S);
-        if (r == hipSuccess) r = launch_scan_u32(buf<uint32_t>(ctx, SB_FIRST), buf<uint32_t>(ctx, SB_SUBSTART), ncl, buf<uint64_t>(ctx, SB_SCAN2), S);
-        if (r == hipSuccess) r = hipMemsetAsync(buf<void>(ctx, SB_FIRST), 0, (size_t)ncl * 4, S);
-        if (r == hipSuccess) r = launch_loop_subscribers(true, nl, buf<uint32_t>(ctx, SB_CSTART), buf<uint32_t>(ctx, SB_CNT), buf<GreedyCand>(ctx, SB_CAND),
-                                                         buf<uint32_t>(ctx, SB_FIRST), buf<uint32_t>(ctx, SB_SUBSTART), buf<uint64_t>(ctx, SB_SUBS), S);
-        if (r == hipSuccess) r = launch_loop_sort_subscribers(ncl, buf<uint32_t>(ctx, SB_SUBSTART), buf<uint64_t>(ctx, SB_SUBS), buf<uint64_t>(ctx, SB_SUBS2), S);
-        uint32_t *d_first = buf<uint32_t>(ctx, SB_FIRST), *d_taken = d_first + ncl, *d_clcursor = d_first + 2 * (size_t)ncl;
-        // (taken[], the statuses, the join slots and the counters are set by k_loop_init)
-        if (r == hipSuccess) r = hipMemcpyAsync(buf<void>(ctx, SB_CSIZE), csize.data(), (size_t)ncl * 8, hipMemcpyHostToDevice, S);
-        if (r == hipSuccess) r = hipMemcpyAsync(buf<void>(ctx, SB_CID), cids.data(), (size_t)ncl * 4, hipMemcpyHostToDevice, S);
-        if (r == hipSuccess) r = launch_loop_init(ncl, buf<long long>(ctx, SB_CSIZE), buf<int32_t>(ctx, SB_CID), buf<void>(ctx, SB_JOINED),
-                                                  buf<uint32_t>(ctx, SB_SUBSTART), d_clcursor, nl, buf<uint32_t>(ctx, SB_ACTIVE),
-                                                  buf<uint32_t>(ctx, SB_DIRTY), buf<uint32_t>(ctx, SB_LCOUNT), d_taken,
-                                                  buf<uint8_t>(ctx, SB_STATUS), d_jslot, S);
-        if (r == hipSuccess && ctx->has_sizes)
-            r = hipMemcpyAsync(buf<void>(ctx, SB_SEQSZ), ctx->sizes.data(), (size_t)n * 4, hipMemcpyHostToDevice, S);
+        LoopIn li;
+        li.n = n; li.nl = (uint32_t)leftover.size(); li.ncl = (uint32_t)usize.size(); li.cand_total = pre_total_c; li.packed = packed;
+        li.csize = &csize; li.cids = &cids; li.pieces = &pieces; li.rows_per = src.rows_per;
         uint32_t rounds = 0;
-        bool done = false;
-        // a second first/accept pass per round saves a third of the rounds; it pays once a round's apply and eval are big enough
-        // first/accept passes per round: an accepted leftover stops blocking the other clusters it lists, so a second pass lets more joins into
-        // the round -- fewer, longer rounds.  Measured (loop ms, generator / default order): 10,000 clusters 3.46 / 4.58 with two passes, 3.66 / 4.72
-        // with three; 15,000: 6.93 / 9.59 against 7.04 / 9.68; 25,000 (10^6 sequences): 19.3 / 29.6 against 19.0 / 27.9 (one pass: 36.8 in the default order)
-        const int accept_passes = sw.loop_passes > 0 ? sw.loop_passes : ncl >= 20000 ? 3 : ncl >= 8192 ? 2 : 1;
-        // Every round accepts at least the earliest open leftover that has a feasible cluster, so nl + 1 rounds always suffice
-        // and a round without a join is the end.  The host keeps enqueuing rounds while it watches the progress word that
-        // k_loop_apply stores into pinned host memory (round << 32 | joins of that round), at most LOOKAHEAD rounds ahead of
-        // the device; rounds enqueued after the end find nothing to do.
-        // where the joiners' rows are read: this device's CSR, or (multi-device) every piece where it lives -- in the peers' memory, or in
-        // the copies the root made of their pieces (no peer access to that device; HMK_MULTI_REPLICATE)
-        RowPieces rowp{};
-        rowp.rows_per = multi ? src.rows_per : 0;
-        for (size_t d = 0; d < pieces.size() && r == hipSuccess; d++) {
-            hmk_ctx *pc = pieces[d].c;
-            rowp.start[d] = buf<uint64_t>(pc, SB_START);
-            rowp.up[d] = buf<uint32_t>(pc, SB_CURSOR);
-            rowp.adj[d] = buf<void>(pc, SB_ADJ);
-            if (multi && d > 0 && (!pc->peer_loads_ok || sw.multi_replicate)) {
-                const uint64_t entries = pc->h_counts[HC_TOTAL];
-                const size_t o_start = 0, o_up = ((size_t)n + 1) * 8, o_adj = (o_up + (size_t)n * 4 + 63) / 64 * 64, bytes = o_adj + std::max<uint64_t>(entries, 1) * esz;
-                DevBuf &rb = pc->sb[SB_REPL];   // (allocated on the ROOT's device, kept in the peer's context)
-                if (rb.cap < bytes) {
-                    if (rb.p) (void)hipFree(rb.p);
-                    rb.p = nullptr; rb.cap = 0;
-                    r = hipMalloc(&rb.p, bytes + bytes / 8);
-                    if (r == hipSuccess) rb.cap = bytes + bytes / 8;
-                }
-                char *rp = (char *)rb.p;
-                if (r == hipSuccess) r = hipMemcpyPeerAsync(rp + o_start, ctx->device, rowp.start[d], pc->device, ((size_t)n + 1) * 8, S);
-                if (r == hipSuccess) r = hipMemcpyPeerAsync(rp + o_up, ctx->device, rowp.up[d], pc->device, (size_t)n * 4, S);
-                if (r == hipSuccess && entries) r = hipMemcpyPeerAsync(rp + o_adj, ctx->device, rowp.adj[d], pc->device, entries * esz, S);
-                rowp.start[d] = (const uint64_t *)(rp + o_start);
-                rowp.up[d] = (const uint32_t *)(rp + o_up);
-                rowp.adj[d] = rp + o_adj;
-            }
-        }
-        if (r != hipSuccess) return false;
-        auto one_round = [&]() {
-            r = launch_loop_round(packed, rowp,
-                                  buf<uint32_t>(ctx, SB_LEFT), nl, buf<uint32_t>(ctx, SB_CSTART), buf<uint32_t>(ctx, SB_CNT),
-                                  buf<GreedyCand>(ctx, SB_CAND), buf<uint8_t>(ctx, SB_STATUS), buf<uint32_t>(ctx, SB_CHOICE),
-                                  buf<uint32_t>(ctx, SB_ACTIVE), buf<uint32_t>(ctx, SB_DIRTY), rounds, d_first, d_taken, d_clcursor,
-                                  ncl, accept_passes, buf<uint32_t>(ctx, SB_ACCEPTED), d_jslot,
-                                  buf<uint32_t>(ctx, SB_SUBSTART), buf<uint64_t>(ctx, SB_SUBS), buf<void>(ctx, SB_JOINED),
-                                  ctx->has_sizes ? buf<int32_t>(ctx, SB_SEQSZ) : nullptr, buf<uint32_t>(ctx, SB_LCOUNT), ctx->h_loop, sw.loop_chain, S);
-            rounds++;
-        };
-        if (nl == 0 || ncl == 0) {
-            done = true;
-        } else {
-            const uint32_t LOOKAHEAD = 2;   // a round is 3-5 small dependent kernels; one round in the queue beside the running one keeps the device busy
-                                            // (1 / 4 rounds in flight measured the same, 3.62 / 3.64 ms on the antibodies example) -- and every round enqueued
-                                            // past the last one is 25 us the call waits for at its end
-            volatile unsigned long long *word = ctx->h_loop;
-            *word = 0;
-            // never spin forever: the deadline runs from the last round the device was SEEN to finish (a long loop is fine, a
-            // stalled device is not) and is looked at on every poll (a few thousand spins apart)
-            auto t_progress = std::chrono::steady_clock::now();
-            uint32_t last_seen = 0;
-            bool stalled = false;
-            while (r == hipSuccess && !done && rounds <= nl + 8) {
-                one_round();
-                for (uint32_t spins = 0;; spins++) {
-                    const unsigned long long w = *word;
-                    const uint32_t seen = (uint32_t)(w >> 32);      // rounds the device has finished
-                    if (seen && (uint32_t)w == 0) { done = true; break; }
-                    if (rounds - seen < LOOKAHEAD) break;
-                    if (seen != last_seen) {
-                        last_seen = seen;
-                        t_progress = std::chrono::steady_clock::now();
-                    }
-                    else if ((spins & 1023u) == 1023u && ms_since(t_progress) > 60e3) { stalled = true; break; }
-                    std::this_thread::yield();
-                }
-                if (stalled) break;
-            }
-            if (stalled) {
-                // No k_loop_* kernel may still be writing cand[] or the progress word when the host path takes over -- but a
-                // device that made no progress for a minute may never drain, and a blocking synchronise would spin forever
-                // after all: poll for ten more seconds, then give the call up (HMK_ERR_DEVICE) instead of falling back.
-                const auto t_drain = std::chrono::steady_clock::now();
-                hipError_t q = hipStreamQuery(S);
-                while (q == hipErrorNotReady && ms_since(t_drain) < 10e3) {
-                    std::this_thread::sleep_for(std::chrono::milliseconds(5));
-                    q = hipStreamQuery(S);
-                }
-                if (q == hipErrorNotReady) {
-                    ctx->wedged = true;
-                    status_inside = HMK_ERR_DEVICE;
-                    hook_err = "the device made no progress for 70 s inside the second loop: call given up (the context is unusable)";
-                }
-                r = hipErrorNotReady;
-            }
-            if (r == hipSuccess && !done) {                         // (only when nl + 8 rounds were not enough: impossible)
-                r = hipStreamSynchronize(S);
-                done = r == hipSuccess && (uint32_t)*word == 0;
-            }
-            // (the round enqueued past the last one changes nothing -- a round without a join is the end -- and is not waited for here:
-            // every join's slot was stored by a kernel that ended before the final round's began; cluster_on_device drains S before it returns)
-        }
-        if (r != hipSuccess || !done) return false;
-        join_slot.resize(nl);
-        if (nl) std::memcpy(join_slot.data(), ctx->h_stage, (size_t)nl * 4);   // (the stream is drained: every store has landed)
-        if (r != hipSuccess) return false;
+        std::string stall;
+        const bool ok = device_second_loop(ctx, S, li, join_slot, &rounds, &stall);
+        if (!stall.empty()) { status_inside = HMK_ERR_DEVICE; hook_err = stall; }
+        if (!ok) return false;
         ph.device_loop_ms = ms_since(tl);
         ph.loop_rounds = rounds;
         lap("device second loop (rounds)");

@@ -151,6 +151,8 @@ struct hmk_ctx {
     PlanLocal plan_local_search;   // searches and clustering calls on one context do not rebuild each other's
     Plan plan_assign;              // the assignments' plans (hmk_assign.cpp: members = the search's queries): cached apart too
     PlanLocal plan_local_assign;
+    Plan plan_continue;            // hmk_greedy_continue (hmk_continue.cpp): members x new (a rectangle) and new x new (a triangle)
+    Plan plan_continue_tri;
     uint64_t *d_edges = nullptr;  // internal buffer of the host-buffer entry points
     uint64_t d_edges_cap = 0;
     unsigned long long *d_counts = nullptr;
@@ -212,7 +214,8 @@ int fail(hmk_ctx *ctx, int code, const std::string &msg);
 #define HMK_QUIET(call) do { if ((call) != hipSuccess) (void)hipGetLastError(); } while (0)
 
 // which: LAUNCH_ALL, or only the band tiles of the plan (LAUNCH_BAND: also zeroes the counts) / only the others
-// (LAUNCH_REST: appends to the counts of the band launch)
+// (LAUNCH_REST: appends to the counts of the band launch).  A plan without a band (every search plan: Group::band = 0) launched with
+// LAUNCH_REST runs ALL its tiles and appends to the counts already there (hmk_continue.cpp's second pass)
 enum { LAUNCH_ALL = 0, LAUNCH_BAND = 1, LAUNCH_REST = 2 };
 
 constexpr int ST_RETRY_OVERFLOW = 1000;   // internal: an edge segment overflowed, grow the buffer and score again
@@ -299,9 +302,16 @@ int build_plan_search(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t
 int build_plan_local_search(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
 // ... into the plan slot `pl` (the assignment's own, hmk_assign.cpp)
 int build_plan_search(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
+// the triangle of the pairs inside [q0, q1) (symmetric matrices; hmk_continue.cpp's new x new) into the plan slot `pl`
+int build_plan_triangle(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1);
 int build_plan_local_search(hmk_ctx *ctx, PlanLocal &pl, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
 // the search's parameter checks of a shifted rectangle (the shift against both ranges, threshold and int16 limits)
 int check_shifted(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
+// ---- hmk_assign.cpp
+// the clusters' argument checks of the assignment and the continuation (`what` names the call in the range message):
+// members[c] = slot c's members, size[c] = its Cluster.size()
+int check_clusters(hmk_ctx *ctx, const char *what, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, const uint32_t *member_cluster,
+                   const int32_t *cluster_id, uint32_t n_clusters, std::vector<uint32_t> &members, std::vector<int64_t> &size);
 // ---- hmk_pass.cpp
 int neighbors_dev_locked(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_parts, void *d_edges,
                          uint64_t capacity, void *d_counts, hipStream_t stream, int which = LAUNCH_ALL,
@@ -345,6 +355,20 @@ hipError_t piece_enqueue_csr(hmk_ctx *c, const EdgeSegs &segs, bool symmetric, b
 int piece_precheck(hmk_ctx *c, const PreIn &in, uint32_t r0, uint32_t r1, uint32_t region_base, uint32_t region_count, hipStream_t q,
                    bool upload, unsigned long long *total);
 hipError_t piece_precheck_upload(hmk_ctx *c, const PreIn &in);   // (the upload alone, on c's copy stream: records c->ev_bandcsr)
+// What the device-side second loop needs besides the pre-check's candidate lists and the uploaded leftover list (SB_LEFT)
+struct LoopIn {
+    uint32_t n = 0, nl = 0, ncl = 0;
+    uint32_t cand_total = 0;                          // candidate entries (< 2^31)
+    bool packed = true;                               // the CSR's entry format
+    const std::vector<int64_t> *csize = nullptr;      // Cluster.size() per slot
+    const std::vector<int32_t> *cids = nullptr;       // Java id per slot
+    const std::vector<EdgeSource::Piece> *pieces = nullptr;   // where the joiners' rows live (one piece: this context's CSR)
+    uint32_t rows_per = 0;                            // (several pieces: rows per piece)
+};
+// The rounds of k_loop_* on S until one joins nobody: join_slot[q] = the slot leftover q joins or -1.  false: did not run to the
+// end (the caller falls back); *stall_err is set when the device stalled and the context was given up (ctx->wedged).
+bool device_second_loop(hmk_ctx *ctx, hipStream_t S, const LoopIn &in, std::vector<int32_t> &join_slot, uint32_t *rounds,
+                        std::string *stall_err);
 int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int32_t *cluster_id, int32_t *result_order,
                       int32_t *member_rank, hmk_greedy_stats *stats, std::chrono::steady_clock::time_point t0);
 // ---- hmk_multi.cpp

@@ -45,19 +45,37 @@ bool is_identity_from(const std::vector<uint32_t> &perm) {
 //                     length) run on the shift-packed or direct tiers, as in the all-vs-all asymmetric pass.
 // No score-bound refinement (hmk_plan.cpp's `refine`): a class whose 8-bit lanes do not fit every pair runs on 16-bit lanes.
 // No key sort.
+// tri (build_plan_triangle): the TRIANGLE of the pairs inside the one range [q0, q1) = [r0, r1) -- hmk_greedy_continue's new x new --
+// under a symmetric matrix: the range is sorted once, the longer bucket supplies the rows, and a class of one length keeps the
+// columns after each row (Tile::diag = 1, as build_plan's triangle); edges (min, max) as above.
+namespace {
+int build_plan_rect(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, bool tri);
+}  // namespace
+
 int build_plan_search(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1) {
-    return build_plan_search(ctx, ctx->plan_search, X, p, thr, q0, q1, r0, r1);
+    return build_plan_rect(ctx, ctx->plan_search, X, p, thr, q0, q1, r0, r1, false);
 }
 
 int build_plan_search(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1) {
+    return build_plan_rect(ctx, pl, X, p, thr, q0, q1, r0, r1, false);
+}
+
+int build_plan_triangle(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1) {
+    return build_plan_rect(ctx, pl, X, p, thr, q0, q1, q0, q1, true);
+}
+
+namespace {
+int build_plan_rect(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, bool tri) {
     if (pl.valid && pl.X == X && pl.p == p && pl.thr == thr && pl.q0 == q0 && pl.q1 == q1 && pl.r0 == r0 && pl.r1 == r1 &&
         pl.no_rows_kernel == ctx->sw.no_rows_kernel)
         return HMK_OK;
     free_plan(pl);
-    const uint32_t nq = q1 - q0, nr = r1 - r0, N = nq + nr;
+    if (tri && !ctx->symmetric) return fail(ctx, HMK_ERR_BAD_ARG, "a triangle plan needs a symmetric matrix");
+    const uint32_t nq = q1 - q0, nr = tri ? 0 : r1 - r0, N = nq + nr;
     uint32_t bq[HMK_MAX_LEN + 2], br[HMK_MAX_LEN + 2];
     std::vector<uint32_t> perm;
-    sort_rectangle(ctx, q0, q1, r0, r1, bq, br, perm);
+    sort_rectangle(ctx, q0, q1, r0, tri ? r0 : r1, bq, br, perm);
+    if (tri) std::memcpy(br, bq, sizeof(br));   // (one range: rows and columns index the same sorted positions)
     int mn = HMK_MAX_LEN, mx = 1;
     for (int l = 1; l <= HMK_MAX_LEN; l++)
         if (bq[l] != bq[l + 1] || br[l] != br[l + 1]) { mn = std::min(mn, l); mx = std::max(mx, l); }
@@ -73,7 +91,7 @@ int build_plan_search(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0
         pl.rows_exact = t1.path == PATH_U8 && rows_kernel_available(X, mn, mn, true);
     }
 
-    struct Cls { TileClass tc; bool rows; int lbk; uint32_t R, rb, re, cb, ce; };
+    struct Cls { TileClass tc; bool rows, tri; int lbk; uint32_t R, rb, re, cb, ce; };
     std::vector<Cls> cl;
     for (int lq = 1; lq <= HMK_MAX_LEN; lq++) {
         const uint32_t nql = bq[lq + 1] - bq[lq];
@@ -81,8 +99,10 @@ int build_plan_search(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0
         for (int lr = 1; lr <= HMK_MAX_LEN; lr++) {
             const uint32_t nrl = br[lr + 1] - br[lr];
             if (!nrl) continue;
-            const bool rows_q = ctx->symmetric && (lq > lr || (lq == lr && nql >= nrl));
+            if (tri && (lr > lq || (lq == lr && nql < 2))) continue;   // (unordered pairs: the longer bucket supplies the rows)
+            const bool rows_q = tri || (ctx->symmetric && (lq > lr || (lq == lr && nql >= nrl)));
             Cls c{};
+            c.tri = tri && lq == lr;
             const int la = rows_q ? lq : lr, lb = rows_q ? lr : lq;
             c.rb = rows_q ? bq[lq] : br[lr]; c.re = rows_q ? bq[lq + 1] : br[lr + 1];
             c.cb = rows_q ? br[lr] : bq[lq]; c.ce = rows_q ? br[lr + 1] : bq[lq + 1];
@@ -125,18 +145,31 @@ int build_plan_search(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0
         std::vector<Tile> &dst = grouped[c.rows ? std::make_tuple((int)PATH_ROWS, (int)tc.la - (int)tc.lb, c.lbk)
                                                 : std::make_tuple((int)tc.path, tc.path == PATH_DIRECT ? 0 : (int)tc.nw,
                                                                   tc.path == PATH_DIRECT ? 0 : c.lbk)];
-        // equal column runs (whole 256-column batches), as in build_plan
-        const uint32_t k_runs = (c.ce - c.cb + COLS - 1) / COLS;
-        const uint32_t run = std::min(COLS, ((c.ce - c.cb + k_runs - 1) / k_runs + 255u) & ~255u);
-        for (uint32_t y0 = c.rb; y0 < c.re; y0 += c.R)
-            for (uint32_t x0 = c.cb; x0 < c.ce; x0 += run) {
+        for (uint32_t y0 = c.rb; y0 < c.re; y0 += c.R) {
+            const uint32_t c_lo = c.tri ? y0 + 1 : c.cb;   // triangle: the columns after the chunk's first row
+            if (c_lo >= c.ce) continue;
+            // equal column runs (whole 256-column batches), as in build_plan
+            const uint32_t k_runs = (c.ce - c_lo + COLS - 1) / COLS;
+            const uint32_t run = std::min(COLS, ((c.ce - c_lo + k_runs - 1) / k_runs + 255u) & ~255u);
+            for (uint32_t x0 = c_lo; x0 < c.ce; x0 += run) {
                 Tile t{};
                 t.row0 = y0; t.nrows = std::min(c.R, c.re - y0);
                 t.col0 = x0; t.ncols = std::min(run, c.ce - x0);
                 t.cls = cls;
-                S.pairs_scored += (uint64_t)t.nrows * t.ncols;
+                uint64_t pairs = (uint64_t)t.nrows * t.ncols;
+                if (c.tri && x0 < y0 + t.nrows) {   // the tile reaches the diagonal: keep column > row
+                    t.diag = 1;
+                    pairs = 0;
+                    for (uint32_t r = y0; r < y0 + t.nrows; r++) {
+                        const uint32_t lo = std::max(x0, r + 1), hi = x0 + t.ncols;
+                        if (hi > lo) pairs += hi - lo;
+                    }
+                    if (pairs == 0) continue;
+                }
+                S.pairs_scored += pairs;
                 dst.push_back(t);
             }
+        }
     }
     std::vector<Tile> tiles;
     for (auto &kv : grouped) {
@@ -184,6 +217,7 @@ int build_plan_search(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0
     pl.valid = true;
     return HMK_OK;
 }
+}  // namespace
 
 // The rectangle of a LocalAlignmentScorer search: rows = queries (seq1, lines), columns = references (seq2), one class per
 // (query length, reference length); the tiles' edges come out m = row = query (row_is_m, k_local.hip).

@@ -125,7 +125,9 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "          hammock-hip search -i <queries> --database <references> -d <directory> [-f fasta|tab] [-m <file>] [-x <int>]\n"
               << "                      [-p <int>] [-g <int>] [--best <int>] [--device <int>]\n"
               << "          hammock-hip assign -i <new sequences> --clusters <initial_clusters_sequences.tsv> -d <directory> [--best <int>]\n"
-              << "                      [--skip_singletons] [-f fasta|tab] [-m <file>] [-x <int>] [-p <int>] [-g <int>] [--device <int>]\n\n"
+              << "                      [--skip_singletons] [-f fasta|tab] [-m <file>] [-x <int>] [-p <int>] [-g <int>] [--device <int>]\n"
+              << "          hammock-hip continue -i <new sequences> --clusters <initial_clusters_sequences.tsv> -d <directory> [-f fasta|tab]\n"
+              << "                      [-m <file>] [-x <int>] [-p <int>] [-g <int>] [-R <order>] [-S <int>] [-l <labels>] [--device <int>]\n\n"
               << "-i, --input <file>\n\tA path to an input file\n\n"
               << "-d, --output_directory <directory>\n\tA directory to store all output files in\n\n"
               << "-t, --threads <int>\n\tAccepted for compatibility (the GPU path ignores it)\n\n"
@@ -143,7 +145,7 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "--devices <int,int,...>\n\tShard the pair space over several GPUs of the node (the first one runs the merge)\n\n"
               << "--database <file>\n\t(search) the reference sequences every query (-i) is scored against\n\n"
               << "--best <int>\n\t(search) keep only the best 1..32 hits of each query; (assign) report the best 1..32 feasible clusters (default 1)\n\n"
-              << "--clusters <file>\n\t(assign) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv)\n\n"
+              << "--clusters <file>\n\t(assign, continue) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv)\n\n"
               << "--skip_singletons\n\t(assign) only clusters of more than one unique sequence are candidates\n\n"
               << "--java_hashset <8|7|6>\n\t(clinkage) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
 }
@@ -708,6 +710,232 @@ int runAssign(const std::vector<std::string> &args) {
     }
 }
 
+// `hammock-hip continue -i new.fa --clusters initial_clusters_sequences.tsv -d dir ...`: continues the greedy clustering of a cluster
+// file with new sequences -- the second loop of LimitedGreedySequenceClusterer.cluster (LimitedGreedySequenceClusterer.java:59-67,
+// hmk_greedy_continue) with the file's clusters of more than one unique sequence as actualClusters (:41-50) and the new sequences,
+// ordered by -R as greedy orders its input (sortSequences), as actualSequences.  A new sequence that joins a cluster is a member for
+// every later one; one that joins nothing is a singleton with id max(loaded id) + 1 + k, k counting them in processing order.
+// Phase 1 does not run: new sequences never seed clusters.  The file's singletons are neither candidates nor leftovers.  A new
+// sequence already in the file adds its counts and labels to that line's sequence instead.  Defaults: -x and -g are greedy's over
+// the file's sequences (they should be the original run's), -x then clamped by the shortest sequence of both sides; -p 0.  Writes
+// the stage-1 files of greedy (label columns: the file's, then new labels in first-seen order) and new_sequences.tsv.
+int runContinue(const std::vector<std::string> &args) {
+    Options o;
+    const std::string PARENT_DIR = parentDir();
+    o.matrixFile = PARENT_DIR + "/matrices/blosum62.txt";  // Hammock.java:45
+    parseCommonArgs(args, o);
+    parseGreedyArgs(args, o);
+    std::string clustersFile;
+    bool haveClusters = false, havePenalty = false;
+    for (size_t i = 1; i < args.size(); i++) {
+        const bool more = args.size() > i + 1;
+        if (args[i] == "--clusters" && more) { clustersFile = args[++i]; haveClusters = true; }
+        else if ((args[i] == "-p" || args[i] == "--gap_penalty") && more) havePenalty = true;
+    }
+    if (!o.devices.empty()) throw CLIException("Error. --devices is not available in mode continue (a continuation runs on one device, --device).");
+    if (!o.haveInput) throw CLIException("Error. Parameter input file (-i or --input) missing with no default.");
+    if (!haveClusters) throw CLIException("Error. Parameter cluster file (--clusters) missing with no default.");
+    if (!(o.inputType == "fasta" || o.inputType == "tab"))
+        throw CLIException("Error. Parameter -f value may be either \"fasta\" or \"tab\" in mode continue.");
+    if (o.haveDir) {
+        if (exists(o.workingDirectory)) throw CLIException("Error. Output directory exists. Exiting to prevent data loss.");
+        mkdir(o.workingDirectory.c_str(), 0777);
+    } else {
+        std::string name;
+        mkdir((PARENT_DIR + "/dist").c_str(), 0777);
+        for (int i = 1; i < 9999; i++) {
+            name = PARENT_DIR + "/dist/Hammock_result_" + std::to_string(i);
+            if (!exists(name)) { mkdir(name.c_str(), 0777); break; }
+        }
+        o.workingDirectory = name;
+        std::cerr << "Creating default output directory: " << name << std::endl;
+    }
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        logger.logAndStderr(std::string("\nHammock version ") + VERSION +
+                            " Run with --help for a brief description of command line parameters.\n");
+        const std::vector<std::vector<int>> scoringMatrix = FileIOManager::loadScoringMatrix(o.matrixFile);
+        std::shared_future<std::shared_ptr<NativeContext>> contextReady = std::async(std::launch::async, [&scoringMatrix, &o]() {
+            return std::make_shared<NativeContext>(scoringMatrix, o.device);
+        });
+        logger.logWithTime("Program started in mode \"continue\".");
+        std::string argsString;
+        for (auto &a : args) argsString += " " + a;
+        logger.logWithoutTime("Command-line arguments: \n" + argsString + "\n");
+        logger.logAndStderr("Loading clusters...");
+        std::vector<ClusterPtr> loaded = FileIOManager::loadClustersFromCsv(clustersFile);
+        // the file's label columns and its line order (the original-order file lists the file's sequences first, as they came)
+        std::vector<std::string> labels;
+        std::vector<UniqueSequencePtr> lineOrder;
+        std::unordered_map<std::string, UniqueSequencePtr> inFile;
+        for (auto &cl : loaded) for (auto &s : cl->getSequences()) inFile.emplace(s->getSequenceString(), s);
+        {
+            const std::vector<std::string> lines = FileIOManager::readLines(clustersFile);
+            std::vector<std::string> header = FileIOManager::splitChar(lines[0], CSV_SEPARATOR, true);
+            const long seqAt = 1;   // (files greedy writes: cluster_id, sequence, labels...)
+            for (const char *drop : {"alignment", "sum"}) {
+                const auto at = std::find(header.begin(), header.end(), drop);
+                if (at != header.end()) header.erase(at);
+            }
+            labels.assign(header.begin() + 2, header.end());
+            for (size_t k = 1; k < lines.size(); k++) {
+                const std::vector<std::string> f = FileIOManager::splitChar(lines[k], CSV_SEPARATOR, true);
+                if ((long)f.size() <= seqAt) continue;
+                const auto it = inFile.find(f[seqAt]);
+                if (it != inFile.end()) lineOrder.push_back(it->second);
+            }
+        }
+        if (o.haveLabels) labels = FileIOManager::splitChar(o.labelString, ',', true);
+        size_t nLoadedSeqs = 0;
+        for (auto &cl : loaded) nLoadedSeqs += cl->getSequences().size();
+        logger.logAndStderr(std::to_string(loaded.size()) + " clusters of " + std::to_string(nLoadedSeqs) + " sequences loaded.");
+        logger.logAndStderr("Loading new sequences...");
+        std::vector<UniqueSequencePtr> input = o.inputType == "fasta" ? FileIOManager::loadUniqueSequencesFromFasta(o.inputFileName)
+                                                                      : FileIOManager::loadUniqueSequencesFromTable(o.inputFileName);
+        logger.logAndStderr(std::to_string(input.size()) + " unique new sequences loaded.");
+        if (input.empty()) throw FileFormatException("Error. No new sequences.");
+        if (nLoadedSeqs == 0) throw FileFormatException("Error. The cluster file holds no clusters.");
+        // new labels after the file's, in first-seen order
+        if (!o.haveLabels)
+            for (auto &s : input)
+                for (auto &e : s->getLabelsMap())
+                    if (std::find(labels.begin(), labels.end(), e.first) == labels.end()) labels.push_back(e.first);
+        // a new sequence already in the file: its counts and labels go to that sequence, which then is not new
+        std::vector<UniqueSequencePtr> newSequences;
+        size_t merged = 0;
+        for (auto &s : input) {
+            const auto it = inFile.find(s->getSequenceString());
+            if (it == inFile.end()) { newSequences.push_back(s); continue; }
+            for (auto &e : s->getLabelsMap()) it->second->addLabelCount(e.first, e.second);
+            merged++;
+        }
+        logger.logAndStderr(std::to_string(merged) + " new sequences were already in the cluster file: their counts and labels were added there.");
+        // (Cluster.size() sums its sequences' sizes when it is made: made again after the merge)
+        std::vector<ClusterPtr> clusters;
+        int maxId = INT32_MIN;
+        for (auto &cl : loaded) { clusters.push_back(std::make_shared<Cluster>(cl->getSequences(), cl->getId())); maxId = std::max(maxId, cl->getId()); }
+        std::vector<UniqueSequencePtr> fileSequences, both;
+        for (auto &cl : clusters) for (auto &s : cl->getSequences()) fileSequences.push_back(s);
+        both = fileSequences;
+        both.insert(both.end(), newSequences.begin(), newSequences.end());
+        const SequenceListSummary summary = summariseSequences(fileSequences), bothSummary = summariseSequences(both);
+        if (bothSummary.maxLength > HMK_MAX_LEN)
+            throw HammockException("Error. The longest sequence has " + std::to_string(bothSummary.maxLength) + " amino acids; the GPU kernels of hammock-hip "
+                                   "take sequences of up to " + std::to_string(HMK_MAX_LEN) + " (Hammock's domain is 7-20).");
+        if (!o.haveMaxShift) {
+            o.maxShift = checkMaxShift(bothSummary, (int)javaRound(summary.meanLength() / 4));
+            logger.logAndStderr("Max shift not set. Setting automatically to: " + std::to_string(o.maxShift) + " (it should be the original run's)");
+        } else {
+            const int correct = checkMaxShift(bothSummary, o.maxShift);
+            if (o.maxShift != correct) {
+                o.maxShift = correct;
+                logger.logAndStderr("Setting max shift to " + std::to_string(correct) +
+                                    " as the length of the shortest sequence is only " + std::to_string(correct + 1));
+            }
+        }
+        if (!o.haveThreshold) {
+            o.sequenceClusteringThreshold = (int)javaRound(summary.meanLength() * 1.7);
+            logger.logAndStderr("Greedy clustering threshold not set. Setting automatically to: " + std::to_string(o.sequenceClusteringThreshold) +
+                                " (it should be the original run's)");
+        }
+        if (!havePenalty) logger.logAndStderr("Gap penalty not set. Setting automatically to: " + std::to_string(o.shiftPenalty));
+        sortSequences(newSequences, o.order, o.seed, labels);                                    // :407, as greedy orders its input
+
+        // the candidates' members first, the new sequences behind them: members [0, nm), new [nm, n)
+        std::vector<ClusterPtr> candidates;
+        for (auto &cl : clusters)
+            if (cl->getUniqueSize() > 1) candidates.push_back(cl);                               // :41-50
+        std::vector<UniqueSequencePtr> upload;
+        std::vector<uint32_t> memberCluster;
+        std::vector<int32_t> clusterId;
+        for (uint32_t c = 0; c < (uint32_t)candidates.size(); c++) {
+            clusterId.push_back(candidates[c]->getId());
+            for (auto &s : candidates[c]->getSequences()) { upload.push_back(s); memberCluster.push_back(c); }
+        }
+        const uint32_t nm = (uint32_t)upload.size(), nq = (uint32_t)newSequences.size();
+        upload.insert(upload.end(), newSequences.begin(), newSequences.end());
+        const uint32_t n = (uint32_t)upload.size();
+        std::vector<int32_t> joined(nq, -1), rank(nq, -1);
+        hmk_continue_stats stats{};
+        logger.logAndStderr("Continuing the clustering...");
+        const auto time0 = std::chrono::steady_clock::now();
+        if (nq) {
+            size_t total = 0;
+            for (auto &s : upload) total += s->getSequence().size();
+            std::vector<uint8_t> res(total);
+            std::vector<uint32_t> off(n + 1, 0);
+            std::vector<int32_t> sizes(n);
+            for (uint32_t k = 0; k < n; k++) {
+                off[k + 1] = off[k] + (uint32_t)upload[k]->getSequence().size();
+                for (size_t r = 0; r < upload[k]->getSequence().size(); r++) res[off[k] + r] = (uint8_t)upload[k]->getSequence()[r];
+                sizes[k] = upload[k]->size();
+            }
+            const std::shared_ptr<NativeContext> nc = contextReady.get();
+            hmk_ctx *c = nc->get();
+            int st = hmk_set_sequences(c, res.data(), off.data(), sizes.data(), n);
+            if (st) nc->raise(st, nullptr);
+            st = hmk_greedy_continue(c, nm, n, 0, nm, memberCluster.data(), clusterId.data(), (uint32_t)candidates.size(), o.maxShift,
+                                     o.shiftPenalty, o.sequenceClusteringThreshold, joined.data(), rank.data(), &stats);
+            if (st) nc->raise(st, nullptr);
+        }
+        // :61-62 in loop order, then :64-67: the new singletons behind the loaded clusters
+        std::vector<ClusterPtr> result(clusters);
+        std::vector<int32_t> finalId(nq);
+        int k = 0;
+        for (uint32_t q = 0; q < nq; q++) {
+            if (joined[q] >= 0) {
+                candidates[joined[q]]->insert(newSequences[q]);
+                finalId[q] = candidates[joined[q]]->getId();
+            } else {
+                finalId[q] = maxId + 1 + k++;
+                result.push_back(std::make_shared<Cluster>(std::vector<UniqueSequencePtr>{newSequences[q]}, finalId[q]));
+            }
+        }
+        const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - time0).count();
+        logger.logAndStderr("Ready. Clustering time: " + std::to_string(ms));
+        logger.logAndStderr("Candidate clusters: " + std::to_string(candidates.size()) + ", new sequences joined: " + std::to_string(stats.n_joined) +
+                            " of " + std::to_string(nq) + ", pairs scored: " + std::to_string(stats.pairs_scored) + ", neighbour edges: " +
+                            std::to_string(stats.n_edges) + ", GPU passes: " + std::to_string(stats.kernel_ms) + " ms, loop: " +
+                            std::to_string(stats.loop_ms) + " ms in " + std::to_string(stats.loop_rounds) + " rounds");
+        logger.logAndStderr("Resulting clusers: " + std::to_string(result.size()));
+        logger.logAndStderr("Saving results to output files...");
+        std::vector<UniqueSequencePtr> originalOrder(lineOrder);
+        for (auto &s : input)
+            if (std::find(newSequences.begin(), newSequences.end(), s) != newSequences.end()) originalOrder.push_back(s);
+        const std::string seqCsv = o.workingDirectory + "/initial_clusters_sequences.tsv";
+        const std::string orderedCsv = o.workingDirectory + "/initial_clusters_sequences_original_order.tsv";
+        const std::string clustersCsv = o.workingDirectory + "/initial_clusters.tsv";
+        FileIOManager::saveInitialClusters(result, seqCsv, orderedCsv, clustersCsv, labels, originalOrder);
+        const std::string newCsv = o.workingDirectory + "/new_sequences.tsv";
+        {
+            std::ofstream out(newCsv);
+            if (!out) throw HammockException("cannot write " + newCsv);
+            out << "sequence\tcluster_id\tjoined\n";
+            for (uint32_t q = 0; q < nq; q++) out << newSequences[q]->getSequenceString() << '\t' << finalId[q] << '\t' << (joined[q] >= 0 ? 1 : 0) << '\n';
+        }
+        logger.logAndStderr("Greedy clustering results in: " + clustersCsv);
+        logger.logAndStderr("and: " + seqCsv);
+        logger.logAndStderr("and: " + orderedCsv);
+        logger.logAndStderr("New sequences in: " + newCsv);
+        logger.logWithTime("Program successfully ended.");
+        return 0;
+    } catch (const CLIException &) {
+        throw;
+    } catch (const FileFormatException &e) {
+        logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
+        return 3;
+    } catch (const DataException &e) {
+        logger.logAndStderr("Error. Maybe wrong input file format or wrong set of labels? Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(std::string("cz.krejciadam.hammock.DataException: ") + e.what());
+        return 5;
+    } catch (const std::exception &e) {
+        logger.logAndStderr("Error. Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(e.what());
+        return 6;
+    }
+}
+
 // `hammock-hip io-selftest ...`: exposes the loaders / orderings to the CPU test-suite (no GPU involved)
 int ioSelftest(const std::vector<std::string> &args) {
     if (args.size() >= 3 && args[1] == "matrix") {
@@ -825,6 +1053,7 @@ int main(int argc, char **argv) {
         if (args[0] == "clinkage") return runSequenceClustering(args, true);
         if (args[0] == "search") return runSearch(args);
         if (args[0] == "assign") return runAssign(args);
+        if (args[0] == "continue") return runContinue(args);
         if (args[0] == "io-selftest") return ioSelftest(args);
         if (args[0] == "dump-matrix") {   // the default matrix in the text format FileIOManager.loadScoringMatrix reads
             std::cout << "# BLOSUM62 substitution matrix (public NCBI table), 24 x 24, order " << AMINO_ACIDS << "\n"

@@ -260,6 +260,49 @@ int hmk_assign_local(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32
                      uint32_t *best_cluster, int32_t *best_score, uint32_t *n_feasible,
                      hmk_neighbor_stats *stats);
 
+/* ---- continuing a greedy clustering with new sequences ---------------------------- */
+
+typedef struct {
+    uint64_t n_edges;            /* edges at or above the threshold: new x members plus new x new */
+    uint64_t pairs_scored;       /* pairs the two passes scored (members x members is never scored) */
+    uint32_t n_joined;           /* new sequences that joined a cluster */
+    uint32_t loop_rounds;        /* rounds of the device-side loop */
+    uint32_t host_precheck;      /* 1: the device pre-check could not hold the lists (a row overflowed its tables, or a region of
+                                    its buffer overran twice): the host built them */
+    uint32_t reserved;
+    double kernel_ms;            /* the two passes (device time) */
+    double loop_ms;              /* CSR, pre-check and loop (wall) */
+} hmk_continue_stats;
+
+/* Continues a greedy clustering: the second loop of LimitedGreedySequenceClusterer.cluster
+ * (LimitedGreedySequenceClusterer.java:59-67) with actualClusters = the given clusters (members in the given order) and
+ * actualSequences = the new sequences in index order, scorer ShiftedScorer(matrix, shift_penalty, max_shift), cluster
+ * scorer ClinkageClusterScorer(threshold).  One uploaded set (hmk_set_sequences) holds both sides:
+ *   members    [r0, r1): member r is in slot member_cluster[r - r0] of [0, n_clusters); slot c has the Java id
+ *              cluster_id[c] (distinct).  Cluster.size() starts as the sum of the members' uploaded sizes.
+ *   new        [q0, q1), disjoint from the members, taken in the order q0, q0 + 1, ... (either side may come first).
+ * New sequence x joins the cluster findNearestClusterParallel returns (ClinkageSequenceClusterer.java:243-294) if its
+ * complete-linkage score is >= threshold: cluster c is feasible iff every member m of c -- the new sequences that joined
+ * c before x included -- has score(m, x) >= threshold; feasible clusters rank by score, then size() descending, then id
+ * ascending.  A joiner adds its uploaded size to size() (Cluster.java:70-74).  A new sequence that joins nothing stays a
+ * singleton and is never a candidate for a later one (remainingSequences, :63-65): new sequences never seed clusters
+ * (phase 1, :77-120, does not run).  So continuing is NOT greedy on the old sequences followed by the new ones: there,
+ * phase 1 could have absorbed a new sequence into a fresh cluster.
+ * Only new x members and new x new are scored, on the GPU; the pre-check and the loop run on the device
+ * (hmk_greedy_cluster's k_greedy_precheck and k_loop_* rounds).
+ *   joined[x - q0]       the slot x joined, or -1
+ *   member_rank[x - q0]  x's position in Cluster.getSequences() after the call (the slot's member count plus the earlier
+ *                        new sequences that joined it), or -1
+ *   checks     HMK_ERR_BAD_ARG before the device is looked at (a host-only context answers them): the checks of
+ *              hmk_assign_shifted, and an asymmetric matrix -- the device loop needs score(a, b) = score(b, a), and all
+ *              17 matrices the reference ships are symmetric.  Then the checks of hmk_search_shifted.  Never
+ *              HMK_ERR_CAPACITY (the call grows its own scratch).  Zero slots: every new sequence stays alone.
+ * On a hmk_create_multi context the call runs on the root device. */
+int hmk_greedy_continue(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1,
+                        const uint32_t *member_cluster, const int32_t *cluster_id, uint32_t n_clusters,
+                        int max_shift, int shift_penalty, int threshold, int32_t *joined, int32_t *member_rank,
+                        hmk_continue_stats *stats);
+
 /* ---- greedy clustering -------------------------------------------------- */
 
 typedef struct {
