@@ -29,7 +29,7 @@ SYMBOLS = [
     "hmk_score_pairs_shifted", "hmk_score_with_shift", "hmk_score_pairs_local", "hmk_score_block_shifted", "hmk_score_block_local",
     "hmk_neighbors_shifted", "hmk_neighbors_local", "hmk_neighbors_shifted_dev", "hmk_compact_edges_dev", "hmk_pack_rows_dev", "hmk_unpack_rows_dev",
     "hmk_neighbors_last_plan", "hmk_search_shifted", "hmk_search_local", "hmk_search_best_shifted",
-    "hmk_assign_shifted", "hmk_assign_local", "hmk_greedy_continue",
+    "hmk_assign_shifted", "hmk_assign_local", "hmk_match_clusters_shifted", "hmk_match_clusters_local", "hmk_greedy_continue",
     "hmk_greedy_cluster", "hmk_greedy_from_edges", "hmk_greedy_from_edges_dev", "hmk_greedy_last_phases",
     "hmk_clinkage_cluster", "hmk_clinkage_from_edges", "hmk_set_java_hashset", "hmk_reserve",
 ]
@@ -122,6 +122,10 @@ def _load():
                                      C.POINTER(NeighborStats)]
     L.hmk_assign_local.argtypes = [vp, u32, u32, u32, u32, p_u32, p_i32, u32, i32, i32, i32, u32, p_u32, p_i32, p_u32,
                                    C.POINTER(NeighborStats)]
+    L.hmk_match_clusters_shifted.argtypes = [vp, u32, u32, p_u32, u32, u32, u32, p_u32, p_i32, u32, i32, i32, i32, u32, p_u32, p_i32, p_u32,
+                                             C.POINTER(NeighborStats)]
+    L.hmk_match_clusters_local.argtypes = [vp, u32, u32, p_u32, u32, u32, u32, p_u32, p_i32, u32, i32, i32, i32, u32, p_u32, p_i32, p_u32,
+                                           C.POINTER(NeighborStats)]
     L.hmk_greedy_continue.argtypes = [vp, u32, u32, u32, u32, p_u32, p_i32, u32, i32, i32, i32, p_i32, p_i32, C.POINTER(ContinueStats)]
     L.hmk_greedy_cluster.argtypes = [vp, i32, i32, i32, i32, p_i32, p_i32, p_i32, C.POINTER(GreedyStats)]
     L.hmk_greedy_from_edges_dev.argtypes = [vp, vp, u64, i32, i32, p_i32, p_i32, p_i32, C.POINTER(GreedyStats)]

@@ -330,6 +330,53 @@ class Context:
         """The same with LocalAlignmentScorer(seq1 = member, seq2 = new)."""
         return self._assign(N.lib.hmk_assign_local, q0, q1, r0, r1, member_cluster, cluster_id, gap_open, gap_extend, threshold, k)
 
+    # -- match of query clusters to existing clusters -----------------------------------------
+    # Upload both sides together once and rank, for every query cluster, the existing clusters every one of whose members scores at
+    # or above the threshold against every query member (ClinkageClusterScorer.clusterScore(existing, query cluster),
+    # ClinkageSequenceClusterer.java:263): the assignment with query clusters of any size.  Query clusters matched to the same
+    # existing cluster are not checked against each other.
+    def _match(self, fn, q0, q1, query_cluster, r0, r1, member_cluster, cluster_id, a, b, threshold, k):
+        qc = np.ascontiguousarray(np.asarray(query_cluster, dtype=np.int64).ravel())
+        if qc.size != max(int(q1) - int(q0), 0):
+            raise ValueError(f"query_cluster has {qc.size} entries for the {int(q1) - int(q0)} query sequences [q0, q1)")
+        if (qc < 0).any() or (qc > 0xFFFFFFFF).any():
+            raise ValueError("query_cluster holds values outside uint32")
+        mc = np.ascontiguousarray(np.asarray(member_cluster, dtype=np.int64).ravel())
+        cid = np.ascontiguousarray(np.asarray(cluster_id, dtype=np.int64).ravel())
+        if mc.size != max(int(r1) - int(r0), 0):
+            raise ValueError(f"member_cluster has {mc.size} entries for the {int(r1) - int(r0)} members [r0, r1)")
+        if (mc < 0).any() or (mc > 0xFFFFFFFF).any():
+            raise ValueError("member_cluster holds values outside uint32")
+        if (cid < -2 ** 31).any() or (cid >= 2 ** 31).any():
+            raise ValueError("cluster_id holds values outside int32")
+        nb = int(qc.max()) + 1 if qc.size else 0
+        qc, mc, cid = qc.astype(np.uint32), mc.astype(np.uint32), cid.astype(np.int32)
+        kk = max(int(k), 1)
+        best = np.empty((nb, kk), dtype=np.uint32)
+        score = np.empty((nb, kk), dtype=np.int32)
+        nf = np.empty(max(nb, 1), dtype=np.uint32)
+        stats = N.NeighborStats()
+        st = fn(self._h, int(q0), int(q1), _ptr(qc, C.c_uint32), nb, int(r0), int(r1), _ptr(mc, C.c_uint32), _ptr(cid, C.c_int32), int(cid.size),
+                int(a), int(b), int(threshold), int(k), _ptr(best, C.c_uint32), _ptr(score, C.c_int32), _ptr(nf, C.c_uint32), C.byref(stats))
+        if st:
+            self._raise(st)
+        self.last_match_stats = stats
+        return best, score, nf[:nb].copy()
+
+    def match_clusters_shifted(self, q0, q1, query_cluster, r0, r1, member_cluster, cluster_id, max_shift, shift_penalty, threshold, k=1):
+        """Query clusters (sequence x of [q0, q1) in query slot query_cluster[x - q0]; n_query_clusters = max + 1, every slot
+        non-empty) against the clusters of the members [r0, r1) (as assign_shifted's), ShiftedScorer, complete linkage over both
+        sides' members -> (best_cluster uint32[nb, k] = slots, best_score int32[nb, k], n_feasible uint32[nb]).  Ranked and padded
+        as assign_shifted's, which it equals when every query slot holds one sequence.  kernel_ms of last_match_stats includes
+        the pass, both aggregation levels and the selection."""
+        return self._match(N.lib.hmk_match_clusters_shifted, q0, q1, query_cluster, r0, r1, member_cluster, cluster_id, max_shift,
+                           shift_penalty, threshold, k)
+
+    def match_clusters_local(self, q0, q1, query_cluster, r0, r1, member_cluster, cluster_id, gap_open, gap_extend, threshold, k=1):
+        """The same with LocalAlignmentScorer(seq1 = member, seq2 = query)."""
+        return self._match(N.lib.hmk_match_clusters_local, q0, q1, query_cluster, r0, r1, member_cluster, cluster_id, gap_open, gap_extend,
+                           threshold, k)
+
     # -- continuing a greedy clustering with new sequences --------------------------------------
     # Upload members and new sequences together once -- set_sequences(members + new, sizes=...) -- and run the greedy's second loop
     # (LimitedGreedySequenceClusterer.java:59-67) over the new sequences in index order, seeded with the given clusters: a new

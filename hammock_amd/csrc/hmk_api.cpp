@@ -105,6 +105,8 @@ void hmk_destroy(hmk_ctx *ctx) {
         free_plan_local(ctx->plan_local_search);
         free_plan(ctx->plan_assign);
         free_plan_local(ctx->plan_local_assign);
+        free_plan(ctx->plan_match);
+        free_plan_local(ctx->plan_local_match);
         free_plan(ctx->plan_continue);
         free_plan(ctx->plan_continue_tri);
         if (ctx->d_res32) HMK_QUIET(hipFree(ctx->d_res32));
@@ -182,6 +184,8 @@ int hmk_set_sequences(hmk_ctx *ctx, const uint8_t *residues, const uint32_t *off
         free_plan_local(ctx->plan_local_search);
         free_plan(ctx->plan_assign);
         free_plan_local(ctx->plan_local_assign);
+        free_plan(ctx->plan_match);
+        free_plan_local(ctx->plan_local_match);
         free_plan(ctx->plan_continue);
         free_plan(ctx->plan_continue_tri);
         if (ctx->d_res32) (void)hipFree(ctx->d_res32);

@@ -11,12 +11,6 @@ namespace {
 
 enum { ASSIGN_SHIFTED = 0, ASSIGN_LOCAL = 1 };
 
-// The host's order of the clusters: size() descending, then cluster_id ascending -- the tie-breaks of the ranking after the
-// score.  rank_of[slot], slot_of_rank[rank], members_of_rank[rank].
-struct ClusterOrder {
-    std::vector<uint32_t> rank_of, slot_of_rank, members_of_rank;
-};
-
 }  // namespace
 
 // the checks of the clusters' description that the assignment and hmk_greedy_continue (hmk_continue.cpp) make before the device is
@@ -50,15 +44,12 @@ int check_clusters(hmk_ctx *ctx, const char *what, uint32_t q0, uint32_t q1, uin
     return HMK_OK;
 }
 
-namespace {
-
-// the argument checks before the device is looked at (a host-only context answers them too); fills `order`
-int check_assign(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, const uint32_t *member_cluster, const int32_t *cluster_id,
-                 uint32_t n_clusters, uint32_t k, ClusterOrder *order) {
+int check_assign(hmk_ctx *ctx, const char *what, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, const uint32_t *member_cluster,
+                 const int32_t *cluster_id, uint32_t n_clusters, uint32_t k, ClusterOrder *order) {
     if (k < 1 || k > 32) return fail(ctx, HMK_ERR_BAD_ARG, "k must be 1..32");
     std::vector<uint32_t> members;
     std::vector<int64_t> size;
-    const int st = check_clusters(ctx, "assignment", q0, q1, r0, r1, member_cluster, cluster_id, n_clusters, members, size);
+    const int st = check_clusters(ctx, what, q0, q1, r0, r1, member_cluster, cluster_id, n_clusters, members, size);
     if (st) return st;
     order->slot_of_rank.resize(n_clusters);
     for (uint32_t c = 0; c < n_clusters; c++) order->slot_of_rank[c] = c;
@@ -75,6 +66,34 @@ int check_assign(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r
     return HMK_OK;
 }
 
+// the pass of the rectangle members [r0, r1) x new [q0, q1) into ctx->d_edges, the members as the search's queries, which every
+// tier emits as m = seq1 (hmk_search.cpp), in the plan slots `pl` / `pll`; -> the shards' counts, their total, the stats
+// (kernel_ms = the pass)
+int cluster_pass(hmk_ctx *ctx, bool local, Plan &pl, PlanLocal &pll, int a, int b, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1,
+                 unsigned long long counts[HMK_EDGE_SHARDS], uint64_t *total, hmk_neighbor_stats *S) {
+    int st = !local ? build_plan_search(ctx, pl, a, b, thr, r0, r1, q0, q1) : build_plan_local_search(ctx, pll, r0, r1, q0, q1);
+    if (st) return st;
+    double ms = 0;
+    st = neighbors_grow(ctx, 0, counts, &ms, [&](uint64_t *d_edges, uint64_t cap, unsigned long long *d_counts) {
+        return !local ? launch_plan(ctx, pl, a, b, thr, d_edges, cap, d_counts, nullptr)
+                      : launch_plan_local(ctx, pll, a, b, thr, d_edges, cap, d_counts, nullptr);
+    });
+    if (st) return st;
+    *total = 0;
+    for (int s = 0; s < HMK_EDGE_SHARDS; s++) *total += counts[s];
+    if (!local) {
+        *S = pl.stats;
+    } else {
+        S->pairs_scored = pll.pairs;
+        S->n_tiles = pll.n_tiles;
+    }
+    S->n_edges = *total;
+    S->kernel_ms = ms;
+    return HMK_OK;
+}
+
+namespace {
+
 uint64_t max_count(const unsigned long long counts[HMK_EDGE_SHARDS]) {
     return *std::max_element(counts, counts + HMK_EDGE_SHARDS);
 }
@@ -86,7 +105,7 @@ int assign(hmk_ctx *ctx, int scorer, uint32_t q0, uint32_t q1, uint32_t r0, uint
     std::lock_guard<std::mutex> lock(ctx->mu);
     refresh_switches(ctx);
     ClusterOrder order;
-    int st = check_assign(ctx, q0, q1, r0, r1, member_cluster, cluster_id, n_clusters, k, &order);
+    int st = check_assign(ctx, "assignment", q0, q1, r0, r1, member_cluster, cluster_id, n_clusters, k, &order);
     if (st) return st;
     const uint32_t nq = q1 - q0, nm = r1 - r0;
     if (nq && (!best_cluster || !best_score || !n_feasible)) return fail(ctx, HMK_ERR_BAD_ARG, "null output buffer");
@@ -112,26 +131,11 @@ int assign(hmk_ctx *ctx, int scorer, uint32_t q0, uint32_t q1, uint32_t r0, uint
     uint32_t *d_cl = buf<uint32_t>(ctx, SB_ASSIGN_CL);
     HIPCHK(ctx, hipMemcpy(d_cl, cl.data(), cl.size() * 4, hipMemcpyHostToDevice));
 
-    // the pass: the members are the search's queries, which every tier emits as m = seq1 (hmk_search.cpp)
-    st = scorer == ASSIGN_SHIFTED ? build_plan_search(ctx, ctx->plan_assign, a, b, thr, r0, r1, q0, q1)
-                                  : build_plan_local_search(ctx, ctx->plan_local_assign, r0, r1, q0, q1);
-    if (st) return st;
     unsigned long long counts[HMK_EDGE_SHARDS];
-    double ms = 0;
-    st = neighbors_grow(ctx, 0, counts, &ms, [&](uint64_t *d_edges, uint64_t cap, unsigned long long *d_counts) {
-        return scorer == ASSIGN_SHIFTED ? launch_plan(ctx, ctx->plan_assign, a, b, thr, d_edges, cap, d_counts, nullptr)
-                                        : launch_plan_local(ctx, ctx->plan_local_assign, a, b, thr, d_edges, cap, d_counts, nullptr);
-    });
-    if (st) return st;
     uint64_t total = 0;
-    for (int s = 0; s < HMK_EDGE_SHARDS; s++) total += counts[s];
-    if (scorer == ASSIGN_SHIFTED) {
-        S = ctx->plan_assign.stats;
-    } else {
-        S.pairs_scored = ctx->plan_local_assign.pairs;
-        S.n_tiles = ctx->plan_local_assign.n_tiles;
-    }
-    S.n_edges = total;
+    st = cluster_pass(ctx, scorer == ASSIGN_LOCAL, ctx->plan_assign, ctx->plan_local_assign, a, b, thr, q0, q1, r0, r1, counts, &total, &S);
+    if (st) return st;
+    const double ms = S.kernel_ms;
     if (total > 0xFFFFFFFFull) return fail(ctx, HMK_ERR_OOM, "more than 2^32 - 1 member hits above the threshold: raise the threshold");
 
     const uint64_t nk = (uint64_t)nq * k;

@@ -53,6 +53,9 @@ enum {
                                                                                      // per-query counts + cursors, run starts, scan scratch, best-k
                                                                                      // (the assignment, hmk_assign.cpp, uses them too)
     SB_ASSIGN_CL,                                   // the assignment's clusters: member -> rank, members per rank, slot of each rank
+    SB_MATCH_CL,                                    // the match's clusters (hmk_match.cpp): SB_ASSIGN_CL's + query member -> query slot, members per query slot
+    SB_MATCH_REC,                                   // ... per query member its feasible (rank, min score) records
+    SB_MATCH_SCR,                                   // ... feasible counts per query member, per query slot counts + cursors + long runs, run starts
     SB_N
 };
 
@@ -151,6 +154,8 @@ struct hmk_ctx {
     PlanLocal plan_local_search;   // searches and clustering calls on one context do not rebuild each other's
     Plan plan_assign;              // the assignments' plans (hmk_assign.cpp: members = the search's queries): cached apart too
     PlanLocal plan_local_assign;
+    Plan plan_match;               // the cluster matches' plans (hmk_match.cpp: the assignment's rectangle): cached apart too
+    PlanLocal plan_local_match;
     Plan plan_continue;            // hmk_greedy_continue (hmk_continue.cpp): members x new (a rectangle) and new x new (a triangle)
     Plan plan_continue_tri;
     uint64_t *d_edges = nullptr;  // internal buffer of the host-buffer entry points
@@ -312,6 +317,20 @@ int check_shifted(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t q1,
 // members[c] = slot c's members, size[c] = its Cluster.size()
 int check_clusters(hmk_ctx *ctx, const char *what, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, const uint32_t *member_cluster,
                    const int32_t *cluster_id, uint32_t n_clusters, std::vector<uint32_t> &members, std::vector<int64_t> &size);
+// The host's order of the clusters: size() descending, then cluster_id ascending -- the tie-breaks of the ranking after the
+// score.  rank_of[slot], slot_of_rank[rank], members_of_rank[rank].
+struct ClusterOrder {
+    std::vector<uint32_t> rank_of, slot_of_rank, members_of_rank;
+};
+// the assignment's argument checks (k, then check_clusters) before the device is looked at (a host-only context answers them
+// too); fills `order`.  hmk_match.cpp makes them too.
+int check_assign(hmk_ctx *ctx, const char *what, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, const uint32_t *member_cluster,
+                 const int32_t *cluster_id, uint32_t n_clusters, uint32_t k, ClusterOrder *order);
+// the pass of the rectangle members [r0, r1) x new [q0, q1) into ctx->d_edges in the plan slot pl (shifted) / pll (local: `local`),
+// with the members as the search's queries (seq1); -> the shards' counts, their total; *S = the pass's stats (symmetric kept
+// for the local scorer), kernel_ms = the pass
+int cluster_pass(hmk_ctx *ctx, bool local, Plan &pl, PlanLocal &pll, int a, int b, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1,
+                 unsigned long long counts[HMK_EDGE_SHARDS], uint64_t *total, hmk_neighbor_stats *S);
 // ---- hmk_pass.cpp
 int neighbors_dev_locked(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_parts, void *d_edges,
                          uint64_t capacity, void *d_counts, hipStream_t stream, int which = LAUNCH_ALL,

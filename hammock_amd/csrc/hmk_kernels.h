@@ -160,6 +160,24 @@ hipError_t launch_assign(const uint64_t *edges, uint64_t cap_per_shard, const un
                          uint32_t q0, uint32_t nq, uint32_t r0, uint32_t nm, uint32_t k, const uint32_t *member_rank, const uint32_t *members_of_rank,
                          const uint32_t *slot_of_rank, uint32_t *scratch, uint32_t *start, uint64_t *scan_scratch, uint64_t *rec,
                          uint64_t rec_capacity, uint32_t *best_cluster, int32_t *best_score, uint32_t *n_feasible, hipStream_t s);
+// ... its first half alone: the edges' (cluster rank, score) records gathered into their new sequence's run rec[start[x] ..
+// start[x + 1]) (scratch: uint32[2 nq + 1] zeroed here, counts and cursors)
+hipError_t launch_assign_gather(const uint64_t *edges, uint64_t cap_per_shard, const unsigned long long *counts, uint64_t max_count, uint32_t q0,
+                                uint32_t nq, uint32_t r0, uint32_t nm, const uint32_t *member_rank, uint32_t *scratch, uint32_t *start,
+                                uint64_t *scan_scratch, uint64_t *rec, uint64_t rec_capacity, hipStream_t s);
+
+// match of query clusters to existing clusters (k_match.hip).  The segments of a pass over the query members [q0, q0 + nq) and the
+// existing members [r0, r0 + nm), `total` edges in all.  Level 1: per query member, every feasible existing cluster (rank, min
+// score) into feas[start[x] ..].  Level 2: per query cluster b (query_slot[x - q0], query_members[b] members) the ranks feasible for
+// all of its members, their minimum, and the best k by (score, size, ~id).  member_rank / members_of_rank / slot_of_rank as
+// launch_assign's.  Outputs best_cluster / best_score [nb * k] (unused slots 0xFFFFFFFF / INT32_MIN), n_feasible[nb].
+// scratch: uint32[3 nq + 1], start: uint32[nq + 1], scan_scratch: scan_scratch_bytes(max(nq, nb)), rec / feas: uint64[total],
+// scratch2: uint32[nq + 3 nb + 1], start2: uint32[nb + 1]
+hipError_t launch_match(const uint64_t *edges, uint64_t cap_per_shard, const unsigned long long *counts, uint64_t max_count, uint64_t total,
+                        uint32_t q0, uint32_t nq, uint32_t r0, uint32_t nm, uint32_t nb, uint32_t k, const uint32_t *member_rank,
+                        const uint32_t *members_of_rank, const uint32_t *slot_of_rank, const uint32_t *query_slot, const uint32_t *query_members,
+                        uint32_t *scratch, uint32_t *start, uint64_t *scan_scratch, uint64_t *rec, uint64_t *feas, uint64_t rec_capacity,
+                        uint32_t *scratch2, uint32_t *start2, uint32_t *best_cluster, int32_t *best_score, uint32_t *n_feasible, hipStream_t s);
 
 // force the deferred load of the code objects a clustering call launches from (hmk_create)
 hipError_t warm_neighbors_module();

@@ -8,6 +8,7 @@
 // GPUs of the node behind one context, the first is the root: hmk_create_multi).
 // Extra mode that the reference does not have: `hammock-hip search` (runSearch), queries against a reference set.
 // Extra mode that the reference does not have: `hammock-hip assign` (runAssign), new sequences into the clusters of a cluster file.
+// Extra mode that the reference does not have: `hammock-hip match` (runMatch), the clusters of one cluster file against another's.
 #include <future>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -127,7 +128,9 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "          hammock-hip assign -i <new sequences> --clusters <initial_clusters_sequences.tsv> -d <directory> [--best <int>]\n"
               << "                      [--skip_singletons] [-f fasta|tab] [-m <file>] [-x <int>] [-p <int>] [-g <int>] [--device <int>]\n"
               << "          hammock-hip continue -i <new sequences> --clusters <initial_clusters_sequences.tsv> -d <directory> [-f fasta|tab]\n"
-              << "                      [-m <file>] [-x <int>] [-p <int>] [-g <int>] [-R <order>] [-S <int>] [-l <labels>] [--device <int>]\n\n"
+              << "                      [-m <file>] [-x <int>] [-p <int>] [-g <int>] [-R <order>] [-S <int>] [-l <labels>] [--device <int>]\n"
+              << "          hammock-hip match -i <query clusters.tsv> --clusters <initial_clusters_sequences.tsv> -d <directory> [--best <int>]\n"
+              << "                      [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [-g <int>] [--device <int>]\n\n"
               << "-i, --input <file>\n\tA path to an input file\n\n"
               << "-d, --output_directory <directory>\n\tA directory to store all output files in\n\n"
               << "-t, --threads <int>\n\tAccepted for compatibility (the GPU path ignores it)\n\n"
@@ -144,9 +147,9 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "--device <int>\n\tHIP device ordinal (default 0)\n\n"
               << "--devices <int,int,...>\n\tShard the pair space over several GPUs of the node (the first one runs the merge)\n\n"
               << "--database <file>\n\t(search) the reference sequences every query (-i) is scored against\n\n"
-              << "--best <int>\n\t(search) keep only the best 1..32 hits of each query; (assign) report the best 1..32 feasible clusters (default 1)\n\n"
-              << "--clusters <file>\n\t(assign, continue) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv)\n\n"
-              << "--skip_singletons\n\t(assign) only clusters of more than one unique sequence are candidates\n\n"
+              << "--best <int>\n\t(search) keep only the best 1..32 hits of each query; (assign, match) report the best 1..32 feasible clusters (default 1)\n\n"
+              << "--clusters <file>\n\t(assign, continue, match) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv)\n\n"
+              << "--skip_singletons\n\t(assign, match) only clusters of more than one unique sequence are candidates\n\n"
               << "--java_hashset <8|7|6>\n\t(clinkage) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
 }
 
@@ -710,6 +713,178 @@ int runAssign(const std::vector<std::string> &args) {
     }
 }
 
+// `hammock-hip match -i query_clusters.tsv --clusters clusters.tsv -d dir ...`: every cluster of the -i cluster file (singletons
+// included) against the clusters of the --clusters file, complete linkage over both clusters' members with ShiftedScorer
+// (ClinkageClusterScorer.clusterScore(existing, query cluster): seq1 = existing member), the feasible clusters ranked as
+// findNearestClusterParallel ranks them (score, then size(), then id) to <dir>/cluster_matches.tsv, in the -i file's cluster order.
+// A match means the union of the two clusters is still a complete-linkage cluster; query clusters are matched one by one and
+// never checked against each other.  Defaults are assign's: -x and -g are greedy's over the --clusters file's sequences, -x then
+// clamped by the shortest sequence of both files; -p 0; --best 1.  --skip_singletons: only --clusters clusters of more than one
+// unique sequence are candidates.
+int runMatch(const std::vector<std::string> &args) {
+    Options o;
+    const std::string PARENT_DIR = parentDir();
+    o.matrixFile = PARENT_DIR + "/matrices/blosum62.txt";  // Hammock.java:45
+    parseCommonArgs(args, o);
+    parseGreedyArgs(args, o);
+    std::string clustersFile;
+    bool haveClusters = false, havePenalty = false, skipSingletons = false;
+    int best = 1;
+    for (size_t i = 1; i < args.size(); i++) {
+        const bool more = args.size() > i + 1;
+        if (args[i] == "--clusters" && more) { clustersFile = args[++i]; haveClusters = true; }
+        else if (args[i] == "--best" && more) {
+            best = javaIntegerDecode(args[++i]);
+            if (best < 1 || best > 32) throw CLIException("Error. --best may be 1 to 32.");
+        } else if (args[i] == "--skip_singletons") skipSingletons = true;
+        else if ((args[i] == "-p" || args[i] == "--gap_penalty") && more) havePenalty = true;
+    }
+    if (!o.devices.empty()) throw CLIException("Error. --devices is not available in mode match (a match runs on one device, --device).");
+    if (!o.haveInput) throw CLIException("Error. Parameter input file (-i or --input) missing with no default.");
+    if (!haveClusters) throw CLIException("Error. Parameter cluster file (--clusters) missing with no default.");
+    if (o.haveDir) {
+        if (exists(o.workingDirectory)) throw CLIException("Error. Output directory exists. Exiting to prevent data loss.");
+        mkdir(o.workingDirectory.c_str(), 0777);
+    } else {
+        std::string name;
+        mkdir((PARENT_DIR + "/dist").c_str(), 0777);
+        for (int i = 1; i < 9999; i++) {
+            name = PARENT_DIR + "/dist/Hammock_result_" + std::to_string(i);
+            if (!exists(name)) { mkdir(name.c_str(), 0777); break; }
+        }
+        o.workingDirectory = name;
+        std::cerr << "Creating default output directory: " << name << std::endl;
+    }
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        logger.logAndStderr(std::string("\nHammock version ") + VERSION +
+                            " Run with --help for a brief description of command line parameters.\n");
+        const std::vector<std::vector<int>> scoringMatrix = FileIOManager::loadScoringMatrix(o.matrixFile);
+        std::shared_future<std::shared_ptr<NativeContext>> contextReady = std::async(std::launch::async, [&scoringMatrix, &o]() {
+            return std::make_shared<NativeContext>(scoringMatrix, o.device);
+        });
+        logger.logWithTime("Program started in mode \"match\".");
+        std::string argsString;
+        for (auto &a : args) argsString += " " + a;
+        logger.logWithoutTime("Command-line arguments: \n" + argsString + "\n");
+        logger.logAndStderr("Loading clusters...");
+        const std::vector<ClusterPtr> clusters = FileIOManager::loadClustersFromCsv(clustersFile);
+        std::vector<UniqueSequencePtr> clusterSequences;
+        for (auto &cl : clusters) for (auto &s : cl->getSequences()) clusterSequences.push_back(s);
+        logger.logAndStderr(std::to_string(clusters.size()) + " clusters of " + std::to_string(clusterSequences.size()) + " sequences loaded.");
+        logger.logAndStderr("Loading query clusters...");
+        const std::vector<ClusterPtr> queries = FileIOManager::loadClustersFromCsv(o.inputFileName);
+        std::vector<UniqueSequencePtr> querySequences;
+        for (auto &cl : queries) for (auto &s : cl->getSequences()) querySequences.push_back(s);
+        logger.logAndStderr(std::to_string(queries.size()) + " query clusters of " + std::to_string(querySequences.size()) + " sequences loaded.");
+        if (querySequences.empty()) throw FileFormatException("Error. No query clusters to match.");
+        if (clusterSequences.empty()) throw FileFormatException("Error. The cluster file holds no clusters.");
+        for (auto &s : clusterSequences)
+            if (s->size() < 1) throw FileFormatException("Error in cluster file: " + clustersFile + " - the sequence " + s->getSequenceString() +
+                                                         " has no occurrences (Cluster.size() counts them).");
+        std::vector<UniqueSequencePtr> both(querySequences);
+        both.insert(both.end(), clusterSequences.begin(), clusterSequences.end());
+        const SequenceListSummary summary = summariseSequences(clusterSequences), bothSummary = summariseSequences(both);
+        if (bothSummary.maxLength > HMK_MAX_LEN)
+            throw HammockException("Error. The longest sequence has " + std::to_string(bothSummary.maxLength) + " amino acids; the GPU kernels of hammock-hip "
+                                   "take sequences of up to " + std::to_string(HMK_MAX_LEN) + " (Hammock's domain is 7-20).");
+        if (!o.haveMaxShift) {
+            o.maxShift = checkMaxShift(bothSummary, (int)javaRound(summary.meanLength() / 4));
+            logger.logAndStderr("Max shift not set. Setting automatically to: " + std::to_string(o.maxShift));
+        } else {
+            const int correct = checkMaxShift(bothSummary, o.maxShift);
+            if (o.maxShift != correct) {
+                o.maxShift = correct;
+                logger.logAndStderr("Setting max shift to " + std::to_string(correct) +
+                                    " as the length of the shortest sequence is only " + std::to_string(correct + 1));
+            }
+        }
+        if (!o.haveThreshold) {
+            o.sequenceClusteringThreshold = (int)javaRound(summary.meanLength() * 1.7);
+            logger.logAndStderr("Match threshold not set. Setting automatically to: " + std::to_string(o.sequenceClusteringThreshold));
+        }
+        if (!havePenalty) logger.logAndStderr("Gap penalty not set. Setting automatically to: " + std::to_string(o.shiftPenalty));
+
+        // the query clusters' sequences, then the candidates' members: queries [0, nq), members [nq, n)
+        std::vector<ClusterPtr> candidates;
+        for (auto &cl : clusters)
+            if (!skipSingletons || cl->getUniqueSize() > 1) candidates.push_back(cl);
+        std::vector<UniqueSequencePtr> upload;
+        std::vector<uint32_t> queryCluster, memberCluster;
+        std::vector<int32_t> clusterId;
+        for (uint32_t b = 0; b < (uint32_t)queries.size(); b++)
+            for (auto &s : queries[b]->getSequences()) { upload.push_back(s); queryCluster.push_back(b); }
+        const uint32_t nq = (uint32_t)upload.size(), nb = (uint32_t)queries.size();
+        for (uint32_t c = 0; c < (uint32_t)candidates.size(); c++) {
+            clusterId.push_back(candidates[c]->getId());
+            for (auto &s : candidates[c]->getSequences()) { upload.push_back(s); memberCluster.push_back(c); }
+        }
+        const uint32_t n = (uint32_t)upload.size();
+        size_t total = 0;
+        for (auto &s : upload) total += s->getSequence().size();
+        std::vector<uint8_t> res(total);
+        std::vector<uint32_t> off(n + 1, 0);
+        std::vector<int32_t> sizes(n);
+        for (uint32_t k = 0; k < n; k++) {
+            off[k + 1] = off[k] + (uint32_t)upload[k]->getSequence().size();
+            for (size_t r = 0; r < upload[k]->getSequence().size(); r++) res[off[k] + r] = (uint8_t)upload[k]->getSequence()[r];
+            sizes[k] = k < nq ? 1 : upload[k]->size();   // (a query sequence's size plays no part)
+        }
+        const std::shared_ptr<NativeContext> nc = contextReady.get();
+        hmk_ctx *c = nc->get();
+        int st = hmk_set_sequences(c, res.data(), off.data(), sizes.data(), n);
+        if (st) nc->raise(st, nullptr);
+        logger.logAndStderr("Matching...");
+        const auto time0 = std::chrono::steady_clock::now();
+        std::vector<uint32_t> bestCluster((size_t)nb * best), nFeasible(nb);
+        std::vector<int32_t> bestScore((size_t)nb * best);
+        hmk_neighbor_stats stats{};
+        st = hmk_match_clusters_shifted(c, 0, nq, queryCluster.data(), nb, nq, n, memberCluster.data(), clusterId.data(), (uint32_t)candidates.size(),
+                                        o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold, (uint32_t)best, bestCluster.data(), bestScore.data(),
+                                        nFeasible.data(), &stats);
+        if (st) nc->raise(st, nullptr);
+        const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - time0).count();
+        size_t matched = 0;
+        for (uint32_t b = 0; b < nb; b++) matched += nFeasible[b] > 0;
+        logger.logAndStderr("Ready. Match time: " + std::to_string(ms));
+        logger.logAndStderr("Candidate clusters: " + std::to_string(candidates.size()) + ", query clusters matched: " + std::to_string(matched) + " of " +
+                            std::to_string(nb) + ", pairs scored: " + std::to_string(stats.pairs_scored) + ", GPU kernels: " +
+                            std::to_string(stats.kernel_ms) + " ms");
+        const std::string outFile = o.workingDirectory + "/cluster_matches.tsv";
+        {
+            std::ofstream out(outFile);
+            if (!out) throw HammockException("cannot write " + outFile);
+            out << "cluster_id\trank\tmatched_cluster_id\tscore\tmatched_size\tfeasible_clusters\n";
+            for (uint32_t b = 0; b < nb; b++) {
+                const int id = queries[b]->getId();
+                if (nFeasible[b] == 0) { out << id << "\tNA\tNA\tNA\tNA\t0\n"; continue; }
+                for (uint32_t t = 0; t < std::min<uint32_t>(nFeasible[b], (uint32_t)best); t++) {
+                    const ClusterPtr &cl = candidates[bestCluster[(size_t)b * best + t]];
+                    out << id << '\t' << t + 1 << '\t' << cl->getId() << '\t' << bestScore[(size_t)b * best + t] << '\t' << cl->size() << '\t'
+                        << nFeasible[b] << '\n';
+                }
+            }
+        }
+        logger.logAndStderr("Matches in: " + outFile);
+        logger.logWithTime("Program successfully ended.");
+        return 0;
+    } catch (const CLIException &) {
+        throw;
+    } catch (const FileFormatException &e) {
+        logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
+        return 3;
+    } catch (const DataException &e) {
+        logger.logAndStderr("Error. Maybe wrong input file format or wrong set of labels? Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(std::string("cz.krejciadam.hammock.DataException: ") + e.what());
+        return 5;
+    } catch (const std::exception &e) {
+        logger.logAndStderr("Error. Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(e.what());
+        return 6;
+    }
+}
+
 // `hammock-hip continue -i new.fa --clusters initial_clusters_sequences.tsv -d dir ...`: continues the greedy clustering of a cluster
 // file with new sequences -- the second loop of LimitedGreedySequenceClusterer.cluster (LimitedGreedySequenceClusterer.java:59-67,
 // hmk_greedy_continue) with the file's clusters of more than one unique sequence as actualClusters (:41-50) and the new sequences,
@@ -1054,6 +1229,7 @@ int main(int argc, char **argv) {
         if (args[0] == "search") return runSearch(args);
         if (args[0] == "assign") return runAssign(args);
         if (args[0] == "continue") return runContinue(args);
+        if (args[0] == "match") return runMatch(args);
         if (args[0] == "io-selftest") return ioSelftest(args);
         if (args[0] == "dump-matrix") {   // the default matrix in the text format FileIOManager.loadScoringMatrix reads
             std::cout << "# BLOSUM62 substitution matrix (public NCBI table), 24 x 24, order " << AMINO_ACIDS << "\n"

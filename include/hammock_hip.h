@@ -260,6 +260,42 @@ int hmk_assign_local(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32
                      uint32_t *best_cluster, int32_t *best_score, uint32_t *n_feasible,
                      hmk_neighbor_stats *stats);
 
+/* ---- match of query clusters to existing clusters -------------------------------- */
+
+/* Which existing cluster does each query cluster match?  ClinkageClusterScorer.clusterScore(existing cluster, query cluster)
+ * (ClinkageClusterScorer.java:30-49) ranked as findNearestClusterParallel ranks it (ClinkageSequenceClusterer.java:137-177,
+ * 258-293), for every query cluster at once -- hmk_assign_shifted is the case of one member per query cluster.  One uploaded
+ * set (hmk_set_sequences) holds both sides:
+ *   queries    [q0, q1): sequence x belongs to query slot query_cluster[x - q0] in [0, n_query_clusters); every slot has a
+ *              member.
+ *   members    [r0, r1), disjoint from the queries, with member_cluster, cluster_id and n_clusters as hmk_assign_shifted's
+ *              (Cluster.size() = the sum of the members' uploaded sizes).
+ * score(m, x) = sequenceScore(seq1 = member m, seq2 = query x), the orientation of ClinkageSequenceClusterer.java:263.
+ * Existing cluster a is feasible for query cluster b iff every pair (m in a, x in b) has score(m, x) >= threshold; its
+ * complete-linkage score is then the minimum over those pairs.  Feasible clusters rank by score descending, then size()
+ * descending, then cluster_id ascending; rank 1 is the cluster findNearestClusterParallel(existing clusters, b) returns.
+ * A match means the union of the two clusters is still a complete-linkage cluster.  Classification, not merging: two query
+ * clusters matched to the same existing cluster are not checked against each other.
+ *   outputs    best_cluster[b * k + t] = the slot of rank t + 1, best_score[b * k + t] its score; unused entries
+ *              UINT32_MAX / INT32_MIN.  n_feasible[b] = ALL feasible clusters (not capped at k); 0 = no match.  With one
+ *              member per query slot all three equal hmk_assign_shifted's on the same arguments.
+ *   checks     HMK_ERR_BAD_ARG (before the device is looked at: a host-only context answers them): those of
+ *              hmk_assign_shifted; a null query_cluster with a non-empty query range; a query_cluster value >= n_query_clusters;
+ *              a query slot without a member.  Then the checks of hmk_search_shifted.  Never HMK_ERR_CAPACITY (the call grows
+ *              its own scratch); more than 2^32 - 1 hits: HMK_ERR_OOM.
+ *   stats      as hmk_assign_shifted's; kernel_ms includes the pass, both aggregation levels and the selection.
+ * On a hmk_create_multi context the match runs on the root device. */
+int hmk_match_clusters_shifted(hmk_ctx *ctx, uint32_t q0, uint32_t q1, const uint32_t *query_cluster, uint32_t n_query_clusters,
+                               uint32_t r0, uint32_t r1, const uint32_t *member_cluster, const int32_t *cluster_id, uint32_t n_clusters,
+                               int max_shift, int shift_penalty, int threshold, uint32_t k,
+                               uint32_t *best_cluster, int32_t *best_score, uint32_t *n_feasible, hmk_neighbor_stats *stats);
+/* The same with LocalAlignmentScorer(matrix, gap_open, gap_extend).sequenceScore(seq1 = member, seq2 = query), under the
+ * preconditions of hmk_search_local. */
+int hmk_match_clusters_local(hmk_ctx *ctx, uint32_t q0, uint32_t q1, const uint32_t *query_cluster, uint32_t n_query_clusters,
+                             uint32_t r0, uint32_t r1, const uint32_t *member_cluster, const int32_t *cluster_id, uint32_t n_clusters,
+                             int gap_open, int gap_extend, int threshold, uint32_t k,
+                             uint32_t *best_cluster, int32_t *best_score, uint32_t *n_feasible, hmk_neighbor_stats *stats);
+
 /* ---- continuing a greedy clustering with new sequences ---------------------------- */
 
 typedef struct {
