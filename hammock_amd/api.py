@@ -499,6 +499,77 @@ class Context:
             self._raise(st)
         return cid[:self.n], order[:stats.n_result_clusters], stats
 
+    # -- merging given clusters by complete linkage ---------------------------------------
+    @staticmethod
+    def _merge_args(r0, r1, member_cluster, cluster_id):
+        mc = np.ascontiguousarray(np.asarray(member_cluster, dtype=np.int64).ravel())
+        if mc.size != max(int(r1) - int(r0), 0):
+            raise ValueError(f"member_cluster has {mc.size} entries for the {int(r1) - int(r0)} members [r0, r1)")
+        if (mc < 0).any() or (mc > 0xFFFFFFFF).any():
+            raise ValueError("member_cluster holds values outside uint32")
+        cid = None
+        if cluster_id is not None:
+            cid = np.ascontiguousarray(np.asarray(cluster_id, dtype=np.int64).ravel())
+            if (cid < -2 ** 31).any() or (cid >= 2 ** 31).any():
+                raise ValueError("cluster_id holds values outside int32")
+            cid = cid.astype(np.int32)
+        return mc.astype(np.uint32), cid
+
+    def cluster_pairs_shifted(self, r0, r1, member_cluster, n_clusters, max_shift, shift_penalty, threshold, capacity=None):
+        """hmk_cluster_pairs_shifted: the pairs of given clusters (members [r0, r1), member r in slot member_cluster[r - r0])
+        that are feasible for each other -> packed pairs uint64[] (x = smaller slot, m = larger slot, score = the
+        complete-linkage score; edge_fields unpacks them).  Statistics: last_merge_stats."""
+        mc, _ = self._merge_args(r0, r1, member_cluster, None)
+        cap = int(capacity) if capacity is not None else 1 << 16
+        while True:
+            buf = np.empty(max(cap, 1), dtype=np.uint64)
+            n = C.c_uint64(0)
+            stats = N.MergeStats()
+            st = N.lib.hmk_cluster_pairs_shifted(self._h, int(r0), int(r1), _ptr(mc, C.c_uint32), int(n_clusters), int(max_shift),
+                                                 int(shift_penalty), int(threshold), _ptr(buf, C.c_uint64), cap, C.byref(n), C.byref(stats))
+            if st == N.HMK_ERR_CAPACITY and capacity is None:
+                cap = int(n.value)
+                continue
+            if st:
+                self._raise(st)
+            self.last_merge_stats = stats
+            return buf[:n.value].copy()
+
+    def _merge_out(self, nm, ncl):
+        merged = np.full(max(ncl, 1), -1, dtype=np.int32)
+        order = np.full(max(ncl, 1), -1, dtype=np.int32)
+        self.member_rank = np.zeros(max(nm, 1), dtype=np.int32)
+        return merged, order, N.MergeStats()
+
+    def clinkage_merge(self, r0, r1, member_cluster, cluster_id, max_shift, shift_penalty, threshold):
+        """hmk_clinkage_merge: the reference's complete-linkage agglomeration started from the given clusters (members
+        [r0, r1), member r in slot member_cluster[r - r0], slot c with Java id cluster_id[c]) -> (merged_id int32[n_clusters],
+        result_order int32[n_result]); member_rank in self.member_rank[:r1 - r0], statistics in last_merge_stats."""
+        mc, cid = self._merge_args(r0, r1, member_cluster, cluster_id)
+        merged, order, stats = self._merge_out(mc.size, cid.size)
+        st = N.lib.hmk_clinkage_merge(self._h, int(r0), int(r1), _ptr(mc, C.c_uint32), _ptr(cid, C.c_int32), int(cid.size), int(max_shift),
+                                      int(shift_penalty), int(threshold), _ptr(merged, C.c_int32), _ptr(order, C.c_int32),
+                                      _ptr(self.member_rank, C.c_int32), C.byref(stats))
+        if st:
+            self._raise(st)
+        self.last_merge_stats = stats
+        self.member_rank = self.member_rank[:mc.size]
+        return merged[:cid.size], order[:stats.n_result_clusters]
+
+    def clinkage_merge_from_edges(self, edges, r0, r1, member_cluster, cluster_id):
+        """hmk_clinkage_merge_from_edges: the same from a sequence-level edge list (works on a host-only context)."""
+        edges = np.ascontiguousarray(edges, dtype=np.uint64)
+        mc, cid = self._merge_args(r0, r1, member_cluster, cluster_id)
+        merged, order, stats = self._merge_out(mc.size, cid.size)
+        st = N.lib.hmk_clinkage_merge_from_edges(self._h, _ptr(edges, C.c_uint64), edges.size, int(r0), int(r1), _ptr(mc, C.c_uint32),
+                                                 _ptr(cid, C.c_int32), int(cid.size), _ptr(merged, C.c_int32), _ptr(order, C.c_int32),
+                                                 _ptr(self.member_rank, C.c_int32), C.byref(stats))
+        if st:
+            self._raise(st)
+        self.last_merge_stats = stats
+        self.member_rank = self.member_rank[:mc.size]
+        return merged[:cid.size], order[:stats.n_result_clusters]
+
     def greedy_phases(self):
         """hmk_greedy_last_phases: per-phase milliseconds of the last greedy_cluster / greedy_from_edges_dev call."""
         ph = N.GreedyPhases()

@@ -109,6 +109,7 @@ void hmk_destroy(hmk_ctx *ctx) {
         free_plan_local(ctx->plan_local_match);
         free_plan(ctx->plan_continue);
         free_plan(ctx->plan_continue_tri);
+        free_plan(ctx->plan_merge);
         if (ctx->d_res32) HMK_QUIET(hipFree(ctx->d_res32));
         if (ctx->d_len) HMK_QUIET(hipFree(ctx->d_len));
         if (ctx->d_M) HMK_QUIET(hipFree(ctx->d_M));
@@ -124,6 +125,7 @@ void hmk_destroy(hmk_ctx *ctx) {
         if (ctx->xfer_stream) HMK_QUIET(hipStreamDestroy(ctx->xfer_stream));   // (this device's transfers to the others, hmk_multi.cpp)
         if (ctx->h_start) HMK_QUIET(hipHostFree(ctx->h_start));
         if (ctx->h_stage) HMK_QUIET(hipHostFree(ctx->h_stage));
+        if (ctx->h_merge) HMK_QUIET(hipHostFree(ctx->h_merge));
         if (ctx->h_adj) HMK_QUIET(hipHostFree(ctx->h_adj));
         if (ctx->h_counts) HMK_QUIET(hipHostFree(ctx->h_counts));
         if (ctx->h_loop) HMK_QUIET(hipHostFree(ctx->h_loop));
@@ -188,6 +190,7 @@ int hmk_set_sequences(hmk_ctx *ctx, const uint8_t *residues, const uint32_t *off
         free_plan_local(ctx->plan_local_match);
         free_plan(ctx->plan_continue);
         free_plan(ctx->plan_continue_tri);
+        free_plan(ctx->plan_merge);
         if (ctx->d_res32) (void)hipFree(ctx->d_res32);
         if (ctx->d_len) (void)hipFree(ctx->d_len);
         ctx->d_res32 = nullptr;

@@ -15,8 +15,10 @@
 //   findNearestClusterParallel(activeClusters, top, ..) (ClinkageSequenceClusterer.java:137-177,258-293)
 //     = arg-max over the candidates of (score, Cluster.size(), smaller id); null if there is none.
 //
-// Every cluster keeps its candidate list sorted by cluster id.  New ids only grow (currentId++, :97), so appending the
-// merged cluster to its candidates' lists keeps them sorted; entries of merged-away clusters are dropped lazily.
+// Every cluster keeps its candidate list sorted (by the clusters' dense numbers, see chain_impl).  New ids and numbers only grow
+// (currentId++, :97), so appending the merged cluster to its candidates' lists keeps them sorted; entries of merged-away clusters are
+// dropped lazily.  The chain starts from given clusters (hmk_merge.cpp: :50-55 replaced); one cluster per sequence with the ids 1 .. n,
+// what :50-55 make, is the case hmk_clinkage_cluster runs.
 // The arbitrary start of every chain is activeClusters.iterator().next() of a java.util.HashSet<Cluster>: its iteration
 // order (Java 8+: Cluster.hashCode() = 79 * 7 + id, HashMap.hash = h ^ h >>> 16, power-of-two table from 16, load factor
 // 0.75, insertion-ordered chains, no shrinking) is emulated, as is the order of the returned list (the HashSet
@@ -33,11 +35,13 @@ namespace hmk {
 
 namespace {
 
-// java.util.HashSet<Cluster> keyed by cluster id (see the header comment).
+// java.util.HashSet<Cluster> keyed by cluster id (see the header comment).  The set holds the clusters' DENSE numbers (slot c of a
+// given cluster, n_clusters + k of the k-th merge); rid[number] is the Java id the hash is taken of.
 //   version 8 (default): Java 8 and later -- hash = h ^ h >>> 16, a new node is APPENDED to its bucket's chain, a resize splits
 //                        the chains preserving their order.  A bucket that reaches 8 nodes in a table of 64+ would be
 //                        treeified (its iteration order then starts at the tree's root): that is not modelled; it cannot
-//                        happen for the consecutive ids used here at load factor 0.75, and `unmodelled()` says so if it did.
+//                        happen for consecutive ids at load factor 0.75 (hmk_clinkage_cluster), it can for ids a caller of
+//                        hmk_clinkage_merge chose, and `unmodelled()` says so.
 //   version 7: JDK 7u6 ... 7u80 (the reference is a Java 1.7 project, nbproject/project.properties:45-46) --
 //              hash = h ^ h >>> 20 ^ h >>> 12, then h ^ h >>> 7 ^ h >>> 4; a new entry goes to the HEAD of its chain; addEntry
 //              resizes BEFORE inserting when size >= threshold and the target bucket is not empty; transfer() walks the old
@@ -45,20 +49,21 @@ namespace {
 //   version 6: JDK 6 and JDK 7 before 7u6 -- as 7, but the entry is inserted first and the table resized when size++ >= threshold.
 class JavaClusterSet {
     std::vector<int32_t> head_, tail_, next_;
+    const int32_t *rid_;
     uint32_t cap_ = 16, size_ = 0, lowest_ = 0;
     int version_ = 8;
     bool unmodelled_ = false;
-    uint32_t bucket(int32_t id) const {
-        uint32_t h = (uint32_t)(553 + id);   // Cluster.java:178-183
+    uint32_t bucket(int32_t ix) const {
+        uint32_t h = (uint32_t)(553 + rid_[ix]);   // Cluster.java:178-183
         if (version_ == 8) h ^= h >> 16;
         else { h ^= (h >> 20) ^ (h >> 12); h ^= (h >> 7) ^ (h >> 4); }
         return h & (cap_ - 1);
     }
-    void append(int32_t id) {   // Java 8+
-        const uint32_t b = bucket(id);
-        next_[id] = -1;
-        if (head_[b] < 0) head_[b] = id; else next_[tail_[b]] = id;
-        tail_[b] = id;
+    void append(int32_t ix) {   // Java 8+
+        const uint32_t b = bucket(ix);
+        next_[ix] = -1;
+        if (head_[b] < 0) head_[b] = ix; else next_[tail_[b]] = ix;
+        tail_[b] = ix;
         lowest_ = std::min(lowest_, b);
         if (cap_ >= 64) {       // TREEIFY_THRESHOLD = 8, MIN_TREEIFY_CAPACITY = 64
             uint32_t len = 0;
@@ -66,11 +71,11 @@ class JavaClusterSet {
             if (len >= 8) unmodelled_ = true;
         }
     }
-    void push_head(int32_t id) {   // Java <= 7: table[i] = new Entry(.., table[i])
-        const uint32_t b = bucket(id);
-        next_[id] = head_[b];
-        if (head_[b] < 0) tail_[b] = id;
-        head_[b] = id;
+    void push_head(int32_t ix) {   // Java <= 7: table[i] = new Entry(.., table[i])
+        const uint32_t b = bucket(ix);
+        next_[ix] = head_[b];
+        if (head_[b] < 0) tail_[b] = ix;
+        head_[b] = ix;
         lowest_ = std::min(lowest_, b);
     }
     void grow() {
@@ -82,31 +87,32 @@ class JavaClusterSet {
         head_.assign(cap_, -1);
         tail_.assign(cap_, -1);
         lowest_ = cap_;
-        for (int32_t id2 : order) { if (version_ == 8) append(id2); else push_head(id2); }
+        for (int32_t ix2 : order) { if (version_ == 8) append(ix2); else push_head(ix2); }
     }
 public:
-    JavaClusterSet(uint32_t max_id, int version) : head_(16, -1), tail_(16, -1), next_((size_t)max_id + 1, -1), version_(version) {}
+    // rid: the Java ids by dense number (the array may still be filled in behind the numbers already added)
+    JavaClusterSet(uint32_t numbers, const int32_t *rid, int version) : head_(16, -1), tail_(16, -1), next_((size_t)numbers, -1), rid_(rid), version_(version) {}
     uint32_t size() const { return size_; }
     bool unmodelled() const { return unmodelled_; }
-    void add(int32_t id) {
+    void add(int32_t ix) {
         const uint32_t threshold = cap_ / 4 * 3;
         if (version_ == 8) {
-            append(id);
+            append(ix);
             if (++size_ > threshold) grow();   // resize(): chains are split preserving their order
         } else if (version_ == 7) {
-            if (size_ >= threshold && head_[bucket(id)] >= 0) grow();
-            push_head(id);
+            if (size_ >= threshold && head_[bucket(ix)] >= 0) grow();
+            push_head(ix);
             size_++;
         } else {
-            push_head(id);
+            push_head(ix);
             if (size_++ >= threshold) grow();
         }
     }
-    void remove(int32_t id) {
-        const uint32_t b = bucket(id);
+    void remove(int32_t ix) {
+        const uint32_t b = bucket(ix);
         int32_t prev = -1;
         for (int32_t cur = head_[b]; cur >= 0; prev = cur, cur = next_[cur]) {
-            if (cur != id) continue;
+            if (cur != ix) continue;
             if (prev < 0) head_[b] = next_[cur]; else next_[prev] = next_[cur];
             if (tail_[b] == cur) tail_[b] = prev;
             size_--;
@@ -123,38 +129,42 @@ public:
     }
 };
 
-struct CNbr { int32_t id, score; };   // candidate cluster, complete-linkage score
+using CNbr = ClinkCand;   // candidate cluster (dense number), complete-linkage score
 
-template <class NbrT>
-int clinkage_impl(uint32_t n, const int32_t *sizes, const uint64_t *start, const NbrT *adj, int32_t *cluster_id,
-                  int32_t *result_order, int32_t *member_rank, hmk_clinkage_stats *st, std::string *err, int hashset_version) {
+// The chain from seeds.  Every array is indexed by the clusters' dense numbers: given ids go up to 2^30.  A merged cluster gets the
+// next number and the next id, both larger than every earlier one, so appending it to its candidates' lists keeps them sorted by
+// number; the join only needs SOME common order of the two lists, and the arg-max's tie-break (score, size, smaller id) does not
+// depend on the order of a list.
+int chain_impl(ClinkSeeds &S, int32_t *cluster_id, int32_t *result_order, int32_t *member_rank, hmk_clinkage_stats *st, std::string *err,
+               int hashset_version) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (n == 0) {   // activeClusters.iterator().next() on an empty set, :118
+    const uint32_t ns = S.n_clusters;
+    if (ns == 0) {   // activeClusters.iterator().next() on an empty set, :118
         if (err) *err = "the reference throws NoSuchElementException here (ClinkageSequenceClusterer.java:118): empty input";
         return HMK_ERR_REFERENCE_WOULD_CRASH;
     }
-    const uint32_t max_id = 2 * n + 2;
-    std::vector<std::vector<CNbr>> cand((size_t)max_id + 1);
-    std::vector<char> alive((size_t)max_id + 1, 0);
-    std::vector<int64_t> csize((size_t)max_id + 1, 0);   // Cluster.size()
-    // member lists as chains over the sequences: head / tail per cluster, next per sequence (top's members, then the
-    // nearest's, :105-106)
-    std::vector<int32_t> mhead((size_t)max_id + 1, -1), mtail((size_t)max_id + 1, -1), mnext(n, -1);
-    JavaClusterSet active(max_id, hashset_version), ready(max_id, hashset_version);
-    int32_t current_id = 1;
-    for (uint32_t k = 0; k < n; k++) {   // :50-55: one cluster per sequence, ids from 1 in list order
-        const int32_t id = current_id++;
-        std::vector<CNbr> &l = cand[id];
-        l.reserve(start[k + 1] - start[k]);
-        for (uint64_t q = start[k]; q < start[k + 1]; q++) l.push_back(CNbr{(int32_t)adj[q].id() + 1, adj[q].score()});
-        std::sort(l.begin(), l.end(), [](const CNbr &a, const CNbr &b) { return a.id < b.id; });
-        alive[id] = 1;
-        csize[id] = sizes ? sizes[k] : 1;
-        mhead[id] = mtail[id] = (int32_t)k;
-        active.add(id);
+    const size_t numbers = 2 * (size_t)ns;   // at most ns - 1 merges
+    std::vector<std::vector<CNbr>> &cand = S.cand;
+    cand.resize(numbers);
+    std::vector<int32_t> rid(numbers, 0);
+    std::vector<char> alive(numbers, 0);
+    std::vector<int64_t> csize(numbers, 0);   // Cluster.size()
+    // member lists as chains over the members: head / tail per cluster, next per member (top's members, then the nearest's, :105-106)
+    std::vector<int32_t> &mhead = S.mhead, &mtail = S.mtail, &mnext = S.mnext;
+    mhead.resize(numbers, -1);
+    mtail.resize(numbers, -1);
+    JavaClusterSet active((uint32_t)numbers, rid.data(), hashset_version), ready((uint32_t)numbers, rid.data(), hashset_version);
+    int32_t current_id = 0, next_ix = (int32_t)ns;
+    for (uint32_t c = 0; c < ns; c++) {   // :50-55 replaced: the given clusters in slot order
+        rid[c] = S.id[c];
+        current_id = std::max(current_id, S.id[c]);
+        alive[c] = 1;
+        csize[c] = S.size[c];
+        active.add((int32_t)c);
     }
+    current_id++;   // (:50-55 leave currentId one past the last id given out)
     std::vector<int32_t> stack;
-    std::vector<char> on_stack((size_t)max_id + 1, 0);
+    std::vector<char> on_stack(numbers, 0);
     std::vector<CNbr> merged;
     while (active.size() > 1) {                       // :63
         stack.push_back(active.first());              // :70-71
@@ -167,11 +177,11 @@ int clinkage_impl(uint32_t n, const int32_t *sizes, const uint64_t *start, const
             int32_t nearest = -1, best = 0;
             for (size_t q = 0; q < l.size(); q++) {
                 const CNbr e = l[q];
-                if (!alive[e.id]) continue;
+                if (!alive[e.ix]) continue;
                 l[w++] = e;
                 if (nearest < 0 || e.score > best ||
-                    (e.score == best && (csize[e.id] > csize[nearest] || (csize[e.id] == csize[nearest] && e.id < nearest)))) {
-                    nearest = e.id;
+                    (e.score == best && (csize[e.ix] > csize[nearest] || (csize[e.ix] == csize[nearest] && rid[e.ix] < rid[nearest])))) {
+                    nearest = e.ix;
                     best = e.score;
                 }
             }
@@ -191,30 +201,31 @@ int clinkage_impl(uint32_t n, const int32_t *sizes, const uint64_t *start, const
                 on_stack[top] = on_stack[nearest] = 0;
                 active.remove(top);
                 active.remove(nearest);
-                const int32_t nid = current_id;
+                const int32_t nix = next_ix++;
+                rid[nix] = current_id;
                 // join (:102): candidates of the merged cluster = common candidates, element-wise min score
                 merged.clear();
                 const std::vector<CNbr> &a = cand[top], &b = cand[nearest];
                 for (size_t i = 0, j = 0; i < a.size() && j < b.size();) {
-                    if (a[i].id < b[j].id) i++;
-                    else if (a[i].id > b[j].id) j++;
+                    if (a[i].ix < b[j].ix) i++;
+                    else if (a[i].ix > b[j].ix) j++;
                     else {
-                        if (alive[a[i].id] && a[i].id != top && a[i].id != nearest)
-                            merged.push_back(CNbr{a[i].id, std::min(a[i].score, b[j].score)});
+                        if (alive[a[i].ix] && a[i].ix != top && a[i].ix != nearest)
+                            merged.push_back(CNbr{a[i].ix, std::min(a[i].score, b[j].score)});
                         i++; j++;
                     }
                 }
                 alive[top] = alive[nearest] = 0;
-                alive[nid] = 1;
-                csize[nid] = csize[top] + csize[nearest];
+                alive[nix] = 1;
+                csize[nix] = csize[top] + csize[nearest];
                 mnext[mtail[top]] = mhead[nearest];   // :105-106
-                mhead[nid] = mhead[top];
-                mtail[nid] = mtail[nearest];
-                for (const CNbr &e : merged) cand[e.id].push_back(CNbr{nid, e.score});   // nid is the largest id: stays sorted
-                cand[nid] = merged;
+                mhead[nix] = mhead[top];
+                mtail[nix] = mtail[nearest];
+                for (const CNbr &e : merged) cand[e.ix].push_back(CNbr{nix, e.score});   // nix is the largest number: stays sorted
+                cand[nix] = merged;
                 std::vector<CNbr>().swap(cand[top]);
                 std::vector<CNbr>().swap(cand[nearest]);
-                active.add(nid);
+                active.add(nix);
                 st->merges++;
             } else {
                 if (on_stack[nearest]) {
@@ -224,7 +235,7 @@ int clinkage_impl(uint32_t n, const int32_t *sizes, const uint64_t *start, const
                     // then, and the run ends in NoSuchElementException (:118, the active set ran empty) or returns a list in
                     // which a sequence belongs to two clusters -- nothing an int32 cluster_id[n] can reproduce.
                     if (err)
-                        *err = "the reference's nearest-neighbour chain returns to cluster " + std::to_string(nearest) +
+                        *err = "the reference's nearest-neighbour chain returns to cluster " + std::to_string(rid[nearest]) +
                                ", which is still on its stack (ClinkageSequenceClusterer.java:96-113 has no check): it goes on with a "
                                "stale Cluster object and throws NoSuchElementException (:118) or returns a sequence in two clusters";
                     return HMK_ERR_REFERENCE_WOULD_CRASH;
@@ -236,26 +247,59 @@ int clinkage_impl(uint32_t n, const int32_t *sizes, const uint64_t *start, const
     }
     ready.add(active.first());                        // :118
     int32_t out = 0;
-    ready.for_each([&](int32_t id) {                  // :121-123: the HashSet's iteration order
+    ready.for_each([&](int32_t ix) {                  // :121-123: the HashSet's iteration order
         int32_t pos = 0;
-        for (int32_t k = mhead[id]; k >= 0; k = mnext[k]) {
-            cluster_id[k] = id;
+        for (int32_t k = mhead[ix]; k >= 0; k = mnext[k]) {
+            cluster_id[k] = rid[ix];
             if (member_rank) member_rank[k] = pos;
             pos++;
         }
-        if (result_order) result_order[out] = id;
+        if (result_order) result_order[out] = rid[ix];
         out++;
     });
     st->n_result_clusters = out;
     st->chain_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (active.unmodelled() || ready.unmodelled()) {   // never seen; a result whose order rests on an unmodelled tree bin is refused
+    if (active.unmodelled() || ready.unmodelled()) {   // a result whose order rests on an unmodelled tree bin is refused
         if (err) *err = "clinkage: a HashSet bucket reached 8 entries (Java 8+ would treeify it): its iteration order is not modelled";
         return HMK_ERR_BAD_ARG;
     }
     return HMK_OK;
 }
 
+// the singleton case (:50-55 as the reference has them): one cluster per sequence, ids from 1 in list order, the candidate lists
+// are the adjacency rows
+template <class NbrT>
+int clinkage_impl(uint32_t n, const int32_t *sizes, const uint64_t *start, const NbrT *adj, int32_t *cluster_id,
+                  int32_t *result_order, int32_t *member_rank, hmk_clinkage_stats *st, std::string *err, int hashset_version) {
+    const auto t0 = std::chrono::steady_clock::now();
+    ClinkSeeds S;
+    S.n_clusters = S.n_members = n;
+    S.id.resize(n);
+    S.size.resize(n);
+    S.mhead.resize(n);
+    S.mtail.resize(n);
+    S.mnext.assign(n, -1);
+    S.cand.resize(n);
+    for (uint32_t k = 0; k < n; k++) {
+        std::vector<CNbr> &l = S.cand[k];
+        l.reserve(start[k + 1] - start[k]);
+        for (uint64_t q = start[k]; q < start[k + 1]; q++) l.push_back(CNbr{(int32_t)adj[q].id(), adj[q].score()});
+        std::sort(l.begin(), l.end(), [](const CNbr &a, const CNbr &b) { return a.ix < b.ix; });
+        S.id[k] = (int32_t)k + 1;
+        S.size[k] = sizes ? sizes[k] : 1;
+        S.mhead[k] = S.mtail[k] = (int32_t)k;
+    }
+    const int r = chain_impl(S, cluster_id, result_order, member_rank, st, err, hashset_version);
+    if (r == HMK_OK) st->chain_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return r;
+}
+
 }  // namespace
+
+int clinkage_from_seeds(int hashset_version, ClinkSeeds &seeds, int32_t *cluster_id, int32_t *result_order, int32_t *member_rank,
+                        hmk_clinkage_stats *st, std::string *err) {
+    return chain_impl(seeds, cluster_id, result_order, member_rank, st, err, hashset_version);
+}
 
 int clinkage_from_csr(int hashset_version, uint32_t n, const int32_t *sizes, const uint64_t *start, const Nbr *adj, int32_t *cluster_id,
                       int32_t *result_order, int32_t *member_rank, hmk_clinkage_stats *st, std::string *err) {

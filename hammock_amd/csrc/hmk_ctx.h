@@ -56,6 +56,10 @@ enum {
     SB_MATCH_CL,                                    // the match's clusters (hmk_match.cpp): SB_ASSIGN_CL's + query member -> query slot, members per query slot
     SB_MATCH_REC,                                   // ... per query member its feasible (rank, min score) records
     SB_MATCH_SCR,                                   // ... feasible counts per query member, per query slot counts + cursors + long runs, run starts
+    SB_MERGE_CL,                                    // the merge's clusters (hmk_merge.cpp): slot starts, members by slot, member -> slot
+    SB_MERGE_LEN, SB_MERGE_MSTART,                  // ... row lengths in that order, their prefix sums
+    SB_MERGE_TMP,                                   // ... per slot its feasible (slot, min score) records, at the slot's run offset
+    SB_MERGE_CNT, SB_MERGE_OSTART, SB_MERGE_SCR, SB_MERGE_SCAN,   // ... feasible counts, their prefix sums, long-run list, scan scratch
     SB_N
 };
 
@@ -158,6 +162,7 @@ struct hmk_ctx {
     PlanLocal plan_local_match;
     Plan plan_continue;            // hmk_greedy_continue (hmk_continue.cpp): members x new (a rectangle) and new x new (a triangle)
     Plan plan_continue_tri;
+    Plan plan_merge;               // hmk_clinkage_merge / hmk_cluster_pairs_shifted (hmk_merge.cpp): the triangle inside the members' range
     uint64_t *d_edges = nullptr;  // internal buffer of the host-buffer entry points
     uint64_t d_edges_cap = 0;
     unsigned long long *d_counts = nullptr;
@@ -180,6 +185,8 @@ struct hmk_ctx {
     void *h_stage = nullptr;  // pinned: what the merge uploads after phase 1 (cluster_of, sizes, leftovers, ...)
     size_t h_stage_cap = 0;
     void *h_adj = nullptr;    // pinned: adjacency rows fetched so far
+    void *h_merge = nullptr;  // pinned: the cluster-level lists of hmk_merge.cpp (k_merge_compact stores them here)
+    size_t h_merge_cap = 0;
     size_t h_adj_cap = 0;
     unsigned long long *h_loop = nullptr;    // pinned, coherent: progress word of the device-side second loop (written by k_loop_apply)
     unsigned long long *h_counts = nullptr;  // pinned: final segment counts [HMK_EDGE_SHARDS], band snapshot [HMK_EDGE_SHARDS], misc (HC_* below)

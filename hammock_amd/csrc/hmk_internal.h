@@ -217,6 +217,21 @@ int clinkage_from_csr(int hashset_version, uint32_t n, const int32_t *sizes, con
 int clinkage_from_csr_packed(int hashset_version, uint32_t n, const int32_t *sizes, const uint64_t *start, const NbrPacked *adj, int32_t *cluster_id,
                              int32_t *result_order, int32_t *member_rank, hmk_clinkage_stats *st, std::string *err);
 
+// The same chain started from given clusters (hmk_merge.cpp): ClinkageSequenceClusterer.java:50-55 replaced by "the given clusters,
+// added in slot order".  Clusters are numbered densely -- slot c for a given cluster, n_clusters + k for the k-th merge -- and carry
+// their Java id beside that number (the hash, the tie-break, the outputs).
+struct ClinkCand { int32_t ix, score; };   // candidate cluster (dense number), complete-linkage score
+struct ClinkSeeds {
+    uint32_t n_clusters = 0, n_members = 0;
+    std::vector<int32_t> id;                     // Java id per slot (distinct, >= 1)
+    std::vector<int64_t> size;                   // Cluster.size() per slot
+    std::vector<int32_t> mhead, mtail, mnext;    // Cluster.getSequences() as chains over the members: head / tail per slot, next per member
+    std::vector<std::vector<ClinkCand>> cand;    // per slot its feasible clusters, sorted by dense number (the chain takes them over)
+};
+// cluster_id[n_members]: Java id of the returned cluster holding member k; result_order[n_clusters], member_rank[n_members] may be NULL
+int clinkage_from_seeds(int hashset_version, ClinkSeeds &seeds, int32_t *cluster_id, int32_t *result_order, int32_t *member_rank,
+                        hmk_clinkage_stats *st, std::string *err);
+
 }  // namespace hmk
 
 #endif

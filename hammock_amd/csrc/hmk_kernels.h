@@ -179,6 +179,22 @@ hipError_t launch_match(const uint64_t *edges, uint64_t cap_per_shard, const uns
                         uint32_t *scratch, uint32_t *start, uint64_t *scan_scratch, uint64_t *rec, uint64_t *feas, uint64_t rec_capacity,
                         uint32_t *scratch2, uint32_t *start2, uint32_t *best_cluster, int32_t *best_score, uint32_t *n_feasible, hipStream_t s);
 
+// the cluster-level graph of given clusters (k_merge.hip) from the CSR (start[] indexed by the sequence itself, adj: NbrPacked[] with
+// base = thr or Nbr[]) of the members [r0, r0 + nm): for every cluster A the clusters B != A with hits == |A| * |B|, with the minimum
+// score.  cl_start[ncl + 1] / cl_members[nm] (absolute indices): the slots' members; cluster_of[nm]: slot of member r0 + i.
+// upper_only: keep B > A only.  entries: the CSR's entry count (< 2^32).  Two steps with the host in between (it sizes `out`):
+//   launch_merge_graph   mlen / mstart: uint32[nm + 1] (row lengths in cl_members order, their prefix sums), tmp: uint64[entries],
+//                        cnt: uint32[ncl] feasible clusters per slot, ostart: uint32[ncl + 1] their prefix sums, scratch: uint32[ncl + 2]
+//                        (long-run list), scan_scratch: scan_scratch_bytes(max(nm, ncl) + 1)
+//   launch_merge_compact out[ostart[A] + i] = A << 40 | B << 16 | (score & 0xFFFF) (HMK_EDGE_*), stored through out (the host's pinned
+//                        block by its device address)
+hipError_t launch_merge_graph(bool packed, const uint64_t *start, const void *adj, int thr, uint32_t r0, uint32_t nm, uint32_t ncl,
+                              const uint32_t *cl_start, const uint32_t *cl_members, const uint32_t *cluster_of, bool upper_only, uint64_t entries,
+                              uint32_t *mlen, uint32_t *mstart, uint64_t *tmp, uint32_t *cnt, uint32_t *ostart, uint32_t *scratch,
+                              uint64_t *scan_scratch, hipStream_t s);
+hipError_t launch_merge_compact(uint32_t ncl, const uint32_t *cl_start, const uint32_t *mstart, const uint64_t *tmp, const uint32_t *cnt,
+                                const uint32_t *ostart, int thr, uint64_t *out, uint64_t out_capacity, hipStream_t s);
+
 // force the deferred load of the code objects a clustering call launches from (hmk_create)
 hipError_t warm_neighbors_module();
 hipError_t warm_edges_module();

@@ -10,6 +10,7 @@
 // Extra mode that the reference does not have: `hammock-hip assign` (runAssign), new sequences into the clusters of a cluster file.
 // Extra mode that the reference does not have: `hammock-hip match` (runMatch), the clusters of one cluster file against another's.
 #include <future>
+#include <unordered_set>
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -130,7 +131,9 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "          hammock-hip continue -i <new sequences> --clusters <initial_clusters_sequences.tsv> -d <directory> [-f fasta|tab]\n"
               << "                      [-m <file>] [-x <int>] [-p <int>] [-g <int>] [-R <order>] [-S <int>] [-l <labels>] [--device <int>]\n"
               << "          hammock-hip match -i <query clusters.tsv> --clusters <initial_clusters_sequences.tsv> -d <directory> [--best <int>]\n"
-              << "                      [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [-g <int>] [--device <int>]\n\n"
+              << "                      [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [-g <int>] [--device <int>]\n"
+              << "          hammock-hip merge -i <clusters.tsv> [--clusters <other clusters.tsv>] -d <directory> [--skip_singletons] [-m <file>]\n"
+              << "                      [-x <int>] [-p <int>] [-g <int>] [--java_hashset <int>] [--device <int>]\n\n"
               << "-i, --input <file>\n\tA path to an input file\n\n"
               << "-d, --output_directory <directory>\n\tA directory to store all output files in\n\n"
               << "-t, --threads <int>\n\tAccepted for compatibility (the GPU path ignores it)\n\n"
@@ -148,9 +151,9 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "--devices <int,int,...>\n\tShard the pair space over several GPUs of the node (the first one runs the merge)\n\n"
               << "--database <file>\n\t(search) the reference sequences every query (-i) is scored against\n\n"
               << "--best <int>\n\t(search) keep only the best 1..32 hits of each query; (assign, match) report the best 1..32 feasible clusters (default 1)\n\n"
-              << "--clusters <file>\n\t(assign, continue, match) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv)\n\n"
-              << "--skip_singletons\n\t(assign, match) only clusters of more than one unique sequence are candidates\n\n"
-              << "--java_hashset <8|7|6>\n\t(clinkage) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
+              << "--clusters <file>\n\t(assign, continue, match) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv);\n\t(merge) a second cluster file: its clusters keep their ids, the -i file's are renumbered behind them\n\n"
+              << "--skip_singletons\n\t(assign, match, merge) only clusters of more than one unique sequence are candidates\n\n"
+              << "--java_hashset <8|7|6>\n\t(clinkage, merge) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
 }
 
 std::string labelsToString(bool have, const std::vector<std::string> &labels) {  // List.toString() / "null"
@@ -1111,6 +1114,281 @@ int runContinue(const std::vector<std::string> &args) {
     }
 }
 
+// `hammock-hip merge -i clusters.tsv [--clusters other.tsv] -d dir ...`: merges the clusters of one or two cluster files by complete
+// linkage -- ClinkageSequenceClusterer.cluster (ClinkageSequenceClusterer.java:43-124) started from the given clusters instead of
+// from one cluster per sequence (:50-55; hmk_clinkage_merge).  One file: its clusters are merged among themselves.  With --clusters:
+// that file's clusters keep their ids and come first in slot order; the -i file's clusters follow, renumbered
+// max(--clusters id) + 1 + k in file order; a sequence present in both files stays in its --clusters cluster, gets the -i line's
+// counts and labels added (the rule of continue) and leaves its -i cluster, which disappears when it becomes empty.
+// --skip_singletons: clusters of one unique sequence are not candidates and are written through unchanged.  Merged clusters get the
+// ids max(every id) + 2, + 3, ... in merge order (:97, counted from the largest id of all the clusters, so that a merged cluster
+// never takes the id of a cluster that was written through; a file whose ids start below 1 -- greedy numbers clusters by their
+// seed's index, from 0 -- goes to the library with its ids shifted up, which only the HashSet orders see).  Defaults of -x / -g are match's (greedy's over the first file's
+// sequences, -x clamped by the shortest sequence of all); -p 0.  Writes the stage-1 files of greedy for the merged clustering
+// (label columns: the first file's, then the other's new ones) and merged_clusters.tsv, one line per given cluster in slot order.
+struct MergeInput {
+    std::vector<ClusterPtr> clusters;          // slot order over both files (ids final: the -i file's renumbered)
+    std::vector<int> sourceFile, sourceId;     // per cluster: 0 = --clusters (or the only file), 1 = -i; its id in that file
+    std::vector<std::string> labels;
+    std::vector<UniqueSequencePtr> lineOrder;  // the files' sequences in line order
+    size_t duplicates = 0, emptied = 0;
+};
+
+static MergeInput loadMergeInput(const std::string &firstFile, const std::string &secondFile) {
+    MergeInput in;
+    std::unordered_map<std::string, UniqueSequencePtr> inFirst;
+    int maxId = INT32_MIN;
+    auto header = [&](const std::string &file, const std::vector<ClusterPtr> &loaded) {
+        std::unordered_map<std::string, std::vector<UniqueSequencePtr>> byString;   // (every line is a sequence of its own, duplicates included)
+        for (auto &cl : loaded) for (auto &s : cl->getSequences()) byString[s->getSequenceString()].push_back(s);
+        const std::vector<std::string> lines = FileIOManager::readLines(file);
+        std::vector<std::string> h = FileIOManager::splitChar(lines[0], CSV_SEPARATOR, true);
+        for (const char *drop : {"alignment", "sum"}) {
+            const auto at = std::find(h.begin(), h.end(), drop);
+            if (at != h.end()) h.erase(at);
+        }
+        for (size_t k = 2; k < h.size(); k++)
+            if (std::find(in.labels.begin(), in.labels.end(), h[k]) == in.labels.end()) in.labels.push_back(h[k]);
+        std::unordered_map<std::string, size_t> taken;
+        for (size_t k = 1; k < lines.size(); k++) {
+            const std::vector<std::string> f = FileIOManager::splitChar(lines[k], CSV_SEPARATOR, true);
+            if (f.size() < 2) continue;
+            const auto it = byString.find(f[1]);
+            if (it == byString.end()) continue;
+            size_t &t = taken[f[1]];
+            if (t < it->second.size()) in.lineOrder.push_back(it->second[t++]);
+        }
+    };
+    const std::vector<ClusterPtr> first = FileIOManager::loadClustersFromCsv(firstFile);
+    header(firstFile, first);
+    for (auto &cl : first) {
+        in.clusters.push_back(cl);
+        in.sourceFile.push_back(0);
+        in.sourceId.push_back(cl->getId());
+        maxId = std::max(maxId, cl->getId());
+        for (auto &s : cl->getSequences()) inFirst.emplace(s->getSequenceString(), s);
+    }
+    if (secondFile.empty()) return in;
+    const std::vector<ClusterPtr> second = FileIOManager::loadClustersFromCsv(secondFile);
+    const size_t firstLines = in.lineOrder.size();
+    header(secondFile, second);
+    std::unordered_set<const UniqueSequence *> dropped;
+    int k = 0;
+    for (auto &cl : second) {
+        std::vector<UniqueSequencePtr> kept;
+        for (auto &s : cl->getSequences()) {
+            const auto it = inFirst.find(s->getSequenceString());
+            if (it == inFirst.end()) { kept.push_back(s); continue; }
+            for (auto &e : s->getLabelsMap()) it->second->addLabelCount(e.first, e.second);
+            dropped.insert(s.get());
+            in.duplicates++;
+        }
+        const int id = maxId + 1 + k++;
+        if (kept.empty()) { in.emptied++; continue; }
+        in.clusters.push_back(std::make_shared<Cluster>(kept, id));
+        in.sourceFile.push_back(1);
+        in.sourceId.push_back(cl->getId());
+    }
+    in.lineOrder.erase(std::remove_if(in.lineOrder.begin() + firstLines, in.lineOrder.end(),
+                                      [&](const UniqueSequencePtr &s) { return dropped.count(s.get()) != 0; }), in.lineOrder.end());
+    // (Cluster.size() sums its sequences' sizes when it is made: the first file's clusters again, after the counts were added)
+    for (size_t c = 0; c < in.clusters.size(); c++)
+        if (in.sourceFile[c] == 0) in.clusters[c] = std::make_shared<Cluster>(in.clusters[c]->getSequences(), in.clusters[c]->getId());
+    return in;
+}
+
+int runMerge(const std::vector<std::string> &args) {
+    Options o;
+    const std::string PARENT_DIR = parentDir();
+    o.matrixFile = PARENT_DIR + "/matrices/blosum62.txt";  // Hammock.java:45
+    parseCommonArgs(args, o);
+    parseGreedyArgs(args, o);
+    std::string clustersFile;
+    bool havePenalty = false, skipSingletons = false;
+    int javaHashset = 8;
+    for (size_t i = 1; i < args.size(); i++) {
+        const bool more = args.size() > i + 1;
+        if (args[i] == "--clusters" && more) clustersFile = args[++i];
+        else if (args[i] == "--skip_singletons") skipSingletons = true;
+        else if (args[i] == "--java_hashset" && more) {
+            javaHashset = javaIntegerDecode(args[++i]);
+            if (javaHashset != 8 && javaHashset != 7 && javaHashset != 6) throw CLIException("Error. --java_hashset may be 8, 7 or 6.");
+        } else if ((args[i] == "-p" || args[i] == "--gap_penalty") && more) havePenalty = true;
+    }
+    if (!o.devices.empty()) throw CLIException("Error. --devices is not available in mode merge (a merge runs on one device, --device).");
+    if (!o.haveInput) throw CLIException("Error. Parameter input file (-i or --input) missing with no default.");
+    if (o.haveDir) {
+        if (exists(o.workingDirectory)) throw CLIException("Error. Output directory exists. Exiting to prevent data loss.");
+        mkdir(o.workingDirectory.c_str(), 0777);
+    } else {
+        std::string name;
+        mkdir((PARENT_DIR + "/dist").c_str(), 0777);
+        for (int i = 1; i < 9999; i++) {
+            name = PARENT_DIR + "/dist/Hammock_result_" + std::to_string(i);
+            if (!exists(name)) { mkdir(name.c_str(), 0777); break; }
+        }
+        o.workingDirectory = name;
+        std::cerr << "Creating default output directory: " << name << std::endl;
+    }
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        logger.logAndStderr(std::string("\nHammock version ") + VERSION +
+                            " Run with --help for a brief description of command line parameters.\n");
+        const std::vector<std::vector<int>> scoringMatrix = FileIOManager::loadScoringMatrix(o.matrixFile);
+        std::shared_future<std::shared_ptr<NativeContext>> contextReady = std::async(std::launch::async, [&scoringMatrix, &o]() {
+            return std::make_shared<NativeContext>(scoringMatrix, o.device);
+        });
+        logger.logWithTime("Program started in mode \"merge\".");
+        std::string argsString;
+        for (auto &a : args) argsString += " " + a;
+        logger.logWithoutTime("Command-line arguments: \n" + argsString + "\n");
+        logger.logAndStderr("Loading clusters...");
+        const std::string firstFile = clustersFile.empty() ? o.inputFileName : clustersFile;
+        MergeInput in = loadMergeInput(firstFile, clustersFile.empty() ? std::string() : o.inputFileName);
+        if (o.haveLabels) in.labels = FileIOManager::splitChar(o.labelString, ',', true);
+        std::vector<UniqueSequencePtr> all, firstSequences;
+        for (size_t c = 0; c < in.clusters.size(); c++)
+            for (auto &s : in.clusters[c]->getSequences()) { all.push_back(s); if (in.sourceFile[c] == 0) firstSequences.push_back(s); }
+        logger.logAndStderr(std::to_string(in.clusters.size()) + " clusters of " + std::to_string(all.size()) + " sequences loaded.");
+        if (!clustersFile.empty())
+            logger.logAndStderr(std::to_string(in.duplicates) + " sequences of the input file were already in the cluster file: their counts and labels "
+                                "were added there (" + std::to_string(in.emptied) + " input clusters became empty).");
+        if (firstSequences.empty()) throw FileFormatException("Error. The cluster file holds no clusters.");
+        for (auto &s : all)
+            if (s->size() < 1) throw FileFormatException("Error in cluster file - the sequence " + s->getSequenceString() +
+                                                         " has no occurrences (Cluster.size() counts them).");
+        const SequenceListSummary summary = summariseSequences(firstSequences), allSummary = summariseSequences(all);
+        if (allSummary.maxLength > HMK_MAX_LEN)
+            throw HammockException("Error. The longest sequence has " + std::to_string(allSummary.maxLength) + " amino acids; the GPU kernels of hammock-hip "
+                                   "take sequences of up to " + std::to_string(HMK_MAX_LEN) + " (Hammock's domain is 7-20).");
+        if (!o.haveMaxShift) {
+            o.maxShift = checkMaxShift(allSummary, (int)javaRound(summary.meanLength() / 4));
+            logger.logAndStderr("Max shift not set. Setting automatically to: " + std::to_string(o.maxShift));
+        } else {
+            const int correct = checkMaxShift(allSummary, o.maxShift);
+            if (o.maxShift != correct) {
+                o.maxShift = correct;
+                logger.logAndStderr("Setting max shift to " + std::to_string(correct) +
+                                    " as the length of the shortest sequence is only " + std::to_string(correct + 1));
+            }
+        }
+        if (!o.haveThreshold) {
+            o.sequenceClusteringThreshold = (int)javaRound(summary.meanLength() * 1.7);
+            logger.logAndStderr("Merge threshold not set. Setting automatically to: " + std::to_string(o.sequenceClusteringThreshold));
+        }
+        if (!havePenalty) logger.logAndStderr("Gap penalty not set. Setting automatically to: " + std::to_string(o.shiftPenalty));
+
+        // the candidates' members, slot by slot
+        std::vector<uint32_t> candidates;   // indices into in.clusters
+        int maxId = INT32_MIN, minId = INT32_MAX;
+        for (size_t c = 0; c < in.clusters.size(); c++) {
+            maxId = std::max(maxId, in.clusters[c]->getId());
+            minId = std::min(minId, in.clusters[c]->getId());
+            if (!skipSingletons || in.clusters[c]->getUniqueSize() > 1) candidates.push_back((uint32_t)c);
+        }
+        std::vector<UniqueSequencePtr> upload;
+        std::vector<uint32_t> memberCluster;
+        std::vector<int32_t> clusterId;
+        // (hmk_clinkage_merge takes ids from 1; greedy numbers its clusters by their seed's index, from 0: such ids go to the library
+        // shifted up and come back shifted down)
+        const int idShift = minId < 1 ? 1 - minId : 0;
+        for (uint32_t c = 0; c < (uint32_t)candidates.size(); c++) {
+            clusterId.push_back(in.clusters[candidates[c]]->getId() + idShift);
+            for (auto &s : in.clusters[candidates[c]]->getSequences()) { upload.push_back(s); memberCluster.push_back(c); }
+        }
+        const uint32_t n = (uint32_t)upload.size(), ncl = (uint32_t)candidates.size();
+        std::vector<int32_t> mergedId(std::max<uint32_t>(ncl, 1)), resultOrder(std::max<uint32_t>(ncl, 1)), rank(std::max<uint32_t>(n, 1));
+        hmk_merge_stats stats{};
+        logger.logAndStderr("Merging...");
+        const auto time0 = std::chrono::steady_clock::now();
+        if (ncl >= 1) {
+            size_t total = 0;
+            for (auto &s : upload) total += s->getSequence().size();
+            std::vector<uint8_t> res(total);
+            std::vector<uint32_t> off(n + 1, 0);
+            std::vector<int32_t> sizes(n);
+            for (uint32_t k = 0; k < n; k++) {
+                off[k + 1] = off[k] + (uint32_t)upload[k]->getSequence().size();
+                for (size_t r = 0; r < upload[k]->getSequence().size(); r++) res[off[k] + r] = (uint8_t)upload[k]->getSequence()[r];
+                sizes[k] = upload[k]->size();
+            }
+            const std::shared_ptr<NativeContext> nc = contextReady.get();
+            hmk_ctx *c = nc->get();
+            int st = hmk_set_sequences(c, res.data(), off.data(), sizes.data(), n);
+            if (st) nc->raise(st, nullptr);
+            st = hmk_set_java_hashset(c, javaHashset);
+            if (st) nc->raise(st, nullptr);
+            st = hmk_clinkage_merge(c, 0, n, memberCluster.data(), clusterId.data(), ncl, o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold,
+                                    mergedId.data(), resultOrder.data(), rank.data(), &stats);
+            if (st) nc->raise(st, nullptr);
+        }
+        const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - time0).count();
+        // the returned clusters in list order (:121-123), members in Cluster.getSequences() order (:105-106); then the clusters that
+        // were written through.  A merged cluster's id counts from the largest id of ALL clusters.
+        int maxCandidateId = INT32_MIN;
+        for (int32_t id : clusterId) maxCandidateId = std::max(maxCandidateId, id);
+        auto finalIdOf = [&](int32_t id) { return id > maxCandidateId ? id - maxCandidateId + maxId : id - idShift; };
+        std::unordered_map<int32_t, std::vector<UniqueSequencePtr>> membersOf;
+        std::unordered_map<int32_t, int> sourcesOf;
+        for (uint32_t c = 0; c < ncl; c++) sourcesOf[mergedId[c]]++;
+        for (uint32_t k = 0; k < n; k++) {
+            std::vector<UniqueSequencePtr> &m = membersOf[mergedId[memberCluster[k]]];
+            if (m.size() <= (size_t)rank[k]) m.resize((size_t)rank[k] + 1);
+            m[rank[k]] = upload[k];
+        }
+        std::vector<ClusterPtr> result;
+        for (int32_t t = 0; t < stats.n_result_clusters; t++)
+            result.push_back(std::make_shared<Cluster>(membersOf[resultOrder[t]], finalIdOf(resultOrder[t])));
+        std::vector<int32_t> slotOf(in.clusters.size(), -1);
+        for (uint32_t c = 0; c < ncl; c++) slotOf[candidates[c]] = (int32_t)c;
+        for (size_t c = 0; c < in.clusters.size(); c++)
+            if (slotOf[c] < 0) result.push_back(in.clusters[c]);
+        logger.logAndStderr("Ready. Merge time: " + std::to_string(ms));
+        logger.logAndStderr("Candidate clusters: " + std::to_string(ncl) + ", merges: " + std::to_string(stats.merges) + ", feasible cluster pairs: " +
+                            std::to_string(stats.cluster_pairs) + ", pairs scored: " + std::to_string(stats.pairs_scored) + ", neighbour edges: " +
+                            std::to_string(stats.n_edges) + ", GPU pass: " + std::to_string(stats.kernel_ms) + " ms, cluster graph: " +
+                            std::to_string(stats.graph_ms) + " ms, chain: " + std::to_string(stats.chain_ms) + " ms");
+        logger.logAndStderr("Resulting clusers: " + std::to_string(result.size()));
+        logger.logAndStderr("Saving results to output files...");
+        const std::string seqCsv = o.workingDirectory + "/initial_clusters_sequences.tsv";
+        const std::string orderedCsv = o.workingDirectory + "/initial_clusters_sequences_original_order.tsv";
+        const std::string clustersCsv = o.workingDirectory + "/initial_clusters.tsv";
+        FileIOManager::saveInitialClusters(result, seqCsv, orderedCsv, clustersCsv, in.labels, in.lineOrder);
+        const std::string mergedCsv = o.workingDirectory + "/merged_clusters.tsv";
+        {
+            std::ofstream out(mergedCsv);
+            if (!out) throw HammockException("cannot write " + mergedCsv);
+            out << "source_file\tsource_cluster_id\tcluster_id\tmerged\n";
+            for (size_t c = 0; c < in.clusters.size(); c++) {
+                const std::string &file = in.sourceFile[c] == 0 ? firstFile : o.inputFileName;
+                if (slotOf[c] < 0) { out << file << '\t' << in.sourceId[c] << '\t' << in.clusters[c]->getId() << "\t0\n"; continue; }
+                const int32_t id = mergedId[slotOf[c]];
+                out << file << '\t' << in.sourceId[c] << '\t' << finalIdOf(id) << '\t' << (sourcesOf[id] > 1 ? 1 : 0) << '\n';
+            }
+        }
+        logger.logAndStderr("Merged clustering in: " + clustersCsv);
+        logger.logAndStderr("and: " + seqCsv);
+        logger.logAndStderr("and: " + orderedCsv);
+        logger.logAndStderr("Given clusters in: " + mergedCsv);
+        logger.logWithTime("Program successfully ended.");
+        return 0;
+    } catch (const CLIException &) {
+        throw;
+    } catch (const FileFormatException &e) {
+        logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
+        return 3;
+    } catch (const DataException &e) {
+        logger.logAndStderr("Error. Maybe wrong input file format or wrong set of labels? Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(std::string("cz.krejciadam.hammock.DataException: ") + e.what());
+        return 5;
+    } catch (const std::exception &e) {
+        logger.logAndStderr("Error. Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(e.what());
+        return 6;
+    }
+}
+
 // `hammock-hip io-selftest ...`: exposes the loaders / orderings to the CPU test-suite (no GPU involved)
 int ioSelftest(const std::vector<std::string> &args) {
     if (args.size() >= 3 && args[1] == "matrix") {
@@ -1230,6 +1508,7 @@ int main(int argc, char **argv) {
         if (args[0] == "assign") return runAssign(args);
         if (args[0] == "continue") return runContinue(args);
         if (args[0] == "match") return runMatch(args);
+        if (args[0] == "merge") return runMerge(args);
         if (args[0] == "io-selftest") return ioSelftest(args);
         if (args[0] == "dump-matrix") {   // the default matrix in the text format FileIOManager.loadScoringMatrix reads
             std::cout << "# BLOSUM62 substitution matrix (public NCBI table), 24 x 24, order " << AMINO_ACIDS << "\n"

@@ -444,6 +444,65 @@ int hmk_set_java_hashset(hmk_ctx *ctx, int version);
 int hmk_clinkage_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t n_edges, int32_t *cluster_id,
                             int32_t *result_order, int32_t *member_rank, hmk_clinkage_stats *stats);
 
+/* ---- merging given clusters by complete linkage ----------------------------------- */
+
+typedef struct {
+    uint64_t n_edges;          /* sequence-level edges at or above the threshold */
+    uint64_t pairs_scored;
+    uint64_t cluster_pairs;    /* unordered pairs of given clusters that are feasible for each other */
+    int32_t  merges, searches, n_result_clusters, reserved;
+    double   kernel_ms;        /* the scoring pass (device) */
+    double   graph_ms;         /* CSR + cluster graph (device) */
+    double   chain_ms;         /* host nearest-neighbour chain */
+} hmk_merge_stats;
+
+/* The cluster-level graph of given clusters.  Members [r0, r1) of the hmk_set_sequences set with member_cluster and n_clusters
+ * as hmk_assign_shifted takes them.  Clusters a and b are feasible for each other iff every pair (member of a, member of b)
+ * scores >= threshold with ShiftedScorer(matrix, shift_penalty, max_shift); their complete-linkage score is then the minimum
+ * over those pairs (ClinkageClusterScorer.java:30-49).  Scores inside a cluster are never looked at.
+ *   pairs      every unordered pair {a, b} of slots, a != b, feasible for each other, once, packed as HMK_EDGE_* with x = the
+ *              smaller slot, m = the larger slot, score = the complete-linkage score; order unspecified.  HMK_ERR_CAPACITY and
+ *              *n_pairs = the number needed if `capacity` is too small.
+ *   checks     HMK_ERR_BAD_ARG before the device is looked at (a host-only context answers them): the range and slot checks of
+ *              hmk_assign_shifted (without ids), an asymmetric matrix, two clusters whose member counts multiply to 2^32 or
+ *              more.  Then the checks of hmk_search_shifted.
+ * Only the triangle inside [r0, r1) is scored; the sequence-level edges and their CSR stay on the device, the cluster graph is
+ * built there (k_merge.hip) and only the cluster pairs cross to the host.  On a hmk_create_multi context the call runs on the
+ * root device. */
+int hmk_cluster_pairs_shifted(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_cluster, uint32_t n_clusters,
+                              int max_shift, int shift_penalty, int threshold, uint64_t *pairs, uint64_t capacity,
+                              uint64_t *n_pairs, hmk_merge_stats *stats);
+
+/* Merges given clusters: ClinkageSequenceClusterer(ShiftedScorer(matrix, shift_penalty, max_shift), threshold).cluster
+ * (ClinkageSequenceClusterer.java:43-124) with its seeding (:50-55, one cluster per sequence) replaced by "activeClusters =
+ * the given clusters, added in slot order 0, 1, ..."; every other line is the reference's.
+ *   slot c     a Cluster with Java id cluster_id[c] (distinct, within [1, 2^30]) and the members of the slot in index order
+ *              (Cluster.getSequences()); size() = the sum of the members' uploaded sizes, getUniqueSize() = the member count.
+ *   ids        currentId after the seeding is max(cluster_id) + 1, so merged clusters get max + 2, max + 3, ... in merge
+ *              order (:97); with the slots being the singletons 1 ... n this is hmk_clinkage_cluster.
+ *   ranking    cluster score = ClinkageClusterScorer.clusterScore; nearest cluster by score, then size() descending, then
+ *              smaller id (:137-177, :258-293); chain starts and the returned list's order are HashSet<Cluster> iteration
+ *              orders (:70, :118-123) of the Java version hmk_set_java_hashset selects.
+ *   inside     scores inside a given cluster are never looked at: it need not be a complete-linkage cluster itself.
+ *   merged_id[n_clusters]     id of the returned cluster that holds slot c (its own id if it merged with nothing)
+ *   result_order[n_clusters]  ids of the returned clusters in list order, first n_result_clusters valid; may be NULL
+ *   member_rank[r1 - r0]      position in the returned Cluster.getSequences() (:105-106); may be NULL
+ * Zero clusters: HMK_ERR_REFERENCE_WOULD_CRASH (NoSuchElementException, :118); so is a chain that returns to a cluster still
+ * on its stack (see hmk_clinkage_cluster).  One cluster: returned as it is.  A HashSet bucket that Java 8+ would turn into a
+ * tree bin is not modelled: HMK_ERR_BAD_ARG.  With the consecutive ids of hmk_clinkage_cluster that cannot happen; with
+ * caller-chosen ids it can (eight ids in one bucket of a table of 64 or more), so choose consecutive ids where possible.
+ * Checks as hmk_cluster_pairs_shifted's, plus duplicate ids and an id outside [1, 2^30]; never HMK_ERR_CAPACITY. */
+int hmk_clinkage_merge(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_cluster, const int32_t *cluster_id,
+                       uint32_t n_clusters, int max_shift, int shift_penalty, int threshold, int32_t *merged_id,
+                       int32_t *result_order, int32_t *member_rank, hmk_merge_stats *stats);
+
+/* The same from a sequence-level edge list as hmk_neighbors_shifted produces it (indices of the uploaded set, each unordered
+ * pair once, any order; edges with an end outside [r0, r1) or with both ends in one slot are ignored).  Works on a host-only
+ * context (device = -1): the cluster graph is built on the host. */
+int hmk_clinkage_merge_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t n_edges, uint32_t r0, uint32_t r1,
+                                  const uint32_t *member_cluster, const int32_t *cluster_id, uint32_t n_clusters,
+                                  int32_t *merged_id, int32_t *result_order, int32_t *member_rank, hmk_merge_stats *stats);
+
 /* Where the time of the last hmk_greedy_cluster / hmk_greedy_from_edges_dev call of this context went
  * (milliseconds; the span of Hammock.java:406-411 minus the sort).  score_ms and csr_ms are device times (HIP events on
  * the call's stream), the others host wall time.  The parts overlap (phase 1 runs while the rest of the pair space is
