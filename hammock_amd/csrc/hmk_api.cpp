@@ -539,14 +539,17 @@ int hmk_create_multi(const int32_t *matrix, const int *devices, int n_devices, h
         if (st) { hmk_destroy(root); return st; }
         root->peers.push_back(peer);
         if (devices[d] != devices[0]) {   // direct xGMI copies peer -> root (a refusal leaves the staged path, still correct)
+            // the root's kernels read this device's pieces in place only where both directions are enabled; otherwise the root copies
+            // the finished pieces to itself (SB_REPL, what HMK_MULTI_REPLICATE forces)
+            auto enabled = [](hipError_t e) { return e == hipSuccess || e == hipErrorPeerAccessAlreadyEnabled; };
             int can = 0;
-            if (hipDeviceCanAccessPeer(&can, devices[0], devices[d]) == hipSuccess && can) {
-                (void)hipSetDevice(devices[0]);
-                (void)hipDeviceEnablePeerAccess(devices[d], 0);
-                (void)hipSetDevice(devices[d]);
-                (void)hipDeviceEnablePeerAccess(devices[0], 0);
-                (void)hipGetLastError();   // "already enabled" is fine
+            bool ok = hipDeviceCanAccessPeer(&can, devices[0], devices[d]) == hipSuccess && can;
+            if (ok) {
+                ok = hipSetDevice(devices[0]) == hipSuccess && enabled(hipDeviceEnablePeerAccess(devices[d], 0));
+                ok = hipSetDevice(devices[d]) == hipSuccess && enabled(hipDeviceEnablePeerAccess(devices[0], 0)) && ok;
             }
+            (void)hipGetLastError();   // ("already enabled", or a refusal: neither may stay behind as the thread's last error)
+            peer->peer_loads_ok = ok;
         }
     }
     (void)hipSetDevice(devices[0]);

@@ -20,6 +20,7 @@ void Switches::read() {
     local_signed = flag("HMK_LOCAL_SIGNED");
     local_no_pk = flag("HMK_LOCAL_NO_PK");
     multi_replicate = flag("HMK_MULTI_REPLICATE");
+    multi_force_copies = flag("HMK_MULTI_FORCE_COPIES");
     if (const char *v = getenv("HMK_SECOND_LOOP")) second_loop = std::strcmp(v, "device") == 0 ? 1 : 2;
     phase1_threads = std::max(0, num("HMK_PHASE1_THREADS", 0));
     phase1_window = std::max(0, num("HMK_PHASE1_WINDOW", 0));

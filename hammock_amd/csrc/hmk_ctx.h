@@ -77,6 +77,8 @@ struct Switches {
     bool local_no_pk = false;     // HMK_LOCAL_NO_PK: one column sequence per lane in the tagged-max DP
     bool multi_replicate = false; // HMK_MULTI_REPLICATE: a multi-device root copies the peers' finished adjacency pieces to itself instead of
                                   // reading them in place (what a machine without peer access between two of its devices runs)
+    bool multi_force_copies = false;   // HMK_MULTI_FORCE_COPIES: contexts of one call that share a device exchange through copies and inboxes,
+                                  // as distinct devices do (tests: the exchange's slot, offset and capacity arithmetic on one GPU)
     int second_loop = 0;          // HMK_SECOND_LOOP=device|host: 1 / 2 force that implementation of the second loop (0: the default choice)
     int phase1_threads = 0, phase1_window = 0;        // HMK_PHASE1_THREADS, HMK_PHASE1_WINDOW (GreedyOptions)
     int host_band_rows = 0, host_band_far_t = 0;      // HMK_PHASE1_HOST_BAND=rows[,far_t] (GreedyOptions)
@@ -198,6 +200,7 @@ struct hmk_ctx {
     // the stream this device's blocks travel to the other devices on (multi-device calls; a stream of this device)
     hipStream_t xfer_stream = nullptr;
     bool peer_loads_ok = true;   // (a peer:) the root's kernels may read this device's memory in place
+    uint64_t inbox_entries = 0;  // entries per sender an overflowing block grew this device's inbox to (grow-only, like the buffer: the next call needs no retry)
 
     // hmk_reserve sizes the two buffers a clustering call needs LAST (adjacency, bucket records: 2 x 11 GB at 10^6) on its own
     // thread: on some hosts a fresh 11 GB of device memory takes 0.3-1.5 s to get, and a call has 0.27 s of scoring to do

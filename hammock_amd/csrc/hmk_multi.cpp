@@ -35,7 +35,13 @@ struct DevJob {
     uint64_t need_edges = 0, need_inbox = 0;   // (-2) what the next attempt must hold
     double t_band = 0, t_scored = 0, t_sent = 0, t_csr = 0, t_pre = 0;   // HMK_GREEDY_TIMING: ms since the call began
     unsigned long long route_off[HMK_MAX_DEVICES + 1] = {0};   // (valid once sent_state is 1) where its block for owner t begins in its SB_ROUTE
+    // HMK_GREEDY_TIMING: peer copies this device issued -- edge blocks, band blocks, block / band sizes, degree slices, candidate regions and lists
+    unsigned copies_edge = 0, copies_band = 0, copies_count = 0, copies_deg = 0, copies_cand = 0;
 };
+
+// Two contexts of one call share a device (a device list that names a GPU several times): a block is then read where its sender left it,
+// no copy and no inbox.  HMK_MULTI_FORCE_COPIES (tests) takes that shortcut away: the one GPU's contexts exchange as distinct GPUs would.
+static inline bool same_device(const hmk_ctx *a, const hmk_ctx *b, const Switches &sw) { return a->device == b->device && !sw.multi_force_copies; }
 
 int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, int max_clusters, int32_t *cluster_id,
                          int32_t *result_order, int32_t *member_rank, hmk_greedy_stats *stats, hmk_clinkage_stats *clink) {
@@ -57,6 +63,7 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
     const bool symmetric = ctx->symmetric;
     const bool fuse = symmetric;   // the pass counts upper and lower degrees itself (asymmetric scores: a counting pass over the blocks)
     std::vector<uint64_t> want_edges(G, 0), want_inbox(G, 0);   // grown by an attempt that overflowed
+    unsigned copies[5] = {0, 0, 0, 0, 0};   // HMK_GREEDY_TIMING: the call's peer copies by kind, every attempt's
     int st = HMK_OK;
     for (int attempt = 0; attempt < 4; attempt++) {
         // ---- every buffer of every device, before anything is enqueued (a hipMalloc waits for running kernels) ------------------
@@ -85,7 +92,7 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
             HIPCHK(ctx, ensure_buf(c, SB_ROUTE, 2 * c->d_edges_cap * sizeof(uint64_t)));
             HIPCHK(ctx, ensure_buf(c, SB_ROUTECNT, 3 * (HMK_MAX_DEVICES + 1) * sizeof(unsigned long long)));
             // what one sender deals to one owner: 2 / G of its shard where the rows are spread evenly, + a half
-            inbox_cap[d] = std::max<uint64_t>({(uint64_t)((double)c->d_edges_cap * 2.0 / G * 1.5) + 65536, want_inbox[d]});
+            inbox_cap[d] = std::max<uint64_t>({(uint64_t)((double)c->d_edges_cap * 2.0 / G * 1.5) + 65536, want_inbox[d], c->inbox_entries});
             jobs.emplace_back(new DevJob());
             DevJob &J = *jobs.back();
             J.c = c;
@@ -204,10 +211,15 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
                     J.band_total = h_rcnt[16];
                     if (J.band_total > J.band_region) set_state(&DevJob::band_state, J, -1);
                     else {
-                        if (c->device != ctx->device) {   // (a context on the root's own device is read where its block lies: below, band_segs)
-                            if (J.band_total)
+                        if (!same_device(c, ctx, ctx->sw)) {   // (a context on the root's own device is read where its block lies: below, band_segs)
+                            if (J.band_total) {
                                 e = hipMemcpyPeerAsync(root_band + J.band_off, ctx->device, buf<uint64_t>(c, SB_PEERBAND), c->device, J.band_total * sizeof(uint64_t), X);
-                            if (e == hipSuccess) e = hipMemcpyPeerAsync(root_cnt + HMK_MAX_SEGS + d, ctx->device, d_rcnt + HMK_MAX_DEVICES, c->device, 8, X);
+                                J.copies_band++;
+                            }
+                            if (e == hipSuccess) {
+                                e = hipMemcpyPeerAsync(root_cnt + HMK_MAX_SEGS + d, ctx->device, d_rcnt + HMK_MAX_DEVICES, c->device, 8, X);
+                                J.copies_count++;
+                            }
                             if (e == hipSuccess) e = hipStreamSynchronize(X);   // (landed: the root's copy stream needs no event of another device)
                         }
                         if (e != hipSuccess) { hip_fail("band hand-over", e); return; }
@@ -229,7 +241,7 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
             {
                 bool too_small = false;
                 for (uint32_t t = 0; t < G; t++)
-                    if (t != d && dev(t)->device != c->device && h_rcnt[t] > inbox_cap[t]) {   // (the owner's inbox is too small for this block: grown for the next attempt)
+                    if (t != d && !same_device(dev(t), c, ctx->sw) && h_rcnt[t] > inbox_cap[t]) {   // (the owner's inbox is too small for this block: grown for the next attempt)
                         std::lock_guard<std::mutex> l(mu);
                         jobs[t]->need_inbox = std::max<uint64_t>(jobs[t]->need_inbox, h_rcnt[t] + h_rcnt[t] / 8 + 65536);
                         too_small = true;
@@ -245,12 +257,18 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
                 const uint32_t o_r0 = jobs[t]->r0, o_len = jobs[t]->r1 - jobs[t]->r0;
                 // (an owner on this very device -- a device list that names a GPU several times -- reads the block where it lies: a copy
                 // inside one device is a blit kernel that waits for workgroup slots beside every context's pass)
-                if (o->device != c->device) {
-                    if (h_rcnt[t])
+                if (!same_device(o, c, ctx->sw)) {
+                    if (h_rcnt[t]) {
                         e = hipMemcpyPeerAsync(buf<uint64_t>(o, SB_PEER) + (uint64_t)slot * inbox_cap[t], o->device, d_route + off[t], c->device, h_rcnt[t] * sizeof(uint64_t), X);
-                    if (e == hipSuccess) e = hipMemcpyPeerAsync(buf<unsigned long long>(o, SB_PEERCNT) + slot, o->device, d_rcnt + t, c->device, 8, X);
+                        J.copies_edge++;
+                    }
+                    if (e == hipSuccess) {
+                        e = hipMemcpyPeerAsync(buf<unsigned long long>(o, SB_PEERCNT) + slot, o->device, d_rcnt + t, c->device, 8, X);
+                        J.copies_count++;
+                    }
                 }
                 if (e == hipSuccess && p_deg && o_len) {
+                    J.copies_deg += 2;
                     uint32_t *slice = buf<uint32_t>(o, SB_PEERDEG) + (size_t)slot * 2 * rows_per;
                     e = hipMemcpyPeerAsync(slice, o->device, p_deg + o_r0, c->device, (size_t)o_len * 4, X);
                     if (e == hipSuccess) e = hipMemcpyPeerAsync(slice + o_len, o->device, p_deg_lo + o_r0, c->device, (size_t)o_len * 4, X);
@@ -269,7 +287,7 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
                 for (uint32_t k = 0; k + 1 < G; k++) {
                     const uint32_t sender = k < d ? k : k + 1;
                     hmk_ctx *sc = dev(sender);
-                    if (sc->device == c->device) {   // (its block, where the sender dealt it)
+                    if (same_device(sc, c, ctx->sw)) {   // (its block, where the sender dealt it)
                         const DevJob &SJ = *jobs[sender];
                         in.s[in.n++] = EdgeSeg{buf<uint64_t>(sc, SB_ROUTE) + SJ.route_off[d], buf<unsigned long long>(sc, SB_ROUTECNT) + d, SJ.route_off[d + 1] - SJ.route_off[d]};
                     } else
@@ -292,6 +310,7 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
             const int fit = piece_precheck(c, pre_in, J.r0, J.r1, rb, rc, Q, true, &J.pre_total);
             if (fit != 0) { set_state(&DevJob::pre_state, J, -1); return; }
             if (d) {   // its regions of the candidate buffer and its leftovers' (first entry, count) to the root
+                J.copies_cand++;
                 e = hipMemcpyPeerAsync(buf<GreedyCand>(ctx, SB_CAND) + (size_t)rb * pre_in.region_cap, ctx->device,
                                        buf<GreedyCand>(c, SB_CAND) + (size_t)rb * pre_in.region_cap, c->device, (size_t)rc * pre_in.region_cap * sizeof(GreedyCand), X);
                 // the leftover list is [orphans | the sequences phase 1 never reached], ids ascending in each part: its leftovers are (at most)
@@ -304,6 +323,7 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
                     const uint32_t *pb = left + (part ? split : 0), *pe = left + (part ? pre_in.nl : split);
                     const uint32_t q0 = (uint32_t)(std::lower_bound(pb, pe, J.r0) - left), q1 = (uint32_t)(std::lower_bound(pb, pe, J.r1) - left);
                     if (q1 <= q0) continue;
+                    J.copies_cand += 2;
                     e = hipMemcpyPeerAsync(buf<uint32_t>(ctx, SB_CNT) + q0, ctx->device, buf<uint32_t>(c, SB_CNT) + q0, c->device, (size_t)(q1 - q0) * 4, X);
                     if (e == hipSuccess)
                         e = hipMemcpyPeerAsync(buf<uint32_t>(ctx, SB_CSTART) + q0, ctx->device, buf<uint32_t>(c, SB_CSTART) + q0, c->device, (size_t)(q1 - q0) * 4, X);
@@ -366,7 +386,7 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
         src.band_segs = shard_segments(ctx->d_edges, src.seg_cap, buf<unsigned long long>(ctx, SB_BCOUNTS));
         for (uint32_t d = 1; d < G; d++) {
             hmk_ctx *pc = dev(d);
-            if (pc->device == ctx->device)   // (a context on the root's own device: its compacted band block and that block's size, where they lie)
+            if (same_device(pc, ctx, ctx->sw))   // (a context on the root's own device: its compacted band block and that block's size, where they lie)
                 src.band_segs.s[src.band_segs.n++] = EdgeSeg{buf<uint64_t>(pc, SB_PEERBAND), buf<unsigned long long>(pc, SB_ROUTECNT) + HMK_MAX_DEVICES, jobs[d]->band_region};
             else
                 src.band_segs.s[src.band_segs.n++] = EdgeSeg{root_band + jobs[d]->band_off, root_cnt + HMK_MAX_SEGS + d, jobs[d]->band_region};
@@ -418,7 +438,18 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
             if (jp->sent_state == -2) overflow = true;
             want_edges[jp->d] = std::max(want_edges[jp->d], jp->need_edges);
             want_inbox[jp->d] = std::max(want_inbox[jp->d], jp->need_inbox);
+            jp->c->inbox_entries = std::max(jp->c->inbox_entries, jp->need_inbox);
+            copies[0] += jp->copies_edge; copies[1] += jp->copies_band; copies[2] += jp->copies_count; copies[3] += jp->copies_deg; copies[4] += jp->copies_cand;
         }
+        if (ctx->sw.greedy_timing && overflow)   // (one line per reason and device: what the next attempt is sized for)
+            for (auto &jp : jobs) {
+                if (jp->need_edges)
+                    fprintf(stderr, "[hmk greedy] attempt %d retried: edge segment overflow on device %u of %u (HIP device %d), needs %llu entries\n",
+                            attempt, jp->d, G, jp->c->device, (unsigned long long)jp->need_edges);
+                if (jp->need_inbox)
+                    fprintf(stderr, "[hmk greedy] attempt %d retried: inbox too small on device %u of %u (HIP device %d), needs %llu entries per sender\n",
+                            attempt, jp->d, G, jp->c->device, (unsigned long long)jp->need_inbox);
+            }
         if (st == HMK_OK || st == HMK_ERR_REFERENCE_WOULD_CRASH) {   // (a crash-parity exit during phase 1 never reached before_full)
             const int err = first_error();
             if (err && !overflow) st = err;
@@ -426,6 +457,9 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
         if (st == ST_RETRY_OVERFLOW || (overflow && (st == HMK_OK || st == HMK_ERR_REFERENCE_WOULD_CRASH))) { st = ST_RETRY_OVERFLOW; continue; }
         break;
     }
+    if (ctx->sw.greedy_timing)
+        fprintf(stderr, "[hmk greedy] peer copies of %u devices%s: %u edge blocks, %u band blocks, %u counts, %u degree slices, %u candidate regions\n",
+                G, ctx->sw.multi_force_copies ? " (HMK_MULTI_FORCE_COPIES)" : "", copies[0], copies[1], copies[2], copies[3], copies[4]);
     if (st == ST_RETRY_OVERFLOW) return fail(ctx, HMK_ERR_DEVICE, "internal edge buffer kept overflowing");
     float ms = 0;
     if (hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_edges) == hipSuccess) ctx->phases.score_ms = ctx->phases.exchange_ms = ms;   // the root's shard, the exchange, the pieces

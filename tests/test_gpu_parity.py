@@ -494,11 +494,14 @@ def test_greedy_3e5_vs_oracle(gpu, blosum62, coracle):
 def test_greedy_multi_device_context(gpu, blosum62, coracle, devices, monkeypatch):
     """hmk_create_multi: the multi-GPU form below the C ABI.  On a one-GPU box the device list names it one, two, three and
     eight times -- every "device" has its own context, worker thread, plan (shard d of n, band tiles first), edge buffer and
-    streams, and OWNS a range of rows: its edges are dealt into one block per owning device and travel device to device
-    (hipMemcpyPeerAsync), every device builds the CSR of its own rows and pre-checks the leftovers whose rows it holds; the
-    root builds the band's adjacency, runs phase 1 on the host and the second loop over all candidate lists, reading a joiner's
-    row where it lives.  With two or more GPUs the same test runs on distinct ordinals (peer access, real xGMI copies).  Must
-    equal the single-device call and the oracle."""
+    streams, and OWNS a range of rows: its edges are dealt into one block per owning device, every device builds the CSR of
+    its own rows and pre-checks the leftovers whose rows it holds; the root builds the band's adjacency, runs phase 1 on the
+    host and the second loop over all candidate lists, reading a joiner's row where it lives.  Contexts on ONE ordinal copy
+    (hipMemcpyPeerAsync inside the device) only the degree slices, the candidate regions and lists and, with
+    HMK_MULTI_REPLICATE, the finished pieces; the edge blocks, their sizes and the peers' band blocks are read where their
+    sender left them -- no inbox, no slot, no capacity check, no gathered band.  Those run on one GPU under
+    HMK_MULTI_FORCE_COPIES (tests/test_multi_exchange.py), and here on distinct ordinals wherever two or more GPUs are visible
+    (peer access, real xGMI copies).  Must equal the single-device call and the oracle."""
     n = 40000
     res, off = synth_peptides(21, n, 12)
     rng = np.random.default_rng(21)
@@ -589,30 +592,44 @@ def test_greedy_after_reserve_with_late_buffers(gpu, blosum62, coracle, monkeypa
         del ctx
 
 
-def test_greedy_edge_buffer_overflow_retry(gpu, blosum62, coracle, monkeypatch):
+def test_greedy_edge_buffer_overflow_retry(gpu, blosum62, coracle, monkeypatch, capfd):
     """The first guess of the edge buffer is too small (forced: HMK_EDGE_GUESS): segments overflow, edges are dropped, and
     the CSR / band kernels enqueued behind the pass run on that truncated edge set before the host sees the counters.
     They must stay inside their buffers (degrees are counted for STORED edges only) and the call must come back with the
-    right clustering after growing the buffer and scoring again -- single device, two devices, both second-loop paths."""
+    right clustering after growing the buffer and scoring again -- single device, two devices, both second-loop paths, and two
+    and three contexts exchanging through inboxes (HMK_MULTI_FORCE_COPIES: the retry's copies and its line on stderr are checked)."""
+    import re
     n = 50000
     res, off = synth_peptides(31, n, 12)
     st, ocid, oorder, ostats = coracle.greedy_cluster(blosum62, res, off, None, 0, 3, 0, 20, 1250, 8)
     assert st == 0
     monkeypatch.setenv("HMK_EDGE_GUESS", "1")
-    cases = [(0, None), (0, "host"), ([0, 0], None)]
+    cases = [(0, None, False), (0, "host", False), ([0, 0], None, False), ([0, 0], None, True), ([0, 0, 0], None, True)]
     if gpu_count() >= 2:
-        cases.append(([0, 1], None))   # distinct GPUs when the box has them
-    for devices, mode in cases:
+        cases.append(([0, 1], None, False))   # distinct GPUs when the box has them
+    for devices, mode, forced in cases:
+        for var in ("HMK_MULTI_FORCE_COPIES", "HMK_GREEDY_TIMING"):
+            if forced:
+                monkeypatch.setenv(var, "1")
+            else:
+                monkeypatch.delenv(var, raising=False)
         if mode:
             monkeypatch.setenv("HMK_SECOND_LOOP", mode)
         else:
             monkeypatch.delenv("HMK_SECOND_LOOP", raising=False)
         ctx = hammock_amd.Context(blosum62, device=devices)   # fresh context: no buffer grown by an earlier call
         ctx.set_sequences(residues=res, offsets=off)
+        capfd.readouterr()
         cid, order, stats = ctx.greedy_cluster(3, 0, 20, 1250)
+        err = capfd.readouterr().err
         assert stats.n_edges > 16 * 65536                     # more edges than the forced first buffer holds
         assert np.array_equal(cid, ocid) and np.array_equal(order, oorder)
         assert np.array_equal(ctx.member_rank[:n], ostats.member_rank)
+        if forced:
+            G = len(devices)
+            assert len(re.findall(r"attempt \d+ retried: edge segment overflow on device \d+ of %d " % G, err)) >= 1
+            edge_blocks, counts = map(int, re.search(r"peer copies of %d devices \(HMK_MULTI_FORCE_COPIES\): (\d+) edge blocks, \d+ band blocks, (\d+) counts" % G, err).groups())
+            assert edge_blocks >= G * (G - 1) and counts >= G * (G - 1)   # (the attempt that overflowed gave up before its copies)
 
 
 def test_one_context_many_calls(gpu, blosum62, coracle):
