@@ -99,17 +99,7 @@ void hmk_destroy(hmk_ctx *ctx) {
     if (ctx->has_device) {
         HMK_QUIET(hipSetDevice(ctx->device));
         (void)join_late_buffers(ctx);
-        free_plan(ctx->plan);
-        free_plan_local(ctx->plan_local);
-        free_plan(ctx->plan_search);
-        free_plan_local(ctx->plan_local_search);
-        free_plan(ctx->plan_assign);
-        free_plan_local(ctx->plan_local_assign);
-        free_plan(ctx->plan_match);
-        free_plan_local(ctx->plan_local_match);
-        free_plan(ctx->plan_continue);
-        free_plan(ctx->plan_continue_tri);
-        free_plan(ctx->plan_merge);
+        free_plans(ctx);
         if (ctx->d_res32) HMK_QUIET(hipFree(ctx->d_res32));
         if (ctx->d_len) HMK_QUIET(hipFree(ctx->d_len));
         if (ctx->d_M) HMK_QUIET(hipFree(ctx->d_M));
@@ -180,17 +170,7 @@ int hmk_set_sequences(hmk_ctx *ctx, const uint8_t *residues, const uint32_t *off
     if (ctx->has_device) {
         int st = need_device(ctx);
         if (st) return st;
-        free_plan(ctx->plan);
-        free_plan_local(ctx->plan_local);
-        free_plan(ctx->plan_search);
-        free_plan_local(ctx->plan_local_search);
-        free_plan(ctx->plan_assign);
-        free_plan_local(ctx->plan_local_assign);
-        free_plan(ctx->plan_match);
-        free_plan_local(ctx->plan_local_match);
-        free_plan(ctx->plan_continue);
-        free_plan(ctx->plan_continue_tri);
-        free_plan(ctx->plan_merge);
+        free_plans(ctx);
         if (ctx->d_res32) (void)hipFree(ctx->d_res32);
         if (ctx->d_len) (void)hipFree(ctx->d_len);
         ctx->d_res32 = nullptr;

@@ -1,6 +1,6 @@
 // hmk_assign.cpp -- assignment of new sequences [q0, q1) to the existing clusters of the members [r0, r1) of the hmk_set_sequences
 // set (NearestClusterRunner / findNearestClusterParallel, ClinkageSequenceClusterer.java:137-177, 243-294, with
-// ClinkageClusterScorer.java:30-49).  The pass is the search's rectangle (hmk_search.cpp) with the members on the side the planner
+// ClinkageClusterScorer.java:30-49).  The pass is the search's rectangle (hmk_plan.cpp) with the members on the side the planner
 // emits as m = seq1, in the assignment's own plan slots; the aggregation per (new sequence, cluster) and the best-k selection run
 // on the device (k_assign.hip); the extern "C" entry points.
 #include "hmk_ctx.h"
@@ -67,7 +67,7 @@ int check_assign(hmk_ctx *ctx, const char *what, uint32_t q0, uint32_t q1, uint3
 }
 
 // the pass of the rectangle members [r0, r1) x new [q0, q1) into ctx->d_edges, the members as the search's queries, which every
-// tier emits as m = seq1 (hmk_search.cpp), in the plan slots `pl` / `pll`; -> the shards' counts, their total, the stats
+// tier emits as m = seq1 (hmk_plan.cpp), in the plan slots `pl` / `pll`; -> the shards' counts, their total, the stats
 // (kernel_ms = the pass)
 int cluster_pass(hmk_ctx *ctx, bool local, Plan &pl, PlanLocal &pll, int a, int b, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1,
                  unsigned long long counts[HMK_EDGE_SHARDS], uint64_t *total, hmk_neighbor_stats *S) {

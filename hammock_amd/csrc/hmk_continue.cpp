@@ -1,6 +1,6 @@
 // hmk_continue.cpp -- continuing a greedy clustering with new sequences: the second loop of LimitedGreedySequenceClusterer.cluster
 // (LimitedGreedySequenceClusterer.java:59-67) with actualClusters = given clusters and actualSequences = the new sequences [q0, q1)
-// of the hmk_set_sequences set.  Scoring: members x new (the search's rectangle, hmk_search.cpp) and new x new (its triangle) into
+// of the hmk_set_sequences set.  Scoring: members x new (the search's rectangle, hmk_plan.cpp) and new x new (its triangle) into
 // one edge list; the CSR of the new rows (piece_enqueue_csr), the pre-check (piece_precheck) and the rounds (device_second_loop) of
 // hmk_cluster.cpp; the extern "C" entry point.
 #include "hmk_ctx.h"

@@ -91,7 +91,16 @@ struct Switches {
     void read();
 };
 
-struct Plan {
+// the device copies every plan has (hmk_plan.cpp: upload_plan)
+struct PlanArrays {
+    uint8_t *d_res_sorted = nullptr;
+    uint32_t *d_perm = nullptr;
+    bool perm_identity = false;
+    TileClass *d_classes = nullptr;
+    Tile *d_tiles = nullptr;
+};
+
+struct Plan : PlanArrays {
     bool valid = false;
     int X = 0, p = 0, thr = 0;
     uint32_t part = 0, n_parts = 1;
@@ -105,26 +114,16 @@ struct Plan {
     uint32_t *d_keyrun = nullptr;  // NeighborParams::keyrun / keytab (null: the plan is not key-sorted)
     uint32_t *d_keytab = nullptr;
     uint32_t cols_per_tile = 16384;
-    uint8_t *d_res_sorted = nullptr;
-    uint32_t *d_perm = nullptr;
-    bool perm_identity = false;
     uint8_t *d_mb = nullptr;
-    TileClass *d_classes = nullptr;
-    Tile *d_tiles = nullptr;
     std::vector<Group> groups;
     hmk_neighbor_stats stats{};
     uint64_t band_pairs = 0;   // pairs inside the band tiles (of stats.pairs_scored)
     uint32_t q0 = 0, q1 = 0, r0 = 0, r1 = 0;   // a search plan (build_plan_search): its query and reference ranges
 };
 
-struct PlanLocal {
+struct PlanLocal : PlanArrays {
     bool valid = false;
     uint32_t part = 0, n_parts = 1;
-    uint8_t *d_res_sorted = nullptr;
-    uint32_t *d_perm = nullptr;
-    bool perm_identity = false;
-    TileClass *d_classes = nullptr;
-    Tile *d_tiles = nullptr;
     uint32_t n_tiles = 0;
     uint64_t pairs = 0;
     uint32_t q0 = 0, q1 = 0, r0 = 0, r1 = 0;   // a search plan (build_plan_local_search): its query and reference ranges
@@ -305,22 +304,20 @@ uint64_t first_edge_capacity(const hmk_ctx *ctx, uint32_t n);
 int grow_edge_buffer(hmk_ctx *ctx, uint64_t cap);
 // ---- hmk_plan.cpp
 void free_plan(Plan &pl);
+void free_plan_local(PlanLocal &pl);
+void free_plans(hmk_ctx *ctx);   // every plan slot of the context
 void classify(const hmk_ctx *ctx, int la, int lb, int X, int p, int thr, TileClass *out, long long row_bound = -1,
               long long *u8_row_limit = nullptr);
 // key_sort_ok: a plain single-part pass (no band, no degree counters) that may take the key-sorted order
 int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_parts, int64_t band_rows = -1, bool key_sort_ok = false);
-void free_plan_local(PlanLocal &pl);
 int build_plan_local(hmk_ctx *ctx, uint32_t part, uint32_t n_parts);
-// ---- hmk_search.cpp
-// the rectangle queries [q0, q1) x references [r0, r1) (disjoint, non-empty): ctx->plan_search / ctx->plan_local_search
-int build_plan_search(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
-int build_plan_local_search(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
-// ... into the plan slot `pl` (the assignment's own, hmk_assign.cpp)
+// the rectangle queries [q0, q1) x references [r0, r1) (disjoint, non-empty) into the plan slot `pl` (the search's, the
+// assignment's, ... own)
 int build_plan_search(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
+int build_plan_local_search(hmk_ctx *ctx, PlanLocal &pl, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
 // the triangle of the pairs inside [q0, q1) (symmetric matrices; hmk_continue.cpp's new x new) into the plan slot `pl`
 int build_plan_triangle(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1);
-int build_plan_local_search(hmk_ctx *ctx, PlanLocal &pl, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
-// the search's parameter checks of a shifted rectangle (the shift against both ranges, threshold and int16 limits)
+// the parameter checks of a shifted rectangle (the shift against both ranges, threshold and int16 limits)
 int check_shifted(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
 // ---- hmk_assign.cpp
 // the clusters' argument checks of the assignment and the continuation (`what` names the call in the range message):

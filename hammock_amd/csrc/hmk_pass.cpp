@@ -60,7 +60,7 @@ int neighbors_dev_locked(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uin
     return launch_plan(ctx, ctx->plan, X, p, thr, d_edges, capacity, d_counts, stream, which, d_deg, d_deg_lo);
 }
 
-// the launches of a built plan (the all-vs-all plan or a search plan, hmk_search.cpp)
+// the launches of a built plan (the all-vs-all plan or a search plan, hmk_plan.cpp)
 int launch_plan(hmk_ctx *ctx, const Plan &pl, int X, int p, int thr, void *d_edges, uint64_t capacity, void *d_counts,
                 hipStream_t stream, int which, uint32_t *d_deg, uint32_t *d_deg_lo) {
     if (which != LAUNCH_REST) HIPCHK(ctx, hipMemsetAsync(d_counts, 0, HMK_EDGE_SHARDS * sizeof(unsigned long long), stream));

@@ -1,5 +1,7 @@
-// hmk_plan.cpp -- the planner of the neighbour passes: length buckets, score bounds and lane classes (classify), kernel
-// selection per class, tiles and launch groups (build_plan); the LocalAlignmentScorer pass's plan (build_plan_local).
+// hmk_plan.cpp -- the planner of every neighbour pass.  The steps all plans share (length sort, kernel choice per class, the tiles
+// of a row chunk, launch-group order, device copies, parameter checks); score bounds and lane classes (classify); the builders:
+// build_plan (all-vs-all: triangle or full square), build_plan_search / build_plan_triangle (the rectangle of two ranges, the
+// triangle of one), build_plan_local and build_plan_local_search (the LocalAlignmentScorer passes).
 #include "hmk_ctx.h"
 
 namespace hmk { namespace impl {
@@ -38,15 +40,223 @@ void parallel_stable_sort(std::vector<T> &v, Cmp before) {
     if (from != &v) v.swap(other);
 }
 
-void free_plan(Plan &pl) {
+namespace {
+
+// ---- the steps every builder shares ------------------------------------------------------------------------------------------
+// bucket starts by length: the sequences of length l are the sorted positions [l] .. [l + 1]
+using Buckets = uint32_t[HMK_MAX_LEN + 2];
+
+// "sorted order": the caller ranges [a0, a1) and then [b0, b1) (empty: one range), each counting-sorted by length (stable: a
+// bucket keeps the caller's order)
+void sort_by_length(const hmk_ctx *ctx, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, Buckets &ba, Buckets &bb,
+                    std::vector<uint32_t> &perm) {
+    const uint32_t lo[2] = {a0, b0}, hi[2] = {a1, b1};
+    uint32_t *const bucket[2] = {ba, bb};
+    perm.resize((size_t)(a1 - a0) + (b1 - b0));
+    for (int side = 0; side < 2; side++) {
+        uint32_t *b = bucket[side];
+        std::fill(b, b + HMK_MAX_LEN + 2, 0u);
+        for (uint32_t k = lo[side]; k < hi[side]; k++) b[ctx->len[k] + 1]++;
+        b[0] = side ? a1 - a0 : 0u;
+        for (int l = 0; l <= HMK_MAX_LEN; l++) b[l + 1] += b[l];
+        Buckets fill;
+        std::memcpy(fill, b, sizeof(fill));
+        for (uint32_t k = lo[side]; k < hi[side]; k++) perm[fill[ctx->len[k]]++] = k;
+    }
+}
+
+// The kernel of a class: row-packed kernels (k_neighbors_rows.hip) take every 8-bit-lane class they have an instantiation for,
+// the shift-packed or direct tiers the rest.  key = the launch group: (kernel family, entry dwords | length difference, column capacity)
+using GroupKey = std::tuple<int, int, int>;
+struct KernelChoice { bool rows; int lbk; uint32_t R; GroupKey key; };   // lbk: column capacity; R: rows per tile
+
+KernelChoice choose_kernel(const TileClass &tc, int X, bool use_rows, bool rows_exact, bool exact) {
+    const int la = tc.la, lb = tc.lb;
+    KernelChoice k;
+    k.rows = use_rows && tc.path == PATH_U8 && la >= lb && (rows_exact || rows_kernel_available(X, la, lb, false));
+    k.lbk = k.rows ? (rows_exact ? lb : rows_cap_for(lb)) : exact ? 12 : swar_lbmax_for(lb);
+    k.R = k.rows ? (uint32_t)rows_per_tile_rows(X, la - lb, k.lbk, rows_exact)
+                 : tc.path == PATH_DIRECT ? 16u : (uint32_t)swar_rows_per_tile(k.lbk, tc.nw, exact);
+    k.key = k.rows ? GroupKey((int)PATH_ROWS, la - lb, k.lbk)
+                   : GroupKey((int)tc.path, tc.path == PATH_DIRECT ? 0 : (int)tc.nw, tc.path == PATH_DIRECT ? 0 : k.lbk);
+    return k;
+}
+
+uint32_t add_class(std::vector<TileClass> &classes, hmk_neighbor_stats &S, const TileClass &tc, bool rows) {
+    classes.push_back(tc);
+    if (tc.path == PATH_U8) S.classes_u8++;
+    else if (tc.path == PATH_U16) S.classes_u16++;
+    else S.classes_direct++;
+    if (rows) S.classes_rows++;
+    return (uint32_t)classes.size() - 1;
+}
+
+// a band (build_plan): the tiles of a chunk whose rows are in it, or whose first column is below col_end, are flagged (Tile::pad0,
+// host side only) and their pairs counted
+struct Band { bool rows; uint32_t col_end; uint64_t pairs; };
+
+// The tiles of the row chunk [r0, r0 + nr) against the columns [c_lo, c_hi), appended to dst; -> the pairs they hold.
+// equal_runs: equal column runs of whole 256-column batches instead of full runs of `cols` + one short rest -- no tiny tiles whose
+// table build is not amortised, and an even tail (the local plans take full runs).
+// diag: rows and columns index the same sorted positions, and a tile that reaches the diagonal keeps only column > row (1) or
+// drops the diagonal (2); 0: two different sets.  Tiles left without a pair are not emitted.
+uint64_t emit_tiles(std::vector<Tile> &dst, uint32_t cls, uint32_t r0, uint32_t nr, uint32_t c_lo, uint32_t c_hi, uint32_t cols,
+                    bool equal_runs, uint32_t diag, Band *band = nullptr) {
+    if (c_lo >= c_hi) return 0;
+    uint32_t run = cols;
+    if (equal_runs) {
+        const uint32_t k_runs = (c_hi - c_lo + cols - 1) / cols;
+        run = std::min(cols, ((c_hi - c_lo + k_runs - 1) / k_runs + 255u) & ~255u);
+    }
+    uint64_t total = 0;
+    for (uint32_t c0 = c_lo; c0 < c_hi; c0 += run) {
+        Tile t{};
+        t.row0 = r0; t.nrows = nr;
+        t.col0 = c0; t.ncols = std::min(run, c_hi - c0);
+        t.cls = cls;
+        t.diag = (c0 < r0 + nr && c0 + t.ncols > r0) ? diag : 0u;
+        uint64_t pairs = (uint64_t)nr * t.ncols;
+        if (t.diag == 1) {
+            pairs = 0;
+            for (uint32_t r = r0; r < r0 + nr; r++) {
+                const uint32_t lo = std::max(c0, r + 1), hi = c0 + t.ncols;
+                if (hi > lo) pairs += hi - lo;
+            }
+        } else if (t.diag == 2) {
+            for (uint32_t r = r0; r < r0 + nr; r++)
+                if (r >= c0 && r < c0 + t.ncols) pairs--;
+        }
+        if (pairs == 0) continue;
+        total += pairs;
+        if (band && (band->rows || c0 < band->col_end)) {
+            t.pad0 = 1u;
+            band->pairs += pairs;
+        }
+        dst.push_back(t);
+    }
+    return total;
+}
+
+// The launch groups and the flat tile array they index.  Workgroups are dispatched in tile order: biggest tiles first keeps the
+// tail of a launch short; band tiles before all others (they are launched on their own by hmk_greedy_cluster).
+// (10^6 sequences: a million tiles; the stable sort of them was 30 of the plan's 55 ms on one thread)
+std::vector<Tile> order_groups(std::map<GroupKey, std::vector<Tile>> &grouped, const std::vector<TileClass> &classes, int X,
+                               std::vector<Group> &groups) {
+    std::vector<Tile> tiles;
+    for (auto &kv : grouped) {
+        if (kv.second.empty()) continue;
+        parallel_stable_sort(kv.second, [](const Tile &a, const Tile &b) {
+            if (a.pad0 != b.pad0) return a.pad0 > b.pad0;
+            return (uint64_t)a.nrows * a.ncols > (uint64_t)b.nrows * b.ncols;
+        });
+        uint32_t n_band = 0;
+        uint64_t work = 0;
+        for (const Tile &t : kv.second) {
+            n_band += t.pad0;
+            const TileClass &tc = classes[t.cls];
+            const int lb = std::min((int)tc.la, (int)tc.lb), d = std::abs((int)tc.la - (int)tc.lb);
+            work += (uint64_t)t.nrows * t.ncols * (uint64_t)std::max(1, lb * (2 * X + d + 1) - X * (X + 1));
+        }
+        groups.push_back(Group{std::get<0>(kv.first), std::get<1>(kv.first), std::get<2>(kv.first), (uint32_t)tiles.size(),
+                               (uint32_t)kv.second.size(), n_band, work});
+        tiles.insert(tiles.end(), kv.second.begin(), kv.second.end());
+    }
+    return tiles;
+}
+
+// The device copies every plan has.  Residues in sorted order: `stride` bytes per sequence (zero-padded) and `tail` bytes after
+// the last, each residue times `mul` (the exact kernel reads them pre-multiplied by its entry size).
+int upload_plan(hmk_ctx *ctx, PlanArrays &pl, const std::vector<uint32_t> &perm, size_t stride, size_t tail, int mul,
+                const std::vector<TileClass> &classes, const std::vector<Tile> &tiles) {
+    const uint32_t n = (uint32_t)perm.size();
+    std::vector<uint8_t> res_sorted((size_t)n * stride + tail, 0);
+    {   // (rows are independent: several threads for large sets -- 10 ms on one at 10^6)
+        const unsigned hw = usable_cpus();
+        const unsigned T = n >= (1u << 18) ? std::max(1u, std::min(8u, hw ? hw : 1u)) : 1u;
+        auto fill = [&](uint32_t lo, uint32_t hi) {
+            for (uint32_t s = lo; s < hi; s++) {
+                const uint32_t k = perm[s];
+                uint8_t *row = &res_sorted[(size_t)s * stride];
+                if (mul == 1) std::memcpy(row, &ctx->res[ctx->off[k]], ctx->len[k]);
+                else for (uint32_t q = 0; q < ctx->len[k]; q++) row[q] = (uint8_t)(ctx->res[ctx->off[k] + q] * mul);
+            }
+        };
+        std::vector<std::thread> pool;
+        for (unsigned t = 1; t < T; t++) pool.emplace_back(fill, (uint32_t)((uint64_t)n * t / T), (uint32_t)((uint64_t)n * (t + 1) / T));
+        fill(0, (uint32_t)((uint64_t)n / T));
+        for (std::thread &th : pool) th.join();
+    }
+    HIPCHK(ctx, hipMalloc((void **)&pl.d_res_sorted, res_sorted.size()));
+    HIPCHK(ctx, hipMemcpy(pl.d_res_sorted, res_sorted.data(), res_sorted.size(), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMalloc((void **)&pl.d_perm, (size_t)n * 4));
+    HIPCHK(ctx, hipMemcpy(pl.d_perm, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    // (identity: the sorted positions ARE the caller indices -- one length; a rectangle's references right behind queries from 0)
+    pl.perm_identity = true;
+    for (uint32_t q = 0; q < n && pl.perm_identity; q++) pl.perm_identity = perm[q] == q;
+    HIPCHK(ctx, hipMalloc((void **)&pl.d_classes, std::max<size_t>(1, classes.size()) * sizeof(TileClass)));
+    if (!classes.empty())
+        HIPCHK(ctx, hipMemcpy(pl.d_classes, classes.data(), classes.size() * sizeof(TileClass), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMalloc((void **)&pl.d_tiles, std::max<size_t>(1, tiles.size()) * sizeof(Tile)));
+    if (!tiles.empty())
+        HIPCHK(ctx, hipMemcpy(pl.d_tiles, tiles.data(), tiles.size() * sizeof(Tile), hipMemcpyHostToDevice));
+    return HMK_OK;
+}
+
+void free_arrays(PlanArrays &pl) {
     if (pl.d_res_sorted) (void)hipFree(pl.d_res_sorted);
     if (pl.d_perm) (void)hipFree(pl.d_perm);
-    if (pl.d_mb) (void)hipFree(pl.d_mb);
     if (pl.d_classes) (void)hipFree(pl.d_classes);
     if (pl.d_tiles) (void)hipFree(pl.d_tiles);
+}
+
+// the matrix as biased bytes (what the shifted tiers' tables are built from)
+int upload_biased_matrix(hmk_ctx *ctx, Plan &pl) {
+    const int bias = ctx->min_m < 0 ? -ctx->min_m : 0;
+    uint8_t mb[576];
+    for (int e = 0; e < 576; e++) {
+        const long long v = (long long)ctx->M[e] + bias;
+        mb[e] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);  // only read by classes that passed the range check
+    }
+    HIPCHK(ctx, hipMalloc((void **)&pl.d_mb, 576));
+    HIPCHK(ctx, hipMemcpy(pl.d_mb, mb, 576, hipMemcpyHostToDevice));
+    return HMK_OK;
+}
+
+// what every shifted pass checks on its parameters after max_shift >= 0; `shortest`: the shortest sequence the pass scores
+int check_shift_threshold_scores(hmk_ctx *ctx, int X, int p, int thr, int shortest) {
+    if (X >= shortest)
+        return fail(ctx, HMK_ERR_SHIFT_TOO_BIG, "Shift too big: " + std::to_string(shortest - 1) + " is maximum, but " + std::to_string(X) +
+                                                    " found");  // ShiftedScorer.java:59-62
+    if (thr < -30000 || thr > 30000) return fail(ctx, HMK_ERR_BAD_ARG, "threshold outside [-30000, 30000]");
+    // edge scores travel as int16: the largest score any pair (of the whole set) can reach must fit
+    const long long top = (long long)ctx->max_len * std::max(0, ctx->max_m) +
+                          (long long)std::max(0, p) * ((ctx->max_len - ctx->min_len) + 2LL * X);
+    if (top > 32767)
+        return fail(ctx, HMK_ERR_BAD_ARG, "scores up to " + std::to_string(top) + " are possible with this matrix / shift penalty: "
+                                           "they do not fit the int16 score of a packed edge");
+    return HMK_OK;
+}
+
+}  // namespace
+
+void free_plan(Plan &pl) {
+    free_arrays(pl);
+    if (pl.d_mb) (void)hipFree(pl.d_mb);
     if (pl.d_keyrun) (void)hipFree(pl.d_keyrun);
     if (pl.d_keytab) (void)hipFree(pl.d_keytab);
     pl = Plan();
+}
+
+void free_plan_local(PlanLocal &pl) {
+    free_arrays(pl);
+    pl = PlanLocal();
+}
+
+void free_plans(hmk_ctx *ctx) {
+    for (Plan *pl : {&ctx->plan, &ctx->plan_search, &ctx->plan_assign, &ctx->plan_match, &ctx->plan_continue, &ctx->plan_continue_tri,
+                     &ctx->plan_merge})
+        free_plan(*pl);
+    for (PlanLocal *pl : {&ctx->plan_local, &ctx->plan_local_search, &ctx->plan_local_assign, &ctx->plan_local_match}) free_plan_local(*pl);
 }
 
 // Lane layout of one (row length, column length) class; see DESIGN.md "SWAR tables".
@@ -125,29 +335,12 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
     if (n == 0) return fail(ctx, HMK_ERR_NO_SEQUENCES, "no sequences set (hmk_set_sequences)");
     if (X < 0) return fail(ctx, HMK_ERR_BAD_ARG, "max_shift must be >= 0");
     if (n_parts == 0 || part >= n_parts) return fail(ctx, HMK_ERR_BAD_ARG, "part must be < n_parts");
-    if (X >= ctx->min_len)
-        return fail(ctx, HMK_ERR_SHIFT_TOO_BIG,
-                    "Shift too big: " + std::to_string(ctx->min_len - 1) + " is maximum, but " + std::to_string(X) +
-                        " found");  // ShiftedScorer.java:59-62
-    if (thr < -30000 || thr > 30000) return fail(ctx, HMK_ERR_BAD_ARG, "threshold outside [-30000, 30000]");
-    {   // edge scores travel as int16: the largest score any pair can reach must fit
-        const long long top = (long long)ctx->max_len * std::max(0, ctx->max_m) +
-                              (long long)std::max(0, p) * ((ctx->max_len - ctx->min_len) + 2LL * X);
-        if (top > 32767)
-            return fail(ctx, HMK_ERR_BAD_ARG, "scores up to " + std::to_string(top) + " are possible with this matrix / shift penalty: "
-                                               "they do not fit the int16 score of a packed edge");
-    }
+    int st = check_shift_threshold_scores(ctx, X, p, thr, ctx->min_len);
+    if (st) return st;
 
-    // ---- bucket by length ("sorted order") --------------------------------------
-    uint32_t bucket[HMK_MAX_LEN + 2] = {0};
-    for (uint32_t k = 0; k < n; k++) bucket[ctx->len[k] + 1]++;
-    for (int l = 0; l <= HMK_MAX_LEN; l++) bucket[l + 1] += bucket[l];
-    std::vector<uint32_t> perm(n);
-    {
-        uint32_t fill[HMK_MAX_LEN + 2];
-        std::memcpy(fill, bucket, sizeof(fill));
-        for (uint32_t k = 0; k < n; k++) perm[fill[ctx->len[k]]++] = k;
-    }
+    Buckets bucket, none;
+    std::vector<uint32_t> perm;
+    sort_by_length(ctx, 0, n, 0, 0, bucket, none, perm);
     // Per-sequence score bound: no pair involving sequence k scores above bound[k] = sum over its residues
     // of the best (non-negative) cell of that residue's matrix row/column.  If some class does not fit
     // 8-bit lanes for arbitrary pairs, its bucket is ordered by this bound and the rows below the class's
@@ -227,9 +420,9 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
     pl.lbmax = swar_lbmax_for(ctx->max_len);
     pl.lpad = ctx->max_len <= 16 ? 16 : 32;
     // The exact hot kernel: every sequence has length 12, max shift 3, and the (12, 12) class fits 8-bit
-    // lanes in 8-byte entries.  It reads residues pre-multiplied by the entry size (see res_sorted below).
-    // Row-packed kernels (k_neighbors_rows.hip) take every 8-bit-lane class they have an instantiation for; a set of one
-    // length may have one with the length at compile time.  HMK_NO_ROWS_KERNEL=1: the shift-packed kernels of round 1-2.
+    // lanes in 8-byte entries.  It reads residues pre-multiplied by the entry size (upload_plan's mul).
+    // A set of one length may have a row-packed kernel with the length at compile time.  HMK_NO_ROWS_KERNEL=1: the shift-packed
+    // kernels of round 1-2.
     const bool use_rows = !ctx->sw.no_rows_kernel;
     pl.no_rows_kernel = ctx->sw.no_rows_kernel;
     pl.exact = false;
@@ -295,14 +488,11 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
 
     // ---- classes and tiles --------------------------------------------------------
     std::vector<TileClass> classes;
-    std::map<int, int> class_of;  // la * 64 + lb
-    std::map<std::tuple<int, int, int>, std::vector<Tile>> grouped;  // (path, nw, column capacity)
-    const uint32_t COLS = pl.cols_per_tile;
-    const bool equal_runs = true;
+    std::map<GroupKey, std::vector<Tile>> grouped;
     hmk_neighbor_stats &S = pl.stats;
     S = hmk_neighbor_stats{};
     S.symmetric = ctx->symmetric;
-    uint64_t row_chunk_counter = 0;
+    uint64_t row_chunk_counter = 0;   // over every chunk of every class, in class order: chunk c belongs to part c % n_parts
     for (int la = 1; la <= HMK_MAX_LEN; la++) {
         const uint32_t rb = bucket[la], re = bucket[la + 1];
         if (rb == re) continue;
@@ -338,128 +528,30 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
                 if (split < re) ranges.push_back(Range{split, re, tc0});
             }
             for (const Range &rg : ranges) {
-                const TileClass &tc = rg.tc;
-                const int cls = (int)classes.size();
-                classes.push_back(tc);
-                class_of[la * 64 + lb] = cls;
-                if (tc.path == PATH_U8) S.classes_u8++;
-                else if (tc.path == PATH_U16) S.classes_u16++;
-                else S.classes_direct++;
-                // launch group: (kernel family, entry dwords | length difference, column capacity)
-                const bool rows = use_rows && tc.path == PATH_U8 && la >= lb &&
-                                  (pl.rows_exact || rows_kernel_available(X, la, lb, false));
-                const int lbk = rows ? (pl.rows_exact ? lb : rows_cap_for(lb)) : pl.exact ? 12 : swar_lbmax_for(lb);
-                const uint32_t R = rows ? (uint32_t)rows_per_tile_rows(X, la - lb, lbk, pl.rows_exact)
-                                        : tc.path == PATH_DIRECT ? 16u : (uint32_t)swar_rows_per_tile(lbk, tc.nw, pl.exact);
-                if (rows) S.classes_rows++;
-                std::vector<Tile> &dst = grouped[rows ? std::make_tuple((int)PATH_ROWS, la - lb, lbk)
-                                                      : std::make_tuple((int)tc.path, tc.path == PATH_DIRECT ? 0 : (int)tc.nw,
-                                                                        tc.path == PATH_DIRECT ? 0 : lbk)];
-                for (uint32_t r0 = rg.lo; r0 < rg.hi; r0 += R) {
-                    const bool mine = (row_chunk_counter++ % n_parts) == part;
-                    if (!mine) continue;
-                    const uint32_t nr = std::min(R, rg.hi - r0);
-                    uint32_t c_lo = cb, c_hi = ce;
-                    if (same && ctx->symmetric) c_lo = r0 + 1;  // triangle: columns after the first row of the chunk
-                    // equal column runs (whole 256-column batches) instead of full runs + one short rest:
-                    // no tiny tiles whose table build is not amortised, and an even tail
-                    uint32_t run = COLS;
-                    if (c_hi > c_lo && equal_runs) {
-                        const uint32_t k_runs = (c_hi - c_lo + COLS - 1) / COLS;
-                        run = ((c_hi - c_lo + k_runs - 1) / k_runs + 255u) & ~255u;
-                        run = std::min(run, COLS);
-                    }
-                    for (uint32_t c0 = c_lo; c0 < c_hi; c0 += run) {
-                        Tile t{};
-                        t.row0 = r0; t.nrows = nr;
-                        t.col0 = c0; t.ncols = std::min(run, c_hi - c0);
-                        t.cls = (uint32_t)cls;
-                        const bool overlap = same && c0 < r0 + nr && c0 + t.ncols > r0;
-                        t.diag = overlap ? (ctx->symmetric ? 1u : 2u) : 0u;
-                        uint64_t pairs = (uint64_t)nr * t.ncols;
-                        if (t.diag == 1) {
-                            pairs = 0;
-                            for (uint32_t r = r0; r < r0 + nr; r++) {
-                                const uint32_t lo = std::max(c0, r + 1), hi = c0 + t.ncols;
-                                if (hi > lo) pairs += hi - lo;
-                            }
-                        } else if (t.diag == 2) {
-                            for (uint32_t r = r0; r < r0 + nr; r++)
-                                if (r >= c0 && r < c0 + t.ncols) pairs--;
-                        }
-                        if (pairs == 0) continue;
-                        S.pairs_scored += pairs;
-                        t.pad0 = (r0 < band_end[la] || c0 < band_end[lb]) ? 1u : 0u;   // band tile (host-side flag)
-                        if (t.pad0) pl.band_pairs += pairs;
-                        dst.push_back(t);
-                    }
+                const KernelChoice k = choose_kernel(rg.tc, X, use_rows, pl.rows_exact, pl.exact);
+                const uint32_t cls = add_class(classes, S, rg.tc, k.rows);
+                std::vector<Tile> &dst = grouped[k.key];
+                const bool tri = same && ctx->symmetric;   // triangle: the columns after the first row of a chunk, column > row
+                for (uint32_t r0 = rg.lo; r0 < rg.hi; r0 += k.R) {
+                    if ((row_chunk_counter++ % n_parts) != part) continue;
+                    Band band{r0 < band_end[la], band_end[lb], 0};
+                    S.pairs_scored += emit_tiles(dst, cls, r0, std::min(k.R, rg.hi - r0), tri ? r0 + 1 : cb, ce, pl.cols_per_tile, true,
+                                                 tri ? 1u : same ? 2u : 0u, &band);
+                    pl.band_pairs += band.pairs;
                 }
             }
         }
     }
     plan_lap("classes and tiles");
-    std::vector<Tile> tiles;
-    for (auto &kv : grouped) {
-        if (kv.second.empty()) continue;
-        // workgroups are dispatched in tile order: biggest tiles first keeps the tail of the launch short
-        // (band tiles first: they are launched on their own by hmk_greedy_cluster)
-        // (10^6 sequences: a million tiles; the stable sort of them was 30 of the plan's 55 ms on one thread)
-        parallel_stable_sort(kv.second, [](const Tile &a, const Tile &b) {
-            if (a.pad0 != b.pad0) return a.pad0 > b.pad0;
-            return (uint64_t)a.nrows * a.ncols > (uint64_t)b.nrows * b.ncols;
-        });
-        uint32_t n_band = 0;
-        uint64_t work = 0;
-        for (const Tile &t : kv.second) {
-            n_band += t.pad0;
-            const TileClass &tc = classes[t.cls];
-            const int lb = std::min((int)tc.la, (int)tc.lb), d = std::abs((int)tc.la - (int)tc.lb);
-            work += (uint64_t)t.nrows * t.ncols * (uint64_t)std::max(1, lb * (2 * X + d + 1) - X * (X + 1));
-        }
-        pl.groups.push_back(Group{std::get<0>(kv.first), std::get<1>(kv.first), std::get<2>(kv.first),
-                                  (uint32_t)tiles.size(), (uint32_t)kv.second.size(), n_band, work});
-        tiles.insert(tiles.end(), kv.second.begin(), kv.second.end());
-    }
+    const std::vector<Tile> tiles = order_groups(grouped, classes, X, pl.groups);
     S.n_tiles = (uint32_t)tiles.size();
     plan_lap("tile order");
 
     // ---- device copies ------------------------------------------------------------
-    std::vector<uint8_t> res_sorted((size_t)n * pl.lpad + 16, 0);   // + 16: the row-packed kernel's unaligned tail loads may touch the bytes after the last row
-    {   // (rows are independent: several threads for large sets -- 10 ms on one at 10^6)
-        const unsigned hw = usable_cpus();
-        const unsigned T = n >= (1u << 18) ? std::max(1u, std::min(8u, hw ? hw : 1u)) : 1u;
-        auto fill = [&](uint32_t lo, uint32_t hi) {
-            for (uint32_t s = lo; s < hi; s++) {
-                const uint32_t k = perm[s];
-                for (uint32_t q = 0; q < ctx->len[k]; q++)
-                    res_sorted[(size_t)s * pl.lpad + q] = (uint8_t)(ctx->res[ctx->off[k] + q] * (pl.exact ? 8 : 1));
-            }
-        };
-        std::vector<std::thread> pool;
-        for (unsigned t = 1; t < T; t++) pool.emplace_back(fill, (uint32_t)((uint64_t)n * t / T), (uint32_t)((uint64_t)n * (t + 1) / T));
-        fill(0, (uint32_t)((uint64_t)n / T));
-        for (std::thread &th : pool) th.join();
-    }
-    const int bias = ctx->min_m < 0 ? -ctx->min_m : 0;
-    uint8_t mb[576];
-    for (int e = 0; e < 576; e++) {
-        const long long v = (long long)ctx->M[e] + bias;
-        mb[e] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);  // only read by classes that passed the range check
-    }
-    HIPCHK(ctx, hipMalloc((void **)&pl.d_res_sorted, res_sorted.size()));
-    HIPCHK(ctx, hipMemcpy(pl.d_res_sorted, res_sorted.data(), res_sorted.size(), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMalloc((void **)&pl.d_perm, (size_t)n * 4));
-    HIPCHK(ctx, hipMemcpy(pl.d_perm, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    pl.perm_identity = true;
-    for (uint32_t q = 0; q < n && pl.perm_identity; q++) pl.perm_identity = perm[q] == q;
-    HIPCHK(ctx, hipMalloc((void **)&pl.d_mb, 576));
-    HIPCHK(ctx, hipMemcpy(pl.d_mb, mb, 576, hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMalloc((void **)&pl.d_classes, std::max<size_t>(1, classes.size()) * sizeof(TileClass)));
-    if (!classes.empty())
-        HIPCHK(ctx, hipMemcpy(pl.d_classes, classes.data(), classes.size() * sizeof(TileClass), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMalloc((void **)&pl.d_tiles, std::max<size_t>(1, tiles.size()) * sizeof(Tile)));
-    if (!tiles.empty())
-        HIPCHK(ctx, hipMemcpy(pl.d_tiles, tiles.data(), tiles.size() * sizeof(Tile), hipMemcpyHostToDevice));
+    // (+ 16: the row-packed kernel's unaligned tail loads may touch the bytes after the last row)
+    st = upload_plan(ctx, pl, perm, (size_t)pl.lpad, 16, pl.exact ? 8 : 1, classes, tiles);
+    if (!st) st = upload_biased_matrix(ctx, pl);
+    if (st) return st;
     if (key_sorted) {   // run ids, and the key table built on the device from the sorted residues (hipMemcpy above: they are there)
         const uint32_t n_groups = (n + 7) / 8;
         const size_t tab_dwords = (size_t)n_groups * 2 * HMK_ALPHABET * KEYTAB_DWORDS;
@@ -474,13 +566,142 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
     plan_lap("device copies");
     return HMK_OK;
 }
-// ---- LocalAlignmentScorer neighbour pass: plan (tiles of ordered length classes) + launch ----------------
-void free_plan_local(PlanLocal &pl) {
-    if (pl.d_res_sorted) (void)hipFree(pl.d_res_sorted);
-    if (pl.d_perm) (void)hipFree(pl.d_perm);
-    if (pl.d_classes) (void)hipFree(pl.d_classes);
-    if (pl.d_tiles) (void)hipFree(pl.d_tiles);
-    pl = PlanLocal();
+
+// The rectangle of a shifted search.  One class per (query length, reference length); every tile holds rows of one side and a
+// column run of the other (no triangle: Tile::diag = 0, no pair inside one side).  Which side supplies the rows:
+//   symmetric matrix  the side with the LONGER sequences (the row-packed kernels need row length >= column length), at equal lengths
+//                     the side with MORE sequences (rows are the parallel dimension: 10^2 queries x 10^5 references are 6,250
+//                     row groups of references, not 13 of queries).  The kernels emit (min, max) caller indices; the search turns
+//                     every edge to m = query afterwards (k_search.hip).
+//   asymmetric        the references: every shifted tier scores sequenceScore(seq1 = column, seq2 = row) and emits (x = row,
+//                     m = column) (k_neighbors.hip, the all-vs-all asymmetric pass), so with the queries as columns the edges
+//                     come out m = query = seq1 as they are.  Classes the row-packed kernels cannot take (row length < column
+//                     length) run on the shift-packed or direct tiers, as in the all-vs-all asymmetric pass.
+// No score-bound refinement (build_plan's `refine`): a class whose 8-bit lanes do not fit every pair runs on 16-bit lanes.
+// No key sort, no band, no parts.
+// tri (build_plan_triangle): the TRIANGLE of the pairs inside the one range [q0, q1) = [r0, r1) -- hmk_greedy_continue's new x new --
+// under a symmetric matrix: the range is sorted once, the longer bucket supplies the rows, and a class of one length keeps the
+// columns after each row (Tile::diag = 1, as build_plan's triangle); edges (min, max) as above.
+static int build_plan_rect(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, bool tri) {
+    if (pl.valid && pl.X == X && pl.p == p && pl.thr == thr && pl.q0 == q0 && pl.q1 == q1 && pl.r0 == r0 && pl.r1 == r1 &&
+        pl.no_rows_kernel == ctx->sw.no_rows_kernel)
+        return HMK_OK;
+    free_plan(pl);
+    if (tri && !ctx->symmetric) return fail(ctx, HMK_ERR_BAD_ARG, "a triangle plan needs a symmetric matrix");
+    Buckets bq, br;
+    std::vector<uint32_t> perm;
+    sort_by_length(ctx, q0, q1, r0, tri ? r0 : r1, bq, br, perm);
+    if (tri) std::memcpy(br, bq, sizeof(br));   // (one range: rows and columns index the same sorted positions)
+    int mn = HMK_MAX_LEN, mx = 1;
+    for (int l = 1; l <= HMK_MAX_LEN; l++)
+        if (bq[l] != bq[l + 1] || br[l] != br[l + 1]) { mn = std::min(mn, l); mx = std::max(mx, l); }
+    pl.lpad = mx <= 16 ? 16 : 32;
+    pl.lbmax = swar_lbmax_for(mx);
+    const bool use_rows = !ctx->sw.no_rows_kernel;
+    pl.no_rows_kernel = ctx->sw.no_rows_kernel;
+    pl.exact = false;
+    pl.rows_exact = false;
+    if (use_rows && mn == mx) {
+        TileClass t1;
+        classify(ctx, mn, mn, X, p, thr, &t1);
+        pl.rows_exact = t1.path == PATH_U8 && rows_kernel_available(X, mn, mn, true);
+    }
+
+    struct Cls { TileClass tc; KernelChoice k; bool tri; uint32_t rb, re, cb, ce; };
+    std::vector<Cls> cl;
+    for (int lq = 1; lq <= HMK_MAX_LEN; lq++) {
+        const uint32_t nql = bq[lq + 1] - bq[lq];
+        if (!nql) continue;
+        for (int lr = 1; lr <= HMK_MAX_LEN; lr++) {
+            const uint32_t nrl = br[lr + 1] - br[lr];
+            if (!nrl) continue;
+            if (tri && (lr > lq || (lq == lr && nql < 2))) continue;   // (unordered pairs: the longer bucket supplies the rows)
+            const bool rows_q = tri || (ctx->symmetric && (lq > lr || (lq == lr && nql >= nrl)));
+            Cls c{};
+            c.tri = tri && lq == lr;
+            c.rb = rows_q ? bq[lq] : br[lr]; c.re = rows_q ? bq[lq + 1] : br[lr + 1];
+            c.cb = rows_q ? br[lr] : bq[lq]; c.ce = rows_q ? br[lr + 1] : bq[lq + 1];
+            classify(ctx, rows_q ? lq : lr, rows_q ? lr : lq, X, p, thr, &c.tc);
+            c.k = choose_kernel(c.tc, X, use_rows, pl.rows_exact, false);
+            cl.push_back(c);
+        }
+    }
+    // Column runs from the rectangle (not from n): the longest run that still leaves ~8 rounds of workgroups (256 CUs x 7), not
+    // below 4,096 columns (a tile's dead time, build_plan) -- unless the rows alone make less than one round (a handful of rows
+    // against many columns: 5 references x 5 x 10^4 queries under an asymmetric matrix), where shorter runs are the only parallelism.
+    uint64_t row_groups = 0;
+    for (const Cls &c : cl) row_groups += (c.re - c.rb + c.k.R - 1) / c.k.R;
+    auto tiles_at = [&](uint32_t cols) {
+        uint64_t t = 0;
+        for (const Cls &c : cl) t += (uint64_t)((c.re - c.rb + c.k.R - 1) / c.k.R) * ((c.ce - c.cb + cols - 1) / cols);
+        return t;
+    };
+    const uint32_t floor_cols = row_groups >= 1792 ? 4096 : 1024;
+    pl.cols_per_tile = 65536;
+    while (pl.cols_per_tile > floor_cols && tiles_at(pl.cols_per_tile) < 8 * 1792) pl.cols_per_tile /= 2;
+
+    std::vector<TileClass> classes;
+    std::map<GroupKey, std::vector<Tile>> grouped;
+    hmk_neighbor_stats &S = pl.stats;
+    S = hmk_neighbor_stats{};
+    S.symmetric = ctx->symmetric;
+    for (const Cls &c : cl) {
+        const uint32_t cls = add_class(classes, S, c.tc, c.k.rows);
+        std::vector<Tile> &dst = grouped[c.k.key];
+        for (uint32_t y0 = c.rb; y0 < c.re; y0 += c.k.R)   // (triangle: the columns after the chunk's first row)
+            S.pairs_scored += emit_tiles(dst, cls, y0, std::min(c.k.R, c.re - y0), c.tri ? y0 + 1 : c.cb, c.ce, pl.cols_per_tile, true,
+                                         c.tri ? 1u : 0u);
+    }
+    const std::vector<Tile> tiles = order_groups(grouped, classes, X, pl.groups);
+    S.n_tiles = (uint32_t)tiles.size();
+
+    int st = upload_plan(ctx, pl, perm, (size_t)pl.lpad, 16, 1, classes, tiles);   // (+ 16: as build_plan)
+    if (!st) st = upload_biased_matrix(ctx, pl);
+    if (st) return st;
+    pl.X = X; pl.p = p; pl.thr = thr;
+    pl.q0 = q0; pl.q1 = q1; pl.r0 = r0; pl.r1 = r1;
+    pl.valid = true;
+    return HMK_OK;
+}
+
+int build_plan_search(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1) {
+    return build_plan_rect(ctx, pl, X, p, thr, q0, q1, r0, r1, false);
+}
+
+int build_plan_triangle(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1) {
+    return build_plan_rect(ctx, pl, X, p, thr, q0, q1, q0, q1, true);
+}
+
+// ---- LocalAlignmentScorer passes: tiles of ordered (row length, column length) classes, 16 rows (the local kernels' rows per
+// tile) against full column runs; sequences in 32-byte rows ------------------------------------------------------------------
+// rows = the buckets bq, columns = br of the sorted order `perm`; `self`: both are the same set, no sequence is paired with itself
+static int finish_plan_local(hmk_ctx *ctx, PlanLocal &pl, const Buckets &bq, const Buckets &br, const std::vector<uint32_t> &perm,
+                             uint32_t cols, uint32_t part, uint32_t n_parts, bool self) {
+    std::vector<TileClass> classes;
+    std::vector<Tile> tiles;
+    constexpr uint32_t R = 16;
+    uint64_t row_chunk_counter = 0;
+    pl.pairs = 0;
+    for (int la = 1; la <= HMK_MAX_LEN; la++) {          // rows = seq1 (lines)
+        const uint32_t rb = bq[la], re = bq[la + 1];
+        if (rb == re) continue;
+        for (int lb = 1; lb <= HMK_MAX_LEN; lb++) {      // columns = seq2
+            const uint32_t cb = br[lb], ce = br[lb + 1];
+            if (cb == ce) continue;
+            TileClass tc{};
+            tc.la = (uint8_t)la;
+            tc.lb = (uint8_t)lb;
+            const uint32_t cls = (uint32_t)classes.size();
+            classes.push_back(tc);
+            for (uint32_t r0 = rb; r0 < re; r0 += R) {
+                if ((row_chunk_counter++ % n_parts) != part) continue;
+                pl.pairs += emit_tiles(tiles, cls, r0, std::min(R, re - r0), cb, ce, cols, false, self && la == lb ? 2u : 0u);
+            }
+        }
+    }
+    pl.n_tiles = (uint32_t)tiles.size();
+    pl.part = part; pl.n_parts = n_parts;
+    return upload_plan(ctx, pl, perm, 32, 0, 1, classes, tiles);
 }
 
 int build_plan_local(hmk_ctx *ctx, uint32_t part, uint32_t n_parts) {
@@ -490,68 +711,43 @@ int build_plan_local(hmk_ctx *ctx, uint32_t part, uint32_t n_parts) {
     const uint32_t n = ctx->n;
     if (n == 0) return fail(ctx, HMK_ERR_NO_SEQUENCES, "no sequences set (hmk_set_sequences)");
     if (n_parts == 0 || part >= n_parts) return fail(ctx, HMK_ERR_BAD_ARG, "part must be < n_parts");
-    uint32_t bucket[HMK_MAX_LEN + 2] = {0};
-    for (uint32_t k = 0; k < n; k++) bucket[ctx->len[k] + 1]++;
-    for (int l = 0; l <= HMK_MAX_LEN; l++) bucket[l + 1] += bucket[l];
-    std::vector<uint32_t> perm(n);
-    {
-        uint32_t fill[HMK_MAX_LEN + 2];
-        std::memcpy(fill, bucket, sizeof(fill));
-        for (uint32_t k = 0; k < n; k++) perm[fill[ctx->len[k]]++] = k;
-    }
-    std::vector<TileClass> classes;
-    std::vector<Tile> tiles;
-    const uint32_t R = 16, COLS = 16384;
-    uint64_t row_chunk_counter = 0;
-    pl.pairs = 0;
-    for (int la = 1; la <= HMK_MAX_LEN; la++) {          // rows = seq1 (lines)
-        const uint32_t rb = bucket[la], re = bucket[la + 1];
-        if (rb == re) continue;
-        for (int lb = 1; lb <= HMK_MAX_LEN; lb++) {      // columns = seq2
-            const uint32_t cb = bucket[lb], ce = bucket[lb + 1];
-            if (cb == ce) continue;
-            TileClass tc{};
-            tc.la = (uint8_t)la;
-            tc.lb = (uint8_t)lb;
-            const uint32_t cls = (uint32_t)classes.size();
-            classes.push_back(tc);
-            for (uint32_t r0 = rb; r0 < re; r0 += R) {
-                if ((row_chunk_counter++ % n_parts) != part) continue;
-                const uint32_t nr = std::min(R, re - r0);
-                for (uint32_t c0 = cb; c0 < ce; c0 += COLS) {
-                    Tile t{};
-                    t.row0 = r0; t.nrows = nr; t.col0 = c0; t.ncols = std::min(COLS, ce - c0); t.cls = cls;
-                    const bool overlap = la == lb && c0 < r0 + nr && c0 + t.ncols > r0;
-                    t.diag = overlap ? 2u : 0u;
-                    uint64_t pairs = (uint64_t)nr * t.ncols;
-                    if (overlap)
-                        for (uint32_t r = r0; r < r0 + nr; r++)
-                            if (r >= c0 && r < c0 + t.ncols) pairs--;
-                    if (pairs == 0) continue;
-                    pl.pairs += pairs;
-                    tiles.push_back(t);
-                }
-            }
-        }
-    }
-    pl.n_tiles = (uint32_t)tiles.size();
-    std::vector<uint8_t> res_sorted((size_t)n * 32, 0);
-    for (uint32_t s = 0; s < n; s++) std::memcpy(&res_sorted[(size_t)s * 32], &ctx->res[ctx->off[perm[s]]], ctx->len[perm[s]]);
-    HIPCHK(ctx, hipMalloc((void **)&pl.d_res_sorted, res_sorted.size()));
-    HIPCHK(ctx, hipMemcpy(pl.d_res_sorted, res_sorted.data(), res_sorted.size(), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMalloc((void **)&pl.d_perm, (size_t)n * 4));
-    HIPCHK(ctx, hipMemcpy(pl.d_perm, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    pl.perm_identity = true;
-    for (uint32_t q = 0; q < n && pl.perm_identity; q++) pl.perm_identity = perm[q] == q;
-    HIPCHK(ctx, hipMalloc((void **)&pl.d_classes, std::max<size_t>(1, classes.size()) * sizeof(TileClass)));
-    if (!classes.empty())
-        HIPCHK(ctx, hipMemcpy(pl.d_classes, classes.data(), classes.size() * sizeof(TileClass), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMalloc((void **)&pl.d_tiles, std::max<size_t>(1, tiles.size()) * sizeof(Tile)));
-    if (!tiles.empty())
-        HIPCHK(ctx, hipMemcpy(pl.d_tiles, tiles.data(), tiles.size() * sizeof(Tile), hipMemcpyHostToDevice));
-    pl.part = part; pl.n_parts = n_parts;
+    Buckets bucket, none;
+    std::vector<uint32_t> perm;
+    sort_by_length(ctx, 0, n, 0, 0, bucket, none, perm);
+    const int st = finish_plan_local(ctx, pl, bucket, bucket, perm, 16384, part, n_parts, true);
+    if (st) return st;
     pl.valid = true;
     return HMK_OK;
+}
+
+// The rectangle of a LocalAlignmentScorer search: rows = queries (seq1, lines), columns = references (seq2), one class per
+// (query length, reference length); the tiles' edges come out m = row = query (row_is_m, k_local.hip).
+int build_plan_local_search(hmk_ctx *ctx, PlanLocal &pl, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1) {
+    if (pl.valid && pl.q0 == q0 && pl.q1 == q1 && pl.r0 == r0 && pl.r1 == r1) return HMK_OK;
+    free_plan_local(pl);
+    Buckets bq, br;
+    std::vector<uint32_t> perm;
+    sort_by_length(ctx, q0, q1, r0, r1, bq, br, perm);
+    uint64_t row_chunks = 0;
+    for (int l = 1; l <= HMK_MAX_LEN; l++) row_chunks += (bq[l + 1] - bq[l] + 15) / 16;
+    // column runs of up to 16,384 (build_plan_local), shorter while the rectangle would not fill the GPU once (few queries)
+    uint32_t cols = 16384;
+    while (cols > 1024 && row_chunks * (((uint64_t)(r1 - r0) + cols - 1) / cols) < 4 * 1792) cols /= 2;
+    const int st = finish_plan_local(ctx, pl, bq, br, perm, cols, 0, 1, false);
+    if (st) return st;
+    pl.q0 = q0; pl.q1 = q1; pl.r0 = r0; pl.r1 = r1;
+    pl.valid = true;
+    return HMK_OK;
+}
+
+// what a shifted pass over the ranges [q0, q1) and [r0, r1) checks on its parameters: the all-vs-all pass's checks (build_plan),
+// the shift against the two ranges' shortest sequence, as hmk_score_block_shifted does
+int check_shifted(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1) {
+    if (X < 0) return fail(ctx, HMK_ERR_BAD_ARG, "max_shift must be >= 0");
+    int mn = 255;
+    for (uint32_t k = q0; k < q1; k++) mn = std::min<int>(mn, ctx->len[k]);
+    for (uint32_t k = r0; k < r1; k++) mn = std::min<int>(mn, ctx->len[k]);
+    return check_shift_threshold_scores(ctx, X, p, thr, mn);
 }
 
 } }  // namespace hmk::impl

@@ -1,4 +1,4 @@
-"""The rectangle and triangle plans (build_plan_rect, hmk_search.cpp: build_plan_search / build_plan_triangle, and build_plan_local_search)
+"""The rectangle and triangle plans (build_plan_rect, hmk_plan.cpp: build_plan_search / build_plan_triangle, and build_plan_local_search)
 tested as hard as the all-vs-all planner is in test_gpu_parity.py.  Everything is integer and bit-exact: every comparison is
 np.array_equal on sorted packed edges or on (index, score) tables against oracle.c_oracle.
 
