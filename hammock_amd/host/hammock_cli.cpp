@@ -6,9 +6,8 @@
 //
 // Extra flags that the reference does not have: --device <k> (HIP ordinal, default 0) and --devices a,b,.. (several
 // GPUs of the node behind one context, the first is the root: hmk_create_multi).
-// Extra mode that the reference does not have: `hammock-hip search` (runSearch), queries against a reference set.
-// Extra mode that the reference does not have: `hammock-hip assign` (runAssign), new sequences into the clusters of a cluster file.
-// Extra mode that the reference does not have: `hammock-hip match` (runMatch), the clusters of one cluster file against another's.
+// Extra modes that the reference does not have: search, assign, match, continue and merge (runSearch, runAssign, ...), each described
+// above its run function.  Every run function is a list of the shared steps below (parseModeArgs ... writeRankedTable) and what is its own.
 #include <future>
 #include <unordered_set>
 #include <sys/stat.h>
@@ -53,10 +52,16 @@ struct Options {
     int cacheSizeLimit = 1;   // clinkage: -L is parsed and logged, never used (Hammock.java:89,1004-1008,459)
     int device = 0;
     std::vector<int> devices;   // --devices 0,1,..: pair space sharded over several GPUs
-    int javaHashSet = 8;        // --java_hashset 8|7|6 (clinkage): whose java.util.HashSet iteration order is emulated
+    int javaHashSet = 8;        // --java_hashset 8|7|6 (clinkage, merge): whose java.util.HashSet iteration order is emulated
+    // the newer modes' own (parseModeArgs)
+    std::string clustersFile, database, parentDir;
+    bool haveClusters = false, haveDatabase = false, havePenalty = false, skipSingletons = false;
+    int best = 0;
 };
 
 void parseCommonArgs(const std::vector<std::string> &args, Options &o) {  // Hammock.java:824-908
+    o.parentDir = parentDir();
+    o.matrixFile = o.parentDir + "/matrices/blosum62.txt";  // Hammock.java:45
     for (size_t i = 1; i < args.size(); i++) {
         const std::string &a = args[i];
         const bool more = args.size() > i + 1;
@@ -166,57 +171,224 @@ std::string labelsToString(bool have, const std::vector<std::string> &labels) { 
 // Hammock.java:1421-1427 (the list's shortest length comes from the one summary pass; the mean length, :1554-1563, too)
 int checkMaxShift(const SequenceListSummary &summary, int maxShift) { return std::min(maxShift, summary.minLength - 1); }
 
+// ---- the steps the modes' run functions are made of --------------------------------------------------------------------
+using ContextFuture = std::shared_future<std::shared_ptr<NativeContext>>;
+
+long long millisSince(std::chrono::steady_clock::time_point time0) {
+    return std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - time0).count();
+}
+
+// The newer modes' arguments: greedy's (-f -g -x -R -S -p) and their own.  Each parser walks all of args on its own, as the
+// reference's do; only --clusters, --database and --best take their value here.  bestDefault < 0: the mode has no --best.
+void parseModeArgs(const std::vector<std::string> &args, Options &o, int bestDefault) {
+    parseGreedyArgs(args, o);
+    o.best = std::max(bestDefault, 0);
+    for (size_t i = 1; i < args.size(); i++) {
+        const bool more = args.size() > i + 1;
+        if (args[i] == "--clusters" && more) { o.clustersFile = args[++i]; o.haveClusters = true; }
+        else if (args[i] == "--database" && more) { o.database = args[++i]; o.haveDatabase = true; }
+        else if (args[i] == "--best" && more && bestDefault >= 0) {
+            o.best = javaIntegerDecode(args[++i]);
+            if (o.best < 1 || o.best > 32) throw CLIException("Error. --best may be 1 to 32.");
+        } else if (args[i] == "--skip_singletons") o.skipSingletons = true;
+        else if ((args[i] == "-p" || args[i] == "--gap_penalty") && more) o.havePenalty = true;
+    }
+}
+
+void requireInput(const Options &o) {  // checkCommonArgs, Hammock.java:1207-1211
+    if (!o.haveInput) throw CLIException("Error. Parameter input file (-i or --input) missing with no default.");
+}
+void requireClusters(const Options &o) {
+    if (!o.haveClusters) throw CLIException("Error. Parameter cluster file (--clusters) missing with no default.");
+}
+void requireOneDevice(const Options &o, const std::string &mode, const std::string &aRun) {
+    if (!o.devices.empty())
+        throw CLIException("Error. --devices is not available in mode " + mode + " (" + aRun + " runs on one device, --device).");
+}
+void requireFastaOrTab(const Options &o, const std::string &mode) {
+    if (!(o.inputType == "fasta" || o.inputType == "tab"))
+        throw CLIException("Error. Parameter -f value may be either \"fasta\" or \"tab\" in mode " + mode + ".");
+}
+
+// checkCommonArgs, Hammock.java:1212-1232: -d must not exist; without it, dist/Hammock_result_<i> beside the binary
+void makeOutputDirectory(Options &o, const std::string &parentDir) {
+    if (o.haveDir) {
+        if (exists(o.workingDirectory)) throw CLIException("Error. Output directory exists. Exiting to prevent data loss.");
+        mkdir(o.workingDirectory.c_str(), 0777);
+        return;
+    }
+    std::string name;
+    mkdir((parentDir + "/dist").c_str(), 0777);
+    for (int i = 1; i < 9999; i++) {
+        name = parentDir + "/dist/Hammock_result_" + std::to_string(i);
+        if (!exists(name)) { mkdir(name.c_str(), 0777); break; }
+    }
+    o.workingDirectory = name;
+    std::cerr << "Creating default output directory: " << name << std::endl;
+}
+
+// The banner, the matrix (Hammock.java:1264) and the GPU context: HIP start-up, queues and code objects take 70-150 ms, so the
+// context is created on another thread while the caller reads and summarises its input.  clustering (greedy, clinkage): over
+// --devices when given, with --java_hashset applied; the other modes run on --device alone.
+ContextFuture beginRun(const Options &o, const Logger &logger, bool clustering) {
+    logger.logAndStderr(std::string("\nHammock version ") + VERSION +
+                        " Run with --help for a brief description of command line parameters.\n");
+    const std::vector<std::vector<int>> scoringMatrix = FileIOManager::loadScoringMatrix(o.matrixFile);
+    const std::vector<int> devices = clustering ? o.devices : std::vector<int>();
+    const int javaHashSet = clustering ? o.javaHashSet : 8;
+    return std::async(std::launch::async, [scoringMatrix, devices, device = o.device, javaHashSet]() {
+        std::shared_ptr<NativeContext> c = devices.empty() ? std::make_shared<NativeContext>(scoringMatrix, device)
+                                                           : std::make_shared<NativeContext>(scoringMatrix, devices);
+        if (javaHashSet != 8 && hmk_set_java_hashset(c->get(), javaHashSet) != HMK_OK) throw HammockException("hmk_set_java_hashset failed");
+        return c;
+    });
+}
+
+void logRunStart(const Logger &logger, const std::string &mode, const std::vector<std::string> &args) {  // Hammock.java:225-229, :244-248
+    logger.logWithTime("Program started in mode \"" + mode + "\".");
+    std::string argsString;
+    for (auto &a : args) argsString += " " + a;
+    logger.logWithoutTime("Command-line arguments: \n" + argsString + "\n");
+}
+
+// The catch ladder of a run (Hammock.java:146-167), called from `catch (...)`: logs the exception in flight and returns the exit
+// code; a CLIException goes on to main.  Only greedy and clinkage give a NullPointerException the reference's exit code 4 (:153-157).
+// Of the other modes' calls hmk_clinkage_merge can return HMK_ERR_REFERENCE_WOULD_CRASH (the chain returns to a cluster on its
+// stack); hmk_greedy_continue cannot.  Merge reports it as any other error, 6.
+int reportRunError(const Logger &logger, bool clustering) {
+    auto other = [&](const std::exception &e) {  // :163-167
+        logger.logAndStderr("Error. Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(e.what());
+        return 6;
+    };
+    try {
+        throw;
+    } catch (const CLIException &) {
+        throw;
+    } catch (const FileFormatException &e) {  // :148-152
+        logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
+        return 3;
+    } catch (const NullPointerException &e) {  // :153-157
+        if (!clustering) return other(e);
+        logger.logAndStderr("Error. Maybe wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(std::string("java.lang.NullPointerException: ") + e.what());
+        return 4;
+    } catch (const DataException &e) {  // :158-162
+        logger.logAndStderr("Error. Maybe wrong input file format or wrong set of labels? Run with --help for a brief description of command line parameters. Trace: \n");
+        logger.logAndStderr(std::string("cz.krejciadam.hammock.DataException: ") + e.what());
+        return 5;
+    } catch (const std::exception &e) {
+        return other(e);
+    }
+}
+
+// Hammock.java:803-811 after a limit the reference does not have.  clamp: the list whose longest sequence must fit the kernels and
+// whose shortest one bounds the shift; mean: the list whose mean length sets the default.
+void settleMaxShift(Options &o, const Logger &logger, const SequenceListSummary &clamp, const SequenceListSummary &mean, const std::string &note) {
+    if (clamp.maxLength > HMK_MAX_LEN)   // say so here instead of failing inside the clusterer
+        throw HammockException("Error. The longest sequence has " + std::to_string(clamp.maxLength) + " amino acids; the GPU kernels of hammock-hip "
+                               "take sequences of up to " + std::to_string(HMK_MAX_LEN) + " (Hammock's domain is 7-20).");
+    if (!o.haveMaxShift) {
+        o.maxShift = checkMaxShift(clamp, (int)javaRound(mean.meanLength() / 4));
+        logger.logAndStderr("Max shift not set. Setting automatically to: " + std::to_string(o.maxShift) + note);
+        return;
+    }
+    const int correct = checkMaxShift(clamp, o.maxShift);
+    if (o.maxShift != correct) {
+        o.maxShift = correct;
+        logger.logAndStderr("Setting max shift to " + std::to_string(correct) +
+                            " as the length of the shortest sequence is only " + std::to_string(correct + 1));
+    }
+}
+
+void settleThreshold(Options &o, const Logger &logger, const SequenceListSummary &mean, const std::string &word, const std::string &note) {  // :394-397 / :452-455
+    if (o.haveThreshold) return;
+    o.sequenceClusteringThreshold = (int)javaRound(mean.meanLength() * 1.7);
+    logger.logAndStderr(word + " threshold not set. Setting automatically to: " + std::to_string(o.sequenceClusteringThreshold) + note);
+}
+
+// the newer modes settle all three at once (greedy and clinkage write their statistics file between the first two and have the
+// reference's silent -p 0); only search takes its two means from different lists
+void settleShiftAndThreshold(Options &o, const Logger &logger, const SequenceListSummary &clamp, const SequenceListSummary &shiftMean,
+                             const SequenceListSummary &thresholdMean, const std::string &thresholdWord, const std::string &note = "") {
+    settleMaxShift(o, logger, clamp, shiftMean, note);
+    settleThreshold(o, logger, thresholdMean, thresholdWord, note);
+    if (!o.havePenalty) logger.logAndStderr("Gap penalty not set. Setting automatically to: " + std::to_string(o.shiftPenalty));
+}
+
+std::vector<UniqueSequencePtr> loadSequences(const Options &o, const std::string &file) {  // loadInputSequences, :749-762 ("seq" is checked before)
+    return o.inputType == "fasta" ? FileIOManager::loadUniqueSequencesFromFasta(file) : FileIOManager::loadUniqueSequencesFromTable(file);
+}
+
+std::vector<UniqueSequencePtr> sequencesOf(const std::vector<ClusterPtr> &clusters) {
+    std::vector<UniqueSequencePtr> sequences;
+    for (auto &cl : clusters) for (auto &s : cl->getSequences()) sequences.push_back(s);
+    return sequences;
+}
+
+void requireOccurrences(const std::vector<UniqueSequencePtr> &sequences, const std::string &where) {
+    for (auto &s : sequences)
+        if (s->size() < 1) throw FileFormatException(where + " - the sequence " + s->getSequenceString() + " has no occurrences (Cluster.size() counts them).");
+}
+
+// The candidate clusters of a list (--skip_singletons: those of more than one unique sequence, LimitedGreedySequenceClusterer.java:41-48)
+// as the library takes them: their members appended to `upload`, each member's candidate number, each candidate's id.
+struct Candidates {
+    std::vector<uint32_t> slots;           // indices into the cluster list
+    std::vector<uint32_t> memberCluster;   // per appended member: its candidate
+    std::vector<int32_t> clusterId;        // per candidate: getId() + idShift
+};
+Candidates appendCandidates(const std::vector<ClusterPtr> &clusters, bool skipSingletons, int idShift, std::vector<UniqueSequencePtr> &upload) {
+    Candidates cand;
+    for (uint32_t c = 0; c < (uint32_t)clusters.size(); c++) {
+        if (skipSingletons && clusters[c]->getUniqueSize() <= 1) continue;
+        cand.clusterId.push_back(clusters[c]->getId() + idShift);
+        for (auto &s : clusters[c]->getSequences()) { upload.push_back(s); cand.memberCluster.push_back((uint32_t)cand.slots.size()); }
+        cand.slots.push_back(c);
+    }
+    return cand;
+}
+
+// assignments.tsv and cluster_matches.tsv: per row its best feasible candidates by rank, or one NA line
+void writeRankedTable(const std::string &file, const std::string &header, const std::vector<std::string> &rows, const std::vector<ClusterPtr> &clusters,
+                      const Candidates &cand, uint32_t best, const std::vector<uint32_t> &bestCluster, const std::vector<int32_t> &bestScore,
+                      const std::vector<uint32_t> &nFeasible) {
+    std::ofstream out(file);
+    if (!out) throw HammockException("cannot write " + file);
+    out << header << '\n';
+    for (size_t q = 0; q < rows.size(); q++) {
+        if (nFeasible[q] == 0) { out << rows[q] << "\tNA\tNA\tNA\tNA\t0\n"; continue; }
+        for (uint32_t t = 0; t < std::min(nFeasible[q], best); t++) {
+            const ClusterPtr &cl = clusters[cand.slots[bestCluster[q * best + t]]];
+            out << rows[q] << '\t' << t + 1 << '\t' << cl->getId() << '\t' << bestScore[q * best + t] << '\t' << cl->size() << '\t' << nFeasible[q] << '\n';
+        }
+    }
+}
+
 // greedy mode (Hammock.java:217-234, runGreedyClustering :392-437) and clinkage mode (:236-253, runClinkageClustering
 // :449-489): the two share everything but the clusterer, the ordering step and a few log lines
 int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
     Options o;
-    const std::string PARENT_DIR = parentDir();
-    o.matrixFile = PARENT_DIR + "/matrices/blosum62.txt";  // Hammock.java:45
     parseCommonArgs(args, o);
     if (clinkage) parseClinkageArgs(args, o);
     else parseGreedyArgs(args, o);
-
-    // ---- checkCommonArgs, Hammock.java:1207-1266 ------------------------------------------------
-    if (!o.haveInput) throw CLIException("Error. Parameter input file (-i or --input) missing with no default.");
-    if (o.haveDir) {
-        if (exists(o.workingDirectory)) throw CLIException("Error. Output directory exists. Exiting to prevent data loss.");
-        mkdir(o.workingDirectory.c_str(), 0777);
-    } else {
-        std::string name;
-        mkdir((PARENT_DIR + "/dist").c_str(), 0777);
-        for (int i = 1; i < 9999; i++) {
-            name = PARENT_DIR + "/dist/Hammock_result_" + std::to_string(i);
-            if (!exists(name)) { mkdir(name.c_str(), 0777); break; }
-        }
-        o.workingDirectory = name;
-        std::cerr << "Creating default output directory: " << name << std::endl;
-    }
+    requireInput(o);
+    makeOutputDirectory(o, o.parentDir);
     Logger logger(o.workingDirectory + "/run.log", false);
     try {
-        logger.logAndStderr(std::string("\nHammock version ") + VERSION +
-                            " Run with --help for a brief description of command line parameters.\n");
+        ContextFuture contextReady = beginRun(o, logger, true);
         std::vector<std::string> labels;
         if (o.haveLabels) labels = FileIOManager::splitChar(o.labelString, ',', true);
         const std::string initialClustersSequencesCsv = o.workingDirectory + "/initial_clusters_sequences.tsv";
         const std::string initialClustersSequencesOrderedCsv = o.workingDirectory + "/initial_clusters_sequences_original_order.tsv";
         const std::string initialClusters = o.workingDirectory + "/initial_clusters.tsv";
         const std::string inputStatistics = o.workingDirectory + "/input_statistics.tsv";
-        const std::vector<std::vector<int>> scoringMatrix = FileIOManager::loadScoringMatrix(o.matrixFile);  // :1264
-        // the GPU context (HIP start-up, queues, code objects: 70-150 ms) is created while the input is read and summarised
-        std::shared_future<std::shared_ptr<NativeContext>> contextReady = std::async(std::launch::async, [&scoringMatrix, &o]() {
-            std::shared_ptr<NativeContext> c = o.devices.empty() ? std::make_shared<NativeContext>(scoringMatrix, o.device)
-                                                                 : std::make_shared<NativeContext>(scoringMatrix, o.devices);
-            if (o.javaHashSet != 8 && hmk_set_java_hashset(c->get(), o.javaHashSet) != HMK_OK) throw HammockException("hmk_set_java_hashset failed");
-            return c;
-        });
         // ---- checkGreedyOrClinkageArgs, :1272-1277 ------------------------------------------------
         if (!(o.inputType == "fasta" || o.inputType == "seq" || o.inputType == "tab"))
             throw CLIException("Error. Parameter -f value may be either \"fasta\", \"seq\" or \"tab\". No other values are allowed");
 
-        logger.logWithTime(clinkage ? "Program started in mode \"clinkage\"." : "Program started in mode \"greedy\".");  // :225-229, :244-248
-        std::string argsString;
-        for (auto &a : args) argsString += " " + a;
-        logger.logWithoutTime("Command-line arguments: \n" + argsString + "\n");
+        logRunStart(logger, clinkage ? "clinkage" : "greedy", args);
         logger.logWithoutTime("\nComplete list of input/output parameters: \n-i, --input " + o.inputFileName +
                               "\n-d, --output_directory " + o.workingDirectory + "\n-t, --thread " + std::to_string(o.nThreads) +
                               "\n-l, --labels " + labelsToString(o.haveLabels, labels) + "\n\n");
@@ -237,15 +409,13 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
 
         // ---- loadInputSequences, :749-787 -----------------------------------------------------------
         const auto timeStart = std::chrono::steady_clock::now();
-        auto cliLap = [&](const char *what) {   // HMK_CLI_TIMING=1: where a hammock-hip process spends its time
+        auto cliLap = [timeStart](const char *what) {   // HMK_CLI_TIMING=1: where a hammock-hip process spends its time
             if (std::getenv("HMK_CLI_TIMING"))
                 std::fprintf(stderr, "[hammock-hip] %s at %.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - timeStart).count());
         };
         logger.logAndStderr("Loading input sequences...");
-        std::vector<UniqueSequencePtr> sequences;
-        if (o.inputType == "fasta") sequences = FileIOManager::loadUniqueSequencesFromFasta(o.inputFileName);
-        else if (o.inputType == "tab") sequences = FileIOManager::loadUniqueSequencesFromTable(o.inputFileName);
-        else throw HammockException("Error, this should have been checked.");  // "seq", :759-761
+        if (o.inputType == "seq") throw HammockException("Error, this should have been checked.");  // :759-761
+        std::vector<UniqueSequencePtr> sequences = loadSequences(o, o.inputFileName);
         cliLap("input loaded");
         logger.logAndStderr(std::to_string(sequences.size()) + " unique sequences loaded.");
         SequenceListSummary summary = summariseSequences(sequences);
@@ -266,46 +436,28 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
         }
         logger.logAndStderr(std::to_string(sequences.size()) + " unique sequences after non-specified labels filtered out");
         logger.logAndStderr(std::to_string(summary.total) + " total sequences after non-specified labels fileterd out");
-        const int minLength = summary.minLength, maxLength = summary.maxLength;
-        logger.logAndStderr("Shortest sequence: " + std::to_string(minLength) + " AA. Longest sequence: " + std::to_string(maxLength) + " AA.");
+        logger.logAndStderr("Shortest sequence: " + std::to_string(summary.minLength) + " AA. Longest sequence: " + std::to_string(summary.maxLength) + " AA.");
         if (sequences.empty()) throw FileFormatException("Error. No sequences (with specified labels) to cluster.");
         // the sequence count is known: the context's buffers (24 GB at 10^6) are sized on another thread while this one goes on
         // to the labels, the statistics, the sort and the upload
-        std::future<void> reserved = std::async(std::launch::async, [contextReady, timeStart, count = (uint32_t)sequences.size()]() {
+        std::future<void> reserved = std::async(std::launch::async, [contextReady, cliLap, count = (uint32_t)sequences.size()]() {
             try {   // (a device error is reported by the clustering call)
                 hmk_ctx *c = contextReady.get()->get();
-                if (std::getenv("HMK_CLI_TIMING")) std::fprintf(stderr, "[hammock-hip] hmk_reserve begins at %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - timeStart).count());
+                cliLap("hmk_reserve begins");
                 (void)hmk_reserve(c, count);
-                if (std::getenv("HMK_CLI_TIMING")) std::fprintf(stderr, "[hammock-hip] hmk_reserve done at %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - timeStart).count());
+                cliLap("hmk_reserve done");
             } catch (...) { }
         });
-        if (maxLength > HMK_MAX_LEN)   // the reference has no such limit; say so here instead of failing inside the clusterer
-            throw HammockException("Error. The longest sequence has " + std::to_string(maxLength) + " amino acids; the GPU kernels of hammock-hip "
-                                   "take sequences of up to " + std::to_string(HMK_MAX_LEN) + " (Hammock's domain is 7-20).");
 
         // ---- runGreedyClustering, :392-437 ------------------------------------------------------------
         if (!o.haveLabels) labels = FileIOManager::getSortedLabels(sequences);                 // :796-798
         const std::vector<UniqueSequencePtr> initialSequences(sequences);                       // :800-801
-        if (!o.haveMaxShift) {                                                                  // :803-811
-            o.maxShift = checkMaxShift(summary, (int)javaRound(summary.meanLength() / 4));
-            logger.logAndStderr("Max shift not set. Setting automatically to: " + std::to_string(o.maxShift));
-        } else {
-            const int correct = checkMaxShift(summary, o.maxShift);
-            if (o.maxShift != correct) {
-                o.maxShift = correct;
-                logger.logAndStderr("Setting max shift to " + std::to_string(correct) +
-                                    " as the length of the shortest sequence is only " + std::to_string(correct + 1));
-            }
-        }
+        settleMaxShift(o, logger, summary, summary, "");                                        // :803-811
         cliLap("labels, lengths, max shift");
         logger.logAndStderr("Generating input statistics...");
         FileIOManager::saveInputStatistics(sequences, labels, inputStatistics);                 // :814-816
         cliLap("input statistics written");
-        if (!o.haveThreshold) {                                                                 // :394-397 / :452-455
-            o.sequenceClusteringThreshold = (int)javaRound(summary.meanLength() * 1.7);
-            logger.logAndStderr(std::string(clinkage ? "Clinkage" : "Greedy") + " clustering threshold not set. Setting automatically to: " +
-                                std::to_string(o.sequenceClusteringThreshold));
-        }
+        settleThreshold(o, logger, summary, clinkage ? "Clinkage clustering" : "Greedy clustering", "");
         if (!clinkage && !o.haveLimit) {                                                                     // :398-401
             o.initialClustersLimit = (int)javaRound((double)sequences.size() * 0.025);
             logger.logAndStderr("Initial greedy clusters limit not set. Setting automatically to: " +
@@ -323,11 +475,8 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
             std::fprintf(stderr, "[hammock-hip] sort: %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - time0).count());
         std::vector<ClusterPtr> clusters = clinkage ? clinkageClusterer.cluster(sequences)      // :462
                                                     : clusterer.cluster(sequences);             // :409
-        auto ms = [&]() {
-            return std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - time0).count();
-        };
         cliLap("clustered");
-        logger.logAndStderr("Ready. Clustering time: " + std::to_string(ms()));                // :411 / :463
+        logger.logAndStderr("Ready. Clustering time: " + std::to_string(millisSince(time0)));  // :411 / :463
         logger.logAndStderr("Resulting clusers: " + std::to_string(clusters.size()));          // :412 / :464
         if (clinkage)
             logger.logAndStderr("GPU scoring: " + std::to_string(clinkageClusterer.stats.neighbors_ms) + " ms, host nearest-neighbour chain: " +
@@ -339,7 +488,7 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
                             std::to_string(clusterer.stats.n_edges));
         logger.logAndStderr("Building MSAs... (skipped: Clustal Omega is outside the scope of hammock-hip; the alignment "
                             "column of multi-member clusters is NA)");
-        logger.logAndStderr("Ready. Total time: " + std::to_string(ms()));                     // :427
+        logger.logAndStderr("Ready. Total time: " + std::to_string(millisSince(time0)));       // :427
         logger.logAndStderr("Saving results to output files...");
         // the reference's three calls in a row (:429, :431, :432), written side by side
         FileIOManager::saveInitialClusters(clusters, initialClustersSequencesCsv, initialClustersSequencesOrderedCsv, initialClusters,
@@ -360,24 +509,8 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
         std::fflush(nullptr);
         std::_Exit(0);
         return 0;
-    } catch (const CLIException &) {
-        throw;
-    } catch (const FileFormatException &e) {  // Hammock.java:148-152
-        logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
-        return 3;
-    } catch (const NullPointerException &e) {  // :153-157
-        logger.logAndStderr("Error. Maybe wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(std::string("java.lang.NullPointerException: ") + e.what());
-        return 4;
-    } catch (const DataException &e) {  // :158-162
-        logger.logAndStderr("Error. Maybe wrong input file format or wrong set of labels? Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(std::string("cz.krejciadam.hammock.DataException: ") + e.what());
-        return 5;
-    } catch (const std::exception &e) {  // :163-167
-        logger.logAndStderr("Error. Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(e.what());
-        return 6;
+    } catch (...) {
+        return reportRunError(logger, true);
     }
 }
 
@@ -389,88 +522,33 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
 // query length) (:394-397), -p 0.  --best K: only the best K hits of each query (hmk_search_best_shifted).
 int runSearch(const std::vector<std::string> &args) {
     Options o;
-    const std::string PARENT_DIR = parentDir();
-    o.matrixFile = PARENT_DIR + "/matrices/blosum62.txt";  // Hammock.java:45
     parseCommonArgs(args, o);
-    parseGreedyArgs(args, o);
-    std::string database;
-    bool haveDatabase = false, havePenalty = false;
-    int best = 0;
-    for (size_t i = 1; i < args.size(); i++) {
-        const bool more = args.size() > i + 1;
-        if (args[i] == "--database" && more) { database = args[++i]; haveDatabase = true; }
-        else if (args[i] == "--best" && more) {
-            best = javaIntegerDecode(args[++i]);
-            if (best < 1 || best > 32) throw CLIException("Error. --best may be 1 to 32.");
-        } else if ((args[i] == "-p" || args[i] == "--gap_penalty") && more) havePenalty = true;
-    }
-    if (!o.devices.empty()) throw CLIException("Error. --devices is not available in mode search (a search runs on one device, --device).");
-    if (!o.haveInput) throw CLIException("Error. Parameter input file (-i or --input) missing with no default.");
-    if (!haveDatabase) throw CLIException("Error. Parameter reference file (--database) missing with no default.");
-    if (!(o.inputType == "fasta" || o.inputType == "tab"))
-        throw CLIException("Error. Parameter -f value may be either \"fasta\" or \"tab\" in mode search.");
-    if (o.haveDir) {
-        if (exists(o.workingDirectory)) throw CLIException("Error. Output directory exists. Exiting to prevent data loss.");
-        mkdir(o.workingDirectory.c_str(), 0777);
-    } else {
-        std::string name;
-        mkdir((PARENT_DIR + "/dist").c_str(), 0777);
-        for (int i = 1; i < 9999; i++) {
-            name = PARENT_DIR + "/dist/Hammock_result_" + std::to_string(i);
-            if (!exists(name)) { mkdir(name.c_str(), 0777); break; }
-        }
-        o.workingDirectory = name;
-        std::cerr << "Creating default output directory: " << name << std::endl;
-    }
+    parseModeArgs(args, o, 0);
+    requireOneDevice(o, "search", "a search");
+    requireInput(o);
+    if (!o.haveDatabase) throw CLIException("Error. Parameter reference file (--database) missing with no default.");
+    requireFastaOrTab(o, "search");
+    makeOutputDirectory(o, o.parentDir);
     Logger logger(o.workingDirectory + "/run.log", false);
     try {
-        logger.logAndStderr(std::string("\nHammock version ") + VERSION +
-                            " Run with --help for a brief description of command line parameters.\n");
-        const std::vector<std::vector<int>> scoringMatrix = FileIOManager::loadScoringMatrix(o.matrixFile);
-        std::shared_future<std::shared_ptr<NativeContext>> contextReady = std::async(std::launch::async, [&scoringMatrix, &o]() {
-            return std::make_shared<NativeContext>(scoringMatrix, o.device);
-        });
-        logger.logWithTime("Program started in mode \"search\".");
-        std::string argsString;
-        for (auto &a : args) argsString += " " + a;
-        logger.logWithoutTime("Command-line arguments: \n" + argsString + "\n");
-        auto load = [&](const std::string &file) {
-            return o.inputType == "fasta" ? FileIOManager::loadUniqueSequencesFromFasta(file) : FileIOManager::loadUniqueSequencesFromTable(file);
-        };
+        ContextFuture contextReady = beginRun(o, logger, false);
+        logRunStart(logger, "search", args);
         logger.logAndStderr("Loading query sequences...");
-        const std::vector<UniqueSequencePtr> queries = load(o.inputFileName);
+        const std::vector<UniqueSequencePtr> queries = loadSequences(o, o.inputFileName);
         logger.logAndStderr(std::to_string(queries.size()) + " unique query sequences loaded.");
         logger.logAndStderr("Loading reference sequences...");
-        const std::vector<UniqueSequencePtr> references = load(database);
+        const std::vector<UniqueSequencePtr> references = loadSequences(o, o.database);
         logger.logAndStderr(std::to_string(references.size()) + " unique reference sequences loaded.");
         if (queries.empty() || references.empty()) throw FileFormatException("Error. No sequences to search.");
         std::vector<UniqueSequencePtr> all(queries);
         all.insert(all.end(), references.begin(), references.end());
-        const SequenceListSummary summary = summariseSequences(all), querySummary = summariseSequences(queries);
-        if (summary.maxLength > HMK_MAX_LEN)
-            throw HammockException("Error. The longest sequence has " + std::to_string(summary.maxLength) + " amino acids; the GPU kernels of hammock-hip "
-                                   "take sequences of up to " + std::to_string(HMK_MAX_LEN) + " (Hammock's domain is 7-20).");
-        if (!o.haveMaxShift) {
-            o.maxShift = checkMaxShift(summary, (int)javaRound(summary.meanLength() / 4));
-            logger.logAndStderr("Max shift not set. Setting automatically to: " + std::to_string(o.maxShift));
-        } else {
-            const int correct = checkMaxShift(summary, o.maxShift);
-            if (o.maxShift != correct) {
-                o.maxShift = correct;
-                logger.logAndStderr("Setting max shift to " + std::to_string(correct) +
-                                    " as the length of the shortest sequence is only " + std::to_string(correct + 1));
-            }
-        }
-        if (!o.haveThreshold) {
-            o.sequenceClusteringThreshold = (int)javaRound(querySummary.meanLength() * 1.7);
-            logger.logAndStderr("Search threshold not set. Setting automatically to: " + std::to_string(o.sequenceClusteringThreshold));
-        }
-        if (!havePenalty) logger.logAndStderr("Gap penalty not set. Setting automatically to: " + std::to_string(o.shiftPenalty));
+        const SequenceListSummary summary = summariseSequences(all);
+        settleShiftAndThreshold(o, logger, summary, summary, summariseSequences(queries), "Search");
 
         const std::shared_ptr<NativeContext> nc = contextReady.get();
         hmk_ctx *c = nc->get();
         nc->setSequences(all, false);
-        const uint32_t nq = (uint32_t)queries.size(), n = (uint32_t)all.size();
+        const uint32_t nq = (uint32_t)queries.size(), n = (uint32_t)all.size(), best = (uint32_t)o.best;
         logger.logAndStderr("Searching...");
         const auto time0 = std::chrono::steady_clock::now();
         // hits[q] = (score, reference index in load order)
@@ -479,7 +557,7 @@ int runSearch(const std::vector<std::string> &args) {
         if (best) {
             std::vector<uint32_t> index((size_t)nq * best), count(nq);
             std::vector<int32_t> score((size_t)nq * best);
-            const int st = hmk_search_best_shifted(c, 0, nq, nq, n, o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold, (uint32_t)best,
+            const int st = hmk_search_best_shifted(c, 0, nq, nq, n, o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold, best,
                                                    index.data(), score.data(), count.data(), &stats);
             if (st) nc->raise(st, nullptr);
             for (uint32_t q = 0; q < nq; q++)
@@ -511,8 +589,7 @@ int runSearch(const std::vector<std::string> &args) {
             const int st = hmk_score_with_shift(c, pi.data(), pj.data(), pi.size(), o.maxShift, o.shiftPenalty, sc.data(), shift.data());
             if (st) nc->raise(st, nullptr);
         }
-        const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - time0).count();
-        logger.logAndStderr("Ready. Search time: " + std::to_string(ms));
+        logger.logAndStderr("Ready. Search time: " + std::to_string(millisSince(time0)));
         logger.logAndStderr("Pairs scored: " + std::to_string(stats.pairs_scored) + ", hits reported: " + std::to_string(pi.size()) +
                             ", GPU kernels: " + std::to_string(stats.kernel_ms) + " ms");
         const std::string hitsFile = o.workingDirectory + "/search_hits.tsv";
@@ -531,20 +608,8 @@ int runSearch(const std::vector<std::string> &args) {
         logger.logAndStderr("Search results in: " + hitsFile);
         logger.logWithTime("Program successfully ended.");
         return 0;
-    } catch (const CLIException &) {
-        throw;
-    } catch (const FileFormatException &e) {
-        logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
-        return 3;
-    } catch (const DataException &e) {
-        logger.logAndStderr("Error. Maybe wrong input file format or wrong set of labels? Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(std::string("cz.krejciadam.hammock.DataException: ") + e.what());
-        return 5;
-    } catch (const std::exception &e) {
-        logger.logAndStderr("Error. Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(e.what());
-        return 6;
+    } catch (...) {
+        return reportRunError(logger, false);
     }
 }
 
@@ -557,162 +622,64 @@ int runSearch(const std::vector<std::string> &args) {
 // sequence are candidates (LimitedGreedySequenceClusterer.java:41-48).
 int runAssign(const std::vector<std::string> &args) {
     Options o;
-    const std::string PARENT_DIR = parentDir();
-    o.matrixFile = PARENT_DIR + "/matrices/blosum62.txt";  // Hammock.java:45
     parseCommonArgs(args, o);
-    parseGreedyArgs(args, o);
-    std::string clustersFile;
-    bool haveClusters = false, havePenalty = false, skipSingletons = false;
-    int best = 1;
-    for (size_t i = 1; i < args.size(); i++) {
-        const bool more = args.size() > i + 1;
-        if (args[i] == "--clusters" && more) { clustersFile = args[++i]; haveClusters = true; }
-        else if (args[i] == "--best" && more) {
-            best = javaIntegerDecode(args[++i]);
-            if (best < 1 || best > 32) throw CLIException("Error. --best may be 1 to 32.");
-        } else if (args[i] == "--skip_singletons") skipSingletons = true;
-        else if ((args[i] == "-p" || args[i] == "--gap_penalty") && more) havePenalty = true;
-    }
-    if (!o.devices.empty()) throw CLIException("Error. --devices is not available in mode assign (an assignment runs on one device, --device).");
-    if (!o.haveInput) throw CLIException("Error. Parameter input file (-i or --input) missing with no default.");
-    if (!haveClusters) throw CLIException("Error. Parameter cluster file (--clusters) missing with no default.");
-    if (!(o.inputType == "fasta" || o.inputType == "tab"))
-        throw CLIException("Error. Parameter -f value may be either \"fasta\" or \"tab\" in mode assign.");
-    if (o.haveDir) {
-        if (exists(o.workingDirectory)) throw CLIException("Error. Output directory exists. Exiting to prevent data loss.");
-        mkdir(o.workingDirectory.c_str(), 0777);
-    } else {
-        std::string name;
-        mkdir((PARENT_DIR + "/dist").c_str(), 0777);
-        for (int i = 1; i < 9999; i++) {
-            name = PARENT_DIR + "/dist/Hammock_result_" + std::to_string(i);
-            if (!exists(name)) { mkdir(name.c_str(), 0777); break; }
-        }
-        o.workingDirectory = name;
-        std::cerr << "Creating default output directory: " << name << std::endl;
-    }
+    parseModeArgs(args, o, 1);
+    requireOneDevice(o, "assign", "an assignment");
+    requireInput(o);
+    requireClusters(o);
+    requireFastaOrTab(o, "assign");
+    makeOutputDirectory(o, o.parentDir);
     Logger logger(o.workingDirectory + "/run.log", false);
     try {
-        logger.logAndStderr(std::string("\nHammock version ") + VERSION +
-                            " Run with --help for a brief description of command line parameters.\n");
-        const std::vector<std::vector<int>> scoringMatrix = FileIOManager::loadScoringMatrix(o.matrixFile);
-        std::shared_future<std::shared_ptr<NativeContext>> contextReady = std::async(std::launch::async, [&scoringMatrix, &o]() {
-            return std::make_shared<NativeContext>(scoringMatrix, o.device);
-        });
-        logger.logWithTime("Program started in mode \"assign\".");
-        std::string argsString;
-        for (auto &a : args) argsString += " " + a;
-        logger.logWithoutTime("Command-line arguments: \n" + argsString + "\n");
+        ContextFuture contextReady = beginRun(o, logger, false);
+        logRunStart(logger, "assign", args);
         logger.logAndStderr("Loading clusters...");
-        const std::vector<ClusterPtr> clusters = FileIOManager::loadClustersFromCsv(clustersFile);
-        std::vector<UniqueSequencePtr> clusterSequences;
-        for (auto &cl : clusters) for (auto &s : cl->getSequences()) clusterSequences.push_back(s);
+        const std::vector<ClusterPtr> clusters = FileIOManager::loadClustersFromCsv(o.clustersFile);
+        const std::vector<UniqueSequencePtr> clusterSequences = sequencesOf(clusters);
         logger.logAndStderr(std::to_string(clusters.size()) + " clusters of " + std::to_string(clusterSequences.size()) + " sequences loaded.");
         logger.logAndStderr("Loading new sequences...");
-        const std::vector<UniqueSequencePtr> newSequences = o.inputType == "fasta" ? FileIOManager::loadUniqueSequencesFromFasta(o.inputFileName)
-                                                                                   : FileIOManager::loadUniqueSequencesFromTable(o.inputFileName);
+        const std::vector<UniqueSequencePtr> newSequences = loadSequences(o, o.inputFileName);
         logger.logAndStderr(std::to_string(newSequences.size()) + " unique new sequences loaded.");
         if (newSequences.empty()) throw FileFormatException("Error. No sequences to assign.");
         if (clusterSequences.empty()) throw FileFormatException("Error. The cluster file holds no clusters.");
-        for (auto &s : clusterSequences)
-            if (s->size() < 1) throw FileFormatException("Error in cluster file: " + clustersFile + " - the sequence " + s->getSequenceString() +
-                                                         " has no occurrences (Cluster.size() counts them).");
+        requireOccurrences(clusterSequences, "Error in cluster file: " + o.clustersFile);
         std::vector<UniqueSequencePtr> both(newSequences);
         both.insert(both.end(), clusterSequences.begin(), clusterSequences.end());
-        const SequenceListSummary summary = summariseSequences(clusterSequences), bothSummary = summariseSequences(both);
-        if (bothSummary.maxLength > HMK_MAX_LEN)
-            throw HammockException("Error. The longest sequence has " + std::to_string(bothSummary.maxLength) + " amino acids; the GPU kernels of hammock-hip "
-                                   "take sequences of up to " + std::to_string(HMK_MAX_LEN) + " (Hammock's domain is 7-20).");
-        if (!o.haveMaxShift) {
-            o.maxShift = checkMaxShift(bothSummary, (int)javaRound(summary.meanLength() / 4));
-            logger.logAndStderr("Max shift not set. Setting automatically to: " + std::to_string(o.maxShift));
-        } else {
-            const int correct = checkMaxShift(bothSummary, o.maxShift);
-            if (o.maxShift != correct) {
-                o.maxShift = correct;
-                logger.logAndStderr("Setting max shift to " + std::to_string(correct) +
-                                    " as the length of the shortest sequence is only " + std::to_string(correct + 1));
-            }
-        }
-        if (!o.haveThreshold) {
-            o.sequenceClusteringThreshold = (int)javaRound(summary.meanLength() * 1.7);
-            logger.logAndStderr("Assignment threshold not set. Setting automatically to: " + std::to_string(o.sequenceClusteringThreshold));
-        }
-        if (!havePenalty) logger.logAndStderr("Gap penalty not set. Setting automatically to: " + std::to_string(o.shiftPenalty));
+        const SequenceListSummary summary = summariseSequences(clusterSequences);
+        settleShiftAndThreshold(o, logger, summariseSequences(both), summary, summary, "Assignment");
 
         // the candidates' members behind the new sequences: new [0, nq), members [nq, n)
-        std::vector<ClusterPtr> candidates;
-        for (auto &cl : clusters)
-            if (!skipSingletons || cl->getUniqueSize() > 1) candidates.push_back(cl);
         std::vector<UniqueSequencePtr> upload(newSequences);
-        std::vector<uint32_t> memberCluster;
-        std::vector<int32_t> clusterId;
-        for (uint32_t c = 0; c < (uint32_t)candidates.size(); c++) {
-            clusterId.push_back(candidates[c]->getId());
-            for (auto &s : candidates[c]->getSequences()) { upload.push_back(s); memberCluster.push_back(c); }
-        }
-        const uint32_t nq = (uint32_t)newSequences.size(), n = (uint32_t)upload.size();
-        size_t total = 0;
-        for (auto &s : upload) total += s->getSequence().size();
-        std::vector<uint8_t> res(total);
-        std::vector<uint32_t> off(n + 1, 0);
-        std::vector<int32_t> sizes(n);
-        for (uint32_t k = 0; k < n; k++) {
-            off[k + 1] = off[k] + (uint32_t)upload[k]->getSequence().size();
-            for (size_t r = 0; r < upload[k]->getSequence().size(); r++) res[off[k] + r] = (uint8_t)upload[k]->getSequence()[r];
-            sizes[k] = k < nq ? 1 : upload[k]->size();   // (a new sequence's size plays no part)
-        }
+        const Candidates cand = appendCandidates(clusters, o.skipSingletons, 0, upload);
+        const uint32_t nq = (uint32_t)newSequences.size(), n = (uint32_t)upload.size(), best = (uint32_t)o.best;
         const std::shared_ptr<NativeContext> nc = contextReady.get();
-        hmk_ctx *c = nc->get();
-        int st = hmk_set_sequences(c, res.data(), off.data(), sizes.data(), n);
-        if (st) nc->raise(st, nullptr);
+        nc->setSequences(upload, true, nq);   // (a new sequence's size plays no part)
         logger.logAndStderr("Assigning...");
         const auto time0 = std::chrono::steady_clock::now();
         std::vector<uint32_t> bestCluster((size_t)nq * best), nFeasible(nq);
         std::vector<int32_t> bestScore((size_t)nq * best);
         hmk_neighbor_stats stats{};
-        st = hmk_assign_shifted(c, 0, nq, nq, n, memberCluster.data(), clusterId.data(), (uint32_t)candidates.size(), o.maxShift, o.shiftPenalty,
-                                o.sequenceClusteringThreshold, (uint32_t)best, bestCluster.data(), bestScore.data(), nFeasible.data(), &stats);
+        const int st = hmk_assign_shifted(nc->get(), 0, nq, nq, n, cand.memberCluster.data(), cand.clusterId.data(), (uint32_t)cand.slots.size(),
+                                          o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold, best, bestCluster.data(), bestScore.data(),
+                                          nFeasible.data(), &stats);
         if (st) nc->raise(st, nullptr);
-        const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - time0).count();
+        const long long ms = millisSince(time0);
         size_t assigned = 0;
         for (uint32_t q = 0; q < nq; q++) assigned += nFeasible[q] > 0;
         logger.logAndStderr("Ready. Assignment time: " + std::to_string(ms));
-        logger.logAndStderr("Candidate clusters: " + std::to_string(candidates.size()) + ", sequences assigned: " + std::to_string(assigned) + " of " +
+        logger.logAndStderr("Candidate clusters: " + std::to_string(cand.slots.size()) + ", sequences assigned: " + std::to_string(assigned) + " of " +
                             std::to_string(nq) + ", pairs scored: " + std::to_string(stats.pairs_scored) + ", GPU kernels: " +
                             std::to_string(stats.kernel_ms) + " ms");
         const std::string outFile = o.workingDirectory + "/assignments.tsv";
-        {
-            std::ofstream out(outFile);
-            if (!out) throw HammockException("cannot write " + outFile);
-            out << "sequence\trank\tcluster_id\tscore\tcluster_size\tfeasible_clusters\n";
-            for (uint32_t q = 0; q < nq; q++) {
-                const std::string &seq = newSequences[q]->getSequenceString();
-                if (nFeasible[q] == 0) { out << seq << "\tNA\tNA\tNA\tNA\t0\n"; continue; }
-                for (uint32_t t = 0; t < std::min<uint32_t>(nFeasible[q], (uint32_t)best); t++) {
-                    const ClusterPtr &cl = candidates[bestCluster[(size_t)q * best + t]];
-                    out << seq << '\t' << t + 1 << '\t' << cl->getId() << '\t' << bestScore[(size_t)q * best + t] << '\t' << cl->size() << '\t'
-                        << nFeasible[q] << '\n';
-                }
-            }
-        }
+        std::vector<std::string> rows;
+        for (auto &s : newSequences) rows.push_back(s->getSequenceString());
+        writeRankedTable(outFile, "sequence\trank\tcluster_id\tscore\tcluster_size\tfeasible_clusters", rows, clusters, cand, best, bestCluster,
+                         bestScore, nFeasible);
         logger.logAndStderr("Assignments in: " + outFile);
         logger.logWithTime("Program successfully ended.");
         return 0;
-    } catch (const CLIException &) {
-        throw;
-    } catch (const FileFormatException &e) {
-        logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
-        return 3;
-    } catch (const DataException &e) {
-        logger.logAndStderr("Error. Maybe wrong input file format or wrong set of labels? Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(std::string("cz.krejciadam.hammock.DataException: ") + e.what());
-        return 5;
-    } catch (const std::exception &e) {
-        logger.logAndStderr("Error. Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(e.what());
-        return 6;
+    } catch (...) {
+        return reportRunError(logger, false);
     }
 }
 
@@ -726,165 +693,66 @@ int runAssign(const std::vector<std::string> &args) {
 // unique sequence are candidates.
 int runMatch(const std::vector<std::string> &args) {
     Options o;
-    const std::string PARENT_DIR = parentDir();
-    o.matrixFile = PARENT_DIR + "/matrices/blosum62.txt";  // Hammock.java:45
     parseCommonArgs(args, o);
-    parseGreedyArgs(args, o);
-    std::string clustersFile;
-    bool haveClusters = false, havePenalty = false, skipSingletons = false;
-    int best = 1;
-    for (size_t i = 1; i < args.size(); i++) {
-        const bool more = args.size() > i + 1;
-        if (args[i] == "--clusters" && more) { clustersFile = args[++i]; haveClusters = true; }
-        else if (args[i] == "--best" && more) {
-            best = javaIntegerDecode(args[++i]);
-            if (best < 1 || best > 32) throw CLIException("Error. --best may be 1 to 32.");
-        } else if (args[i] == "--skip_singletons") skipSingletons = true;
-        else if ((args[i] == "-p" || args[i] == "--gap_penalty") && more) havePenalty = true;
-    }
-    if (!o.devices.empty()) throw CLIException("Error. --devices is not available in mode match (a match runs on one device, --device).");
-    if (!o.haveInput) throw CLIException("Error. Parameter input file (-i or --input) missing with no default.");
-    if (!haveClusters) throw CLIException("Error. Parameter cluster file (--clusters) missing with no default.");
-    if (o.haveDir) {
-        if (exists(o.workingDirectory)) throw CLIException("Error. Output directory exists. Exiting to prevent data loss.");
-        mkdir(o.workingDirectory.c_str(), 0777);
-    } else {
-        std::string name;
-        mkdir((PARENT_DIR + "/dist").c_str(), 0777);
-        for (int i = 1; i < 9999; i++) {
-            name = PARENT_DIR + "/dist/Hammock_result_" + std::to_string(i);
-            if (!exists(name)) { mkdir(name.c_str(), 0777); break; }
-        }
-        o.workingDirectory = name;
-        std::cerr << "Creating default output directory: " << name << std::endl;
-    }
+    parseModeArgs(args, o, 1);
+    requireOneDevice(o, "match", "a match");
+    requireInput(o);
+    requireClusters(o);
+    makeOutputDirectory(o, o.parentDir);
     Logger logger(o.workingDirectory + "/run.log", false);
     try {
-        logger.logAndStderr(std::string("\nHammock version ") + VERSION +
-                            " Run with --help for a brief description of command line parameters.\n");
-        const std::vector<std::vector<int>> scoringMatrix = FileIOManager::loadScoringMatrix(o.matrixFile);
-        std::shared_future<std::shared_ptr<NativeContext>> contextReady = std::async(std::launch::async, [&scoringMatrix, &o]() {
-            return std::make_shared<NativeContext>(scoringMatrix, o.device);
-        });
-        logger.logWithTime("Program started in mode \"match\".");
-        std::string argsString;
-        for (auto &a : args) argsString += " " + a;
-        logger.logWithoutTime("Command-line arguments: \n" + argsString + "\n");
+        ContextFuture contextReady = beginRun(o, logger, false);
+        logRunStart(logger, "match", args);
         logger.logAndStderr("Loading clusters...");
-        const std::vector<ClusterPtr> clusters = FileIOManager::loadClustersFromCsv(clustersFile);
-        std::vector<UniqueSequencePtr> clusterSequences;
-        for (auto &cl : clusters) for (auto &s : cl->getSequences()) clusterSequences.push_back(s);
+        const std::vector<ClusterPtr> clusters = FileIOManager::loadClustersFromCsv(o.clustersFile);
+        const std::vector<UniqueSequencePtr> clusterSequences = sequencesOf(clusters);
         logger.logAndStderr(std::to_string(clusters.size()) + " clusters of " + std::to_string(clusterSequences.size()) + " sequences loaded.");
         logger.logAndStderr("Loading query clusters...");
         const std::vector<ClusterPtr> queries = FileIOManager::loadClustersFromCsv(o.inputFileName);
-        std::vector<UniqueSequencePtr> querySequences;
-        for (auto &cl : queries) for (auto &s : cl->getSequences()) querySequences.push_back(s);
+        const std::vector<UniqueSequencePtr> querySequences = sequencesOf(queries);
         logger.logAndStderr(std::to_string(queries.size()) + " query clusters of " + std::to_string(querySequences.size()) + " sequences loaded.");
         if (querySequences.empty()) throw FileFormatException("Error. No query clusters to match.");
         if (clusterSequences.empty()) throw FileFormatException("Error. The cluster file holds no clusters.");
-        for (auto &s : clusterSequences)
-            if (s->size() < 1) throw FileFormatException("Error in cluster file: " + clustersFile + " - the sequence " + s->getSequenceString() +
-                                                         " has no occurrences (Cluster.size() counts them).");
+        requireOccurrences(clusterSequences, "Error in cluster file: " + o.clustersFile);
         std::vector<UniqueSequencePtr> both(querySequences);
         both.insert(both.end(), clusterSequences.begin(), clusterSequences.end());
-        const SequenceListSummary summary = summariseSequences(clusterSequences), bothSummary = summariseSequences(both);
-        if (bothSummary.maxLength > HMK_MAX_LEN)
-            throw HammockException("Error. The longest sequence has " + std::to_string(bothSummary.maxLength) + " amino acids; the GPU kernels of hammock-hip "
-                                   "take sequences of up to " + std::to_string(HMK_MAX_LEN) + " (Hammock's domain is 7-20).");
-        if (!o.haveMaxShift) {
-            o.maxShift = checkMaxShift(bothSummary, (int)javaRound(summary.meanLength() / 4));
-            logger.logAndStderr("Max shift not set. Setting automatically to: " + std::to_string(o.maxShift));
-        } else {
-            const int correct = checkMaxShift(bothSummary, o.maxShift);
-            if (o.maxShift != correct) {
-                o.maxShift = correct;
-                logger.logAndStderr("Setting max shift to " + std::to_string(correct) +
-                                    " as the length of the shortest sequence is only " + std::to_string(correct + 1));
-            }
-        }
-        if (!o.haveThreshold) {
-            o.sequenceClusteringThreshold = (int)javaRound(summary.meanLength() * 1.7);
-            logger.logAndStderr("Match threshold not set. Setting automatically to: " + std::to_string(o.sequenceClusteringThreshold));
-        }
-        if (!havePenalty) logger.logAndStderr("Gap penalty not set. Setting automatically to: " + std::to_string(o.shiftPenalty));
+        const SequenceListSummary summary = summariseSequences(clusterSequences);
+        settleShiftAndThreshold(o, logger, summariseSequences(both), summary, summary, "Match");
 
         // the query clusters' sequences, then the candidates' members: queries [0, nq), members [nq, n)
-        std::vector<ClusterPtr> candidates;
-        for (auto &cl : clusters)
-            if (!skipSingletons || cl->getUniqueSize() > 1) candidates.push_back(cl);
-        std::vector<UniqueSequencePtr> upload;
-        std::vector<uint32_t> queryCluster, memberCluster;
-        std::vector<int32_t> clusterId;
-        for (uint32_t b = 0; b < (uint32_t)queries.size(); b++)
-            for (auto &s : queries[b]->getSequences()) { upload.push_back(s); queryCluster.push_back(b); }
-        const uint32_t nq = (uint32_t)upload.size(), nb = (uint32_t)queries.size();
-        for (uint32_t c = 0; c < (uint32_t)candidates.size(); c++) {
-            clusterId.push_back(candidates[c]->getId());
-            for (auto &s : candidates[c]->getSequences()) { upload.push_back(s); memberCluster.push_back(c); }
-        }
-        const uint32_t n = (uint32_t)upload.size();
-        size_t total = 0;
-        for (auto &s : upload) total += s->getSequence().size();
-        std::vector<uint8_t> res(total);
-        std::vector<uint32_t> off(n + 1, 0);
-        std::vector<int32_t> sizes(n);
-        for (uint32_t k = 0; k < n; k++) {
-            off[k + 1] = off[k] + (uint32_t)upload[k]->getSequence().size();
-            for (size_t r = 0; r < upload[k]->getSequence().size(); r++) res[off[k] + r] = (uint8_t)upload[k]->getSequence()[r];
-            sizes[k] = k < nq ? 1 : upload[k]->size();   // (a query sequence's size plays no part)
-        }
+        std::vector<UniqueSequencePtr> upload(querySequences);
+        std::vector<uint32_t> queryCluster;
+        for (uint32_t b = 0; b < (uint32_t)queries.size(); b++) queryCluster.insert(queryCluster.end(), queries[b]->getSequences().size(), b);
+        const Candidates cand = appendCandidates(clusters, o.skipSingletons, 0, upload);
+        const uint32_t nq = (uint32_t)querySequences.size(), nb = (uint32_t)queries.size(), n = (uint32_t)upload.size(), best = (uint32_t)o.best;
         const std::shared_ptr<NativeContext> nc = contextReady.get();
-        hmk_ctx *c = nc->get();
-        int st = hmk_set_sequences(c, res.data(), off.data(), sizes.data(), n);
-        if (st) nc->raise(st, nullptr);
+        nc->setSequences(upload, true, nq);   // (a query sequence's size plays no part)
         logger.logAndStderr("Matching...");
         const auto time0 = std::chrono::steady_clock::now();
         std::vector<uint32_t> bestCluster((size_t)nb * best), nFeasible(nb);
         std::vector<int32_t> bestScore((size_t)nb * best);
         hmk_neighbor_stats stats{};
-        st = hmk_match_clusters_shifted(c, 0, nq, queryCluster.data(), nb, nq, n, memberCluster.data(), clusterId.data(), (uint32_t)candidates.size(),
-                                        o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold, (uint32_t)best, bestCluster.data(), bestScore.data(),
-                                        nFeasible.data(), &stats);
+        const int st = hmk_match_clusters_shifted(nc->get(), 0, nq, queryCluster.data(), nb, nq, n, cand.memberCluster.data(), cand.clusterId.data(),
+                                                  (uint32_t)cand.slots.size(), o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold, best,
+                                                  bestCluster.data(), bestScore.data(), nFeasible.data(), &stats);
         if (st) nc->raise(st, nullptr);
-        const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - time0).count();
+        const long long ms = millisSince(time0);
         size_t matched = 0;
         for (uint32_t b = 0; b < nb; b++) matched += nFeasible[b] > 0;
         logger.logAndStderr("Ready. Match time: " + std::to_string(ms));
-        logger.logAndStderr("Candidate clusters: " + std::to_string(candidates.size()) + ", query clusters matched: " + std::to_string(matched) + " of " +
+        logger.logAndStderr("Candidate clusters: " + std::to_string(cand.slots.size()) + ", query clusters matched: " + std::to_string(matched) + " of " +
                             std::to_string(nb) + ", pairs scored: " + std::to_string(stats.pairs_scored) + ", GPU kernels: " +
                             std::to_string(stats.kernel_ms) + " ms");
         const std::string outFile = o.workingDirectory + "/cluster_matches.tsv";
-        {
-            std::ofstream out(outFile);
-            if (!out) throw HammockException("cannot write " + outFile);
-            out << "cluster_id\trank\tmatched_cluster_id\tscore\tmatched_size\tfeasible_clusters\n";
-            for (uint32_t b = 0; b < nb; b++) {
-                const int id = queries[b]->getId();
-                if (nFeasible[b] == 0) { out << id << "\tNA\tNA\tNA\tNA\t0\n"; continue; }
-                for (uint32_t t = 0; t < std::min<uint32_t>(nFeasible[b], (uint32_t)best); t++) {
-                    const ClusterPtr &cl = candidates[bestCluster[(size_t)b * best + t]];
-                    out << id << '\t' << t + 1 << '\t' << cl->getId() << '\t' << bestScore[(size_t)b * best + t] << '\t' << cl->size() << '\t'
-                        << nFeasible[b] << '\n';
-                }
-            }
-        }
+        std::vector<std::string> rows;
+        for (auto &cl : queries) rows.push_back(std::to_string(cl->getId()));
+        writeRankedTable(outFile, "cluster_id\trank\tmatched_cluster_id\tscore\tmatched_size\tfeasible_clusters", rows, clusters, cand, best,
+                         bestCluster, bestScore, nFeasible);
         logger.logAndStderr("Matches in: " + outFile);
         logger.logWithTime("Program successfully ended.");
         return 0;
-    } catch (const CLIException &) {
-        throw;
-    } catch (const FileFormatException &e) {
-        logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
-        return 3;
-    } catch (const DataException &e) {
-        logger.logAndStderr("Error. Maybe wrong input file format or wrong set of labels? Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(std::string("cz.krejciadam.hammock.DataException: ") + e.what());
-        return 5;
-    } catch (const std::exception &e) {
-        logger.logAndStderr("Error. Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(e.what());
-        return 6;
+    } catch (...) {
+        return reportRunError(logger, false);
     }
 }
 
@@ -899,56 +767,26 @@ int runMatch(const std::vector<std::string> &args) {
 // the stage-1 files of greedy (label columns: the file's, then new labels in first-seen order) and new_sequences.tsv.
 int runContinue(const std::vector<std::string> &args) {
     Options o;
-    const std::string PARENT_DIR = parentDir();
-    o.matrixFile = PARENT_DIR + "/matrices/blosum62.txt";  // Hammock.java:45
     parseCommonArgs(args, o);
-    parseGreedyArgs(args, o);
-    std::string clustersFile;
-    bool haveClusters = false, havePenalty = false;
-    for (size_t i = 1; i < args.size(); i++) {
-        const bool more = args.size() > i + 1;
-        if (args[i] == "--clusters" && more) { clustersFile = args[++i]; haveClusters = true; }
-        else if ((args[i] == "-p" || args[i] == "--gap_penalty") && more) havePenalty = true;
-    }
-    if (!o.devices.empty()) throw CLIException("Error. --devices is not available in mode continue (a continuation runs on one device, --device).");
-    if (!o.haveInput) throw CLIException("Error. Parameter input file (-i or --input) missing with no default.");
-    if (!haveClusters) throw CLIException("Error. Parameter cluster file (--clusters) missing with no default.");
-    if (!(o.inputType == "fasta" || o.inputType == "tab"))
-        throw CLIException("Error. Parameter -f value may be either \"fasta\" or \"tab\" in mode continue.");
-    if (o.haveDir) {
-        if (exists(o.workingDirectory)) throw CLIException("Error. Output directory exists. Exiting to prevent data loss.");
-        mkdir(o.workingDirectory.c_str(), 0777);
-    } else {
-        std::string name;
-        mkdir((PARENT_DIR + "/dist").c_str(), 0777);
-        for (int i = 1; i < 9999; i++) {
-            name = PARENT_DIR + "/dist/Hammock_result_" + std::to_string(i);
-            if (!exists(name)) { mkdir(name.c_str(), 0777); break; }
-        }
-        o.workingDirectory = name;
-        std::cerr << "Creating default output directory: " << name << std::endl;
-    }
+    parseModeArgs(args, o, -1);
+    requireOneDevice(o, "continue", "a continuation");
+    requireInput(o);
+    requireClusters(o);
+    requireFastaOrTab(o, "continue");
+    makeOutputDirectory(o, o.parentDir);
     Logger logger(o.workingDirectory + "/run.log", false);
     try {
-        logger.logAndStderr(std::string("\nHammock version ") + VERSION +
-                            " Run with --help for a brief description of command line parameters.\n");
-        const std::vector<std::vector<int>> scoringMatrix = FileIOManager::loadScoringMatrix(o.matrixFile);
-        std::shared_future<std::shared_ptr<NativeContext>> contextReady = std::async(std::launch::async, [&scoringMatrix, &o]() {
-            return std::make_shared<NativeContext>(scoringMatrix, o.device);
-        });
-        logger.logWithTime("Program started in mode \"continue\".");
-        std::string argsString;
-        for (auto &a : args) argsString += " " + a;
-        logger.logWithoutTime("Command-line arguments: \n" + argsString + "\n");
+        ContextFuture contextReady = beginRun(o, logger, false);
+        logRunStart(logger, "continue", args);
         logger.logAndStderr("Loading clusters...");
-        std::vector<ClusterPtr> loaded = FileIOManager::loadClustersFromCsv(clustersFile);
+        std::vector<ClusterPtr> loaded = FileIOManager::loadClustersFromCsv(o.clustersFile);
         // the file's label columns and its line order (the original-order file lists the file's sequences first, as they came)
         std::vector<std::string> labels;
         std::vector<UniqueSequencePtr> lineOrder;
         std::unordered_map<std::string, UniqueSequencePtr> inFile;
         for (auto &cl : loaded) for (auto &s : cl->getSequences()) inFile.emplace(s->getSequenceString(), s);
         {
-            const std::vector<std::string> lines = FileIOManager::readLines(clustersFile);
+            const std::vector<std::string> lines = FileIOManager::readLines(o.clustersFile);
             std::vector<std::string> header = FileIOManager::splitChar(lines[0], CSV_SEPARATOR, true);
             const long seqAt = 1;   // (files greedy writes: cluster_id, sequence, labels...)
             for (const char *drop : {"alignment", "sum"}) {
@@ -964,12 +802,10 @@ int runContinue(const std::vector<std::string> &args) {
             }
         }
         if (o.haveLabels) labels = FileIOManager::splitChar(o.labelString, ',', true);
-        size_t nLoadedSeqs = 0;
-        for (auto &cl : loaded) nLoadedSeqs += cl->getSequences().size();
+        const size_t nLoadedSeqs = sequencesOf(loaded).size();
         logger.logAndStderr(std::to_string(loaded.size()) + " clusters of " + std::to_string(nLoadedSeqs) + " sequences loaded.");
         logger.logAndStderr("Loading new sequences...");
-        std::vector<UniqueSequencePtr> input = o.inputType == "fasta" ? FileIOManager::loadUniqueSequencesFromFasta(o.inputFileName)
-                                                                      : FileIOManager::loadUniqueSequencesFromTable(o.inputFileName);
+        std::vector<UniqueSequencePtr> input = loadSequences(o, o.inputFileName);
         logger.logAndStderr(std::to_string(input.size()) + " unique new sequences loaded.");
         if (input.empty()) throw FileFormatException("Error. No new sequences.");
         if (nLoadedSeqs == 0) throw FileFormatException("Error. The cluster file holds no clusters.");
@@ -992,44 +828,16 @@ int runContinue(const std::vector<std::string> &args) {
         std::vector<ClusterPtr> clusters;
         int maxId = INT32_MIN;
         for (auto &cl : loaded) { clusters.push_back(std::make_shared<Cluster>(cl->getSequences(), cl->getId())); maxId = std::max(maxId, cl->getId()); }
-        std::vector<UniqueSequencePtr> fileSequences, both;
-        for (auto &cl : clusters) for (auto &s : cl->getSequences()) fileSequences.push_back(s);
-        both = fileSequences;
+        const std::vector<UniqueSequencePtr> fileSequences = sequencesOf(clusters);
+        std::vector<UniqueSequencePtr> both(fileSequences);
         both.insert(both.end(), newSequences.begin(), newSequences.end());
-        const SequenceListSummary summary = summariseSequences(fileSequences), bothSummary = summariseSequences(both);
-        if (bothSummary.maxLength > HMK_MAX_LEN)
-            throw HammockException("Error. The longest sequence has " + std::to_string(bothSummary.maxLength) + " amino acids; the GPU kernels of hammock-hip "
-                                   "take sequences of up to " + std::to_string(HMK_MAX_LEN) + " (Hammock's domain is 7-20).");
-        if (!o.haveMaxShift) {
-            o.maxShift = checkMaxShift(bothSummary, (int)javaRound(summary.meanLength() / 4));
-            logger.logAndStderr("Max shift not set. Setting automatically to: " + std::to_string(o.maxShift) + " (it should be the original run's)");
-        } else {
-            const int correct = checkMaxShift(bothSummary, o.maxShift);
-            if (o.maxShift != correct) {
-                o.maxShift = correct;
-                logger.logAndStderr("Setting max shift to " + std::to_string(correct) +
-                                    " as the length of the shortest sequence is only " + std::to_string(correct + 1));
-            }
-        }
-        if (!o.haveThreshold) {
-            o.sequenceClusteringThreshold = (int)javaRound(summary.meanLength() * 1.7);
-            logger.logAndStderr("Greedy clustering threshold not set. Setting automatically to: " + std::to_string(o.sequenceClusteringThreshold) +
-                                " (it should be the original run's)");
-        }
-        if (!havePenalty) logger.logAndStderr("Gap penalty not set. Setting automatically to: " + std::to_string(o.shiftPenalty));
+        const SequenceListSummary summary = summariseSequences(fileSequences);
+        settleShiftAndThreshold(o, logger, summariseSequences(both), summary, summary, "Greedy clustering", " (it should be the original run's)");
         sortSequences(newSequences, o.order, o.seed, labels);                                    // :407, as greedy orders its input
 
         // the candidates' members first, the new sequences behind them: members [0, nm), new [nm, n)
-        std::vector<ClusterPtr> candidates;
-        for (auto &cl : clusters)
-            if (cl->getUniqueSize() > 1) candidates.push_back(cl);                               // :41-50
         std::vector<UniqueSequencePtr> upload;
-        std::vector<uint32_t> memberCluster;
-        std::vector<int32_t> clusterId;
-        for (uint32_t c = 0; c < (uint32_t)candidates.size(); c++) {
-            clusterId.push_back(candidates[c]->getId());
-            for (auto &s : candidates[c]->getSequences()) { upload.push_back(s); memberCluster.push_back(c); }
-        }
+        const Candidates cand = appendCandidates(clusters, true, 0, upload);                     // :41-50
         const uint32_t nm = (uint32_t)upload.size(), nq = (uint32_t)newSequences.size();
         upload.insert(upload.end(), newSequences.begin(), newSequences.end());
         const uint32_t n = (uint32_t)upload.size();
@@ -1038,22 +846,10 @@ int runContinue(const std::vector<std::string> &args) {
         logger.logAndStderr("Continuing the clustering...");
         const auto time0 = std::chrono::steady_clock::now();
         if (nq) {
-            size_t total = 0;
-            for (auto &s : upload) total += s->getSequence().size();
-            std::vector<uint8_t> res(total);
-            std::vector<uint32_t> off(n + 1, 0);
-            std::vector<int32_t> sizes(n);
-            for (uint32_t k = 0; k < n; k++) {
-                off[k + 1] = off[k] + (uint32_t)upload[k]->getSequence().size();
-                for (size_t r = 0; r < upload[k]->getSequence().size(); r++) res[off[k] + r] = (uint8_t)upload[k]->getSequence()[r];
-                sizes[k] = upload[k]->size();
-            }
             const std::shared_ptr<NativeContext> nc = contextReady.get();
-            hmk_ctx *c = nc->get();
-            int st = hmk_set_sequences(c, res.data(), off.data(), sizes.data(), n);
-            if (st) nc->raise(st, nullptr);
-            st = hmk_greedy_continue(c, nm, n, 0, nm, memberCluster.data(), clusterId.data(), (uint32_t)candidates.size(), o.maxShift,
-                                     o.shiftPenalty, o.sequenceClusteringThreshold, joined.data(), rank.data(), &stats);
+            nc->setSequences(upload, true);
+            const int st = hmk_greedy_continue(nc->get(), nm, n, 0, nm, cand.memberCluster.data(), cand.clusterId.data(), (uint32_t)cand.slots.size(),
+                                               o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold, joined.data(), rank.data(), &stats);
             if (st) nc->raise(st, nullptr);
         }
         // :61-62 in loop order, then :64-67: the new singletons behind the loaded clusters
@@ -1062,16 +858,16 @@ int runContinue(const std::vector<std::string> &args) {
         int k = 0;
         for (uint32_t q = 0; q < nq; q++) {
             if (joined[q] >= 0) {
-                candidates[joined[q]]->insert(newSequences[q]);
-                finalId[q] = candidates[joined[q]]->getId();
+                const ClusterPtr &cl = clusters[cand.slots[joined[q]]];
+                cl->insert(newSequences[q]);
+                finalId[q] = cl->getId();
             } else {
                 finalId[q] = maxId + 1 + k++;
                 result.push_back(std::make_shared<Cluster>(std::vector<UniqueSequencePtr>{newSequences[q]}, finalId[q]));
             }
         }
-        const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - time0).count();
-        logger.logAndStderr("Ready. Clustering time: " + std::to_string(ms));
-        logger.logAndStderr("Candidate clusters: " + std::to_string(candidates.size()) + ", new sequences joined: " + std::to_string(stats.n_joined) +
+        logger.logAndStderr("Ready. Clustering time: " + std::to_string(millisSince(time0)));
+        logger.logAndStderr("Candidate clusters: " + std::to_string(cand.slots.size()) + ", new sequences joined: " + std::to_string(stats.n_joined) +
                             " of " + std::to_string(nq) + ", pairs scored: " + std::to_string(stats.pairs_scored) + ", neighbour edges: " +
                             std::to_string(stats.n_edges) + ", GPU passes: " + std::to_string(stats.kernel_ms) + " ms, loop: " +
                             std::to_string(stats.loop_ms) + " ms in " + std::to_string(stats.loop_rounds) + " rounds");
@@ -1097,20 +893,8 @@ int runContinue(const std::vector<std::string> &args) {
         logger.logAndStderr("New sequences in: " + newCsv);
         logger.logWithTime("Program successfully ended.");
         return 0;
-    } catch (const CLIException &) {
-        throw;
-    } catch (const FileFormatException &e) {
-        logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
-        return 3;
-    } catch (const DataException &e) {
-        logger.logAndStderr("Error. Maybe wrong input file format or wrong set of labels? Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(std::string("cz.krejciadam.hammock.DataException: ") + e.what());
-        return 5;
-    } catch (const std::exception &e) {
-        logger.logAndStderr("Error. Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(e.what());
-        return 6;
+    } catch (...) {
+        return reportRunError(logger, false);
     }
 }
 
@@ -1199,140 +983,68 @@ static MergeInput loadMergeInput(const std::string &firstFile, const std::string
 
 int runMerge(const std::vector<std::string> &args) {
     Options o;
-    const std::string PARENT_DIR = parentDir();
-    o.matrixFile = PARENT_DIR + "/matrices/blosum62.txt";  // Hammock.java:45
     parseCommonArgs(args, o);
-    parseGreedyArgs(args, o);
-    std::string clustersFile;
-    bool havePenalty = false, skipSingletons = false;
-    int javaHashset = 8;
-    for (size_t i = 1; i < args.size(); i++) {
-        const bool more = args.size() > i + 1;
-        if (args[i] == "--clusters" && more) clustersFile = args[++i];
-        else if (args[i] == "--skip_singletons") skipSingletons = true;
-        else if (args[i] == "--java_hashset" && more) {
-            javaHashset = javaIntegerDecode(args[++i]);
-            if (javaHashset != 8 && javaHashset != 7 && javaHashset != 6) throw CLIException("Error. --java_hashset may be 8, 7 or 6.");
-        } else if ((args[i] == "-p" || args[i] == "--gap_penalty") && more) havePenalty = true;
-    }
-    if (!o.devices.empty()) throw CLIException("Error. --devices is not available in mode merge (a merge runs on one device, --device).");
-    if (!o.haveInput) throw CLIException("Error. Parameter input file (-i or --input) missing with no default.");
-    if (o.haveDir) {
-        if (exists(o.workingDirectory)) throw CLIException("Error. Output directory exists. Exiting to prevent data loss.");
-        mkdir(o.workingDirectory.c_str(), 0777);
-    } else {
-        std::string name;
-        mkdir((PARENT_DIR + "/dist").c_str(), 0777);
-        for (int i = 1; i < 9999; i++) {
-            name = PARENT_DIR + "/dist/Hammock_result_" + std::to_string(i);
-            if (!exists(name)) { mkdir(name.c_str(), 0777); break; }
-        }
-        o.workingDirectory = name;
-        std::cerr << "Creating default output directory: " << name << std::endl;
-    }
+    parseModeArgs(args, o, -1);
+    requireOneDevice(o, "merge", "a merge");
+    requireInput(o);
+    makeOutputDirectory(o, o.parentDir);
     Logger logger(o.workingDirectory + "/run.log", false);
     try {
-        logger.logAndStderr(std::string("\nHammock version ") + VERSION +
-                            " Run with --help for a brief description of command line parameters.\n");
-        const std::vector<std::vector<int>> scoringMatrix = FileIOManager::loadScoringMatrix(o.matrixFile);
-        std::shared_future<std::shared_ptr<NativeContext>> contextReady = std::async(std::launch::async, [&scoringMatrix, &o]() {
-            return std::make_shared<NativeContext>(scoringMatrix, o.device);
-        });
-        logger.logWithTime("Program started in mode \"merge\".");
-        std::string argsString;
-        for (auto &a : args) argsString += " " + a;
-        logger.logWithoutTime("Command-line arguments: \n" + argsString + "\n");
+        ContextFuture contextReady = beginRun(o, logger, false);
+        logRunStart(logger, "merge", args);
         logger.logAndStderr("Loading clusters...");
-        const std::string firstFile = clustersFile.empty() ? o.inputFileName : clustersFile;
-        MergeInput in = loadMergeInput(firstFile, clustersFile.empty() ? std::string() : o.inputFileName);
+        const std::string firstFile = o.clustersFile.empty() ? o.inputFileName : o.clustersFile;
+        MergeInput in = loadMergeInput(firstFile, o.clustersFile.empty() ? std::string() : o.inputFileName);
         if (o.haveLabels) in.labels = FileIOManager::splitChar(o.labelString, ',', true);
-        std::vector<UniqueSequencePtr> all, firstSequences;
+        const std::vector<UniqueSequencePtr> all = sequencesOf(in.clusters);
+        std::vector<UniqueSequencePtr> firstSequences;
         for (size_t c = 0; c < in.clusters.size(); c++)
-            for (auto &s : in.clusters[c]->getSequences()) { all.push_back(s); if (in.sourceFile[c] == 0) firstSequences.push_back(s); }
+            if (in.sourceFile[c] == 0) firstSequences.insert(firstSequences.end(), in.clusters[c]->getSequences().begin(), in.clusters[c]->getSequences().end());
         logger.logAndStderr(std::to_string(in.clusters.size()) + " clusters of " + std::to_string(all.size()) + " sequences loaded.");
-        if (!clustersFile.empty())
+        if (!o.clustersFile.empty())
             logger.logAndStderr(std::to_string(in.duplicates) + " sequences of the input file were already in the cluster file: their counts and labels "
                                 "were added there (" + std::to_string(in.emptied) + " input clusters became empty).");
         if (firstSequences.empty()) throw FileFormatException("Error. The cluster file holds no clusters.");
-        for (auto &s : all)
-            if (s->size() < 1) throw FileFormatException("Error in cluster file - the sequence " + s->getSequenceString() +
-                                                         " has no occurrences (Cluster.size() counts them).");
-        const SequenceListSummary summary = summariseSequences(firstSequences), allSummary = summariseSequences(all);
-        if (allSummary.maxLength > HMK_MAX_LEN)
-            throw HammockException("Error. The longest sequence has " + std::to_string(allSummary.maxLength) + " amino acids; the GPU kernels of hammock-hip "
-                                   "take sequences of up to " + std::to_string(HMK_MAX_LEN) + " (Hammock's domain is 7-20).");
-        if (!o.haveMaxShift) {
-            o.maxShift = checkMaxShift(allSummary, (int)javaRound(summary.meanLength() / 4));
-            logger.logAndStderr("Max shift not set. Setting automatically to: " + std::to_string(o.maxShift));
-        } else {
-            const int correct = checkMaxShift(allSummary, o.maxShift);
-            if (o.maxShift != correct) {
-                o.maxShift = correct;
-                logger.logAndStderr("Setting max shift to " + std::to_string(correct) +
-                                    " as the length of the shortest sequence is only " + std::to_string(correct + 1));
-            }
-        }
-        if (!o.haveThreshold) {
-            o.sequenceClusteringThreshold = (int)javaRound(summary.meanLength() * 1.7);
-            logger.logAndStderr("Merge threshold not set. Setting automatically to: " + std::to_string(o.sequenceClusteringThreshold));
-        }
-        if (!havePenalty) logger.logAndStderr("Gap penalty not set. Setting automatically to: " + std::to_string(o.shiftPenalty));
+        requireOccurrences(all, "Error in cluster file");
+        const SequenceListSummary summary = summariseSequences(firstSequences);
+        settleShiftAndThreshold(o, logger, summariseSequences(all), summary, summary, "Merge");
 
         // the candidates' members, slot by slot
-        std::vector<uint32_t> candidates;   // indices into in.clusters
         int maxId = INT32_MIN, minId = INT32_MAX;
-        for (size_t c = 0; c < in.clusters.size(); c++) {
-            maxId = std::max(maxId, in.clusters[c]->getId());
-            minId = std::min(minId, in.clusters[c]->getId());
-            if (!skipSingletons || in.clusters[c]->getUniqueSize() > 1) candidates.push_back((uint32_t)c);
+        for (auto &cl : in.clusters) {
+            maxId = std::max(maxId, cl->getId());
+            minId = std::min(minId, cl->getId());
         }
-        std::vector<UniqueSequencePtr> upload;
-        std::vector<uint32_t> memberCluster;
-        std::vector<int32_t> clusterId;
         // (hmk_clinkage_merge takes ids from 1; greedy numbers its clusters by their seed's index, from 0: such ids go to the library
         // shifted up and come back shifted down)
         const int idShift = minId < 1 ? 1 - minId : 0;
-        for (uint32_t c = 0; c < (uint32_t)candidates.size(); c++) {
-            clusterId.push_back(in.clusters[candidates[c]]->getId() + idShift);
-            for (auto &s : in.clusters[candidates[c]]->getSequences()) { upload.push_back(s); memberCluster.push_back(c); }
-        }
-        const uint32_t n = (uint32_t)upload.size(), ncl = (uint32_t)candidates.size();
+        std::vector<UniqueSequencePtr> upload;
+        const Candidates cand = appendCandidates(in.clusters, o.skipSingletons, idShift, upload);
+        const uint32_t n = (uint32_t)upload.size(), ncl = (uint32_t)cand.slots.size();
         std::vector<int32_t> mergedId(std::max<uint32_t>(ncl, 1)), resultOrder(std::max<uint32_t>(ncl, 1)), rank(std::max<uint32_t>(n, 1));
         hmk_merge_stats stats{};
         logger.logAndStderr("Merging...");
         const auto time0 = std::chrono::steady_clock::now();
         if (ncl >= 1) {
-            size_t total = 0;
-            for (auto &s : upload) total += s->getSequence().size();
-            std::vector<uint8_t> res(total);
-            std::vector<uint32_t> off(n + 1, 0);
-            std::vector<int32_t> sizes(n);
-            for (uint32_t k = 0; k < n; k++) {
-                off[k + 1] = off[k] + (uint32_t)upload[k]->getSequence().size();
-                for (size_t r = 0; r < upload[k]->getSequence().size(); r++) res[off[k] + r] = (uint8_t)upload[k]->getSequence()[r];
-                sizes[k] = upload[k]->size();
-            }
             const std::shared_ptr<NativeContext> nc = contextReady.get();
-            hmk_ctx *c = nc->get();
-            int st = hmk_set_sequences(c, res.data(), off.data(), sizes.data(), n);
+            nc->setSequences(upload, true);
+            int st = hmk_set_java_hashset(nc->get(), o.javaHashSet);
             if (st) nc->raise(st, nullptr);
-            st = hmk_set_java_hashset(c, javaHashset);
-            if (st) nc->raise(st, nullptr);
-            st = hmk_clinkage_merge(c, 0, n, memberCluster.data(), clusterId.data(), ncl, o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold,
-                                    mergedId.data(), resultOrder.data(), rank.data(), &stats);
+            st = hmk_clinkage_merge(nc->get(), 0, n, cand.memberCluster.data(), cand.clusterId.data(), ncl, o.maxShift, o.shiftPenalty,
+                                    o.sequenceClusteringThreshold, mergedId.data(), resultOrder.data(), rank.data(), &stats);
             if (st) nc->raise(st, nullptr);
         }
-        const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - time0).count();
+        const long long ms = millisSince(time0);
         // the returned clusters in list order (:121-123), members in Cluster.getSequences() order (:105-106); then the clusters that
         // were written through.  A merged cluster's id counts from the largest id of ALL clusters.
         int maxCandidateId = INT32_MIN;
-        for (int32_t id : clusterId) maxCandidateId = std::max(maxCandidateId, id);
+        for (int32_t id : cand.clusterId) maxCandidateId = std::max(maxCandidateId, id);
         auto finalIdOf = [&](int32_t id) { return id > maxCandidateId ? id - maxCandidateId + maxId : id - idShift; };
         std::unordered_map<int32_t, std::vector<UniqueSequencePtr>> membersOf;
         std::unordered_map<int32_t, int> sourcesOf;
         for (uint32_t c = 0; c < ncl; c++) sourcesOf[mergedId[c]]++;
         for (uint32_t k = 0; k < n; k++) {
-            std::vector<UniqueSequencePtr> &m = membersOf[mergedId[memberCluster[k]]];
+            std::vector<UniqueSequencePtr> &m = membersOf[mergedId[cand.memberCluster[k]]];
             if (m.size() <= (size_t)rank[k]) m.resize((size_t)rank[k] + 1);
             m[rank[k]] = upload[k];
         }
@@ -1340,7 +1052,7 @@ int runMerge(const std::vector<std::string> &args) {
         for (int32_t t = 0; t < stats.n_result_clusters; t++)
             result.push_back(std::make_shared<Cluster>(membersOf[resultOrder[t]], finalIdOf(resultOrder[t])));
         std::vector<int32_t> slotOf(in.clusters.size(), -1);
-        for (uint32_t c = 0; c < ncl; c++) slotOf[candidates[c]] = (int32_t)c;
+        for (uint32_t c = 0; c < ncl; c++) slotOf[cand.slots[c]] = (int32_t)c;
         for (size_t c = 0; c < in.clusters.size(); c++)
             if (slotOf[c] < 0) result.push_back(in.clusters[c]);
         logger.logAndStderr("Ready. Merge time: " + std::to_string(ms));
@@ -1372,20 +1084,8 @@ int runMerge(const std::vector<std::string> &args) {
         logger.logAndStderr("Given clusters in: " + mergedCsv);
         logger.logWithTime("Program successfully ended.");
         return 0;
-    } catch (const CLIException &) {
-        throw;
-    } catch (const FileFormatException &e) {
-        logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
-        return 3;
-    } catch (const DataException &e) {
-        logger.logAndStderr("Error. Maybe wrong input file format or wrong set of labels? Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(std::string("cz.krejciadam.hammock.DataException: ") + e.what());
-        return 5;
-    } catch (const std::exception &e) {
-        logger.logAndStderr("Error. Run with --help for a brief description of command line parameters. Trace: \n");
-        logger.logAndStderr(e.what());
-        return 6;
+    } catch (...) {
+        return reportRunError(logger, false);
     }
 }
 

@@ -397,26 +397,23 @@ struct SequenceClusterer {  // SequenceClusterer.java:15-26
 // ---- the native context ----------------------------------------------------------------------------------
 class NativeContext {
     hmk_ctx *ctx_ = nullptr;
+    static std::vector<int32_t> flat24(const std::vector<std::vector<int>> &scoringMatrix) {
+        if (scoringMatrix.size() != 24) throw HammockException("scoring matrix must be 24 x 24");
+        std::vector<int32_t> m;
+        for (auto &row : scoringMatrix) {
+            if (row.size() != 24) throw HammockException("scoring matrix must be 24 x 24");
+            m.insert(m.end(), row.begin(), row.end());
+        }
+        return m;
+    }
 public:
     NativeContext(const std::vector<std::vector<int>> &scoringMatrix, int device) {
-        if (scoringMatrix.size() != 24) throw HammockException("scoring matrix must be 24 x 24");
-        int32_t m[576];
-        for (int r = 0; r < 24; r++) {
-            if (scoringMatrix[r].size() != 24) throw HammockException("scoring matrix must be 24 x 24");
-            for (int c = 0; c < 24; c++) m[r * 24 + c] = scoringMatrix[r][c];
-        }
-        const int st = hmk_create(m, device, &ctx_);
+        const int st = hmk_create(flat24(scoringMatrix).data(), device, &ctx_);
         if (st) raise(st, nullptr);
     }
     // several GPUs of the node behind one context (hmk_create_multi): devices[0] is the root
     NativeContext(const std::vector<std::vector<int>> &scoringMatrix, const std::vector<int> &devices) {
-        if (scoringMatrix.size() != 24) throw HammockException("scoring matrix must be 24 x 24");
-        int32_t m[576];
-        for (int r = 0; r < 24; r++) {
-            if (scoringMatrix[r].size() != 24) throw HammockException("scoring matrix must be 24 x 24");
-            for (int c = 0; c < 24; c++) m[r * 24 + c] = scoringMatrix[r][c];
-        }
-        const int st = hmk_create_multi(m, devices.data(), (int)devices.size(), &ctx_);
+        const int st = hmk_create_multi(flat24(scoringMatrix).data(), devices.data(), (int)devices.size(), &ctx_);
         if (st) raise(st, nullptr);
     }
     ~NativeContext() { hmk_destroy(ctx_); }
@@ -433,7 +430,8 @@ public:
             default: throw HammockException(msg);
         }
     }
-    void setSequences(const std::vector<UniqueSequencePtr> &seqs, bool withSizes) const {
+    // withSizes: the sequences' sizes go along, 1 for those before sizedFrom (queries, whose size plays no part)
+    void setSequences(const std::vector<UniqueSequencePtr> &seqs, bool withSizes, size_t sizedFrom = 0) const {
         size_t total = 0;
         for (auto &s : seqs) total += s->getSequence().size();
         std::vector<uint8_t> res(total);
@@ -444,7 +442,7 @@ public:
             for (size_t k = lo; k < hi; k++) {
                 uint8_t *dst = res.data() + off[k];
                 for (int r : seqs[k]->getSequence()) *dst++ = (uint8_t)r;
-                sizes[k] = seqs[k]->size();
+                sizes[k] = k < sizedFrom ? 1 : seqs[k]->size();
             }
         });
         const int st = hmk_set_sequences(ctx_, res.data(), off.data(), withSizes ? sizes.data() : nullptr, (uint32_t)seqs.size());

@@ -227,3 +227,75 @@ def test_result_writers_with_a_string_in_two_clusters(tmp_path):
     spec = [(7, names[0:3]), (3, [names[1], names[3]]), (11, [names[4]]), (2, [names[4], names[5]]), (5, [names[0]])]
     spec += [(100 + k, names[k:k + 7]) for k in range(6, len(names) - 7, 7)]
     _write_and_compare(tmp_path, fa, seqs, spec, order="input")
+
+
+def _java_round(v):
+    import math
+    return int(math.floor(v + 0.5))
+
+
+@pytest.mark.gpu
+def test_cli_modes_log_their_settled_parameters(tmp_path):
+    """Every mode's run.log names its mode, repeats its arguments and says which max shift, threshold and gap penalty it
+    settled on.  The defaults are greedy's (Hammock.java:394-397, :803-811, :1421-1434): max shift = round(mean length / 4)
+    clamped by the shortest sequence - 1, threshold = round(1.7 x mean length) -- each mode over its own lists: greedy and
+    clinkage over their input; assign, continue and match the means over the --clusters file, the clamp over both files;
+    search the shift over the union of both files and the threshold over the queries; merge the means over the --clusters
+    file, the clamp over both.  The peptides are drawn from four letters: some then score 17 and more, greedy's defaults find
+    clusters and the later modes have candidates (of 20 letters the first sequence has no neighbour, where the reference ends in
+    its NullPointerException and the CLI in exit code 4)."""
+    import numpy as np
+    from conftest import random_peptides
+    peptides = ["".join("ARND"[c] for c in p) for p in random_peptides(np.random.default_rng(20261017), 60, 8, 12, alphabet=4)]
+    old, new = peptides[:40], peptides[40:]
+    assert min(map(len, old)) == 8 and min(map(len, new)) == 8
+    old_fa, new_fa = tmp_path / "old.fa", tmp_path / "new.fa"
+    old_fa.write_text("".join(f">{k}\n{s}\n" for k, s in enumerate(old)))
+    new_fa.write_text("".join(f">{k}\n{s}\n" for k, s in enumerate(new, 40)))
+
+    def settled(clamp, shift_mean, threshold_mean):
+        mean = lambda seqs: sum(map(len, seqs)) / len(seqs)  # noqa: E731
+        return min(_java_round(mean(shift_mean) / 4), min(map(len, clamp)) - 1), _java_round(1.7 * mean(threshold_mean))
+
+    def run(mode, word, lists, *argv, suffix="", gap_line=True, shift_line=None):
+        out = tmp_path / ("out_" + mode + str(len(os.listdir(tmp_path))))
+        argv = [mode, *map(str, argv), "-d", str(out)]
+        r = cli(*argv)
+        assert r.returncode == 0, (mode, r.returncode, r.stderr)
+        log = (out / "run.log").read_text()
+        V, T = settled(*lists)
+        print(mode, "max shift", V, "threshold", T)
+        assert f"Program started in mode \"{mode}\".\n" in log
+        assert "Command-line arguments: \n " + " ".join(argv) + "\n" in log
+        if shift_line is None:
+            assert f"Max shift not set. Setting automatically to: {V}{suffix}\n" in log
+        else:
+            assert "Max shift not set" not in log and shift_line + "\n" in log
+        assert f"{word} threshold not set. Setting automatically to: {T}{suffix}\n" in log
+        assert ("Gap penalty not set. Setting automatically to: 0\n" in log) == gap_line
+        assert "Program successfully ended.\n" in log
+        return out
+
+    g = run("greedy", "Greedy clustering", (old, old, old), "-i", old_fa, gap_line=False)
+    run("clinkage", "Clinkage clustering", (old, old, old), "-i", old_fa, gap_line=False)
+    cfile = g / "initial_clusters_sequences.tsv"
+    lines = cfile.read_text().splitlines()
+    in_file = [l.split("\t")[1] for l in lines[1:]]
+    assert sorted(in_file) == sorted(old)
+    both = new + in_file
+    run("assign", "Assignment", (both, in_file, in_file), "-i", new_fa, "--clusters", cfile)
+    run("assign", "Assignment", (both, in_file, in_file), "-i", new_fa, "--clusters", cfile, "-x", 11,
+        shift_line="Setting max shift to 7 as the length of the shortest sequence is only 8")
+    run("continue", "Greedy clustering", (both, in_file, in_file), "-i", new_fa, "--clusters", cfile,
+        suffix=" (it should be the original run's)")
+    run("search", "Search", (new + old, new + old, new), "-i", new_fa, "--database", old_fa)
+    run("match", "Match", (in_file, in_file, in_file), "-i", cfile, "--clusters", cfile)
+    # merge of the file's halves: the first half of its clusters as --clusters, the rest as -i
+    ids = list(dict.fromkeys(l.split("\t")[0] for l in lines[1:]))
+    first_ids = set(ids[:len(ids) // 2])
+    halves = [tmp_path / "half0.tsv", tmp_path / "half1.tsv"]
+    halves[0].write_text("\n".join([lines[0]] + [l for l in lines[1:] if l.split("\t")[0] in first_ids]) + "\n")
+    halves[1].write_text("\n".join([lines[0]] + [l for l in lines[1:] if l.split("\t")[0] not in first_ids]) + "\n")
+    first = [l.split("\t")[1] for l in lines[1:] if l.split("\t")[0] in first_ids]
+    assert 0 < len(first) < len(in_file)
+    run("merge", "Merge", (in_file, first, first), "-i", halves[1], "--clusters", halves[0])
