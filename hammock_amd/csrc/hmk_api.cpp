@@ -1,5 +1,6 @@
-// hmk_api.cpp -- the C ABI of libhammock_hip.so (include/hammock_hip.h): the extern "C" entry points.  Context, planner, passes,
-// the clustering tail and the multi-device call live in hmk_common / hmk_plan / hmk_pass / hmk_cluster / hmk_multi.cpp (hmk_ctx.h).
+// hmk_api.cpp -- the C ABI of libhammock_hip.so (include/hammock_hip.h): the extern "C" entry points -- argument checks, locking and
+// dispatch.  Context, planner, passes, the clustering calls on one device and on several live in hmk_common / hmk_plan / hmk_pass /
+// hmk_cluster / hmk_multi.cpp (hmk_ctx.h).
 // Host code only; the kernels live in k_*.hip (launchers declared in hmk_kernels.h).
 #include "hmk_ctx.h"
 
@@ -60,8 +61,8 @@ int hmk_create(const int32_t *matrix, int device, hmk_ctx **out) {
             return fail(nullptr, HMK_ERR_DEVICE, "libhammock_hip is built for gfx950 (MI355X) only; device is " + arch);
         }
         e = hipSetDevice(device);
-        if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_M, sizeof(ctx->M));
-        if (e == hipSuccess) e = hipMemcpy(ctx->d_M, ctx->M, sizeof(ctx->M), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMalloc(&ctx->d_M.p, sizeof(ctx->M));
+        if (e == hipSuccess) e = hipMemcpy(ctx->d_M.p, ctx->M, ctx->d_M.cap = sizeof(ctx->M), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             delete ctx;
             return fail(nullptr, HMK_ERR_DEVICE, std::string("hmk_create: ") + hipGetErrorString(e));
@@ -90,8 +91,6 @@ int hmk_create(const int32_t *matrix, int device, hmk_ctx **out) {
     return HMK_OK;
 }
 
-// a call whose failure changes nothing here, and never leaves its error behind as the thread's "last error" for the next launch
-// wrapper's hipGetLastError() to pick up
 void hmk_destroy(hmk_ctx *ctx) {
     if (!ctx) return;
     for (hmk_ctx *peer : ctx->peers) hmk_destroy(peer);
@@ -100,32 +99,21 @@ void hmk_destroy(hmk_ctx *ctx) {
         HMK_QUIET(hipSetDevice(ctx->device));
         (void)join_late_buffers(ctx);
         free_plans(ctx);
-        if (ctx->d_res32) HMK_QUIET(hipFree(ctx->d_res32));
-        if (ctx->d_len) HMK_QUIET(hipFree(ctx->d_len));
-        if (ctx->d_M) HMK_QUIET(hipFree(ctx->d_M));
-        if (ctx->d_edges) HMK_QUIET(hipFree(ctx->d_edges));
-        if (ctx->d_counts) HMK_QUIET(hipFree(ctx->d_counts));
-        if (ctx->d_rows_scratch) HMK_QUIET(hipFree(ctx->d_rows_scratch));
-        if (ctx->copy_stream) HMK_QUIET(hipStreamDestroy(ctx->copy_stream));
-        for (int k = 0; k < hmk_ctx::N_SIDE; k++) {
-            if (ctx->side[k]) HMK_QUIET(hipStreamDestroy(ctx->side[k]));
-            if (ctx->ev_join[k]) HMK_QUIET(hipEventDestroy(ctx->ev_join[k]));
-        }
-        if (ctx->ev_fork) HMK_QUIET(hipEventDestroy(ctx->ev_fork));
-        if (ctx->xfer_stream) HMK_QUIET(hipStreamDestroy(ctx->xfer_stream));   // (this device's transfers to the others, hmk_multi.cpp)
-        if (ctx->h_start) HMK_QUIET(hipHostFree(ctx->h_start));
-        if (ctx->h_stage) HMK_QUIET(hipHostFree(ctx->h_stage));
-        if (ctx->h_merge) HMK_QUIET(hipHostFree(ctx->h_merge));
-        if (ctx->h_adj) HMK_QUIET(hipHostFree(ctx->h_adj));
-        if (ctx->h_counts) HMK_QUIET(hipHostFree(ctx->h_counts));
-        if (ctx->h_loop) HMK_QUIET(hipHostFree(ctx->h_loop));
-        for (int b = 0; b < SB_N; b++)
-            if (ctx->sb[b].p) HMK_QUIET(hipFree(ctx->sb[b].p));
-        if (ctx->gstream) HMK_QUIET(hipStreamDestroy(ctx->gstream));
-        for (hipEvent_t ev : {ctx->ev_t0, ctx->ev_band, ctx->ev_edges, ctx->ev_csr, ctx->ev_bandcsr})
+        // the owners, then what they were used on (a failed free or destroy does not stay behind as the thread's last error: HMK_QUIET)
+        for (DevBuf *b : {&ctx->d_res32, &ctx->d_len, &ctx->d_M, &ctx->d_rows_scratch}) b->release();
+        for (DevBuf &b : ctx->sb) b.release();
+        ctx->edges.release();
+        for (PinnedBuf *b : {&ctx->h_start, &ctx->h_stage, &ctx->h_merge, &ctx->h_adj}) b->release();
+        for (void *h : {(void *)ctx->h_counts, (void *)ctx->h_loop})
+            if (h) HMK_QUIET(hipHostFree(h));
+        std::vector<hipStream_t> streams(ctx->side, ctx->side + hmk_ctx::N_SIDE);
+        streams.insert(streams.end(), {ctx->copy_stream, ctx->xfer_stream, ctx->gstream});
+        for (hipStream_t q : streams)
+            if (q) HMK_QUIET(hipStreamDestroy(q));
+        std::vector<hipEvent_t> events(ctx->ev_join, ctx->ev_join + hmk_ctx::N_SIDE);
+        events.insert(events.end(), {ctx->ev_fork, ctx->ev_t0, ctx->ev_band, ctx->ev_edges, ctx->ev_csr, ctx->ev_bandcsr, ctx->ev0, ctx->ev1});
+        for (hipEvent_t ev : events)
             if (ev) HMK_QUIET(hipEventDestroy(ev));
-        if (ctx->ev0) HMK_QUIET(hipEventDestroy(ctx->ev0));
-        if (ctx->ev1) HMK_QUIET(hipEventDestroy(ctx->ev1));
     }
     delete ctx;
 }
@@ -171,10 +159,8 @@ int hmk_set_sequences(hmk_ctx *ctx, const uint8_t *residues, const uint32_t *off
         int st = need_device(ctx);
         if (st) return st;
         free_plans(ctx);
-        if (ctx->d_res32) (void)hipFree(ctx->d_res32);
-        if (ctx->d_len) (void)hipFree(ctx->d_len);
-        ctx->d_res32 = nullptr;
-        ctx->d_len = nullptr;
+        ctx->d_res32.release();
+        ctx->d_len.release();
         // (the padded copy the pair / block scorers read is made at their first use: ensure_res32)
     }
     ctx->n = n;
@@ -260,18 +246,14 @@ int hmk_pack_rows_dev(hmk_ctx *ctx, const void *d_edges, uint64_t capacity, cons
         return fail(ctx, HMK_ERR_BAD_ARG, "hmk_pack_rows_dev: null buffer or capacity < HMK_EDGE_SHARDS");
     if (!ctx->n) return fail(ctx, HMK_ERR_NO_SEQUENCES, "hmk_pack_rows_dev: no sequences set");
     if (adj_capacity > 0xFFFFFFFFull) return fail(ctx, HMK_ERR_BAD_ARG, "hmk_pack_rows_dev: row offsets are 32 bit");
-    if (ctx->d_rows_scratch_n < ctx->n) {
-        if (ctx->d_rows_scratch) {
-            HIPCHK(ctx, hipDeviceSynchronize());  // an earlier call may still be using the old scratch
-            (void)hipFree(ctx->d_rows_scratch);
-            ctx->d_rows_scratch = nullptr;
-            ctx->d_rows_scratch_n = 0;
-        }
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_rows_scratch, pack_rows_scratch_bytes(ctx->n)));
-        ctx->d_rows_scratch_n = ctx->n;
+    if (ctx->d_rows_scratch.cap < pack_rows_scratch_bytes(ctx->n)) {
+        if (ctx->d_rows_scratch.p) HIPCHK(ctx, hipDeviceSynchronize());  // an earlier call may still be using the old scratch
+        ctx->d_rows_scratch.release();
+        HIPCHK(ctx, hipMalloc(&ctx->d_rows_scratch.p, pack_rows_scratch_bytes(ctx->n)));
+        ctx->d_rows_scratch.cap = pack_rows_scratch_bytes(ctx->n);
     }
     HIPCHK(ctx, launch_pack_rows((const uint64_t *)d_edges, capacity / HMK_EDGE_SHARDS, (const unsigned long long *)d_counts,
-                                 ctx->n, threshold, ctx->d_rows_scratch, (uint32_t *)d_row_start, (uint32_t *)d_adj,
+                                 ctx->n, threshold, ctx->d_rows_scratch.as<uint32_t>(), (uint32_t *)d_row_start, (uint32_t *)d_adj,
                                  adj_capacity, (hipStream_t)stream));
     return HMK_OK;
 }
@@ -310,8 +292,7 @@ int hmk_neighbors_shifted(hmk_ctx *ctx, int max_shift, int shift_penalty, int th
     double ms = 0;
     int st = neighbors_internal(ctx, max_shift, shift_penalty, threshold, part, n_parts, capacity, counts, &ms);
     if (st) return st;
-    uint64_t total = 0;
-    for (int s = 0; s < HMK_EDGE_SHARDS; s++) total += counts[s];
+    const uint64_t total = total_of(counts);
     *n_edges = total;
     if (stats) {
         *stats = ctx->plan.stats;
@@ -320,14 +301,7 @@ int hmk_neighbors_shifted(hmk_ctx *ctx, int max_shift, int shift_penalty, int th
     }
     if (total > capacity) return fail(ctx, HMK_ERR_CAPACITY, "edge buffer too small: " + std::to_string(total) + " needed");
     if (total && !edges) return fail(ctx, HMK_ERR_BAD_ARG, "null edge buffer");
-    const uint64_t seg = ctx->d_edges_cap / HMK_EDGE_SHARDS;
-    uint64_t o = 0;
-    for (int s = 0; s < HMK_EDGE_SHARDS; s++) {
-        if (counts[s])
-            HIPCHK(ctx, hipMemcpy(edges + o, ctx->d_edges + (uint64_t)s * seg, counts[s] * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        o += counts[s];
-    }
-    return HMK_OK;
+    return ctx->edges.fetch(ctx, counts, edges);
 }
 
 int hmk_neighbors_local(hmk_ctx *ctx, int gap_open, int gap_extend, int threshold, uint32_t part, uint32_t n_parts,
@@ -342,8 +316,7 @@ int hmk_neighbors_local(hmk_ctx *ctx, int gap_open, int gap_extend, int threshol
         return neighbors_local_dev_locked(ctx, gap_open, gap_extend, threshold, part, n_parts, d_edges, cap, d_counts, nullptr);
     });
     if (st) return st;
-    uint64_t total = 0;
-    for (int s = 0; s < HMK_EDGE_SHARDS; s++) total += counts[s];
+    const uint64_t total = total_of(counts);
     *n_edges = total;
     if (stats) {
         *stats = hmk_neighbor_stats{};
@@ -354,14 +327,7 @@ int hmk_neighbors_local(hmk_ctx *ctx, int gap_open, int gap_extend, int threshol
     }
     if (total > capacity) return fail(ctx, HMK_ERR_CAPACITY, "edge buffer too small: " + std::to_string(total) + " needed");
     if (total && !edges) return fail(ctx, HMK_ERR_BAD_ARG, "null edge buffer");
-    const uint64_t seg = ctx->d_edges_cap / HMK_EDGE_SHARDS;
-    uint64_t o = 0;
-    for (int s = 0; s < HMK_EDGE_SHARDS; s++) {
-        if (counts[s])
-            HIPCHK(ctx, hipMemcpy(edges + o, ctx->d_edges + (uint64_t)s * seg, counts[s] * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        o += counts[s];
-    }
-    return HMK_OK;
+    return ctx->edges.fetch(ctx, counts, edges);
 }
 
 int hmk_greedy_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t n_edges, int symmetric, int threshold,
@@ -378,13 +344,6 @@ int hmk_greedy_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t n_edges,
     if (st) return fail(ctx, st, err);
     return HMK_OK;
 }
-
-// =============================================================================
-// greedy clustering on a device-resident neighbour graph
-// =============================================================================
-}  // extern "C"
-
-extern "C" {
 
 int hmk_greedy_cluster(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, int max_clusters,
                        int32_t *cluster_id, int32_t *result_order, int32_t *member_rank, hmk_greedy_stats *stats) {
@@ -406,103 +365,8 @@ int hmk_greedy_cluster(hmk_ctx *ctx, int max_shift, int shift_penalty, int thres
     if (st) return st;
     if (!ctx->peers.empty())
         return greedy_cluster_multi(ctx, max_shift, shift_penalty, threshold, max_clusters, cluster_id, result_order, member_rank, stats);
-    const auto t0 = std::chrono::steady_clock::now();
-    const bool call_timing = ctx->sw.greedy_timing;
-    auto call_lap = [&](const char *what) {
-        if (call_timing) fprintf(stderr, "[hmk greedy] %s at %.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    };
-    const uint32_t n = ctx->n;
-    hipStream_t S = ctx->gstream;
-    // Band: phase 1 of the merge (LimitedGreedySequenceClusterer.java:77-120) reads the adjacency rows in order and
-    // stops once maxClusters clusters exist, normally a little after row maxClusters.  The tiles that complete the first
-    // band_rows rows are launched first, their rows are handed to the host while the rest of the pair space is being scored.
-    int64_t band_rows = 0;
-    if (max_clusters > 0 && n >= 16384 && !ctx->sw.no_band)
-        band_rows = std::min<int64_t>(n, 2LL * max_clusters + 1024);
-    if (band_rows * 2 > (int64_t)n) band_rows = 0;   // no point: the band would be most of the pass
-    const int64_t band_req = band_rows;
-    st = build_plan(ctx, max_shift, shift_penalty, threshold, 0, 1, band_req);
-    if (st) return st;
-    band_rows = ctx->plan.band_rows;   // 0 if the plan could not order its tiles by band
-    ctx->phases.plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    // adjacency entries are 4 bytes (m << 8 | score - threshold) when no score can exceed threshold + 255
-    const long long top = (long long)ctx->max_len * std::max(0, ctx->max_m) +
-                          (long long)std::max(0, shift_penalty) * ((ctx->max_len - ctx->min_len) + 2LL * max_shift);
-    EdgeSource src;
-    src.symmetric = ctx->symmetric;
-    src.format_known = true;
-    src.packed = top - threshold <= 255 && !ctx->sw.adj_8byte;
-    src.base = threshold;
-    src.check_overflow = true;
-    if (!ctx->d_counts) HIPCHK(ctx, hipMalloc((void **)&ctx->d_counts, HMK_EDGE_SHARDS * sizeof(unsigned long long)));
-    HIPCHK(ctx, ensure_buf(ctx, SB_BCOUNTS, HMK_EDGE_SHARDS * sizeof(unsigned long long)));
-    uint64_t cap = first_edge_capacity(ctx, n);
-    for (int attempt = 0; attempt < 4; attempt++) {
-        st = grow_edge_buffer(ctx, cap);
-        if (st) return st;
-        // Everything cluster_on_device will want, BEFORE the pass is enqueued: a hipMalloc issued while the pass runs returns
-        // when the pass is over (seen at 10^6: the band hand-over of a context's first call was enqueued 340 ms late, i.e.
-        // after the scoring it is meant to overlap).  Grow-only buffers: steady-state calls find them all in place.
-        st = reserve_tail_buffers(ctx, n, src.packed, (uint32_t)std::max<int64_t>(band_rows, 0));
-        if (st) return st;
-        call_lap("edge buffer ready");
-        const uint64_t seg = ctx->d_edges_cap / HMK_EDGE_SHARDS;
-        src.seg_cap = seg;
-        src.segs = shard_segments(ctx->d_edges, seg, ctx->d_counts);
-        src.adj_bound = (ctx->symmetric ? 2 : 1) * ctx->d_edges_cap;
-        src.band_rows = (uint32_t)band_rows;
-        // (Two launches, one after the other: the band launch's END is what lets the hand-over's kernels in -- a kernel of another
-        // stream gets no workgroup slot while a launch still has workgroups waiting.  Band and rest side by side on two streams, one
-        // launch with a counter the band tiles bump, CUs kept free by a mask: all measured, all slower)
-        src.band_segs = shard_segments(ctx->d_edges, seg, buf<unsigned long long>(ctx, SB_BCOUNTS));
-        // the neighbour kernel counts the rows' degrees while it writes the edges (the CSR build's first pass): symmetric scores: the
-        // smaller end counts into up[], the larger into lo[] -- the same number of atomics as one total per row, and the lower counts
-        // give the bucket sizes of the CSR's dealing pass without a pass over the edges (k_lower_count, 2 ms at 10^6)
-        const bool split = ctx->symmetric;
-        HIPCHK(ctx, ensure_buf(ctx, SB_DEG, (size_t)n * (split ? 8 : 4)));
-        uint32_t *d_deg = buf<uint32_t>(ctx, SB_DEG), *d_deg_lo = split ? d_deg + n : nullptr;
-        HIPCHK(ctx, hipMemsetAsync(d_deg, 0, (size_t)n * (split ? 8 : 4), S));
-        src.deg_fused = true;
-        src.deg_split = split;
-        HIPCHK(ctx, hipEventRecord(ctx->ev_t0, S));
-        if (band_rows > 0) {
-            st = neighbors_dev_locked(ctx, max_shift, shift_penalty, threshold, 0, 1, ctx->d_edges, ctx->d_edges_cap, ctx->d_counts, S,
-                                      LAUNCH_BAND, band_req, d_deg, d_deg_lo);
-            if (st) return st;
-            HIPCHK(ctx, hipMemcpyAsync(buf<void>(ctx, SB_BCOUNTS), ctx->d_counts, HMK_EDGE_SHARDS * sizeof(unsigned long long),
-                                       hipMemcpyDeviceToDevice, S));
-            HIPCHK(ctx, hipEventRecord(ctx->ev_band, S));
-            call_lap("band tiles enqueued");
-        }
-        st = neighbors_dev_locked(ctx, max_shift, shift_penalty, threshold, 0, 1, ctx->d_edges, ctx->d_edges_cap, ctx->d_counts, S,
-                                  band_rows > 0 ? LAUNCH_REST : LAUNCH_ALL, band_req, d_deg, d_deg_lo);
-        call_lap("all tiles enqueued");
-        if (st) { (void)hipStreamSynchronize(S); return st; }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_counts, ctx->d_counts, HMK_EDGE_SHARDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, S));
-        HIPCHK(ctx, hipEventRecord(ctx->ev_edges, S));
-        st = cluster_on_device(ctx, src, max_clusters, cluster_id, result_order, member_rank, stats, t0);
-        if (st != ST_RETRY_OVERFLOW) break;
-        unsigned long long mx = 0;
-        for (int q = 0; q < HMK_EDGE_SHARDS; q++) mx = std::max(mx, ctx->h_counts[q]);
-        cap = (uint64_t)HMK_EDGE_SHARDS * (mx + mx / 8 + 1024);  // a segment overflowed: grow and rescore
-    }
-    if (st == ST_RETRY_OVERFLOW) return fail(ctx, HMK_ERR_DEVICE, "internal edge buffer kept overflowing");
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_edges) == hipSuccess) ctx->phases.score_ms = ms;
-    if (hipEventElapsedTime(&ms, ctx->ev_edges, ctx->ev_csr) == hipSuccess) ctx->phases.csr_ms = ms;
-    (void)hipGetLastError();   // (a call that left early never recorded these events: "invalid resource handle" must not stay behind as the thread's last error)
-    ctx->phases.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    stats->neighbors_ms = ctx->phases.score_ms;
-    if (call_timing)
-        fprintf(stderr, "[hmk greedy] call %.2f ms: streams/events/pinned block %.2f, plan %.2f, %d buffer (re)allocations %.2f ms\n",
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count(),
-                std::chrono::duration<double, std::milli>(t0 - t_entry).count(), ctx->phases.plan_ms, g_allocs, g_alloc_ms);
-    return st;
+    return greedy_cluster_single(ctx, max_shift, shift_penalty, threshold, max_clusters, cluster_id, result_order, member_rank, stats, t_entry);
 }
-
-}  // extern "C"
-
-extern "C" {
 
 int hmk_create_multi(const int32_t *matrix, const int *devices, int n_devices, hmk_ctx **out) {
     if (!matrix || !devices || !out || n_devices < 1) return fail(nullptr, HMK_ERR_BAD_ARG, "hmk_create_multi: null argument or no device");
@@ -548,22 +412,12 @@ int hmk_reserve(hmk_ctx *ctx, uint32_t n_sequences) {
     if (st == HMK_OK) st = greedy_streams(ctx);
     if (st) return st;
     const auto t_streams = std::chrono::steady_clock::now();
-    if (!ctx->d_counts) HIPCHK(ctx, hipMalloc((void **)&ctx->d_counts, HMK_EDGE_SHARDS * sizeof(unsigned long long)));
     HIPCHK(ctx, ensure_buf(ctx, SB_BCOUNTS, HMK_EDGE_SHARDS * sizeof(unsigned long long)));
-    {
-        // (a multi-device root scores 1 / devices of the pair space: greedy_cluster_multi takes the larger of its own guess and
-        // what is there, and sizes the root's adjacency from it -- the single-device guess made those twice as large as needed)
-        const uint64_t G = 1 + ctx->peers.size();
-        uint64_t cap = first_edge_capacity(ctx, n_sequences);
-        if (G > 1 && ctx->sw.edge_guess == 0)
-            cap = std::max<uint64_t>({(uint64_t)((double)cap / G * 1.25), (uint64_t)1 << 20, ctx->d_edges_cap});
-        st = grow_edge_buffer(ctx, (cap + HMK_EDGE_SHARDS - 1) / HMK_EDGE_SHARDS * HMK_EDGE_SHARDS);
-    }
+    // (the guess of the call this prepares for: a multi-device root scores 1 / devices of the pair space and sizes its adjacency from that)
+    st = ctx->edges.reserve(ctx, sizing::edge_capacity_guess(ctx->symmetric, n_sequences, 1 + (uint32_t)ctx->peers.size(), ctx->sw.edge_guess, ctx->edges.cap));
     if (st) return st;
     const int64_t maxc = (int64_t)(n_sequences * 0.025 + 0.5);      // Hammock.java:398-401, the default cluster limit
-    int64_t band = n_sequences >= 16384 ? std::min<int64_t>(n_sequences, 2 * maxc + 1024) : 0;
-    if (band * 2 > (int64_t)n_sequences) band = 0;
-    st = reserve_tail_buffers(ctx, n_sequences, true, (uint32_t)band, true, true);
+    st = reserve_tail_buffers(ctx, n_sequences, true, (uint32_t)sizing::band_request(n_sequences, maxc), true, true);
     if (ctx->sw.greedy_timing) {
         auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         std::fprintf(stderr, "[hmk] hmk_reserve(%u): waited for the context %.1f ms, device + streams %.1f ms, buffers %.1f ms\n", n_sequences,
@@ -642,37 +496,7 @@ int hmk_clinkage_cluster(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
     if (st) return st;
     if (!ctx->peers.empty())
         return greedy_cluster_multi(ctx, max_shift, shift_penalty, threshold, 0, cluster_id, result_order, member_rank, nullptr, stats);
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint32_t n = ctx->n;
-    unsigned long long counts[HMK_EDGE_SHARDS];
-    double ms = 0;
-    // clinkage inputs are small (the reference switches to greedy above 10,000 sequences) but dense: MUSI has 16 % of
-    // its pairs above the default threshold for some rows; neighbors_internal grows the buffer until the pass fits
-    const uint64_t guess = (uint64_t)((double)n * (n - 1) / 2 * 0.02) + (1u << 20);
-    st = neighbors_internal(ctx, max_shift, shift_penalty, threshold, 0, 1, std::min<uint64_t>(guess, 1ull << 31), counts, &ms);
-    if (st) return st;
-    uint64_t total = 0;
-    for (int q = 0; q < HMK_EDGE_SHARDS; q++) total += counts[q];
-    hipStream_t S = ctx->gstream;
-    const long long top = (long long)ctx->max_len * std::max(0, ctx->max_m) +
-                          (long long)std::max(0, shift_penalty) * ((ctx->max_len - ctx->min_len) + 2LL * max_shift);
-    EdgeSource src;
-    src.symmetric = true;
-    src.segs = shard_segments(ctx->d_edges, ctx->d_edges_cap / HMK_EDGE_SHARDS, ctx->d_counts);
-    src.format_known = true;
-    src.packed = top - threshold <= 255 && !ctx->sw.adj_8byte;
-    src.base = threshold;
-    src.total_known = total;
-    src.adj_bound = 2 * total;
-    src.clink = stats;
-    HIPCHK(ctx, hipEventRecord(ctx->ev_t0, S));
-    HIPCHK(ctx, hipEventRecord(ctx->ev_edges, S));
-    st = cluster_on_device(ctx, src, 0, cluster_id, result_order, member_rank, nullptr, t0);
-    if (st == ST_RETRY_OVERFLOW) return fail(ctx, HMK_ERR_DEVICE, "internal edge buffer overflow");
-    stats->neighbors_ms = ms;
-    ctx->phases.score_ms = ms;
-    ctx->phases.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return st;
+    return clinkage_cluster_single(ctx, max_shift, shift_penalty, threshold, cluster_id, result_order, member_rank, stats);
 }
 
 int hmk_clinkage_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t n_edges, int32_t *cluster_id, int32_t *result_order,

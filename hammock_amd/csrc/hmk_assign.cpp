@@ -66,7 +66,7 @@ int check_assign(hmk_ctx *ctx, const char *what, uint32_t q0, uint32_t q1, uint3
     return HMK_OK;
 }
 
-// the pass of the rectangle members [r0, r1) x new [q0, q1) into ctx->d_edges, the members as the search's queries, which every
+// the pass of the rectangle members [r0, r1) x new [q0, q1) into ctx->edges, the members as the search's queries, which every
 // tier emits as m = seq1 (hmk_plan.cpp), in the plan slots `pl` / `pll`; -> the shards' counts, their total, the stats
 // (kernel_ms = the pass)
 int cluster_pass(hmk_ctx *ctx, bool local, Plan &pl, PlanLocal &pll, int a, int b, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1,
@@ -79,8 +79,7 @@ int cluster_pass(hmk_ctx *ctx, bool local, Plan &pl, PlanLocal &pll, int a, int 
                       : launch_plan_local(ctx, pll, a, b, thr, d_edges, cap, d_counts, nullptr);
     });
     if (st) return st;
-    *total = 0;
-    for (int s = 0; s < HMK_EDGE_SHARDS; s++) *total += counts[s];
+    *total = total_of(counts);
     if (!local) {
         *S = pl.stats;
     } else {
@@ -93,10 +92,6 @@ int cluster_pass(hmk_ctx *ctx, bool local, Plan &pl, PlanLocal &pll, int a, int 
 }
 
 namespace {
-
-uint64_t max_count(const unsigned long long counts[HMK_EDGE_SHARDS]) {
-    return *std::max_element(counts, counts + HMK_EDGE_SHARDS);
-}
 
 int assign(hmk_ctx *ctx, int scorer, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, const uint32_t *member_cluster, const int32_t *cluster_id,
            uint32_t n_clusters, int a, int b, int thr, uint32_t k, uint32_t *best_cluster, int32_t *best_score, uint32_t *n_feasible,
@@ -152,7 +147,7 @@ int assign(hmk_ctx *ctx, int scorer, uint32_t q0, uint32_t q1, uint32_t r0, uint
     hipError_t e = hipEventCreate(&e1);
     if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
     if (e == hipSuccess)
-        e = launch_assign(ctx->d_edges, ctx->d_edges_cap / HMK_EDGE_SHARDS, ctx->d_counts, max_count(counts), total, q0, nq, r0, nm, k, d_cl,
+        e = launch_assign(ctx->edges.d, ctx->edges.seg_cap(), ctx->edges.counts, max_of(counts), total, q0, nq, r0, nm, k, d_cl,
                           d_cl + nm, d_cl + nm + n_clusters, buf<uint32_t>(ctx, SB_SEARCH_CNT), buf<uint32_t>(ctx, SB_SEARCH_START),
                           buf<uint64_t>(ctx, SB_SEARCH_SCAN), buf<uint64_t>(ctx, SB_SEARCH_OUT), std::max<uint64_t>(total, 1), d_best, d_score,
                           d_nfeas, nullptr);

@@ -1,5 +1,6 @@
 // hmk_cluster.cpp -- cluster_on_device: edges -> CSR on the device, band hand-over, rows to the host merge on demand, pre-check and
-// the device-side second loop (LimitedGreedySequenceClusterer.java:39-120 / ClinkageSequenceClusterer.java:43-124 on the graph).
+// the device-side second loop (LimitedGreedySequenceClusterer.java:39-120 / ClinkageSequenceClusterer.java:43-124 on the graph); and
+// its two single-device callers, greedy_cluster_single / clinkage_cluster_single (their multi-device sibling: hmk_multi.cpp).
 #include "hmk_ctx.h"
 
 namespace hmk { namespace impl {
@@ -75,13 +76,13 @@ int piece_precheck(hmk_ctx *c, const PreIn &in, uint32_t r0, uint32_t r1, uint32
     if (r == hipSuccess) r = ensure_buf(c, SB_OVER, 64);
     if (r == hipSuccess) r = ensure_buf(c, SB_CAND, (size_t)in.region_cap * HMK_PRE_REGIONS * sizeof(GreedyCand));
     if (r == hipSuccess) r = ensure_buf(c, SB_PRECNT, HMK_PRE_REGIONS * sizeof(unsigned long long));
-    if (r == hipSuccess) r = ensure_pinned(&c->h_stage, &c->h_stage_cap, HMK_PRE_REGIONS * sizeof(unsigned long long) + 64, 0);
+    if (r == hipSuccess) r = c->h_stage.ensure(HMK_PRE_REGIONS * sizeof(unsigned long long) + 64, 0);
     if (r == hipSuccess && in.two_stage) r = ensure_buf(c, SB_RETRY, std::max<size_t>(nl, 1) * 4);
     if (r != hipSuccess) return -1;
     uint32_t *d_over = buf<uint32_t>(c, SB_OVER);                      // [0] table overflows, [1] rows of the second stage
     unsigned long long *d_regions = buf<unsigned long long>(c, SB_PRECNT);
     uint32_t *h_misc = (uint32_t *)(c->h_counts + HC_MISC);
-    unsigned long long *h_regions = (unsigned long long *)c->h_stage;   // (the block's first HMK_PRE_REGIONS words; the root's PreIn block lies behind them)
+    unsigned long long *h_regions = (unsigned long long *)c->h_stage.p;   // (the block's first HMK_PRE_REGIONS words; the root's PreIn block lies behind them)
     r = hipStreamWaitEvent(q, c->ev_bandcsr, 0);
     if (r == hipSuccess) r = hipMemsetAsync(d_over, 0, 16, q);
     if (r == hipSuccess) r = hipMemsetAsync(d_regions, 0, HMK_PRE_REGIONS * sizeof(unsigned long long), q);
@@ -130,8 +131,8 @@ bool device_second_loop(hmk_ctx *ctx, hipStream_t S, const LoopIn &in, std::vect
     // which cluster a leftover joins: the kernels STORE it into the host's pinned block (a handful of writes per round; nothing on the
     // device reads it) -- no copy and no second synchronise when the loop is over
     int32_t *d_jslot = nullptr;
-    if (r == hipSuccess) r = ensure_pinned(&ctx->h_stage, &ctx->h_stage_cap, (size_t)std::max<size_t>(nl, 1) * 4 + 64, 0);
-    if (r == hipSuccess) r = hipHostGetDevicePointer((void **)&d_jslot, ctx->h_stage, 0);
+    if (r == hipSuccess) r = ctx->h_stage.ensure((size_t)std::max<size_t>(nl, 1) * 4 + 64, 0);
+    if (r == hipSuccess) r = hipHostGetDevicePointer((void **)&d_jslot, ctx->h_stage.p, 0);
     if (r == hipSuccess) r = ensure_buf(ctx, SB_LCOUNT, 64);
     if (r == hipSuccess && ctx->has_sizes) r = ensure_buf(ctx, SB_SEQSZ, (size_t)n * 4);
     if (r != hipSuccess) return false;
@@ -258,7 +259,7 @@ bool device_second_loop(hmk_ctx *ctx, hipStream_t S, const LoopIn &in, std::vect
     }
     if (r != hipSuccess || !done) return false;
     join_slot.resize(nl);
-    if (nl) std::memcpy(join_slot.data(), ctx->h_stage, (size_t)nl * 4);   // (the stream is drained: every store has landed)
+    if (nl) std::memcpy(join_slot.data(), ctx->h_stage.p, (size_t)nl * 4);   // (the stream is drained: every store has landed)
     *rounds_out = rounds;
     return true;
 }
@@ -296,9 +297,9 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
     HIPCHK(ctx, ensure_buf(ctx, SB_RANGE, 64));
     const bool late_buffers = late_buffers_pending(ctx);   // hmk_reserve's thread is still getting SB_ADJ / SB_PART: the CSR is enqueued later
     if (src.format_known && !late_buffers) HIPCHK(ctx, ensure_buf(ctx, SB_ADJ, std::max<uint64_t>(src.adj_bound, 1) * esz));
-    HIPCHK(ctx, ensure_pinned(&ctx->h_start, &ctx->h_start_cap, ((size_t)n + 1) * 8 + (size_t)n * 4 + 64, 0));
-    uint64_t *h_start = (uint64_t *)ctx->h_start;
-    uint32_t *h_up = (uint32_t *)((char *)ctx->h_start + ((size_t)n + 1) * 8);
+    HIPCHK(ctx, ctx->h_start.ensure(((size_t)n + 1) * 8 + (size_t)n * 4 + 64, 0));
+    uint64_t *h_start = (uint64_t *)ctx->h_start.p;
+    uint32_t *h_up = (uint32_t *)((char *)ctx->h_start.p + ((size_t)n + 1) * 8);
     int *h_range = (int *)(ctx->h_counts + HC_RANGE);
 
     // (multi-device calls enqueue it later, from wait_full(): the peers' edges are not there yet)
@@ -499,8 +500,8 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
                          o_trstart = o_trowner + (size_t)TRN * 4, o_ntop = o_trstart + ((size_t)TRN + 1) * 4, o_fmore = o_ntop + (size_t)R1 * BandPack::NEAR_T * 4,
                          o_near = (o_fmore + R1 + 63) / 64 * 64,
                          o_tr = o_near + (cap * 4 + 63) / 64 * 64;
-            if (e == hipSuccess) e = ensure_pinned(&ctx->h_adj, &ctx->h_adj_cap, o_tr + cap * 4 + 64, 0);
-            char *hb = (char *)ctx->h_adj, *db = nullptr;
+            if (e == hipSuccess) e = ctx->h_adj.ensure(o_tr + cap * 4 + 64, 0);
+            char *hb = (char *)ctx->h_adj.p, *db = nullptr;
             if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&db, hb, 0);
             uint32_t *d_fdeg = buf<uint32_t>(ctx, SB_FDEG), *d_fcur = d_fdeg + n, *d_totals = d_fdeg + 3 * (size_t)n;
             if (e == hipSuccess)
@@ -545,10 +546,10 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
             if (e == hipSuccess) e = hipStreamSynchronize(C);
             if (e == hipSuccess && se[1] > 0) {
                 const size_t len = se[1], from = se[0];
-                e = ensure_pinned(&ctx->h_stage, &ctx->h_stage_cap, len * 4 + 64, 0);
-                if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_stage, buf<uint32_t>(ctx, SB_FADJ) + from, len * 4, hipMemcpyDeviceToHost, C);
+                e = ctx->h_stage.ensure(len * 4 + 64, 0);
+                if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_stage.p, buf<uint32_t>(ctx, SB_FADJ) + from, len * 4, hipMemcpyDeviceToHost, C);
                 if (e == hipSuccess) e = hipStreamSynchronize(C);
-                if (e == hipSuccess) out.assign((const uint32_t *)ctx->h_stage, (const uint32_t *)ctx->h_stage + len);
+                if (e == hipSuccess) out.assign((const uint32_t *)ctx->h_stage.p, (const uint32_t *)ctx->h_stage.p + len);
             }
             if (e != hipSuccess) { hook_fail(HMK_ERR_DEVICE, std::string("band hand-over (a far sequence's list): ") + hipGetErrorString(e)); return false; }
             return true;
@@ -560,13 +561,13 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
             if (e == hipSuccess) e = hipStreamSynchronize(C);
             const uint32_t up = e == hipSuccess ? *h_one : 0u;
             if (up) {
-                e = ensure_pinned(&ctx->h_stage, &ctx->h_stage_cap, (size_t)up * 4 + 64, 0);
-                if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_stage, buf<uint32_t>(ctx, SB_BADJ) + h_start[x], (size_t)up * 4, hipMemcpyDeviceToHost, C);
+                e = ctx->h_stage.ensure((size_t)up * 4 + 64, 0);
+                if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_stage.p, buf<uint32_t>(ctx, SB_BADJ) + h_start[x], (size_t)up * 4, hipMemcpyDeviceToHost, C);
                 if (e == hipSuccess) e = hipStreamSynchronize(C);
             }
             if (e != hipSuccess) { hook_fail(HMK_ERR_DEVICE, std::string("band hand-over (a row's far part): ") + hipGetErrorString(e)); return false; }
             for (uint32_t q = 0; q < up; q++)
-                if ((((const uint32_t *)ctx->h_stage)[q] >> 8) >= R1) out.push_back(((const uint32_t *)ctx->h_stage)[q]);
+                if ((((const uint32_t *)ctx->h_stage.p)[q] >> 8) >= R1) out.push_back(((const uint32_t *)ctx->h_stage.p)[q]);
             return true;
         };
     }
@@ -580,9 +581,9 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
             const int64_t entries = band_csr();
             if (entries < 0 && status_inside != HMK_OK) return 0;
             if (entries >= 0) {
-                e = ensure_pinned(&ctx->h_adj, &ctx->h_adj_cap, std::max<uint64_t>((uint64_t)entries, 1) * esz, 0);
+                e = ctx->h_adj.ensure(std::max<uint64_t>((uint64_t)entries, 1) * esz, 0);
                 if (e == hipSuccess && entries)
-                    e = hipMemcpyAsync(ctx->h_adj, buf<void>(ctx, SB_BADJ), (uint64_t)entries * esz, hipMemcpyDeviceToHost, C);
+                    e = hipMemcpyAsync(ctx->h_adj.p, buf<void>(ctx, SB_BADJ), (uint64_t)entries * esz, hipMemcpyDeviceToHost, C);
                 // the band rows' upper-section sizes travel with them: upper[] must never hold a previous call's values for rows
                 // the merge may read
                 if (e == hipSuccess && symmetric)
@@ -617,9 +618,9 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
             const uint64_t l0 = h_start[a], l1 = h_start[b];                       // (the piece's own offsets)
             const uint64_t a0 = piece_base[d] + l0, a1 = piece_base[d] + l1;
             if (a == rows_lo && rows_here == rows_lo) adj_off = a0;
-            e = ensure_pinned(&ctx->h_adj, &ctx->h_adj_cap, std::max<uint64_t>(a1 - adj_off, 1) * esz, (a0 - adj_off) * esz);
+            e = ctx->h_adj.ensure(std::max<uint64_t>(a1 - adj_off, 1) * esz, (a0 - adj_off) * esz);
             if (e == hipSuccess && a1 > a0)
-                e = hipMemcpyAsync((char *)ctx->h_adj + (a0 - adj_off) * esz, (const char *)buf<void>(pc, SB_ADJ) + l0 * esz, (a1 - a0) * esz,
+                e = hipMemcpyAsync((char *)ctx->h_adj.p + (a0 - adj_off) * esz, (const char *)buf<void>(pc, SB_ADJ) + l0 * esz, (a1 - a0) * esz,
                                    hipMemcpyDeviceToHost, pc->copy_stream);
             if (e == hipSuccess) e = hipStreamSynchronize(pc->copy_stream);
             if (piece_base[d]) for (uint32_t x = a; x <= b; x++) h_start[x] += piece_base[d];
@@ -654,9 +655,9 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
             // Phase 1's result into a pinned block (an "async" upload from pageable memory is staged by the runtime chunk by chunk and
             // the stream waits for it: 0.3 ms for these 0.8 MB at 10^5); it goes up NOW, on the copy stream, while the pass and the CSR
             // build are still running (phase 1 ends before the scoring does at every size)
-            r = ensure_pinned(&ctx->h_stage, &ctx->h_stage_cap, HMK_PRE_REGIONS * sizeof(unsigned long long) + in.b_cof + in.b_us + in.b_left + 64, 0);
+            r = ctx->h_stage.ensure(HMK_PRE_REGIONS * sizeof(unsigned long long) + in.b_cof + in.b_us + in.b_left + 64, 0);
             if (r != hipSuccess) return false;
-            char *hs = (char *)ctx->h_stage + HMK_PRE_REGIONS * sizeof(unsigned long long);   // (the block starts with the single pass's region counters)
+            char *hs = (char *)ctx->h_stage.p + HMK_PRE_REGIONS * sizeof(unsigned long long);   // (the block starts with the single pass's region counters)
             std::memcpy(hs, cluster_of, in.b_cof);
             std::memcpy(hs + in.b_cof, usize.data(), in.b_us);
             std::memcpy(hs + in.b_cof + in.b_us, leftover.data(), in.b_left);
@@ -666,7 +667,7 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
                 uploaded_early = true;
             }
         }
-        in.h_block = (char *)ctx->h_stage + HMK_PRE_REGIONS * sizeof(unsigned long long);
+        in.h_block = (char *)ctx->h_stage.p + HMK_PRE_REGIONS * sizeof(unsigned long long);
         if (!wait_full()) return false;
         const auto tp = std::chrono::steady_clock::now();
         // The candidate buffer is sized from what previous calls needed (or 24 entries per leftover), HMK_PRE_REGIONS regions; a call that
@@ -783,7 +784,7 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
         return true;
     };
 
-    hooks.adj_base = [&]() -> const void * { return (const char *)ctx->h_adj - adj_off * esz; };
+    hooks.adj_base = [&]() -> const void * { return (const char *)ctx->h_adj.p - adj_off * esz; };
     GreedyTimes times{};
     hooks.times = &times;
     std::string err;
@@ -794,9 +795,9 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
         if (!src.format_known && !wait_full()) cst = -1;
         if (cst == HMK_OK && n && hooks.need_rows(n - 1, 0) < n) cst = -1;
         if (cst == HMK_OK)
-            cst = packed ? clinkage_from_csr_packed(ctx->java_hashset, n, szs, h_start, (const NbrPacked *)ctx->h_adj, cluster_id, result_order, member_rank,
+            cst = packed ? clinkage_from_csr_packed(ctx->java_hashset, n, szs, h_start, (const NbrPacked *)ctx->h_adj.p, cluster_id, result_order, member_rank,
                                                     src.clink, &err)
-                         : clinkage_from_csr(ctx->java_hashset, n, szs, h_start, (const Nbr *)ctx->h_adj, cluster_id, result_order, member_rank, src.clink,
+                         : clinkage_from_csr(ctx->java_hashset, n, szs, h_start, (const Nbr *)ctx->h_adj.p, cluster_id, result_order, member_rank, src.clink,
                                              &err);
         (void)hipStreamSynchronize(S);
         (void)hipStreamSynchronize(C);
@@ -817,9 +818,9 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
         }
     }
     const GreedyOptions gopt = greedy_options(ctx);
-    st = packed ? greedy_from_csr_packed(n, szs, h_start, (const NbrPacked *)ctx->h_adj, symmetric ? h_up : nullptr, &hooks, symmetric,
+    st = packed ? greedy_from_csr_packed(n, szs, h_start, (const NbrPacked *)ctx->h_adj.p, symmetric ? h_up : nullptr, &hooks, symmetric,
                                          max_clusters, cluster_id, result_order, member_rank, stats, &err, gopt)
-                : greedy_from_csr(n, szs, h_start, (const Nbr *)ctx->h_adj, symmetric ? h_up : nullptr, &hooks, symmetric, max_clusters,
+                : greedy_from_csr(n, szs, h_start, (const Nbr *)ctx->h_adj.p, symmetric ? h_up : nullptr, &hooks, symmetric, max_clusters,
                                   cluster_id, result_order, member_rank, stats, &err, gopt);
     // nothing of this call may still be running when the buffers are reused (a crash-parity exit leaves the pass in flight)
     if (!ctx->wedged) {
@@ -841,6 +842,125 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
     stats->n_edges = src.total_known ? src.total_known : (symmetric ? h_start[n] / 2 : h_start[n]);
     if (st) return fail(ctx, st, err);
     return HMK_OK;
+}
+
+// hmk_greedy_cluster on one device: plan, edge buffer and the tail's buffers, the pass (band tiles first), cluster_on_device; scored
+// again with a larger buffer when a segment overflowed.
+int greedy_cluster_single(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, int max_clusters, int32_t *cluster_id,
+                          int32_t *result_order, int32_t *member_rank, hmk_greedy_stats *stats, std::chrono::steady_clock::time_point t_entry) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool call_timing = ctx->sw.greedy_timing;
+    auto call_lap = [&](const char *what) {
+        if (call_timing) fprintf(stderr, "[hmk greedy] %s at %.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    };
+    const uint32_t n = ctx->n;
+    hipStream_t S = ctx->gstream;
+    // Band (sizing::band_request): the tiles that complete the first band_rows rows are launched first, their rows are handed to the
+    // host while the rest of the pair space is being scored.
+    const int64_t band_req = ctx->sw.no_band ? 0 : sizing::band_request(n, max_clusters);
+    int st = build_plan(ctx, max_shift, shift_penalty, threshold, 0, 1, band_req);
+    if (st) return st;
+    const int64_t band_rows = ctx->plan.band_rows;   // 0 if the plan could not order its tiles by band
+    ctx->phases.plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    EdgeSource src;
+    src.symmetric = ctx->symmetric;
+    src.format_known = true;
+    src.packed = adjacency_packed(ctx, max_shift, shift_penalty, threshold);
+    src.base = threshold;
+    src.check_overflow = true;
+    HIPCHK(ctx, ensure_buf(ctx, SB_BCOUNTS, HMK_EDGE_SHARDS * sizeof(unsigned long long)));
+    uint64_t cap = sizing::edge_capacity_guess(ctx->symmetric, n, 1, ctx->sw.edge_guess, ctx->edges.cap);
+    for (int attempt = 0; attempt < 4; attempt++) {
+        st = ctx->edges.reserve(ctx, cap);
+        if (st) return st;
+        // Everything cluster_on_device will want, BEFORE the pass is enqueued: a hipMalloc issued while the pass runs returns
+        // when the pass is over (seen at 10^6: the band hand-over of a context's first call was enqueued 340 ms late, i.e.
+        // after the scoring it is meant to overlap).  Grow-only buffers: steady-state calls find them all in place.
+        st = reserve_tail_buffers(ctx, n, src.packed, (uint32_t)std::max<int64_t>(band_rows, 0));
+        if (st) return st;
+        call_lap("edge buffer ready");
+        src.seg_cap = ctx->edges.seg_cap();
+        src.segs = ctx->edges.segs();
+        src.adj_bound = (ctx->symmetric ? 2 : 1) * ctx->edges.cap;
+        src.band_rows = (uint32_t)band_rows;
+        // (Two launches, one after the other: the band launch's END is what lets the hand-over's kernels in -- a kernel of another
+        // stream gets no workgroup slot while a launch still has workgroups waiting.  Band and rest side by side on two streams, one
+        // launch with a counter the band tiles bump, CUs kept free by a mask: all measured, all slower)
+        src.band_segs = shard_segments(ctx->edges.d, src.seg_cap, buf<unsigned long long>(ctx, SB_BCOUNTS));
+        // the neighbour kernel counts the rows' degrees while it writes the edges (the CSR build's first pass): symmetric scores: the
+        // smaller end counts into up[], the larger into lo[] -- the same number of atomics as one total per row, and the lower counts
+        // give the bucket sizes of the CSR's dealing pass without a pass over the edges (k_lower_count, 2 ms at 10^6)
+        const bool split = ctx->symmetric;
+        HIPCHK(ctx, ensure_buf(ctx, SB_DEG, (size_t)n * (split ? 8 : 4)));
+        uint32_t *d_deg = buf<uint32_t>(ctx, SB_DEG), *d_deg_lo = split ? d_deg + n : nullptr;
+        HIPCHK(ctx, hipMemsetAsync(d_deg, 0, (size_t)n * (split ? 8 : 4), S));
+        src.deg_fused = true;
+        src.deg_split = split;
+        HIPCHK(ctx, hipEventRecord(ctx->ev_t0, S));
+        if (band_rows > 0) {
+            st = neighbors_dev_locked(ctx, max_shift, shift_penalty, threshold, 0, 1, ctx->edges.d, ctx->edges.cap, ctx->edges.counts, S,
+                                      LAUNCH_BAND, band_req, d_deg, d_deg_lo);
+            if (st) return st;
+            HIPCHK(ctx, hipMemcpyAsync(buf<void>(ctx, SB_BCOUNTS), ctx->edges.counts, HMK_EDGE_SHARDS * sizeof(unsigned long long),
+                                       hipMemcpyDeviceToDevice, S));
+            HIPCHK(ctx, hipEventRecord(ctx->ev_band, S));
+            call_lap("band tiles enqueued");
+        }
+        st = neighbors_dev_locked(ctx, max_shift, shift_penalty, threshold, 0, 1, ctx->edges.d, ctx->edges.cap, ctx->edges.counts, S,
+                                  band_rows > 0 ? LAUNCH_REST : LAUNCH_ALL, band_req, d_deg, d_deg_lo);
+        call_lap("all tiles enqueued");
+        if (st) { (void)hipStreamSynchronize(S); return st; }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_counts, ctx->edges.counts, HMK_EDGE_SHARDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, S));
+        HIPCHK(ctx, hipEventRecord(ctx->ev_edges, S));
+        st = cluster_on_device(ctx, src, max_clusters, cluster_id, result_order, member_rank, stats, t0);
+        if (st != ST_RETRY_OVERFLOW) break;
+        cap = sizing::edge_capacity_after_overflow(max_of(ctx->h_counts));  // a segment overflowed: grow and rescore
+    }
+    if (st == ST_RETRY_OVERFLOW) return fail(ctx, HMK_ERR_DEVICE, "internal edge buffer kept overflowing");
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_edges) == hipSuccess) ctx->phases.score_ms = ms;
+    if (hipEventElapsedTime(&ms, ctx->ev_edges, ctx->ev_csr) == hipSuccess) ctx->phases.csr_ms = ms;
+    (void)hipGetLastError();   // (a call that left early never recorded these events: "invalid resource handle" must not stay behind as the thread's last error)
+    ctx->phases.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stats->neighbors_ms = ctx->phases.score_ms;
+    if (call_timing)
+        fprintf(stderr, "[hmk greedy] call %.2f ms: streams/events/pinned block %.2f, plan %.2f, %d buffer (re)allocations %.2f ms\n",
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count(),
+                std::chrono::duration<double, std::milli>(t0 - t_entry).count(), ctx->phases.plan_ms, g_allocs, g_alloc_ms);
+    return st;
+}
+
+// hmk_clinkage_cluster on one device: the whole graph through the internal edge buffer, then the nearest-neighbour chain on its CSR.
+int clinkage_cluster_single(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, int32_t *cluster_id, int32_t *result_order,
+                            int32_t *member_rank, hmk_clinkage_stats *stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t n = ctx->n;
+    unsigned long long counts[HMK_EDGE_SHARDS];
+    double ms = 0;
+    // clinkage inputs are small (the reference switches to greedy above 10,000 sequences) but dense: MUSI has 16 % of
+    // its pairs above the default threshold for some rows; neighbors_internal grows the buffer until the pass fits
+    const uint64_t guess = (uint64_t)((double)n * (n - 1) / 2 * 0.02) + (1u << 20);
+    int st = neighbors_internal(ctx, max_shift, shift_penalty, threshold, 0, 1, std::min<uint64_t>(guess, 1ull << 31), counts, &ms);
+    if (st) return st;
+    const uint64_t total = total_of(counts);
+    hipStream_t S = ctx->gstream;
+    EdgeSource src;
+    src.symmetric = true;
+    src.segs = ctx->edges.segs();
+    src.format_known = true;
+    src.packed = adjacency_packed(ctx, max_shift, shift_penalty, threshold);
+    src.base = threshold;
+    src.total_known = total;
+    src.adj_bound = 2 * total;
+    src.clink = stats;
+    HIPCHK(ctx, hipEventRecord(ctx->ev_t0, S));
+    HIPCHK(ctx, hipEventRecord(ctx->ev_edges, S));
+    st = cluster_on_device(ctx, src, 0, cluster_id, result_order, member_rank, nullptr, t0);
+    if (st == ST_RETRY_OVERFLOW) return fail(ctx, HMK_ERR_DEVICE, "internal edge buffer overflow");
+    stats->neighbors_ms = ms;
+    ctx->phases.score_ms = ms;
+    ctx->phases.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return st;
 }
 
 } }  // namespace hmk::impl

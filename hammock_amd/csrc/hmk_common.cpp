@@ -1,5 +1,6 @@
 // hmk_common.cpp -- what every part of the host side uses: error text, the device check, the 32-byte residue copy of the probes,
-// the context's grow-only device and pinned buffers, the clustering calls' streams and events, buffer sizing.
+// the context's grow-only device and pinned buffers and the edge buffer (the owners of hmk_ctx.h), the clustering calls' streams and
+// events, the tail's buffer list.
 #include "hmk_ctx.h"
 
 namespace hmk { namespace impl {
@@ -71,14 +72,14 @@ int need_device(hmk_ctx *ctx) {
 // uploaded at their first use -- the neighbour passes and the clustering calls never read it (they use the plan's sorted
 // copy), and at 10^6 sequences it is 32 MB to build and send in every hmk_set_sequences.
 int ensure_res32(hmk_ctx *ctx) {
-    if (ctx->d_res32 || ctx->n == 0) return HMK_OK;
+    if (ctx->d_res32.p || ctx->n == 0) return HMK_OK;
     const uint32_t n = ctx->n;
     std::vector<uint8_t> res32((size_t)n * 32, 0);
     for (uint32_t k = 0; k < n; k++) std::memcpy(&res32[(size_t)k * 32], ctx->res.data() + ctx->off[k], ctx->len[k]);
-    HIPCHK(ctx, hipMalloc((void **)&ctx->d_res32, res32.size()));
-    HIPCHK(ctx, hipMemcpy(ctx->d_res32, res32.data(), res32.size(), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMalloc((void **)&ctx->d_len, n));
-    HIPCHK(ctx, hipMemcpy(ctx->d_len, ctx->len.data(), n, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMalloc(&ctx->d_res32.p, res32.size()));
+    HIPCHK(ctx, hipMemcpy(ctx->d_res32.p, res32.data(), ctx->d_res32.cap = res32.size(), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMalloc(&ctx->d_len.p, n));
+    HIPCHK(ctx, hipMemcpy(ctx->d_len.p, ctx->len.data(), ctx->d_len.cap = n, hipMemcpyHostToDevice));
     return HMK_OK;
 }
 thread_local double g_alloc_ms = 0.0;
@@ -110,21 +111,46 @@ hipError_t ensure_buf(hmk_ctx *ctx, int which, size_t bytes) {
     return ensure_buf_now(ctx, which, bytes);
 }
 
-// pinned host buffer, grow-only; the first `keep` bytes survive a reallocation
-hipError_t ensure_pinned(void **p, size_t *cap, size_t bytes, size_t keep) {
-    if (*cap >= bytes) return hipSuccess;
+hipError_t PinnedBuf::ensure(size_t bytes, size_t keep) {
+    if (cap >= bytes) return hipSuccess;
     AllocTimer at("hipHostMalloc", bytes + bytes / 4 + (1 << 20));
     void *q = nullptr;
     const size_t want = bytes + bytes / 4 + (1 << 20);
     const hipError_t e = hipHostMalloc(&q, want, hipHostMallocDefault);
     if (e != hipSuccess) return e;
-    if (*p) {
-        if (keep) std::memcpy(q, *p, keep);
-        (void)hipHostFree(*p);
+    if (p) {
+        if (keep) std::memcpy(q, p, keep);
+        (void)hipHostFree(p);
     }
-    *p = q;
-    *cap = want;
+    p = q;
+    cap = want;
     return hipSuccess;
+}
+
+// The edge buffer: the one place that frees and allocates it (HMK_GREEDY_TIMING counts it), and that makes the counts.
+int EdgeBuffer::reserve(hmk_ctx *ctx, uint64_t want) {
+    if (!counts) HIPCHK(ctx, hipMalloc((void **)&counts, HMK_EDGE_SHARDS * sizeof(unsigned long long)));
+    if (cap >= want) return HMK_OK;
+    if (d) (void)hipFree(d);
+    d = nullptr;
+    cap = 0;
+    { AllocTimer at("hipMalloc (edges)", want * sizeof(uint64_t)); HIPCHK(ctx, hipMalloc((void **)&d, want * sizeof(uint64_t))); }
+    cap = want;
+    return HMK_OK;
+}
+int EdgeBuffer::fetch(hmk_ctx *ctx, const unsigned long long n[HMK_EDGE_SHARDS], uint64_t *host_out) const {
+    for (int s = 0; s < HMK_EDGE_SHARDS; s++) {
+        if (n[s]) HIPCHK(ctx, hipMemcpy(host_out, d + (uint64_t)s * seg_cap(), n[s] * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        host_out += n[s];
+    }
+    return HMK_OK;
+}
+// (teardown, and hmk_set_sequences dropping the probes' copies)
+void DevBuf::release() { if (p) HMK_QUIET(hipFree(p)); *this = DevBuf(); }
+void PinnedBuf::release() { if (p) HMK_QUIET(hipHostFree(p)); *this = PinnedBuf(); }
+void EdgeBuffer::release() {
+    for (void *q : {(void *)d, (void *)counts}) if (q) HMK_QUIET(hipFree(q));
+    *this = EdgeBuffer();
 }
 
 int greedy_streams(hmk_ctx *ctx) {
@@ -142,13 +168,13 @@ int greedy_streams(hmk_ctx *ctx) {
     // The first device-to-host copy of more than a few KB on a stream sets up its DMA path: 8-9 ms, measured in the middle of
     // a first clustering call (the band's row starts).  One 64 KB copy through each stream now.
     HIPCHK(ctx, ensure_buf(ctx, SB_DEG, 1 << 20));
-    HIPCHK(ctx, ensure_pinned(&ctx->h_start, &ctx->h_start_cap, 2 * 65536, 0));
+    HIPCHK(ctx, ctx->h_start.ensure(2 * 65536, 0));
     {   // ... and the first blocking upload from pageable memory its staging buffers (hmk_set_sequences: 8 of its 10 ms)
         std::vector<char> pageable(1 << 20, 0);
         HIPCHK(ctx, hipMemcpy(buf<void>(ctx, SB_DEG), pageable.data(), pageable.size(), hipMemcpyHostToDevice));
     }
     for (hipStream_t q : {ctx->gstream, ctx->copy_stream})
-        HIPCHK(ctx, hipMemcpyAsync((char *)ctx->h_start + (q == ctx->gstream ? 0 : 65536), buf<void>(ctx, SB_DEG), 65536, hipMemcpyDeviceToHost, q));
+        HIPCHK(ctx, hipMemcpyAsync((char *)ctx->h_start.p + (q == ctx->gstream ? 0 : 65536), buf<void>(ctx, SB_DEG), 65536, hipMemcpyDeviceToHost, q));
     HIPCHK(ctx, hipStreamSynchronize(ctx->gstream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
     return HMK_OK;
@@ -157,20 +183,31 @@ int greedy_streams(hmk_ctx *ctx) {
 // writes.  Packed symmetric adjacency, at every size (10^5: CSR 0.44 -> 0.31 ms, 10^6: 58 -> 23 ms); asymmetric matrices and
 // 8-byte entries scatter with atomics (k_edge_scatter).
 bool csr_by_bucket(bool symmetric, bool packed) { return symmetric && packed; }
+hipError_t ensure_piece_buffers(hmk_ctx *c, uint32_t n, bool packed, bool symmetric, uint64_t adj_records, uint64_t bucket_records) {
+    const bool bucket = csr_by_bucket(symmetric, packed);
+    const std::pair<int, size_t> want[] = {
+        {SB_ADJ, (symmetric ? 2 : 1) * adj_records * (packed ? sizeof(NbrPacked) : sizeof(Nbr))},
+        {SB_CURSOR, (size_t)n * 8}, {SB_START, ((size_t)n + 1) * 8}, {SB_SCAN, scan_scratch_bytes(n)}, {SB_RANGE, 64},
+        {SB_PART, bucket ? bucket_records * 8 : 0}, {SB_PARTSCR, bucket ? csr_partition_scratch_bytes() : 0},
+        {SB_COF, (size_t)n * 4}, {SB_BITMAP, ((size_t)n + 31) / 32 * 4}, {SB_LEFT, (size_t)n * 4}, {SB_CNT, (size_t)n * 4},
+        {SB_CSTART, ((size_t)n + 1) * 4}, {SB_CAND, (size_t)n * 24 * sizeof(GreedyCand)}};
+    for (const auto &w : want) {
+        const hipError_t e = w.second ? ensure_buf(c, w.first, w.second) : hipSuccess;
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 // The grow-only device and pinned buffers the tail of a clustering call on n sequences asks for (the edge buffer must have
-// its size already): hmk_greedy_cluster before it enqueues the pass, hmk_reserve from a host that knows n early.
+// its size already): greedy_cluster_single before it enqueues the pass, hmk_reserve from a host that knows n early.
 int reserve_tail_buffers(hmk_ctx *ctx, uint32_t n, bool packed, uint32_t r1, bool full, bool late_on_a_thread) {
+    const uint64_t cap = ctx->edges.cap;
     const size_t esz0 = packed ? sizeof(NbrPacked) : sizeof(Nbr);
-    const size_t adj_bytes = std::max<uint64_t>((ctx->symmetric ? 2 : 1) * ctx->d_edges_cap, 1) * esz0;
-    const size_t part_bytes = csr_by_bucket(ctx->symmetric, packed) ? (ctx->d_edges_cap + 1) * 8 : 0;
+    const size_t adj_bytes = (ctx->symmetric ? 2 : 1) * cap * esz0;
+    const size_t part_bytes = csr_by_bucket(ctx->symmetric, packed) ? (cap + 1) * 8 : 0;
     const bool late = late_on_a_thread || late_buffers_pending(ctx);   // (pending: the call's CSR step joins the thread and checks the sizes)
-    if (!late) HIPCHK(ctx, ensure_buf(ctx, SB_ADJ, adj_bytes));
+    HIPCHK(ctx, ensure_piece_buffers(ctx, n, packed, ctx->symmetric, late ? 0 : cap, late ? 0 : cap + 1));
     HIPCHK(ctx, ensure_buf(ctx, SB_DEG, (size_t)n * 8));   // (upper and lower counts of the fused pass)
-    HIPCHK(ctx, ensure_buf(ctx, SB_CURSOR, (size_t)n * 8));
-    HIPCHK(ctx, ensure_buf(ctx, SB_START, ((size_t)n + 1) * 8));
-    HIPCHK(ctx, ensure_buf(ctx, SB_SCAN, scan_scratch_bytes(n)));
-    HIPCHK(ctx, ensure_buf(ctx, SB_RANGE, 64));
-    HIPCHK(ctx, ensure_pinned(&ctx->h_start, &ctx->h_start_cap, ((size_t)n + 1) * 8 + (size_t)n * 4 + 64, 0));
+    HIPCHK(ctx, ctx->h_start.ensure(((size_t)n + 1) * 8 + (size_t)n * 4 + 64, 0));
     if (r1) {
         HIPCHK(ctx, ensure_buf(ctx, SB_BDEG, (size_t)r1 * 4));
         HIPCHK(ctx, ensure_buf(ctx, SB_BCURSOR, (size_t)r1 * 8));
@@ -178,19 +215,9 @@ int reserve_tail_buffers(hmk_ctx *ctx, uint32_t n, bool packed, uint32_t r1, boo
         HIPCHK(ctx, ensure_buf(ctx, SB_BSCAN, scan_scratch_bytes(r1)));
         HIPCHK(ctx, ensure_buf(ctx, SB_BRANGE, 64));
     }
-    if (part_bytes) {
-        if (!late) HIPCHK(ctx, ensure_buf(ctx, SB_PART, part_bytes));
-        HIPCHK(ctx, ensure_buf(ctx, SB_PARTSCR, csr_partition_scratch_bytes()));
-    }
-    HIPCHK(ctx, ensure_buf(ctx, SB_COF, (size_t)n * 4));
-    HIPCHK(ctx, ensure_buf(ctx, SB_BITMAP, ((size_t)n + 31) / 32 * 4));
-    HIPCHK(ctx, ensure_buf(ctx, SB_LEFT, (size_t)n * 4));
-    HIPCHK(ctx, ensure_buf(ctx, SB_CNT, (size_t)n * 4));
-    HIPCHK(ctx, ensure_buf(ctx, SB_CSTART, ((size_t)n + 1) * 4));
-    HIPCHK(ctx, ensure_buf(ctx, SB_CAND, (size_t)n * 24 * sizeof(GreedyCand)));
     if (full) {
         // (hmk_reserve only: these are sized from data a call learns late -- estimates here, grown by the call if they fall short)
-        const uint64_t avg_deg = n ? (ctx->symmetric ? 2 : 1) * ctx->d_edges_cap / n + 1 : 1;
+        const uint64_t avg_deg = n ? (ctx->symmetric ? 2 : 1) * cap / n + 1 : 1;
         if (r1) {   // the band's adjacency: device + pinned host copy (0.8 GB at 10^6: the pinned allocation alone took 0.1 s of a first call)
             const uint64_t entries = (uint64_t)r1 * avg_deg;
             HIPCHK(ctx, ensure_buf(ctx, SB_BADJ, std::max<uint64_t>(entries, 1) * esz0));
@@ -198,7 +225,7 @@ int reserve_tail_buffers(hmk_ctx *ctx, uint32_t n, bool packed, uint32_t r1, boo
             HIPCHK(ctx, ensure_buf(ctx, SB_FADJ, std::max<uint64_t>(entries, 1) * 4));
             HIPCHK(ctx, ensure_buf(ctx, SB_FDEG, (size_t)n * 12 + 64));
             HIPCHK(ctx, ensure_buf(ctx, SB_FSTART, (size_t)n * 4));
-            HIPCHK(ctx, ensure_pinned(&ctx->h_adj, &ctx->h_adj_cap, std::max<uint64_t>(entries, 1) * 2 * esz0 + (size_t)r1 * 64 + 4096, 0));
+            HIPCHK(ctx, ctx->h_adj.ensure(std::max<uint64_t>(entries, 1) * 2 * esz0 + (size_t)r1 * 64 + 4096, 0));
         }
         const size_t ncl = (size_t)(n * 0.025 + 2), nl = n, cands = (size_t)n * 16;   // second loop on the device
         HIPCHK(ctx, ensure_buf(ctx, SB_USIZE, ncl * 4));
@@ -220,7 +247,7 @@ int reserve_tail_buffers(hmk_ctx *ctx, uint32_t n, bool packed, uint32_t r1, boo
         HIPCHK(ctx, ensure_buf(ctx, SB_ACCEPTED, nl * 4));
         HIPCHK(ctx, ensure_buf(ctx, SB_LCOUNT, 64));
         HIPCHK(ctx, ensure_buf(ctx, SB_SEQSZ, (size_t)n * 4));
-        HIPCHK(ctx, ensure_pinned(&ctx->h_stage, &ctx->h_stage_cap, HMK_PRE_REGIONS * sizeof(unsigned long long) + (size_t)n * 12 + ncl * 4 + 64, 0));
+        HIPCHK(ctx, ctx->h_stage.ensure(HMK_PRE_REGIONS * sizeof(unsigned long long) + (size_t)n * 12 + ncl * 4 + 64, 0));
     }
     if (late_on_a_thread) (void)join_late_buffers(ctx);   // (an earlier hmk_reserve's thread may still be writing the two sizes read next)
     if (late_on_a_thread && (ctx->sb[SB_ADJ].cap < adj_bytes || ctx->sb[SB_PART].cap < part_bytes)) {
@@ -234,25 +261,6 @@ int reserve_tail_buffers(hmk_ctx *ctx, uint32_t n, bool packed, uint32_t r1, boo
             return e;
         });
     }
-    return HMK_OK;
-}
-
-uint64_t first_edge_capacity(const hmk_ctx *ctx, uint32_t n) {
-    // first guess of the edge buffer: 0.3 % of the pair space (uniform random 12-mers at the default threshold give
-    // 0.26 %); a segment that overflows makes the call size the buffer to the counts and score again
-    uint64_t guess = (uint64_t)((double)n * (n - 1) / 2 * (ctx->symmetric ? 0.003 : 0.006)) + (1u << 20);
-    if (ctx->sw.edge_guess) guess = ctx->sw.edge_guess;   // tests: force the overflow / retry path
-    uint64_t cap = std::max<uint64_t>({std::min<uint64_t>(guess, 1ull << 31), (uint64_t)1 << 20, ctx->d_edges_cap});
-    return (cap + HMK_EDGE_SHARDS - 1) / HMK_EDGE_SHARDS * HMK_EDGE_SHARDS;
-}
-
-int grow_edge_buffer(hmk_ctx *ctx, uint64_t cap) {
-    if (ctx->d_edges_cap >= cap) return HMK_OK;
-    if (ctx->d_edges) (void)hipFree(ctx->d_edges);
-    ctx->d_edges = nullptr;
-    ctx->d_edges_cap = 0;
-    { AllocTimer at("hipMalloc (edges)", cap * sizeof(uint64_t)); HIPCHK(ctx, hipMalloc((void **)&ctx->d_edges, cap * sizeof(uint64_t))); }
-    ctx->d_edges_cap = cap;
     return HMK_OK;
 }
 

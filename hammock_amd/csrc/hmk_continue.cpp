@@ -96,7 +96,7 @@ int greedy_continue(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_
         return r;
     });
     if (st) return st;
-    for (int s = 0; s < HMK_EDGE_SHARDS; s++) S.n_edges += counts[s];
+    S.n_edges += total_of(counts);
     S.pairs_scored = ctx->plan_continue.stats.pairs_scored + (tri ? ctx->plan_continue_tri.stats.pairs_scored : 0);
     S.kernel_ms = ms;
 
@@ -104,11 +104,8 @@ int greedy_continue(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_
     // ids whichever side of the members the new range lies on, so the caller's layout serves as it is.
     const auto tl = std::chrono::steady_clock::now();
     hipStream_t Q = ctx->gstream;
-    const long long top = (long long)ctx->max_len * std::max(0, ctx->max_m) +
-                          (long long)std::max(0, p) * ((ctx->max_len - ctx->min_len) + 2LL * X);
-    const bool packed = top - thr <= 255 && !ctx->sw.adj_8byte;   // (4-byte entries m << 8 | score - threshold, as hmk_greedy_cluster)
-    const EdgeSegs segs = shard_segments(ctx->d_edges, ctx->d_edges_cap / HMK_EDGE_SHARDS, ctx->d_counts);
-    hipError_t e = piece_enqueue_csr(ctx, segs, true, packed, thr, n, q0, q1, false, false, Q);
+    const bool packed = adjacency_packed(ctx, X, p, thr);   // (4-byte entries m << 8 | score - threshold, as hmk_greedy_cluster)
+    hipError_t e = piece_enqueue_csr(ctx, ctx->edges.segs(), true, packed, thr, n, q0, q1, false, false, Q);
     if (e == hipSuccess) e = hipStreamSynchronize(Q);
     if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("continuation CSR: ") + hipGetErrorString(e));
     if (((const int *)(ctx->h_counts + HC_RANGE))[2] != 0) return fail(ctx, HMK_ERR_DEVICE, "continuation CSR: an edge names a sequence outside [0, n)");
@@ -120,9 +117,9 @@ int greedy_continue(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_
     PreIn in;
     in.n = n; in.nl = nq; in.ncl = n_clusters; in.packed = packed;
     in.b_cof = (size_t)n * 4; in.b_us = (size_t)n_clusters * 4; in.b_left = (size_t)nq * 4;
-    HIPCHK(ctx, ensure_pinned(&ctx->h_stage, &ctx->h_stage_cap, HMK_PRE_REGIONS * sizeof(unsigned long long) + in.b_cof + in.b_us + in.b_left + 64, 0));
+    HIPCHK(ctx, ctx->h_stage.ensure(HMK_PRE_REGIONS * sizeof(unsigned long long) + in.b_cof + in.b_us + in.b_left + 64, 0));
     {
-        char *hs = (char *)ctx->h_stage + HMK_PRE_REGIONS * sizeof(unsigned long long);   // (the block starts with the region counters)
+        char *hs = (char *)ctx->h_stage.p + HMK_PRE_REGIONS * sizeof(unsigned long long);   // (the block starts with the region counters)
         std::memcpy(hs, cluster_of.data(), in.b_cof);
         int32_t *us = (int32_t *)(hs + in.b_cof);
         for (uint32_t c = 0; c < n_clusters; c++) us[c] = (int32_t)members[c];
@@ -144,7 +141,7 @@ int greedy_continue(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_
     int fit = piece_precheck(ctx, in, 0, n, 0, HMK_PRE_REGIONS, Q, true, &total);
     if (fit == 1) {   // a region overran: once more with room for the fullest one (the region counters are the block's first words)
         unsigned long long fullest = 0;
-        for (uint32_t g = 0; g < HMK_PRE_REGIONS; g++) fullest = std::max(fullest, ((const unsigned long long *)ctx->h_stage)[g]);
+        for (uint32_t g = 0; g < HMK_PRE_REGIONS; g++) fullest = std::max(fullest, ((const unsigned long long *)ctx->h_stage.p)[g]);
         if (fullest <= REGION_MAX) {
             in.region_cap = fullest;
             fit = piece_precheck(ctx, in, 0, n, 0, HMK_PRE_REGIONS, Q, false, &total);

@@ -1,7 +1,8 @@
 // hmk_ctx.h -- the context behind the C ABI and what the translation units of libhammock_hip.so's host side share:
-// hmk_api.cpp (the extern "C" entry points), hmk_common.cpp (errors, device, grow-only buffers, streams), hmk_plan.cpp (the
-// neighbour passes' planner), hmk_pass.cpp (launching the passes; the pair and block probes), hmk_cluster.cpp (CSR pipeline, row
-// hand-over, second-loop driver), hmk_multi.cpp (one process, several devices).  Not part of the public ABI.
+// hmk_api.cpp (the extern "C" entry points: argument checks, locking, dispatch), hmk_common.cpp (errors, device, the grow-only
+// buffers and their owners, streams), hmk_sizing.h (the sizing rules, pure functions), hmk_plan.cpp (the neighbour passes' planner),
+// hmk_pass.cpp (launching the passes; the pair and block probes), hmk_cluster.cpp (the single-device clustering calls, CSR pipeline,
+// row hand-over, second-loop driver), hmk_multi.cpp (the same calls on several devices).  Not part of the public ABI.
 #ifndef HMK_CTX_H
 #define HMK_CTX_H
 #include <hip/hip_runtime_api.h>
@@ -17,6 +18,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <tuple>
 #include <thread>
@@ -24,6 +26,7 @@
 
 #include "hmk_internal.h"
 #include "hmk_kernels.h"
+#include "hmk_sizing.h"
 
 using namespace hmk;
 
@@ -38,8 +41,34 @@ struct Group {
     uint64_t work;  // cells its tiles add (pairs x cells per pair): what the launches of a forked pass are balanced by (hmk_pass.cpp)
 };
 
-// grow-only device scratch of the greedy tail (one hipMalloc per buffer and context, not per call)
-struct DevBuf { void *p = nullptr; size_t cap = 0; };
+// grow-only device storage (one hipMalloc per buffer and context, not per call): the greedy tail's scratch sb[] and a few named ones
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    template <class T> T *as() const { return (T *)p; }
+    void release();   // (hmk_common.cpp, as the other owners': a failed free does not stay behind as the thread's last error)
+};
+// pinned host block, grow-only
+struct PinnedBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t bytes, size_t keep);   // the first `keep` bytes survive a reallocation
+    void release();
+};
+// The internal edge buffer of a context: HMK_EDGE_SHARDS segments of seg_cap() entries and the segments' counts.  What the
+// host-buffer entry points, the clustering calls and the searches score into.
+struct EdgeBuffer {
+    uint64_t *d = nullptr;
+    uint64_t cap = 0;
+    unsigned long long *counts = nullptr;
+    int reserve(hmk_ctx *ctx, uint64_t want);   // grow-only (and the counts at first use); the error goes to ctx
+    uint64_t seg_cap() const { return cap / HMK_EDGE_SHARDS; }
+    EdgeSegs segs() const { return shard_segments(d, seg_cap(), counts); }
+    int fetch(hmk_ctx *ctx, const unsigned long long n[HMK_EDGE_SHARDS], uint64_t *host_out) const;   // the segments' entries, back to back
+    void release();
+};
+inline uint64_t total_of(const unsigned long long counts[HMK_EDGE_SHARDS]) { return std::accumulate(counts, counts + HMK_EDGE_SHARDS, (uint64_t)0); }
+inline uint64_t max_of(const unsigned long long counts[HMK_EDGE_SHARDS]) { return *std::max_element(counts, counts + HMK_EDGE_SHARDS); }
 enum {
     SB_DEG, SB_CURSOR, SB_START, SB_SCAN, SB_RANGE, SB_ADJ, SB_PART, SB_PARTSCR,   // full CSR (+ the bucketed lower sections)
     SB_BDEG, SB_BCURSOR, SB_BSTART, SB_BSCAN, SB_BRANGE, SB_BADJ, SB_BCOUNTS,     // band CSR (first rows only)
@@ -149,9 +178,8 @@ struct hmk_ctx {
     std::vector<uint8_t> len;
     int min_len = 0, max_len = 0;
 
-    uint8_t *d_res32 = nullptr;
-    uint8_t *d_len = nullptr;
-    int32_t *d_M = nullptr;
+    DevBuf d_res32, d_len;   // uint8: the probes' padded residues and lengths (ensure_res32)
+    DevBuf d_M;              // int32: the matrix
 
     Plan plan;
     PlanLocal plan_local;
@@ -164,16 +192,13 @@ struct hmk_ctx {
     Plan plan_continue;            // hmk_greedy_continue (hmk_continue.cpp): members x new (a rectangle) and new x new (a triangle)
     Plan plan_continue_tri;
     Plan plan_merge;               // hmk_clinkage_merge / hmk_cluster_pairs_shifted (hmk_merge.cpp): the triangle inside the members' range
-    uint64_t *d_edges = nullptr;  // internal buffer of the host-buffer entry points
-    uint64_t d_edges_cap = 0;
-    unsigned long long *d_counts = nullptr;
+    EdgeBuffer edges;
     // side streams of the neighbour pass: the per-class launches of a mixed-length plan overlap their tails
     static constexpr int N_SIDE = 3;     // streams a mixed-length pass's launches are dealt to (hmk_pass.cpp)
     hipStream_t side[N_SIDE] = {nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[N_SIDE] = {nullptr};
     hipStream_t copy_stream = nullptr;   // band CSR + device-to-host copies of adjacency rows (hmk_greedy_cluster)
-    uint32_t *d_rows_scratch = nullptr;  // deg[n], cursor[n], misfit of hmk_pack_rows_dev
-    uint32_t d_rows_scratch_n = 0;
+    DevBuf d_rows_scratch;               // uint32: deg[n], cursor[n], misfit of hmk_pack_rows_dev
 
     double last_kernel_ms = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -181,14 +206,10 @@ struct hmk_ctx {
     hipStream_t gstream = nullptr;
     hipEvent_t ev_t0 = nullptr, ev_band = nullptr, ev_edges = nullptr, ev_csr = nullptr, ev_bandcsr = nullptr;
     DevBuf sb[SB_N];
-    void *h_start = nullptr;  // pinned: uint64 start[n + 1], then uint32 up[n]
-    size_t h_start_cap = 0;
-    void *h_stage = nullptr;  // pinned: what the merge uploads after phase 1 (cluster_of, sizes, leftovers, ...)
-    size_t h_stage_cap = 0;
-    void *h_adj = nullptr;    // pinned: adjacency rows fetched so far
-    void *h_merge = nullptr;  // pinned: the cluster-level lists of hmk_merge.cpp (k_merge_compact stores them here)
-    size_t h_merge_cap = 0;
-    size_t h_adj_cap = 0;
+    PinnedBuf h_start;   // uint64 start[n + 1], then uint32 up[n]
+    PinnedBuf h_stage;   // what the merge uploads after phase 1 (cluster_of, sizes, leftovers, ...)
+    PinnedBuf h_adj;     // adjacency rows fetched so far
+    PinnedBuf h_merge;   // the cluster-level lists of hmk_merge.cpp (k_merge_compact stores them here)
     unsigned long long *h_loop = nullptr;    // pinned, coherent: progress word of the device-side second loop (written by k_loop_apply)
     unsigned long long *h_counts = nullptr;  // pinned: final segment counts [HMK_EDGE_SHARDS], band snapshot [HMK_EDGE_SHARDS], misc (HC_* below)
     hmk_greedy_phases phases{};
@@ -296,12 +317,16 @@ bool late_buffers_pending(hmk_ctx *ctx);
 hipError_t join_late_buffers(hmk_ctx *ctx);
 hipError_t ensure_buf(hmk_ctx *ctx, int which, size_t bytes);
 template <class T> T *buf(hmk_ctx *ctx, int which) { return (T *)ctx->sb[which].p; }
-hipError_t ensure_pinned(void **p, size_t *cap, size_t bytes, size_t keep);
 int greedy_streams(hmk_ctx *ctx);   // streams, events and pinned blocks of the clustering calls
 bool csr_by_bucket(bool symmetric, bool packed);
+// The CSR and pre-check buffers of one piece of the adjacency on c's device: a single device's whole graph, or a multi-device call's
+// piece.  Entries of the adjacency = (symmetric ? 2 : 1) * adj_records; 0 records: that buffer is sized elsewhere (hmk_reserve's thread).
+hipError_t ensure_piece_buffers(hmk_ctx *c, uint32_t n, bool packed, bool symmetric, uint64_t adj_records, uint64_t bucket_records);
 int reserve_tail_buffers(hmk_ctx *ctx, uint32_t n, bool packed, uint32_t r1, bool full = false, bool late_on_a_thread = false);
-uint64_t first_edge_capacity(const hmk_ctx *ctx, uint32_t n);
-int grow_edge_buffer(hmk_ctx *ctx, uint64_t cap);
+// whether this context's adjacency entries fit 4 bytes at these parameters (sizing::adjacency_packed)
+inline bool adjacency_packed(const hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold) {
+    return sizing::adjacency_packed(ctx->max_len, ctx->min_len, ctx->max_m, shift_penalty, max_shift, threshold, ctx->sw.adj_8byte);
+}
 // ---- hmk_plan.cpp
 void free_plan(Plan &pl);
 void free_plan_local(PlanLocal &pl);
@@ -333,7 +358,7 @@ struct ClusterOrder {
 // too); fills `order`.  hmk_match.cpp makes them too.
 int check_assign(hmk_ctx *ctx, const char *what, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, const uint32_t *member_cluster,
                  const int32_t *cluster_id, uint32_t n_clusters, uint32_t k, ClusterOrder *order);
-// the pass of the rectangle members [r0, r1) x new [q0, q1) into ctx->d_edges in the plan slot pl (shifted) / pll (local: `local`),
+// the pass of the rectangle members [r0, r1) x new [q0, q1) into ctx->edges in the plan slot pl (shifted) / pll (local: `local`),
 // with the members as the search's queries (seq1); -> the shards' counts, their total; *S = the pass's stats (symmetric kept
 // for the local scorer), kernel_ms = the pass
 int cluster_pass(hmk_ctx *ctx, bool local, Plan &pl, PlanLocal &pll, int a, int b, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1,
@@ -397,50 +422,48 @@ bool device_second_loop(hmk_ctx *ctx, hipStream_t S, const LoopIn &in, std::vect
                         std::string *stall_err);
 int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int32_t *cluster_id, int32_t *result_order,
                       int32_t *member_rank, hmk_greedy_stats *stats, std::chrono::steady_clock::time_point t0);
-// ---- hmk_multi.cpp
+// the bodies of hmk_greedy_cluster / hmk_clinkage_cluster on one device, behind the entry points' argument checks (t_entry: the call's
+// start, for HMK_GREEDY_TIMING)
+int greedy_cluster_single(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, int max_clusters, int32_t *cluster_id,
+                          int32_t *result_order, int32_t *member_rank, hmk_greedy_stats *stats, std::chrono::steady_clock::time_point t_entry);
+int clinkage_cluster_single(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, int32_t *cluster_id, int32_t *result_order,
+                            int32_t *member_rank, hmk_clinkage_stats *stats);
+// ---- hmk_multi.cpp (the same two on a context of several devices)
 int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, int max_clusters, int32_t *cluster_id,
                          int32_t *result_order, int32_t *member_rank, hmk_greedy_stats *stats, hmk_clinkage_stats *clink = nullptr);
 
+// A pass into the context's edge buffer, grown until every segment fits: reserve, launch, time, read the counts, check the fit.
 template <typename LaunchFn>
 int neighbors_grow(hmk_ctx *ctx, uint64_t want_cap, unsigned long long counts[HMK_EDGE_SHARDS], double *kernel_ms,
                    LaunchFn launch) {
     int st = need_device(ctx);
     if (st) return st;
-    if (!ctx->d_counts) HIPCHK(ctx, hipMalloc((void **)&ctx->d_counts, HMK_EDGE_SHARDS * sizeof(unsigned long long)));
     uint64_t cap = std::max<uint64_t>(want_cap, (uint64_t)1 << 20);
     cap = (cap + HMK_EDGE_SHARDS - 1) / HMK_EDGE_SHARDS * HMK_EDGE_SHARDS;
     hipEvent_t e0, e1;
     HIPCHK(ctx, hipEventCreate(&e0));
     HIPCHK(ctx, hipEventCreate(&e1));
-    for (int attempt = 0; attempt < 4; attempt++) {
-        if (ctx->d_edges_cap < cap) {
-            if (ctx->d_edges) (void)hipFree(ctx->d_edges);
-            ctx->d_edges = nullptr;
-            ctx->d_edges_cap = 0;
-            HIPCHK(ctx, hipMalloc((void **)&ctx->d_edges, cap * sizeof(uint64_t)));
-            ctx->d_edges_cap = cap;
-        }
+    auto attempt = [&]() -> int {
+        int r = ctx->edges.reserve(ctx, cap);
+        if (r) return r;
         HIPCHK(ctx, hipEventRecord(e0, nullptr));
-        st = launch(ctx->d_edges, ctx->d_edges_cap, ctx->d_counts);
-        if (st) break;
+        r = launch(ctx->edges.d, ctx->edges.cap, ctx->edges.counts);
+        if (r) return r;
         HIPCHK(ctx, hipEventRecord(e1, nullptr));
         HIPCHK(ctx, hipEventSynchronize(e1));
         float ms = 0;
         HIPCHK(ctx, hipEventElapsedTime(&ms, e0, e1));
         if (kernel_ms) *kernel_ms = ms;
-        HIPCHK(ctx, hipMemcpy(counts, ctx->d_counts, HMK_EDGE_SHARDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        unsigned long long mx = 0;
-        for (int s = 0; s < HMK_EDGE_SHARDS; s++) mx = std::max(mx, counts[s]);
-        if (mx <= ctx->d_edges_cap / HMK_EDGE_SHARDS) {
-            st = HMK_OK;
-            break;
-        }
-        cap = (uint64_t)HMK_EDGE_SHARDS * (mx + mx / 8 + 1024);  // a segment overflowed: grow and rescore
-        st = HMK_ERR_CAPACITY;
-    }
+        HIPCHK(ctx, hipMemcpy(counts, ctx->edges.counts, HMK_EDGE_SHARDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        if (max_of(counts) <= ctx->edges.seg_cap()) return HMK_OK;
+        cap = sizing::edge_capacity_after_overflow(max_of(counts));   // a segment overflowed: grow and rescore
+        return ST_RETRY_OVERFLOW;
+    };
+    st = ST_RETRY_OVERFLOW;
+    for (int k = 0; k < 4 && st == ST_RETRY_OVERFLOW; k++) st = attempt();
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    if (st == HMK_ERR_CAPACITY) return fail(ctx, HMK_ERR_DEVICE, "internal edge buffer kept overflowing");
+    if (st == ST_RETRY_OVERFLOW) return fail(ctx, HMK_ERR_DEVICE, "internal edge buffer kept overflowing");
     return st;
 }
 

@@ -86,13 +86,12 @@ int match(hmk_ctx *ctx, int scorer, uint32_t q0, uint32_t q1, const uint32_t *qu
     int32_t *d_score = (int32_t *)(d_best + nk);
     uint32_t *d_nfeas = d_best + 2 * nk;
     uint32_t *d_scr2 = buf<uint32_t>(ctx, SB_MATCH_SCR);
-    const uint64_t max_cnt = *std::max_element(counts, counts + HMK_EDGE_SHARDS);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIPCHK(ctx, hipEventCreate(&e0));
     hipError_t e = hipEventCreate(&e1);
     if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
     if (e == hipSuccess)
-        e = launch_match(ctx->d_edges, ctx->d_edges_cap / HMK_EDGE_SHARDS, ctx->d_counts, max_cnt, total, q0, nq, r0, nm, nb, k, d_cl, d_cl + nm,
+        e = launch_match(ctx->edges.d, ctx->edges.seg_cap(), ctx->edges.counts, max_of(counts), total, q0, nq, r0, nm, nb, k, d_cl, d_cl + nm,
                          d_cl + nm + n_clusters, d_cl + nm + 2 * (size_t)n_clusters, d_cl + nm + 2 * (size_t)n_clusters + nq,
                          buf<uint32_t>(ctx, SB_SEARCH_CNT), buf<uint32_t>(ctx, SB_SEARCH_START), buf<uint64_t>(ctx, SB_SEARCH_SCAN),
                          buf<uint64_t>(ctx, SB_SEARCH_OUT), buf<uint64_t>(ctx, SB_MATCH_REC), cap, d_scr2, d_scr2 + nq + 3 * (size_t)nb + 1,

@@ -130,7 +130,7 @@ int device_graph(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_
         return launch_plan(ctx, ctx->plan_merge, X, p, thr, d_edges, cap, d_counts, nullptr);
     });
     if (st) return st;
-    for (int s = 0; s < HMK_EDGE_SHARDS; s++) S->n_edges += counts[s];
+    S->n_edges += total_of(counts);
     S->pairs_scored = ctx->plan_merge.stats.pairs_scored;
     S->kernel_ms = ms;
     if (2 * S->n_edges > 0xFFFFFFFFull) return fail(ctx, HMK_ERR_OOM, "more than 2^31 - 1 edges above the threshold: raise the threshold");
@@ -158,10 +158,8 @@ int device_graph(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_
     hipStream_t Q = ctx->gstream;
     HIPCHK(ctx, hipMemcpyAsync(d_cl, cl.data(), cl.size() * 4, hipMemcpyHostToDevice, Q));
 
-    const long long top = (long long)ctx->max_len * std::max(0, ctx->max_m) +
-                          (long long)std::max(0, p) * ((ctx->max_len - ctx->min_len) + 2LL * X);
-    const bool packed = top - thr <= 255 && !ctx->sw.adj_8byte;   // (4-byte entries m << 8 | score - threshold, as hmk_greedy_cluster)
-    const EdgeSegs segs = shard_segments(ctx->d_edges, ctx->d_edges_cap / HMK_EDGE_SHARDS, ctx->d_counts);
+    const bool packed = adjacency_packed(ctx, X, p, thr);   // (4-byte entries m << 8 | score - threshold, as hmk_greedy_cluster)
+    const EdgeSegs segs = ctx->edges.segs();
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIPCHK(ctx, hipEventCreate(&e0));
     hipError_t e = hipEventCreate(&e1);
@@ -183,9 +181,9 @@ int device_graph(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_
     }
     if (e == hipSuccess && !bad_edge && total) {
         // the lists to the host: stored by the device into the pinned block
-        e = ensure_pinned(&ctx->h_merge, &ctx->h_merge_cap, total * sizeof(uint64_t) + 64, 0);
+        e = ctx->h_merge.ensure(total * sizeof(uint64_t) + 64, 0);
         uint64_t *d_out = nullptr;
-        if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&d_out, ctx->h_merge, 0);
+        if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&d_out, ctx->h_merge.p, 0);
         if (e == hipSuccess)
             e = launch_merge_compact(n_clusters, d_cl, buf<uint32_t>(ctx, SB_MERGE_MSTART), buf<uint64_t>(ctx, SB_MERGE_TMP), buf<uint32_t>(ctx, SB_MERGE_CNT),
                                      buf<uint32_t>(ctx, SB_MERGE_OSTART), thr, d_out, total, Q);
@@ -227,7 +225,7 @@ int cluster_pairs(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member
     if (stats) *stats = S;
     if (n_rec > capacity) return fail(ctx, HMK_ERR_CAPACITY, "pair buffer too small: " + std::to_string(n_rec) + " cluster pairs");
     if (n_rec && !pairs) return fail(ctx, HMK_ERR_BAD_ARG, "null pair buffer");
-    if (n_rec) std::memcpy(pairs, ctx->h_merge, n_rec * sizeof(uint64_t));
+    if (n_rec) std::memcpy(pairs, ctx->h_merge.p, n_rec * sizeof(uint64_t));
     return HMK_OK;
 }
 
@@ -268,7 +266,7 @@ int merge(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_cluster
     // the device stored slot a's records in one piece at its run start (a << 40 | b << 16 | score), in arbitrary order inside the piece: a
     // sort of the piece's 64-bit words is the sort by candidate, on the host (pieces are short, the words are in cache once copied,
     // and several threads take a share of the slots each)
-    st = lists_from_records(ctx, (const uint64_t *)ctx->h_merge, n_rec, n_clusters, S.cand);
+    st = lists_from_records(ctx, (const uint64_t *)ctx->h_merge.p, n_rec, n_clusters, S.cand);
     if (st) return st;
     stats->cluster_pairs = n_rec / 2;
     return run_chain(ctx, S, member_cluster, merged_id, result_order, member_rank, stats);

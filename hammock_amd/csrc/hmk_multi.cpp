@@ -52,14 +52,8 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
     const uint32_t rows_per = (n + G - 1) / G;
     hipStream_t S = ctx->gstream;
     auto dev = [&](uint32_t d) { return d ? ctx->peers[d - 1] : ctx; };
-    int64_t band_req = 0;
-    if (!clink && max_clusters > 0 && n >= 16384 && !ctx->sw.no_band) band_req = std::min<int64_t>(n, 2LL * max_clusters + 1024);
-    if (band_req * 2 > (int64_t)n) band_req = 0;
-    uint64_t guess = (uint64_t)((double)n * (n - 1) / 2 * (ctx->symmetric ? 0.003 : 0.006) / G * 1.25) + (1u << 20);
-    if (ctx->sw.edge_guess) guess = ctx->sw.edge_guess;   // tests: force the overflow / retry path
-    const long long top = (long long)ctx->max_len * std::max(0, ctx->max_m) +
-                          (long long)std::max(0, shift_penalty) * ((ctx->max_len - ctx->min_len) + 2LL * max_shift);
-    const bool packed = top - threshold <= 255 && !ctx->sw.adj_8byte;
+    const int64_t band_req = clink || ctx->sw.no_band ? 0 : sizing::band_request(n, max_clusters);
+    const bool packed = adjacency_packed(ctx, max_shift, shift_penalty, threshold);
     const bool symmetric = ctx->symmetric;
     const bool fuse = symmetric;   // the pass counts upper and lower degrees itself (asymmetric scores: a counting pass over the blocks)
     std::vector<uint64_t> want_edges(G, 0), want_inbox(G, 0);   // grown by an attempt that overflowed
@@ -75,24 +69,16 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
             if (st == HMK_OK) st = greedy_streams(c);
             if (st) return d ? fail(ctx, st, c->err) : st;
             c->sw = ctx->sw;
-            if (!c->d_counts) HIPCHK(ctx, hipMalloc((void **)&c->d_counts, HMK_EDGE_SHARDS * sizeof(unsigned long long)));
-            uint64_t cap = std::max<uint64_t>({std::min<uint64_t>(guess, 1ull << 31), (uint64_t)1 << 20, c->d_edges_cap, want_edges[d]});
-            cap = (cap + HMK_EDGE_SHARDS - 1) / HMK_EDGE_SHARDS * HMK_EDGE_SHARDS;
-            if (c->d_edges_cap < cap) {
-                if (c->d_edges) (void)hipFree(c->d_edges);
-                c->d_edges = nullptr;
-                c->d_edges_cap = 0;
-                HIPCHK(ctx, hipMalloc((void **)&c->d_edges, cap * sizeof(uint64_t)));
-                c->d_edges_cap = cap;
-            }
+            st = c->edges.reserve(ctx, sizing::edge_capacity_guess(symmetric, n, G, ctx->sw.edge_guess, std::max(c->edges.cap, want_edges[d])));
+            if (st) return st;
             if (!c->xfer_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&c->xfer_stream, hipStreamNonBlocking));
             HIPCHK(ctx, ensure_buf(c, SB_BCOUNTS, HMK_EDGE_SHARDS * sizeof(unsigned long long)));
             HIPCHK(ctx, ensure_buf(c, SB_DEG, (size_t)n * 8));
             // an edge goes to the owner of each end: at most two blocks hold it
-            HIPCHK(ctx, ensure_buf(c, SB_ROUTE, 2 * c->d_edges_cap * sizeof(uint64_t)));
+            HIPCHK(ctx, ensure_buf(c, SB_ROUTE, 2 * c->edges.cap * sizeof(uint64_t)));
             HIPCHK(ctx, ensure_buf(c, SB_ROUTECNT, 3 * (HMK_MAX_DEVICES + 1) * sizeof(unsigned long long)));
             // what one sender deals to one owner: 2 / G of its shard where the rows are spread evenly, + a half
-            inbox_cap[d] = std::max<uint64_t>({(uint64_t)((double)c->d_edges_cap * 2.0 / G * 1.5) + 65536, want_inbox[d], c->inbox_entries});
+            inbox_cap[d] = std::max<uint64_t>({(uint64_t)((double)c->edges.cap * 2.0 / G * 1.5) + 65536, want_inbox[d], c->inbox_entries});
             jobs.emplace_back(new DevJob());
             DevJob &J = *jobs.back();
             J.c = c;
@@ -100,8 +86,8 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
             J.r0 = (uint32_t)std::min<uint64_t>(n, (uint64_t)d * rows_per);
             J.r1 = (uint32_t)std::min<uint64_t>(n, (uint64_t)(d + 1) * rows_per);
             if (d) {   // the peer's own compacted band block
-                HIPCHK(ctx, ensure_buf(c, SB_PEERBAND, (c->d_edges_cap / 2 + 1) * sizeof(uint64_t)));
-                J.band_region = c->d_edges_cap / 2 + 1;
+                HIPCHK(ctx, ensure_buf(c, SB_PEERBAND, (c->edges.cap / 2 + 1) * sizeof(uint64_t)));
+                J.band_region = c->edges.cap / 2 + 1;
             }
         }
         for (uint32_t d = 0; d < G; d++) {   // (the inboxes: every device's capacity is known now)
@@ -112,23 +98,8 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
             HIPCHK(ctx, ensure_buf(c, SB_PEERCNT, 2 * HMK_MAX_SEGS * sizeof(unsigned long long)));   // [s]: sender s's block size; (root) [HMK_MAX_SEGS + s]: its band block's
             HIPCHK(ctx, ensure_buf(c, SB_PEERDEG, std::max<size_t>(G - 1, 1) * 2 * (size_t)rows_per * 4));
             // the piece's CSR and pre-check buffers (grow-only: steady-state calls find them in place)
-            const uint64_t records = 2 * c->d_edges_cap + (G - 1) * inbox_cap[d] + 1;
-            const size_t esz0 = packed ? sizeof(NbrPacked) : sizeof(Nbr);
-            HIPCHK(ctx, ensure_buf(c, SB_ADJ, (symmetric ? 2 : 1) * records * esz0));
-            HIPCHK(ctx, ensure_buf(c, SB_CURSOR, (size_t)n * 8));
-            HIPCHK(ctx, ensure_buf(c, SB_START, ((size_t)n + 1) * 8));
-            HIPCHK(ctx, ensure_buf(c, SB_SCAN, scan_scratch_bytes(n)));
-            HIPCHK(ctx, ensure_buf(c, SB_RANGE, 64));
-            if (csr_by_bucket(symmetric, packed)) {
-                HIPCHK(ctx, ensure_buf(c, SB_PART, records * 8));
-                HIPCHK(ctx, ensure_buf(c, SB_PARTSCR, csr_partition_scratch_bytes()));
-            }
-            HIPCHK(ctx, ensure_buf(c, SB_COF, (size_t)n * 4));
-            HIPCHK(ctx, ensure_buf(c, SB_BITMAP, ((size_t)n + 31) / 32 * 4));
-            HIPCHK(ctx, ensure_buf(c, SB_LEFT, (size_t)n * 4));
-            HIPCHK(ctx, ensure_buf(c, SB_CNT, (size_t)n * 4));
-            HIPCHK(ctx, ensure_buf(c, SB_CSTART, ((size_t)n + 1) * 4));
-            HIPCHK(ctx, ensure_buf(c, SB_CAND, (size_t)n * 24 * sizeof(GreedyCand)));
+            const uint64_t records = 2 * c->edges.cap + (G - 1) * inbox_cap[d] + 1;
+            HIPCHK(ctx, ensure_piece_buffers(c, n, packed, symmetric, records, records));
             HIPCHK(ctx, ensure_buf(c, SB_RETRY, (size_t)n * 4));
         }
         st = need_device(ctx);
@@ -136,7 +107,7 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
         uint64_t boff = 0;
         for (auto &jp : jobs) { jp->band_off = boff; boff += jp->band_region; }
         HIPCHK(ctx, ensure_buf(ctx, SB_PEERBAND, std::max<uint64_t>(boff, 1) * sizeof(uint64_t)));
-        HIPCHK(ctx, ensure_pinned(&ctx->h_start, &ctx->h_start_cap, ((size_t)n + 1) * 8 + (size_t)n * 4 + 64, 0));
+        HIPCHK(ctx, ctx->h_start.ensure(((size_t)n + 1) * 8 + (size_t)n * 4 + 64, 0));
         uint64_t *root_band = buf<uint64_t>(ctx, SB_PEERBAND);
         unsigned long long *root_cnt = buf<unsigned long long>(ctx, SB_PEERCNT);
 
@@ -171,7 +142,7 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
             int r = need_device(c);
             if (r) { fail_job(J, r, c->err); return; }
             hipStream_t Q = c->gstream, X = c->xfer_stream;
-            const uint64_t seg = c->d_edges_cap / HMK_EDGE_SHARDS;
+            const uint64_t seg = c->edges.seg_cap();
             unsigned long long *d_rcnt = buf<unsigned long long>(c, SB_ROUTECNT), *d_roff = d_rcnt + HMK_MAX_DEVICES + 1, *d_rcur = d_roff + HMK_MAX_DEVICES + 1;
             unsigned long long *h_rcnt = c->h_counts + HC_PEER;                          // pinned: the G block sizes, then [16] the band block's
             uint64_t *d_route = buf<uint64_t>(c, SB_ROUTE);
@@ -185,21 +156,21 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
             if (p_deg && (e = hipMemsetAsync(p_deg, 0, (size_t)n * 8, Q)) != hipSuccess) { hip_fail("degree counters", e); return; }
             if (d == 0 && (e = hipEventRecord(c->ev_t0, Q)) != hipSuccess) { hip_fail("hipEventRecord", e); return; }
             if (band) {
-                r = neighbors_dev_locked(c, max_shift, shift_penalty, threshold, d, G, c->d_edges, c->d_edges_cap, c->d_counts, Q, LAUNCH_BAND, band_req, p_deg, p_deg_lo);
+                r = neighbors_dev_locked(c, max_shift, shift_penalty, threshold, d, G, c->edges.d, c->edges.cap, c->edges.counts, Q, LAUNCH_BAND, band_req, p_deg, p_deg_lo);
                 if (r) { fail_job(J, r, c->err); return; }
-                e = hipMemcpyAsync(buf<void>(c, SB_BCOUNTS), c->d_counts, HMK_EDGE_SHARDS * sizeof(unsigned long long), hipMemcpyDeviceToDevice, Q);
-                if (e == hipSuccess && d) e = launch_compact_edges(c->d_edges, seg, buf<unsigned long long>(c, SB_BCOUNTS), buf<uint64_t>(c, SB_PEERBAND), J.band_region, d_rcnt + HMK_MAX_DEVICES, Q);
+                e = hipMemcpyAsync(buf<void>(c, SB_BCOUNTS), c->edges.counts, HMK_EDGE_SHARDS * sizeof(unsigned long long), hipMemcpyDeviceToDevice, Q);
+                if (e == hipSuccess && d) e = launch_compact_edges(c->edges.d, seg, buf<unsigned long long>(c, SB_BCOUNTS), buf<uint64_t>(c, SB_PEERBAND), J.band_region, d_rcnt + HMK_MAX_DEVICES, Q);
                 if (e == hipSuccess && d) e = hipMemcpyAsync(h_rcnt + 16, d_rcnt + HMK_MAX_DEVICES, 8, hipMemcpyDeviceToHost, Q);
                 if (e == hipSuccess) e = hipEventRecord(c->ev_band, Q);
                 if (e != hipSuccess) { hip_fail("band launch", e); return; }
                 if (d == 0) set_state(&DevJob::band_state, J, 1);   // (the root's own band segments: its copy stream waits for ev_band itself)
             } else if (d == 0) set_state(&DevJob::band_state, J, -1);
-            r = neighbors_dev_locked(c, max_shift, shift_penalty, threshold, d, G, c->d_edges, c->d_edges_cap, c->d_counts, Q,
+            r = neighbors_dev_locked(c, max_shift, shift_penalty, threshold, d, G, c->edges.d, c->edges.cap, c->edges.counts, Q,
                                      band ? LAUNCH_REST : LAUNCH_ALL, band_req, p_deg, p_deg_lo);
             if (r) { (void)hipStreamSynchronize(Q); fail_job(J, r, c->err); return; }
-            e = hipMemcpyAsync(c->h_counts, c->d_counts, HMK_EDGE_SHARDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, Q);
+            e = hipMemcpyAsync(c->h_counts, c->edges.counts, HMK_EDGE_SHARDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, Q);
             // the shard's edges, one block per owning device
-            if (e == hipSuccess) e = launch_route_edges(shard_segments(c->d_edges, seg, c->d_counts), rows_per, G, d_rcnt, d_roff, d_rcur, d_route, 2 * c->d_edges_cap, Q);
+            if (e == hipSuccess) e = launch_route_edges(c->edges.segs(), rows_per, G, d_rcnt, d_roff, d_rcur, d_route, 2 * c->edges.cap, Q);
             if (e == hipSuccess) e = hipMemcpyAsync(h_rcnt, d_rcnt, G * sizeof(unsigned long long), hipMemcpyDeviceToHost, Q);
             if (e == hipSuccess) e = hipEventRecord(c->ev_edges, Q);
             if (e != hipSuccess) { hip_fail("shard launch", e); return; }
@@ -232,12 +203,8 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
             e = hipEventSynchronize(c->ev_edges);
             if (e != hipSuccess) { hip_fail("shard", e); return; }
             J.t_scored = now_ms();
-            {
-                unsigned long long mx = 0;
-                J.edges = 0;
-                for (int q = 0; q < HMK_EDGE_SHARDS; q++) { mx = std::max(mx, c->h_counts[q]); J.edges += std::min<unsigned long long>(c->h_counts[q], seg); }
-                if (mx > seg) { J.need_edges = (uint64_t)HMK_EDGE_SHARDS * (mx + mx / 8 + 1024); set_state(&DevJob::sent_state, J, -2); return; }
-            }
+            if (max_of(c->h_counts) > seg) { J.need_edges = sizing::edge_capacity_after_overflow(max_of(c->h_counts)); set_state(&DevJob::sent_state, J, -2); return; }
+            J.edges = total_of(c->h_counts);   // (every segment fits: nothing of a count was dropped)
             {
                 bool too_small = false;
                 for (uint32_t t = 0; t < G; t++)
@@ -382,8 +349,8 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
         src.deg_split = fuse;
         src.rows_per = rows_per;
         for (auto &jp : jobs) src.pieces.push_back(EdgeSource::Piece{jp->c, jp->r0, jp->r1});
-        src.seg_cap = ctx->d_edges_cap / HMK_EDGE_SHARDS;
-        src.band_segs = shard_segments(ctx->d_edges, src.seg_cap, buf<unsigned long long>(ctx, SB_BCOUNTS));
+        src.seg_cap = ctx->edges.seg_cap();
+        src.band_segs = shard_segments(ctx->edges.d, src.seg_cap, buf<unsigned long long>(ctx, SB_BCOUNTS));
         for (uint32_t d = 1; d < G; d++) {
             hmk_ctx *pc = dev(d);
             if (same_device(pc, ctx, ctx->sw))   // (a context on the root's own device: its compacted band block and that block's size, where they lie)

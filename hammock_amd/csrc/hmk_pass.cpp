@@ -111,7 +111,7 @@ int launch_plan(hmk_ctx *ctx, const Plan &pl, int X, int p, int thr, void *d_edg
         const uint32_t t0 = which == LAUNCH_REST ? g.base + g.band : g.base;
         const uint32_t cnt = which == LAUNCH_ALL ? g.count : which == LAUNCH_BAND ? g.band : g.count - g.band;
         if (g.path == PATH_DIRECT)
-            HIPCHK(ctx, launch_neighbors_direct(P, t0, cnt, ctx->d_M, X, p, thr, s));
+            HIPCHK(ctx, launch_neighbors_direct(P, t0, cnt, ctx->d_M.as<int32_t>(), X, p, thr, s));
         else if (g.path == PATH_ROWS)
             HIPCHK(ctx, launch_neighbors_rows(X, g.nw, g.lbk, pl.rows_exact, P, t0, cnt, s));
         else
@@ -183,10 +183,10 @@ int launch_plan_local(hmk_ctx *ctx, const PlanLocal &pl, int gap_open, int gap_e
     P.symmetric = 0;
     P.row_is_m = 1;
     if (literal)
-        HIPCHK(ctx, launch_neighbors_local_literal(P, 0, pl.n_tiles, ctx->d_M, gap_open, gap_extend, thr, stream));
+        HIPCHK(ctx, launch_neighbors_local_literal(P, 0, pl.n_tiles, ctx->d_M.as<int32_t>(), gap_open, gap_extend, thr, stream));
     else
         HIPCHK(ctx, launch_neighbors_local(ctx->max_len, local_enc(ctx, gap_open, gap_extend), ctx->sw.local_signed, ctx->sw.local_no_pk, P, 0, pl.n_tiles,
-                                           ctx->d_M, gap_open, gap_extend, thr, stream));
+                                           ctx->d_M.as<int32_t>(), gap_open, gap_extend, thr, stream));
     return HMK_OK;
 }
 
@@ -243,7 +243,7 @@ int score_pairs(hmk_ctx *ctx, int scorer, const uint32_t *i, const uint32_t *j, 
         if (e == hipSuccess) e = hipMemcpy(d_j, j + o, m * 4, hipMemcpyHostToDevice);
         double acc = ctx->last_kernel_ms;
         timer_start(ctx);
-        if (e == hipSuccess) e = launch_pairs(scorer, ctx->d_res32, ctx->d_len, ctx->d_M, d_i, d_j, m, 0, 0, 1, a, b, d_out, d_shift, nullptr);
+        if (e == hipSuccess) e = launch_pairs(scorer, ctx->d_res32.as<uint8_t>(), ctx->d_len.as<uint8_t>(), ctx->d_M.as<int32_t>(), d_i, d_j, m, 0, 0, 1, a, b, d_out, d_shift, nullptr);
         timer_stop(ctx);
         ctx->last_kernel_ms += (o == 0 ? 0.0 : acc);
         if (e == hipSuccess) e = hipMemcpy(out + o, d_out, m * 4, hipMemcpyDeviceToHost);
@@ -288,10 +288,10 @@ int score_block(hmk_ctx *ctx, int scorer, uint32_t r0, uint32_t r1, uint32_t c0,
     // LocalAlignmentScorer: the register-resident striped kernel when its preconditions hold
     const bool fast_local = scorer == 1 && a <= 0 && b <= 0 && ctx->min_m >= -127 && ctx->max_m <= 127 && !ctx->sw.local_literal;
     if (fast_local)
-        e = launch_local_block(ctx->max_len, local_enc(ctx, a, b), ctx->sw.local_signed, ctx->sw.local_no_pk, ctx->d_res32, ctx->d_len, ctx->d_M, r0, r1,
+        e = launch_local_block(ctx->max_len, local_enc(ctx, a, b), ctx->sw.local_signed, ctx->sw.local_no_pk, ctx->d_res32.as<uint8_t>(), ctx->d_len.as<uint8_t>(), ctx->d_M.as<int32_t>(), r0, r1,
                                c0, c1, a, b, d_out, nullptr);
     else
-        e = launch_pairs(scorer, ctx->d_res32, ctx->d_len, ctx->d_M, nullptr, nullptr, n_pairs, r0, c0, c1 - c0, a, b,
+        e = launch_pairs(scorer, ctx->d_res32.as<uint8_t>(), ctx->d_len.as<uint8_t>(), ctx->d_M.as<int32_t>(), nullptr, nullptr, n_pairs, r0, c0, c1 - c0, a, b,
                          d_out, nullptr, nullptr);
     timer_stop(ctx);
     if (e == hipSuccess) e = hipMemcpy(out, d_out, n_pairs * 4, hipMemcpyDeviceToHost);

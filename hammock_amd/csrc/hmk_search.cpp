@@ -28,8 +28,7 @@ int search_pass(hmk_ctx *ctx, int scorer, int a, int b, int thr, uint32_t q0, ui
                                         : launch_plan_local(ctx, ctx->plan_local_search, a, b, thr, d_edges, cap, d_counts, nullptr);
     });
     if (st) return st;
-    uint64_t total = 0;
-    for (int s = 0; s < HMK_EDGE_SHARDS; s++) total += counts[s];
+    const uint64_t total = total_of(counts);
     if (scorer == SEARCH_SHIFTED) {
         *stats = ctx->plan_search.stats;
     } else {
@@ -40,10 +39,6 @@ int search_pass(hmk_ctx *ctx, int scorer, int a, int b, int thr, uint32_t q0, ui
     stats->n_edges = total;
     stats->kernel_ms = *ms;
     return HMK_OK;
-}
-
-uint64_t max_count(const unsigned long long counts[HMK_EDGE_SHARDS]) {
-    return *std::max_element(counts, counts + HMK_EDGE_SHARDS);
 }
 
 int search_edges(hmk_ctx *ctx, int scorer, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, int a, int b, int thr, uint64_t *edges,
@@ -77,7 +72,7 @@ int search_edges(hmk_ctx *ctx, int scorer, uint32_t q0, uint32_t q1, uint32_t r0
     if (total == 0) return HMK_OK;
     HIPCHK(ctx, ensure_buf(ctx, SB_SEARCH_OUT, total * sizeof(uint64_t)));
     uint64_t *d_out = buf<uint64_t>(ctx, SB_SEARCH_OUT);
-    HIPCHK(ctx, launch_search_compact(ctx->d_edges, ctx->d_edges_cap / HMK_EDGE_SHARDS, ctx->d_counts, max_count(counts), q0, q1 - q0, d_out, total, nullptr));
+    HIPCHK(ctx, launch_search_compact(ctx->edges.d, ctx->edges.seg_cap(), ctx->edges.counts, max_of(counts), q0, q1 - q0, d_out, total, nullptr));
     HIPCHK(ctx, hipMemcpy(edges, d_out, total * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return HMK_OK;
 }
@@ -141,7 +136,7 @@ int hmk_search_best_shifted(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0,
     hipError_t e = hipEventCreate(&e1);
     if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
     if (e == hipSuccess)
-        e = launch_search_best(ctx->d_edges, ctx->d_edges_cap / HMK_EDGE_SHARDS, ctx->d_counts, max_count(counts), q0, nq, k, buf<uint32_t>(ctx, SB_SEARCH_CNT),
+        e = launch_search_best(ctx->edges.d, ctx->edges.seg_cap(), ctx->edges.counts, max_of(counts), q0, nq, k, buf<uint32_t>(ctx, SB_SEARCH_CNT),
                                buf<uint32_t>(ctx, SB_SEARCH_START), buf<uint64_t>(ctx, SB_SEARCH_SCAN), buf<uint64_t>(ctx, SB_SEARCH_OUT),
                                std::max<uint64_t>(total, 1), d_index, d_score, d_nhits, nullptr);
     if (e == hipSuccess) e = hipEventRecord(e1, nullptr);

@@ -1476,6 +1476,49 @@ def test_cpp_host_classes_known_answers(gpu, known_answers, blosum62, coracle, t
     assert r.stdout.splitlines() == expect
 
 
+def test_host_buffer_capacity_contract(gpu, blosum62, coracle):
+    """hmk_neighbors_shifted / hmk_neighbors_local into the caller's buffer (one fetch from the internal segments behind both): a
+    buffer one entry short gets HMK_ERR_CAPACITY and the number needed in n_edges; a buffer of exactly that number gets every
+    edge, the same multiset as an ample one and as the oracle."""
+    import ctypes as C
+    from hammock_amd import _native as N
+    for scorer in ("shifted", "local"):
+        if scorer == "shifted":
+            n, (a, b, thr) = 3000, (3, 0, 20)
+            res, off = synth_peptides(11, n, 12)
+            fn = N.lib.hmk_neighbors_shifted
+            want = oracle_edges(coracle, blosum62, res, off, a, b, thr)
+        else:
+            n, (a, b, thr) = 1500, (-5, -1, 24)
+            res, off = synth_peptides(11, n, 7, 20)
+            fn = N.lib.hmk_neighbors_local
+            idx = np.arange(n, dtype=np.uint32)
+            st, sc = coracle.score_block(blosum62, res, off, idx, idx, 1, a, b)   # [m (seq1), x (seq2)]
+            assert st == 0
+            mm, xx = np.meshgrid(idx, idx, indexing="ij")
+            keep = (sc >= thr) & (mm != xx)
+            want = sorted_edges(hammock_amd.pack_edges(xx[keep], mm[keep], sc[keep]))
+        ctx, _, _ = ctx_for(blosum62, res=res, off=off)
+
+        def call(capacity):
+            buf = np.full(capacity + 1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)   # (one guard entry behind the capacity)
+            n_edges = C.c_uint64(0)
+            st = fn(ctx._h, a, b, thr, 0, 1, buf.ctypes.data_as(C.POINTER(C.c_uint64)), capacity, C.byref(n_edges), None)
+            assert buf[capacity] == 0xFFFFFFFFFFFFFFFF, scorer
+            return st, int(n_edges.value), buf[:capacity]
+
+        st, need, ample = call(1 << 20)
+        assert st == 0 and 1000 < need < 1 << 20, (scorer, st, need)
+        ample = sorted_edges(ample[:need])
+        assert np.array_equal(ample, want), scorer
+        st, got_n, _ = call(need - 1)
+        assert (st, got_n) == (N.HMK_ERR_CAPACITY, need), scorer
+        st, got_n, exact = call(need)
+        assert (st, got_n) == (0, need), scorer
+        assert np.array_equal(sorted_edges(exact), ample), scorer
+        ctx.close()
+
+
 @pytest.mark.parametrize("cfg", [("blosum62", 7, 20, -5, -1, 22), ("blosum62", 12, 12, -5, -1, 25),
                                  ("pam250", 5, 32, -3, -3, 30), ("blosum62", 9, 11, 0, 0, 26),
                                  ("blosum62", 7, 20, -1, 0, 30), ("pam250", 5, 32, -31, -31, 28), ("blosum62", 13, 19, -31, 0, 24)])
