@@ -67,7 +67,10 @@ struct NeighborParams {
 
 // Key-sorted one-length sets: the positions are ordered by the residues at two middle positions; a 64-column window
 // whose columns share a key residue adds that position's cells by scalar loads (keytab) instead of table reads.
-// keytab entry of (row group g, key q, residue c): dwords 2u, 2u + 1 = the 8-byte LDS entry of plane u at the key position, zero padded
+// keytab entry of (row group g, key q, residue c): dwords 2u, 2u + 1 = the 8-byte LDS entry of plane u at the key position, zero padded.
+// Key 0's entries (q = 0) have the plane's initial lane (TileClass::cinit, byte u) added to every byte: a window that shares key 0
+// takes its planes' start values from the entry as loaded.  The table therefore belongs to ONE class's cinit, i.e. to the plan's
+// (max shift, penalty, threshold) -- which is what the plan cache is keyed on (build_plan), and a plan frees its table with itself.
 constexpr int KEYTAB_DWORDS = 16;
 // the shapes that run it: one length, one row group per tile, hits cut out in the loop -- only the BASELINE shape for now
 constexpr bool rows_keyed(int x, int d, int cap, bool exact, int g) { return exact && d == 0 && g == 1 && x == 3 && cap == 12; }

@@ -24,9 +24,10 @@ int rows_per_tile_rows(int X, int d, int cap, bool exact);   // rows per tile of
 hipError_t launch_neighbors_rows(int X, int d, int cap, bool exact, const NeighborParams &P, uint32_t tile_base,
                                  uint32_t n_tiles, hipStream_t s);
 hipError_t warm_neighbors_rows_module();
-// the key table of a key-sorted one-length plan (NeighborParams::keytab) from its sorted residues, on the null stream
+// the key table of a key-sorted one-length plan (NeighborParams::keytab) from its sorted residues, on the null stream; cinit: its
+// class's TileClass::cinit (the planes' initial lanes, folded into key 0's entries)
 hipError_t launch_rows_keytab(const uint8_t *res_sorted, uint32_t lpad, uint32_t n, const uint8_t *mb, int case_b, int X, int L,
-                              uint32_t *keytab, uint32_t n_groups);
+                              const uint32_t (&cinit)[8], uint32_t *keytab, uint32_t n_groups);
 hipError_t launch_neighbors_direct(const NeighborParams &P, uint32_t tile_base, uint32_t n_tiles,
                                    const int32_t *d_matrix, int max_shift, int shift_penalty, int threshold,
                                    hipStream_t s);

@@ -553,12 +553,16 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
     if (!st) st = upload_biased_matrix(ctx, pl);
     if (st) return st;
     if (key_sorted) {   // run ids, and the key table built on the device from the sorted residues (hipMemcpy above: they are there)
+        // (the table holds the class's initial lanes, which depend on (X, p, thr): it lives and dies with this plan, whose cache
+        // key those are; a key-sorted plan has the one class of its one length)
+        if (classes.size() != 1) return fail(ctx, HMK_ERR_DEVICE, "key-sorted plan with more than one class");
         const uint32_t n_groups = (n + 7) / 8;
         const size_t tab_dwords = (size_t)n_groups * 2 * HMK_ALPHABET * KEYTAB_DWORDS;
         HIPCHK(ctx, hipMalloc((void **)&pl.d_keyrun, keyrun.size() * 4));
         HIPCHK(ctx, hipMemcpy(pl.d_keyrun, keyrun.data(), keyrun.size() * 4, hipMemcpyHostToDevice));
         HIPCHK(ctx, hipMalloc((void **)&pl.d_keytab, tab_dwords * 4));
-        HIPCHK(ctx, launch_rows_keytab(pl.d_res_sorted, (uint32_t)pl.lpad, n, pl.d_mb, classes.at(0).case_b, X, L1, pl.d_keytab, n_groups));
+        HIPCHK(ctx, launch_rows_keytab(pl.d_res_sorted, (uint32_t)pl.lpad, n, pl.d_mb, classes.at(0).case_b, X, L1, classes.at(0).cinit, pl.d_keytab,
+                                       n_groups));
         HIPCHK(ctx, hipStreamSynchronize(nullptr));
     }
     pl.X = X; pl.p = p; pl.thr = thr; pl.part = part; pl.n_parts = n_parts;

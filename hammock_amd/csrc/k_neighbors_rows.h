@@ -662,11 +662,31 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
     for (int g = 0; g < G; g++) acc[g] = 0;
     // Key-sorted sets (rows_keyed, P.keyrun set): the wave's 64 columns are a window of the sorted order.  When its first and last
     // live column lie in one run of the key residue, so do all of them: the key position's cells are the same for the whole
-    // wave, their 8-byte entries come from keytab by scalar loads and are summed into the planes' start values on the SALU,
-    // and the body that skips the position runs.  kmode: 0 none, 1 key 0, 3 both keys (wave-uniform).
+    // wave, their 8-byte entries come from keytab by scalar loads, and the body that skips the position runs with them as the
+    // planes' start values.  kmode: 0 none, 1 key 0, 3 both keys (wave-uniform).  A key-0 entry already holds the planes' initial
+    // lanes (k_rows_keytab): mode 1 takes the loaded registers as they come, mode 3 adds the key-1 entry, one s_add per dword.
+    // What depends on the tile only -- the row group's entries, the wave's place in keyrun -- is worked out here, once.
     constexpr bool KEYED = rows_keyed(X, D, CAP, EXACT_LB, G);
+    static_assert(!KEYED || (G == 1 && 2 * ND <= KEYTAB_DWORDS), "key table entry; one row group per tile");
     const bool keyed = KEYED && P.keyrun != nullptr;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t *kt_tile = nullptr, *kr_wave = nullptr;   // keytab of the tile's row group; keyrun of the wave's first column
+    if (keyed) {
+        kt_tile = P.keytab + (size_t)(T.row0 >> 3) * (2 * 24 * KEYTAB_DWORDS);
+        kr_wave = P.keyrun + 2 * (size_t)(T.col0 + wave * 64);
+    }
+    // one key entry, whole: rows 0-3 / 4-7 of every plane
+    auto key_entry = [](const uint32_t *e, uint32_t (&k0)[ND], uint32_t (&k1)[ND]) {
+#pragma unroll
+        for (int u = 0; u + 1 < ND; u += 2) {
+            const u32x4 a = rows_const_load<u32x4>(e + 2 * u);
+            k0[u] = a.x; k1[u] = a.y; k0[u + 1] = a.z; k1[u + 1] = a.w;
+        }
+        if constexpr (ND & 1) {
+            const u32x2 a = rows_const_load<u32x2>(e + 2 * (ND - 1));
+            k0[ND - 1] = a.x; k1[ND - 1] = a.y;
+        }
+    };
     for (uint32_t bt = 0; bt < n_batches; bt++) {
         const uint32_t colrel = bt * 256 + tid;
         const uint32_t col = T.col0 + colrel;
@@ -674,33 +694,14 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
         uint32_t words[S::LPADW], tw[S::TWN];
         S::load_words(res_sorted + (size_t)col * lpad_s, col < col_end, lbs, words, tw);
         int kmode = 0;
-        uint32_t ks0[ND], ks1[ND];   // start values of the planes, rows 0-3 / 4-7
-#pragma unroll
-        for (int u = 0; u < ND; u++) { ks0[u] = ci[u]; ks1[u] = ci[u]; }
+        u32x2 ra;   // the run words of the wave's first column (read where kmode != 0 only)
         if constexpr (KEYED) {
             const uint32_t wc0 = T.col0 + bt * 256 + wave * 64;   // the wave's first column
             if (keyed && wc0 < col_end) {
-                const uint32_t wc1 = min(wc0 + 63u, col_end - 1u);    // ... and its last live one
-                const u32x2 ra = rows_const_load<u32x2>(P.keyrun + 2 * (size_t)wc0), rb = rows_const_load<u32x2>(P.keyrun + 2 * (size_t)wc1);
-                if (ra.x == rb.x) {
-                    kmode = ra.y == rb.y ? 3 : 1;
-                    // both entries are loaded whole (the second one is valid memory whatever kmode is) and the second is masked
-                    static_assert(2 * ND <= KEYTAB_DWORDS, "key table entry");
-                    const uint32_t *kt = P.keytab + (size_t)(T.row0 >> 3) * (2 * 24 * KEYTAB_DWORDS);
-                    const uint32_t *e0 = kt + (ra.x & 31u) * KEYTAB_DWORDS;
-                    const uint32_t *e1 = kt + (24 + (ra.y & 31u)) * KEYTAB_DWORDS;
-                    const uint32_t m1 = kmode == 3 ? ~0u : 0u;
-#pragma unroll
-                    for (int u = 0; u + 1 < ND; u += 2) {   // byte lanes: every partial sum is <= the plane's final lane <= 255, no carry
-                        const u32x4 a = rows_const_load<u32x4>(e0 + 2 * u), b = rows_const_load<u32x4>(e1 + 2 * u);
-                        ks0[u] += a.x + (b.x & m1); ks1[u] += a.y + (b.y & m1);
-                        ks0[u + 1] += a.z + (b.z & m1); ks1[u + 1] += a.w + (b.w & m1);
-                    }
-                    if constexpr (ND & 1) {
-                        const u32x2 a = rows_const_load<u32x2>(e0 + 2 * (ND - 1)), b = rows_const_load<u32x2>(e1 + 2 * (ND - 1));
-                        ks0[ND - 1] += a.x + (b.x & m1); ks1[ND - 1] += a.y + (b.y & m1);
-                    }
-                }
+                const uint32_t last = min(63u, col_end - 1u - wc0);   // ... and its last live one
+                ra = rows_const_load<u32x2>(kr_wave);
+                const u32x2 rb = rows_const_load<u32x2>(kr_wave + 2 * last);
+                if (ra.x == rb.x) kmode = ra.y == rb.y ? 3 : 1;
             }
         }
         uint32_t off[CAP], toff[S::NT];
@@ -711,12 +712,31 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
             constexpr int g = decltype(gt)::value;
             if ((uint32_t)(8 * g) >= T.nrows) return;   // wave-uniform
             uint32_t W0[ND], W1[ND];
-            read_phase_begin(prio);
             if constexpr (KEYED) {
-                if (kmode == 3) S::template accumulate<g, 3>(off, toff, lbs, ks0, ks1, W0, W1);
-                else if (kmode == 1) S::template accumulate<g, 1>(off, toff, lbs, ks0, ks1, W0, W1);
-                else S::template accumulate<g>(off, toff, lbs, ks0, ks1, W0, W1);
+                // (start values in SGPRs: the plane's first add takes them as its scalar operand.  Byte lanes: every partial sum is
+                // <= the plane's final lane <= 255, no carry)
+                uint32_t ks0[ND], ks1[ND];
+                if (kmode == 3) {
+                    uint32_t kb0[ND], kb1[ND];
+                    key_entry(kt_tile + (ra.x & 31u) * KEYTAB_DWORDS, ks0, ks1);
+                    key_entry(kt_tile + (24 + (ra.y & 31u)) * KEYTAB_DWORDS, kb0, kb1);
+#pragma unroll
+                    for (int u = 0; u < ND; u++) { ks0[u] += kb0[u]; ks1[u] += kb1[u]; }
+                    read_phase_begin(prio);
+                    S::template accumulate<g, 3>(off, toff, lbs, ks0, ks1, W0, W1);
+                } else if (kmode == 1) {
+                    key_entry(kt_tile + (ra.x & 31u) * KEYTAB_DWORDS, ks0, ks1);
+                    // (no instruction: the loads are waited for HERE, not at the first add inside the read phase)
+#pragma unroll
+                    for (int u = 0; u < ND; u++) asm volatile("" : "+s"(ks0[u]), "+s"(ks1[u]));
+                    read_phase_begin(prio);
+                    S::template accumulate<g, 1>(off, toff, lbs, ks0, ks1, W0, W1);
+                } else {
+                    read_phase_begin(prio);
+                    S::template accumulate<g>(off, toff, lbs, ci, ci, W0, W1);
+                }
             } else {
+                read_phase_begin(prio);
                 S::template accumulate<g>(off, toff, lbs, ci, ci, W0, W1);
             }
             read_phase_end(prio);
@@ -797,6 +817,7 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
             }
         };
         rows_for_each_group(std::make_integer_sequence<int, G>{}, one_group);
+        kr_wave += 2 * 256;
     }
     flush_stage_rows<X, D, CAP, EXACT_LB, G, MODE>(stage, cnt, cnt_hi, tab_addr, ka_lo, ka_hi);
 }

@@ -49,9 +49,13 @@ hipError_t warm_neighbors_rows_module() { return warm_rows_part_0(); }
 
 // One thread per keytab dword: entry (row group g, key q, residue c), dword 2u + h = byte t: cell(row 8g + 4h + t, key position + u - X, c)
 // + bias, as the tile's table build (rows_tile) writes it -- zero for a row at or past n; dwords past the 2X + 1 planes zero.
+// Key 0's entries hold the planes' START values as well: byte u of cinit (TileClass::cinit of the plan's one class) is added to
+// every byte of dwords 2u, 2u + 1, so a row at or past n holds the initial lane alone -- what the kernel starts such a row at
+// anyway.  No byte carries: initial lane + one cell is a partial sum of a lane classify() proved to end <= 255.
+struct KeytabInit { uint32_t w[8]; };
 __global__ void __launch_bounds__(256) k_rows_keytab(const uint8_t *__restrict__ res_sorted, uint32_t lpad, uint32_t n,
-                                                     const uint8_t *__restrict__ mb, int case_b, int X, int L, uint32_t *__restrict__ keytab,
-                                                     uint32_t n_groups) {
+                                                     const uint8_t *__restrict__ mb, int case_b, int X, int L, const KeytabInit cinit,
+                                                     uint32_t *__restrict__ keytab, uint32_t n_groups) {
     const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (uint64_t)n_groups * 2 * HMK_ALPHABET * KEYTAB_DWORDS) return;
     const int d = (int)(e % KEYTAB_DWORDS), c = (int)(e / KEYTAB_DWORDS % HMK_ALPHABET), q = (int)(e / (KEYTAB_DWORDS * HMK_ALPHABET) % 2);
@@ -67,15 +71,18 @@ __global__ void __launch_bounds__(256) k_rows_keytab(const uint8_t *__restrict__
             }
         }
     }
+    if (q == 0 && u <= 2 * X) v += ((cinit.w[u >> 2] >> ((u & 3) * 8)) & 0xFFu) * 0x01010101u;
     keytab[e] = v;
 }
 
 hipError_t launch_rows_keytab(const uint8_t *res_sorted, uint32_t lpad, uint32_t n, const uint8_t *mb, int case_b, int X, int L,
-                              uint32_t *keytab, uint32_t n_groups) {
+                              const uint32_t (&cinit)[8], uint32_t *keytab, uint32_t n_groups) {
     const uint64_t total = (uint64_t)n_groups * 2 * HMK_ALPHABET * KEYTAB_DWORDS;
     if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rows_keytab, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, res_sorted, lpad, n, mb, case_b, X, L, keytab,
-                       n_groups);
+    KeytabInit ci;
+    for (int k = 0; k < 8; k++) ci.w[k] = cinit[k];
+    hipLaunchKernelGGL(k_rows_keytab, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, res_sorted, lpad, n, mb, case_b, X, L, ci,
+                       keytab, n_groups);
     return hipGetLastError();
 }
 
