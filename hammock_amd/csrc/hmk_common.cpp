@@ -16,6 +16,7 @@ void Switches::read() {
     no_band = flag("HMK_NO_BAND");
     no_rows_kernel = flag("HMK_NO_ROWS_KERNEL");
     key_sort = flag("HMK_NO_KEY_SORT") ? 0 : num("HMK_KEY_SORT_KEYS", 2) == 1 ? 1 : 2;
+    no_row_shared = flag("HMK_NO_ROW_SHARED");
     adj_8byte = flag("HMK_ADJ_8BYTE");
     local_literal = flag("HMK_LOCAL_LITERAL");
     local_signed = flag("HMK_LOCAL_SIGNED");

@@ -38,7 +38,8 @@ struct Tile {
     uint32_t col0, ncols;  // columns [col0, col0 + ncols)
     uint32_t cls;          // index into the TileClass array
     uint32_t diag;         // 1: rows and columns come from the same bucket: keep col > row only
-    uint32_t pad0, pad1;
+    uint32_t pad0;
+    uint32_t row_shared;   // bit g: group g's 8 rows are all live and equal at both key positions (key-sorted plans, k_neighbors_rows.h)
 };
 
 struct NeighborParams {

@@ -319,7 +319,8 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
     Plan &pl = ctx->plan;
     const int want_keys = key_sort_ok ? ctx->sw.key_sort : 0;
     if (pl.valid && pl.X == X && pl.p == p && pl.thr == thr && pl.part == part && pl.n_parts == n_parts &&
-        (band_rows < 0 || pl.band_req == band_rows) && pl.no_rows_kernel == ctx->sw.no_rows_kernel && pl.key_sort == want_keys)
+        (band_rows < 0 || pl.band_req == band_rows) && pl.no_rows_kernel == ctx->sw.no_rows_kernel && pl.key_sort == want_keys &&
+        pl.row_shared == !ctx->sw.no_row_shared)
         return HMK_OK;
     free_plan(pl);
     if (band_rows < 0) band_rows = 0;
@@ -444,6 +445,7 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
     // single-part passes only (key_sort_ok): a clustering call's scoring counts degrees per row group and its CSR build reads the
     // edges in row order (both slower on the sorted order: 10^5 call 4.04 -> 4.44 ms), and shards keep their caller-order rows.
     pl.key_sort = want_keys;
+    pl.row_shared = !ctx->sw.no_row_shared;
     std::vector<uint32_t> keyrun;
     const int L1 = ctx->min_len;
     const bool key_sorted = pl.key_sort > 0 && pl.rows_exact && !(refine && !all_rows_fit) &&
@@ -543,9 +545,24 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
         }
     }
     plan_lap("classes and tiles");
-    const std::vector<Tile> tiles = order_groups(grouped, classes, X, pl.groups);
+    std::vector<Tile> tiles = order_groups(grouped, classes, X, pl.groups);
     S.n_tiles = (uint32_t)tiles.size();
     plan_lap("tile order");
+    // Row-shared groups of a key-sorted plan (k_neighbors_rows.h, RowsShape::rs_row): 8 live rows with the same residue at key
+    // position 0 and the same at key position 1.  A group with a row past the end never is: the merged entries would add cells to
+    // the dead rows' lanes that their zero entries do not.
+    if (key_sorted && pl.row_shared) {
+        const int k0 = rows_key_pos(X, L1, 0), k1 = rows_key_pos(X, L1, 1);
+        auto keys_at = [&](uint32_t q) { const uint32_t k = perm[q]; return (uint32_t)ctx->res[ctx->off[k] + k0] << 8 | ctx->res[ctx->off[k] + k1]; };
+        for (Tile &t : tiles) {
+            for (uint32_t g = 0; 8 * g + 8 <= t.nrows; g++) {
+                bool same = true;
+                for (uint32_t r = 1; r < 8 && same; r++) same = keys_at(t.row0 + 8 * g + r) == keys_at(t.row0 + 8 * g);
+                if (same) t.row_shared |= 1u << g;
+            }
+        }
+        plan_lap("row-shared groups");
+    }
 
     // ---- device copies ------------------------------------------------------------
     // (+ 16: the row-packed kernel's unaligned tail loads may touch the bytes after the last row)

@@ -199,6 +199,25 @@ struct RowsShape {
     // EXACT_LB: plane u reads the column positions [plane_j0(u), plane_j1(u)) but the skipped ones; the k-th of them
     static constexpr int plane_j0(int u) { return X - u > 0 ? X - u : 0; }
     static constexpr int plane_j1(int u) { return NI + X - u < CAP ? NI + X - u : CAP; }   // (row position j + u - X < NI)
+    // Row-shared groups (rs; rows_keyed shapes on a key-sorted plan, Tile::row_shared): the group's 8 rows have the same residue at
+    // row position key_pos(0) and the same at key_pos(1) -- the sorted order's neighbours mostly do.  The entries of those two row
+    // positions would hold eight equal bytes each, two reads for two dwords of information: the tile build writes ONE merged entry
+    // per residue c where position key_pos(0)'s lies, low dword = cell(key_pos(0), c) in its four bytes, high dword =
+    // cell(key_pos(1), c).  The merged read at column position j serves the two planes that pair j with those row positions: its
+    // half h goes to BOTH accumulators of plane key_pos(h) + X - j.  Every accumulator gets the operands it gets from the ordinary
+    // entries, in another order (byte lanes: partial sums stay <= the final lane).  Position key_pos(1)'s entries are not read.
+    static constexpr bool rs_row(int i) { return i == key_pos(0) || i == key_pos(1); }
+    // an ordinary read of plane u at column position j: inside the overlap, not a key start value, not a merged half
+    static constexpr bool ordinary(int u, int skip, bool rs, int j) {
+        return j >= plane_j0(u) && j < plane_j1(u) && !skipped(skip, j) && !(rs && rs_row(j + u - X));
+    }
+    // the column position whose merged read's half h belongs to plane u, and whether the body reads it
+    static constexpr int merged_j(int u, int h) { return key_pos(h) + X - u; }
+    static constexpr bool merged_half(int u, int skip, bool rs, int h) {
+        return rs && u >= 0 && u < ND && merged_j(u, h) >= plane_j0(u) && merged_j(u, h) < plane_j1(u) && !skipped(skip, merged_j(u, h));
+    }
+    // plane u's high half is the read the plane before it issued for its low half (the same column position), or a read of its own
+    static constexpr bool merged_reuse(int u, int skip, bool rs) { return merged_half(u, skip, rs, 1) && merged_half(u - 1, skip, rs, 0); }
     static constexpr int plane_reads(int u, int skip) {
         int n = 0;
         for (int j = plane_j0(u); j < plane_j1(u); j++) n += skipped(skip, j) ? 0 : 1;
@@ -209,15 +228,85 @@ struct RowsShape {
             if (!skipped(skip, j) && k-- == 0) return j;
         return -1;
     }
+    // ... and of a row-shared body: the ordinary reads only
+    static constexpr int rs_plane_reads(int u, int skip) {
+        int n = 0;
+        for (int j = plane_j0(u); j < plane_j1(u); j++) n += ordinary(u, skip, true, j) ? 1 : 0;
+        return n;
+    }
+    static constexpr int rs_plane_pos(int u, int skip, int k) {
+        for (int j = plane_j0(u); j < plane_j1(u); j++)
+            if (ordinary(u, skip, true, j) && k-- == 0) return j;
+        return -1;
+    }
+    // ds_read_b64 of a whole body (all planes)
+    static constexpr int body_reads(int skip, bool rs) {
+        int n = 0;
+        for (int u = 0; u < ND; u++)
+            n += (rs ? rs_plane_reads(u, skip) : plane_reads(u, skip)) + (merged_half(u, skip, rs, 0) ? 1 : 0) + (merged_half(u, skip, rs, 1) && !merged_reuse(u, skip, rs) ? 1 : 0);
+        return n;
+    }
+    // The schedule's proof: every cell (u, j) of the overlap is added exactly once -- by an ordinary read, by a merged half (which
+    // must stand for the row position the cell has) or by a key start value -- and a reused merged read is the one the plane needs.
+    static constexpr bool body_covers(int skip, bool rs) {
+        if (rs && key_pos(1) != key_pos(0) + 1) return false;
+        for (int u = 0; u < ND; u++) {
+            for (int j = plane_j0(u); j < plane_j1(u); j++) {
+                int n = (ordinary(u, skip, rs, j) ? 1 : 0) + (skipped(skip, j) ? 1 : 0);
+                for (int h = 0; h < 2; h++)
+                    if (merged_half(u, skip, rs, h) && merged_j(u, h) == j) n += (j + u - X == key_pos(h)) ? 1 : 2;
+                if (n != 1) return false;
+            }
+            if (merged_reuse(u, skip, rs) && merged_j(u, 1) != merged_j(u - 1, 0)) return false;
+        }
+        return true;
+    }
 
     // All shift sums of (8 rows of group GI) x (this lane's column): W0 / W1[u] = the 8 byte lanes of plane u, started at
-    // c0 / c1[u] (rows 0-3 / 4-7).  SKIP (EXACT_LB only): key positions left out, see key_pos.
-    template <int GI, int SKIP = 0>
+    // c0 / c1[u] (rows 0-3 / 4-7).  SKIP (EXACT_LB only): key positions left out, see key_pos.  RS: the row-shared form.
+    template <int GI, int SKIP = 0, bool RS = false>
     static __device__ __forceinline__ void accumulate(const uint32_t (&off)[CAP], const uint32_t (&toff)[NT], int lbs,
                                                       const uint32_t (&c0)[ND], const uint32_t (&c1)[ND], uint32_t (&W0)[ND], uint32_t (&W1)[ND]) {
         static_assert(SKIP == 0 || EXACT_LB, "key positions are skipped by the one-length forms only");
+        static_assert(!RS || EXACT_LB, "row-shared groups: one-length forms only");
         const uint32_t (&ci)[ND] = c0;
+        if constexpr (RS) {
+            // the row-shared form: the plane's operands are its merged halves (the same dword for rows 0-3 and 4-7), then its
+            // ordinary reads; summed two at a time as below.  A merged read is live across two neighbouring planes only.
+            static_assert(body_covers(SKIP, true), "every cell of the overlap exactly once");
+            u32x2 ml = {0u, 0u}, mh = {0u, 0u};   // merged reads: the plane's low-half one, its high-half one
+#pragma unroll
+            for (int u = 0; u < ND; u++) {
+                const bool hi = merged_half(u, SKIP, true, 1), lo = merged_half(u, SKIP, true, 0);
+                if (hi) {
+                    if (merged_reuse(u, SKIP, true)) mh = ml;
+                    else mh = rows_table_read<u32x2>(off[merged_j(u, 1)] + (uint32_t)pos_addr(GI, key_pos(0)));
+                }
+                if (lo) ml = rows_table_read<u32x2>(off[merged_j(u, 0)] + (uint32_t)pos_addr(GI, key_pos(0)));
+                const int n = rs_plane_reads(u, SKIP) + (hi ? 1 : 0) + (lo ? 1 : 0);
+                uint32_t a0 = c0[u], a1 = c1[u];
+                auto rd = [&](int k) {
+                    if (hi && k-- == 0) return u32x2{mh.y, mh.y};
+                    if (lo && k-- == 0) return u32x2{ml.x, ml.x};
+                    const int j = rs_plane_pos(u, SKIP, k);
+                    return rows_table_read<u32x2>(off[j] + (uint32_t)pos_addr(GI, j + u - X));
+                };
+                int k = 0;
+                if (n & 1) { const u32x2 e = rd(0); a0 += e.x; a1 += e.y; k = 1; }
+#pragma unroll
+                for (; k + 1 < n; k += 2) {
+                    const u32x2 e0 = rd(k), e1 = rd(k + 1);
+                    a0 = a0 + e0.x + e1.x; a1 = a1 + e0.y + e1.y;
+                }
+                // (the plane's adds must stand before the next plane's volatile reads are issued: left alone the adds are sunk
+                // below the reads and the reads' results spill -- see the flush)
+                asm volatile("" : "+v"(a0), "+v"(a1));
+                W0[u] = a0; W1[u] = a1;
+            }
+            return;
+        }
         if constexpr (EXACT_LB) {
+            static_assert(body_covers(SKIP, false), "every cell of the overlap exactly once");
             // everything is known at compile time: plane by plane, the plane's reads summed two at a time (one v_add3 per
             // dword and pair; an odd count starts with a plain add): ceil(reads / 2) VALU instructions per dword, the minimum
 #pragma unroll
@@ -594,6 +683,12 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
     // 32-bit LDS pointer, wave-uniform (kept in a scalar register: nothing to spill around the flush call)
     HMK_LDS uint32_t *stage = (HMK_LDS uint32_t *)stage_all + __builtin_amdgcn_readfirstlane(tid >> 6) * STAGE_CAP;
 
+    // Key-sorted sets (rows_keyed, P.keyrun set), see the batch loop.  row_shared: the planner found the group's 8 rows equal at both
+    // key positions (Tile::row_shared, a scalar load with the tile): merged entries here, the row-shared bodies below.
+    constexpr bool KEYED = rows_keyed(X, D, CAP, EXACT_LB, G);
+    const bool keyed = KEYED && P.keyrun != nullptr;
+    const bool row_shared = keyed && (T.row_shared & 1u) != 0;
+
     build_begin();
     const uint32_t tab_addr = lds_addr(tab);
     for (int e = tid; e < 576; e += 256) mb[e] = P.mb[e];
@@ -610,8 +705,12 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
         const int h = e & 1, ic = e >> 1;
         const int gi = ic / 24, c = ic - gi * 24;
         const int g = gi / (NI + NEND), k = gi - g * (NI + NEND);
-        const int i = k < NI ? k : la - 1 - (k - NI);
+        int i = k < NI ? k : la - 1 - (k - NI);
         const int dst = k < NI ? S::pos_addr(g, k) : S::end_addr(g, k - NI);
+        // a row-shared group's merged entries (RowsShape::rs_row), in place of row position key_pos(0)'s: the high dword holds
+        // key_pos(1)'s cell -- the same expression below, of rows 4-7, which have key_pos(0)'s residue in common with rows 0-3
+        if constexpr (KEYED)
+            if (row_shared && k == S::key_pos(0) && h == 1) i = S::key_pos(1);
         uint32_t v = 0;
         if (i >= 0 && i < la) {
 #pragma unroll
@@ -666,9 +765,10 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
     // planes' start values.  kmode: 0 none, 1 key 0, 3 both keys (wave-uniform).  A key-0 entry already holds the planes' initial
     // lanes (k_rows_keytab): mode 1 takes the loaded registers as they come, mode 3 adds the key-1 entry, one s_add per dword.
     // What depends on the tile only -- the row group's entries, the wave's place in keyrun -- is worked out here, once.
-    constexpr bool KEYED = rows_keyed(X, D, CAP, EXACT_LB, G);
     static_assert(!KEYED || (G == 1 && 2 * ND <= KEYTAB_DWORDS), "key table entry; one row group per tile");
-    const bool keyed = KEYED && P.keyrun != nullptr;
+    // ds_read_b64 per wave-step of the six bodies, windows that share both keys / key 0 / none
+    static_assert(!KEYED || (S::body_reads(3, false) == 58 && S::body_reads(1, false) == 65 && S::body_reads(0, false) == 72), "ordinary bodies");
+    static_assert(!KEYED || (S::body_reads(3, true) == 54 && S::body_reads(1, true) == 60 && S::body_reads(0, true) == 66), "row-shared bodies");
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t *kt_tile = nullptr, *kr_wave = nullptr;   // keytab of the tile's row group; keyrun of the wave's first column
     if (keyed) {
@@ -723,17 +823,20 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
 #pragma unroll
                     for (int u = 0; u < ND; u++) { ks0[u] += kb0[u]; ks1[u] += kb1[u]; }
                     read_phase_begin(prio);
-                    S::template accumulate<g, 3>(off, toff, lbs, ks0, ks1, W0, W1);
+                    if (row_shared) S::template accumulate<g, 3, true>(off, toff, lbs, ks0, ks1, W0, W1);
+                    else S::template accumulate<g, 3>(off, toff, lbs, ks0, ks1, W0, W1);
                 } else if (kmode == 1) {
                     key_entry(kt_tile + (ra.x & 31u) * KEYTAB_DWORDS, ks0, ks1);
                     // (no instruction: the loads are waited for HERE, not at the first add inside the read phase)
 #pragma unroll
                     for (int u = 0; u < ND; u++) asm volatile("" : "+s"(ks0[u]), "+s"(ks1[u]));
                     read_phase_begin(prio);
-                    S::template accumulate<g, 1>(off, toff, lbs, ks0, ks1, W0, W1);
+                    if (row_shared) S::template accumulate<g, 1, true>(off, toff, lbs, ks0, ks1, W0, W1);
+                    else S::template accumulate<g, 1>(off, toff, lbs, ks0, ks1, W0, W1);
                 } else {
                     read_phase_begin(prio);
-                    S::template accumulate<g>(off, toff, lbs, ci, ci, W0, W1);
+                    if (row_shared) S::template accumulate<g, 0, true>(off, toff, lbs, ci, ci, W0, W1);
+                    else S::template accumulate<g>(off, toff, lbs, ci, ci, W0, W1);
                 }
             } else {
                 read_phase_begin(prio);
