@@ -33,6 +33,7 @@ SYMBOLS = [
     "hmk_greedy_cluster", "hmk_greedy_from_edges", "hmk_greedy_from_edges_dev", "hmk_greedy_last_phases",
     "hmk_clinkage_cluster", "hmk_clinkage_from_edges", "hmk_set_java_hashset", "hmk_reserve",
     "hmk_cluster_pairs_shifted", "hmk_clinkage_merge", "hmk_clinkage_merge_from_edges",
+    "hmk_cluster_linkage_shifted",
 ]
 
 
@@ -71,6 +72,12 @@ class MergeStats(C.Structure):
     _fields_ = [("n_edges", C.c_uint64), ("pairs_scored", C.c_uint64), ("cluster_pairs", C.c_uint64), ("merges", C.c_int32),
                 ("searches", C.c_int32), ("n_result_clusters", C.c_int32), ("reserved", C.c_int32), ("kernel_ms", C.c_double),
                 ("graph_ms", C.c_double), ("chain_ms", C.c_double)]
+
+
+class LinkageStats(C.Structure):
+    """hmk_linkage_stats"""
+    _fields_ = [("pairs_scored", C.c_uint64), ("n_multi", C.c_uint32), ("n_violating", C.c_uint32), ("launches", C.c_uint32),
+                ("reserved", C.c_uint32), ("kernel_ms", C.c_double)]
 
 
 class GreedyPhases(C.Structure):
@@ -146,6 +153,8 @@ def _load():
     L.hmk_cluster_pairs_shifted.argtypes = [vp, u32, u32, p_u32, u32, i32, i32, i32, p_u64, u64, p_u64, C.POINTER(MergeStats)]
     L.hmk_clinkage_merge.argtypes = [vp, u32, u32, p_u32, p_i32, u32, i32, i32, i32, p_i32, p_i32, p_i32, C.POINTER(MergeStats)]
     L.hmk_clinkage_merge_from_edges.argtypes = [vp, p_u64, u64, u32, u32, p_u32, p_i32, u32, p_i32, p_i32, p_i32, C.POINTER(MergeStats)]
+    L.hmk_cluster_linkage_shifted.argtypes = [vp, u32, u32, p_u32, u32, i32, i32, i32, p_i32, p_u32, p_u32, p_u64, p_i32, p_u32,
+                                              C.POINTER(LinkageStats)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("hmk_destroy", "hmk_last_error", "hmk_last_kernel_ms"):

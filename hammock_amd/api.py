@@ -535,6 +535,31 @@ class Context:
             self.last_merge_stats = stats
             return buf[:n.value].copy()
 
+    def cluster_linkage_shifted(self, r0, r1, member_cluster, n_clusters, max_shift, shift_penalty, threshold, members=True):
+        """hmk_cluster_linkage_shifted: the complete-linkage scores INSIDE given clusters (members [r0, r1), member r in slot
+        member_cluster[r - r0]) -> (min_score int32[n_clusters], min_a, min_b uint32[n_clusters] -- the pair that attains it,
+        min_a < min_b, indices of the uploaded set -- n_below uint64[n_clusters], member_min int32[r1 - r0], member_below
+        uint32[r1 - r0]); the last two are None with members=False.  A slot is a complete-linkage cluster at these parameters
+        iff its n_below is 0.  Statistics: last_linkage_stats."""
+        mc, _ = self._merge_args(r0, r1, member_cluster, None)
+        ncl = int(n_clusters)
+        min_score = np.empty(max(ncl, 1), dtype=np.int32)
+        min_a = np.empty(max(ncl, 1), dtype=np.uint32)
+        min_b = np.empty(max(ncl, 1), dtype=np.uint32)
+        n_below = np.empty(max(ncl, 1), dtype=np.uint64)
+        member_min = np.empty(max(mc.size, 1), dtype=np.int32) if members else None
+        member_below = np.empty(max(mc.size, 1), dtype=np.uint32) if members else None
+        stats = N.LinkageStats()
+        st = N.lib.hmk_cluster_linkage_shifted(self._h, int(r0), int(r1), _ptr(mc, C.c_uint32), ncl, int(max_shift), int(shift_penalty),
+                                               int(threshold), _ptr(min_score, C.c_int32), _ptr(min_a, C.c_uint32), _ptr(min_b, C.c_uint32),
+                                               _ptr(n_below, C.c_uint64), _ptr(member_min, C.c_int32) if members else None,
+                                               _ptr(member_below, C.c_uint32) if members else None, C.byref(stats))
+        if st:
+            self._raise(st)
+        self.last_linkage_stats = stats
+        return (min_score[:ncl], min_a[:ncl], min_b[:ncl], n_below[:ncl],
+                member_min[:mc.size] if members else None, member_below[:mc.size] if members else None)
+
     def _merge_out(self, nm, ncl):
         merged = np.full(max(ncl, 1), -1, dtype=np.int32)
         order = np.full(max(ncl, 1), -1, dtype=np.int32)

@@ -89,6 +89,7 @@ enum {
     SB_MERGE_LEN, SB_MERGE_MSTART,                  // ... row lengths in that order, their prefix sums
     SB_MERGE_TMP,                                   // ... per slot its feasible (slot, min score) records, at the slot's run offset
     SB_MERGE_CNT, SB_MERGE_OSTART, SB_MERGE_SCR, SB_MERGE_SCAN,   // ... feasible counts, their prefix sums, long-run list, scan scratch
+    SB_LINK_TAB, SB_LINK_OUT,                       // the linkage inside given clusters (hmk_linkage.cpp): members by slot + work prefix sums; accumulators
     SB_N
 };
 

@@ -8,7 +8,9 @@
 // GPUs of the node behind one context, the first is the root: hmk_create_multi).
 // Extra modes that the reference does not have: search, assign, match, continue and merge (runSearch, runAssign, ...), each described
 // above its run function.  Every run function is a list of the shared steps below (parseModeArgs ... writeRankedTable) and what is its own.
+#include <deque>
 #include <future>
+#include <map>
 #include <unordered_set>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -138,7 +140,9 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "          hammock-hip match -i <query clusters.tsv> --clusters <initial_clusters_sequences.tsv> -d <directory> [--best <int>]\n"
               << "                      [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [-g <int>] [--device <int>]\n"
               << "          hammock-hip merge -i <clusters.tsv> [--clusters <other clusters.tsv>] -d <directory> [--skip_singletons] [-m <file>]\n"
-              << "                      [-x <int>] [-p <int>] [-g <int>] [--java_hashset <int>] [--device <int>]\n\n"
+              << "                      [-x <int>] [-p <int>] [-g <int>] [--java_hashset <int>] [--device <int>]\n"
+              << "          hammock-hip check -i <clusters.tsv> -d <directory> [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [-g <int>]\n"
+              << "                      [--device <int>]\n\n"
               << "-i, --input <file>\n\tA path to an input file\n\n"
               << "-d, --output_directory <directory>\n\tA directory to store all output files in\n\n"
               << "-t, --threads <int>\n\tAccepted for compatibility (the GPU path ignores it)\n\n"
@@ -157,7 +161,7 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "--database <file>\n\t(search) the reference sequences every query (-i) is scored against\n\n"
               << "--best <int>\n\t(search) keep only the best 1..32 hits of each query; (assign, match) report the best 1..32 feasible clusters (default 1)\n\n"
               << "--clusters <file>\n\t(assign, continue, match) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv);\n\t(merge) a second cluster file: its clusters keep their ids, the -i file's are renumbered behind them\n\n"
-              << "--skip_singletons\n\t(assign, match, merge) only clusters of more than one unique sequence are candidates\n\n"
+              << "--skip_singletons\n\t(assign, match, merge) only clusters of more than one unique sequence are candidates;\n\t(check) clusters of one unique sequence are left out of cluster_linkage.tsv\n\n"
               << "--java_hashset <8|7|6>\n\t(clinkage, merge) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
 }
 
@@ -1089,6 +1093,124 @@ int runMerge(const std::vector<std::string> &args) {
     }
 }
 
+// `hammock-hip check -i clusters.tsv -d dir [-x -p -g] [--skip_singletons]`: is the clustering of a cluster file (the format the
+// other modes read through --clusters) a set of complete-linkage clusters at these parameters?  hmk_cluster_linkage_shifted over the
+// file's clusters: per cluster the minimum ShiftedScorer score over the pairs of its sequences (ClinkageClusterScorer.java:30-49
+// without the early exit, inside one cluster), the pair that attains it and the number of pairs below the threshold; per sequence
+// its own minimum and count.  Defaults of -x / -g are greedy's over the file's sequences, -x clamped by the shortest one; -p 0.
+// Writes cluster_linkage.tsv (one line per cluster in file order; --skip_singletons leaves clusters of one unique sequence out)
+// and cluster_members.tsv (the sequences of clusters of more than one, in file order).  The exit status says whether the run
+// succeeded, not what it found; a cluster file the loader rejects is an error of the arguments here, 2.
+int runCheck(const std::vector<std::string> &args) {
+    Options o;
+    parseCommonArgs(args, o);
+    parseModeArgs(args, o, -1);
+    requireOneDevice(o, "check", "a check");
+    requireInput(o);
+    makeOutputDirectory(o, o.parentDir);
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        ContextFuture contextReady = beginRun(o, logger, false);
+        logRunStart(logger, "check", args);
+        logger.logAndStderr("Loading clusters...");
+        std::vector<ClusterPtr> clusters;
+        try {
+            clusters = FileIOManager::loadClustersFromCsv(o.inputFileName);
+            if (clusters.empty()) throw FileFormatException("Error. The cluster file holds no clusters.");
+        } catch (const FileFormatException &e) {
+            logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
+            logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
+            return 2;
+        }
+        const std::vector<UniqueSequencePtr> all = sequencesOf(clusters);
+        logger.logAndStderr(std::to_string(clusters.size()) + " clusters of " + std::to_string(all.size()) + " sequences loaded.");
+        const SequenceListSummary summary = summariseSequences(all);
+        settleShiftAndThreshold(o, logger, summary, summary, summary, "Check");
+
+        std::vector<UniqueSequencePtr> upload;
+        const Candidates cand = appendCandidates(clusters, false, 0, upload);
+        const uint32_t n = (uint32_t)upload.size(), ncl = (uint32_t)cand.slots.size();
+        std::vector<int32_t> minScore(ncl), memberMin(n);
+        std::vector<uint32_t> minA(ncl), minB(ncl), memberBelow(n);
+        std::vector<uint64_t> nBelow(ncl);
+        hmk_linkage_stats stats{};
+        logger.logAndStderr("Checking...");
+        const auto time0 = std::chrono::steady_clock::now();
+        {
+            const std::shared_ptr<NativeContext> nc = contextReady.get();
+            nc->setSequences(upload, true);
+            const int st = hmk_cluster_linkage_shifted(nc->get(), 0, n, cand.memberCluster.data(), ncl, o.maxShift, o.shiftPenalty,
+                                                       o.sequenceClusteringThreshold, minScore.data(), minA.data(), minB.data(), nBelow.data(),
+                                                       memberMin.data(), memberBelow.data(), &stats);
+            if (st) nc->raise(st, nullptr);
+        }
+        logger.logAndStderr("Ready. Check time: " + std::to_string(millisSince(time0)));
+        logger.logAndStderr("Clusters of more than one sequence: " + std::to_string(stats.n_multi) + ", pairs scored: " + std::to_string(stats.pairs_scored) +
+                            ", GPU kernels: " + std::to_string(stats.kernel_ms) + " ms");
+        logger.logAndStderr("Saving results to output files...");
+        const std::string linkageCsv = o.workingDirectory + "/cluster_linkage.tsv", membersCsv = o.workingDirectory + "/cluster_members.tsv";
+        {
+            std::ofstream out(linkageCsv);
+            if (!out) throw HammockException("cannot write " + linkageCsv);
+            out << "cluster_id\tunique_size\tsize\tlinkage_score\tpairs_below\tworst_sequence_1\tworst_sequence_2\n";
+            for (uint32_t c = 0; c < ncl; c++) {
+                const Cluster &cl = *clusters[c];
+                if (cl.getUniqueSize() <= 1) {
+                    if (!o.skipSingletons) out << cl.getId() << '\t' << cl.getUniqueSize() << '\t' << cl.size() << "\tNA\t0\tNA\tNA\n";
+                    continue;
+                }
+                out << cl.getId() << '\t' << cl.getUniqueSize() << '\t' << cl.size() << '\t' << minScore[c] << '\t' << nBelow[c] << '\t'
+                    << upload[minA[c]]->getSequenceString() << '\t' << upload[minB[c]]->getSequenceString() << '\n';
+            }
+        }
+        {
+            std::ofstream out(membersCsv);
+            if (!out) throw HammockException("cannot write " + membersCsv);
+            out << "cluster_id\tsequence\tmin_score\tpairs_below\n";
+            // in the file's line order: the loader groups the lines by cluster, so each line finds its sequence again by (id, string),
+            // equal lines in their order
+            std::map<std::pair<int, std::string>, std::deque<uint32_t>> uploaded;
+            for (uint32_t k = 0; k < n; k++)
+                uploaded[{clusters[cand.memberCluster[k]]->getId(), upload[k]->getSequenceString()}].push_back(k);
+            const std::vector<std::string> lines = FileIOManager::readLines(o.inputFileName);
+            std::vector<std::string> header = FileIOManager::splitChar(lines[0], CSV_SEPARATOR, true);
+            std::vector<long> dropped;   // the columns the loader drops, in its order
+            for (const char *drop : {"alignment", "sum"}) {
+                const auto at = std::find(header.begin(), header.end(), drop);
+                if (at == header.end()) continue;
+                dropped.push_back((long)(at - header.begin()));
+                header.erase(at);
+            }
+            for (size_t l = 1; l < lines.size(); l++) {
+                std::vector<std::string> f = FileIOManager::splitChar(lines[l], CSV_SEPARATOR, true);
+                for (long d : dropped) f.erase(f.begin() + d);
+                std::deque<uint32_t> &q = uploaded.at({javaIntegerDecode(f[0]), f[1]});
+                const uint32_t k = q.front();
+                q.pop_front();
+                const Cluster &cl = *clusters[cand.memberCluster[k]];
+                if (cl.getUniqueSize() <= 1) continue;
+                out << cl.getId() << '\t' << upload[k]->getSequenceString() << '\t' << memberMin[k] << '\t' << memberBelow[k] << '\n';
+            }
+        }
+        logger.logAndStderr("Clusters in: " + linkageCsv);
+        logger.logAndStderr("Sequences in: " + membersCsv);
+        std::string lowest = "NA";
+        {
+            int32_t best = INT32_MAX;
+            for (uint32_t c = 0; c < ncl; c++)
+                if (clusters[c]->getUniqueSize() > 1 && minScore[c] < best) {
+                    best = minScore[c];
+                    lowest = std::to_string(best) + " (cluster " + std::to_string(clusters[c]->getId()) + ")";
+                }
+        }
+        logger.logAndStderr(std::to_string(stats.n_violating) + " of " + std::to_string(ncl) + " clusters hold a pair below the threshold " +
+                            std::to_string(o.sequenceClusteringThreshold) + "; lowest linkage score " + lowest);
+        return 0;
+    } catch (...) {
+        return reportRunError(logger, false);
+    }
+}
+
 // `hammock-hip io-selftest ...`: exposes the loaders / orderings to the CPU test-suite (no GPU involved)
 int ioSelftest(const std::vector<std::string> &args) {
     if (args.size() >= 3 && args[1] == "matrix") {
@@ -1209,6 +1331,7 @@ int main(int argc, char **argv) {
         if (args[0] == "continue") return runContinue(args);
         if (args[0] == "match") return runMatch(args);
         if (args[0] == "merge") return runMerge(args);
+        if (args[0] == "check") return runCheck(args);
         if (args[0] == "io-selftest") return ioSelftest(args);
         if (args[0] == "dump-matrix") {   // the default matrix in the text format FileIOManager.loadScoringMatrix reads
             std::cout << "# BLOSUM62 substitution matrix (public NCBI table), 24 x 24, order " << AMINO_ACIDS << "\n"

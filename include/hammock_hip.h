@@ -503,6 +503,44 @@ int hmk_clinkage_merge_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t 
                                   const uint32_t *member_cluster, const int32_t *cluster_id, uint32_t n_clusters,
                                   int32_t *merged_id, int32_t *result_order, int32_t *member_rank, hmk_merge_stats *stats);
 
+/* ---- complete-linkage scores inside given clusters -------------------------------- */
+
+typedef struct {
+    uint64_t pairs_scored;     /* sum over slots of s(s-1)/2 */
+    uint32_t n_multi;          /* slots with two or more members */
+    uint32_t n_violating;      /* slots with a pair below the threshold */
+    uint32_t launches, reserved;
+    double   kernel_ms;        /* device time, HIP events */
+} hmk_linkage_stats;
+
+/* Is a given clustering a set of complete-linkage clusters at these parameters, and which clusters and members break it?  The
+ * half hmk_cluster_pairs_shifted leaves open: that call covers the pairs between clusters, this one the pairs inside a cluster.
+ * Members [r0, r1) of the hmk_set_sequences set with member_cluster and n_clusters as hmk_cluster_pairs_shifted takes them.
+ *   score      score(a, b) = ShiftedScorer(matrix, shift_penalty, max_shift).sequenceScore(seq1 = the larger index, seq2 = the
+ *              smaller) (ShiftedScorer.java:48-100), the orientation of the edges of hmk_neighbors_shifted.
+ *   per slot c, over the unordered pairs {a, b} of distinct members of c:
+ *     min_score[c]         the minimum score: what ClinkageClusterScorer.clusterScore computes without its early exit
+ *                          (ClinkageClusterScorer.java:30-49), applied inside a single cluster
+ *     min_a[c] < min_b[c]  the pair that attains it (indices of the uploaded set); among tied pairs the smallest min_a, then the
+ *                          smallest min_b
+ *     n_below[c]           the number of pairs with score < threshold (a pair scoring exactly the threshold is not below): slot c
+ *                          is a complete-linkage cluster at these parameters iff n_below[c] == 0
+ *     a slot of one member gets INT32_MAX, UINT32_MAX, UINT32_MAX, 0
+ *   per member m (both arrays may be NULL, together): member_min[m - r0] = the minimum score of m against the other members of
+ *     its slot (INT32_MAX in a slot of one member), member_below[m - r0] = how many of those scores are below the threshold: the
+ *     members to evict.
+ *   checks     HMK_ERR_BAD_ARG before the device is looked at (a host-only context answers them): the range and slot checks of
+ *              hmk_cluster_pairs_shifted, a null member_cluster with a non-empty range, a null required output, an asymmetric
+ *              matrix.  Then the checks of hmk_search_shifted over the range (the shift against the shortest length, threshold
+ *              and int16 limits; here the lowest possible score must fit int16 as well).  Never HMK_ERR_CAPACITY.
+ * Every pair inside a slot is scored, sum of s(s-1)/2, and nothing else: no pass over [r0, r1), no edge list.  Slots of few
+ * members have their pairs enumerated flat over all such slots, large ones are tiled (k_linkage.hip); the scratch is
+ * O(members + clusters).  On a hmk_create_multi context the call runs on the root device. */
+int hmk_cluster_linkage_shifted(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_cluster, uint32_t n_clusters,
+                                int max_shift, int shift_penalty, int threshold, int32_t *min_score, uint32_t *min_a,
+                                uint32_t *min_b, uint64_t *n_below, int32_t *member_min, uint32_t *member_below,
+                                hmk_linkage_stats *stats);
+
 /* Where the time of the last hmk_greedy_cluster / hmk_greedy_from_edges_dev call of this context went
  * (milliseconds; the span of Hammock.java:406-411 minus the sort).  score_ms and csr_ms are device times (HIP events on
  * the call's stream), the others host wall time.  The parts overlap (phase 1 runs while the rest of the pair space is
