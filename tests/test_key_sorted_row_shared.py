@@ -126,7 +126,9 @@ def test_rows_past_the_end(M, n):
 def test_byte_lane_edges(M):
     # W at both key positions of every 12-mer (the largest cell, 11, at both): every full group is row-shared and the merged
     # entries hold the largest bytes there are.  classify() proves 8-bit lanes for thresholds 5 .. 80: at 80 the planes start at
-    # the bottom of the byte, at 5 a row of W against itself ends at 255
+    # the bottom of the byte, at 5 a pair that scored 12 x 11 would end at 255.  No pair of this input does: a sequence is never
+    # scored against itself and under BLOSUM62 only W against W is 11, so these lanes stay below the top of the byte -- the
+    # pairs that land on 0 and on 255 are test_score_field_edges.py's, which makes B an exact copy of W
     rng = np.random.default_rng(9)
     rich = "WCHYPFW"
     bases = ["".join(rng.choice(list(rich), 12)) for _ in range(6)] + ["W" * 12]

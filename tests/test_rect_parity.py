@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from conftest import random_peptides
+from lane_model import java_round, lane_path
 
 import hammock_amd
 from hammock_amd.synth import synth_peptides
@@ -55,35 +56,6 @@ def matrix_named(matrices, name):
     else:
         assert base == "blosum62"
     return asymmetric(M) if asym else M.copy()
-
-
-def java_round(v):
-    """Math.round for positive doubles: half up"""
-    return int(np.floor(v + 0.5))
-
-
-def lane_path(M, la, lb, X, p, thr):
-    """classify's rule (hmk_plan.cpp) without a row bound -> "u8" | "u16" | "direct": lanes start at g + penalty - bias * cells and
-    must hold every cell at the matrix maximum, for each of the 2X + d + 1 shifts"""
-    m, nl = min(la, lb), max(la, lb)
-    d = nl - m
-    nd = 2 * X + d + 1
-    bias = -int(M.min()) if M.min() < 0 else 0
-    cell_max = int(M.max()) + bias
-    for name, lane_max, half, max_nd in (("u8", 255, 128, 32), ("u16", 65535, 32768, 16)):
-        if nd > max_nd or cell_max > 255:
-            continue
-        g = half - thr
-        for t in range(nd):
-            s = t - X
-            ncell = m + s if s <= 0 else min(m, nl - s)
-            pen = d * p + (-s * 2 * p if s < 0 else 0) + ((s - d) * 2 * p if s > d else 0)
-            c0 = g + pen - bias * ncell
-            if c0 < 0 or c0 + ncell * cell_max > lane_max:
-                break
-        else:
-            return name
-    return "direct"
 
 
 def predicted_tiers(M, lens_q, lens_r, X, p, thr):
