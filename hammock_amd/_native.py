@@ -33,7 +33,7 @@ SYMBOLS = [
     "hmk_greedy_cluster", "hmk_greedy_from_edges", "hmk_greedy_from_edges_dev", "hmk_greedy_last_phases",
     "hmk_clinkage_cluster", "hmk_clinkage_from_edges", "hmk_set_java_hashset", "hmk_reserve",
     "hmk_cluster_pairs_shifted", "hmk_clinkage_merge", "hmk_clinkage_merge_from_edges",
-    "hmk_cluster_linkage_shifted",
+    "hmk_cluster_linkage_shifted", "hmk_clinkage_split", "hmk_clinkage_split_from_edges",
 ]
 
 
@@ -78,6 +78,13 @@ class LinkageStats(C.Structure):
     """hmk_linkage_stats"""
     _fields_ = [("pairs_scored", C.c_uint64), ("n_multi", C.c_uint32), ("n_violating", C.c_uint32), ("launches", C.c_uint32),
                 ("reserved", C.c_uint32), ("kernel_ms", C.c_double)]
+
+
+class SplitStats(C.Structure):
+    """hmk_split_stats"""
+    _fields_ = [("pairs_scored", C.c_uint64), ("n_edges", C.c_uint64), ("n_multi", C.c_uint32), ("n_split", C.c_uint32),
+                ("n_result_clusters", C.c_uint32), ("merges", C.c_uint32), ("crash_slot", C.c_int32), ("reserved", C.c_int32),
+                ("kernel_ms", C.c_double), ("chain_ms", C.c_double), ("copy_ms", C.c_double)]
 
 
 class GreedyPhases(C.Structure):
@@ -155,6 +162,9 @@ def _load():
     L.hmk_clinkage_merge_from_edges.argtypes = [vp, p_u64, u64, u32, u32, p_u32, p_i32, u32, p_i32, p_i32, p_i32, C.POINTER(MergeStats)]
     L.hmk_cluster_linkage_shifted.argtypes = [vp, u32, u32, p_u32, u32, i32, i32, i32, p_i32, p_u32, p_u32, p_u64, p_i32, p_u32,
                                               C.POINTER(LinkageStats)]
+    L.hmk_clinkage_split.argtypes = [vp, u32, u32, p_u32, u32, i32, i32, i32, p_u32, p_u32, p_i32, p_i32, p_i32, p_u32, C.POINTER(SplitStats)]
+    L.hmk_clinkage_split_from_edges.argtypes = [vp, p_u64, u64, u32, u32, p_u32, u32, p_u32, p_u32, p_i32, p_i32, p_i32, p_u32,
+                                                C.POINTER(SplitStats)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("hmk_destroy", "hmk_last_error", "hmk_last_kernel_ms"):

@@ -595,6 +595,47 @@ class Context:
         self.member_rank = self.member_rank[:mc.size]
         return merged[:cid.size], order[:stats.n_result_clusters]
 
+    # -- splitting given clusters by complete linkage -------------------------------------
+    def _split(self, call, r0, mc, ncl):
+        """runs call(outputs..., stats) -> (split_cluster uint32[nm], n_parts uint32[ncl], part_id int32[nm], member_rank int32[nm],
+        part_order: one int32 array per slot); statistics in last_split_stats"""
+        nm = mc.size
+        split = np.zeros(max(nm, 1), dtype=np.uint32)
+        n_parts = np.zeros(max(ncl, 1), dtype=np.uint32)
+        part_id = np.zeros(max(nm, 1), dtype=np.int32)
+        rank = np.zeros(max(nm, 1), dtype=np.int32)
+        order = np.zeros(max(nm, 1), dtype=np.int32)
+        start = np.zeros(ncl + 1, dtype=np.uint32)
+        stats = N.SplitStats()
+        st = call(_ptr(split, C.c_uint32), _ptr(n_parts, C.c_uint32), _ptr(part_id, C.c_int32), _ptr(rank, C.c_int32), _ptr(order, C.c_int32),
+                  _ptr(start, C.c_uint32), C.byref(stats))
+        if st == N.HMK_ERR_REFERENCE_WOULD_CRASH:
+            raise ReferenceWouldCrash(N.lib.hmk_last_error(self._h).decode(), 0, int(stats.crash_slot))
+        if st:
+            self._raise(st)
+        self.last_split_stats = stats
+        n_parts = n_parts[:ncl]
+        lists = [order[int(start[c]):int(start[c]) + int(n_parts[c])].copy() for c in range(ncl)] if nm else [order[:0] for _ in range(ncl)]
+        return split[:nm], n_parts, part_id[:nm], rank[:nm], lists
+
+    def clinkage_split(self, r0, r1, member_cluster, n_clusters, max_shift, shift_penalty, threshold):
+        """hmk_clinkage_split: the reference's complete-linkage clustering run INSIDE each given cluster (members [r0, r1), member r
+        in slot member_cluster[r - r0]) -> (split_cluster uint32[r1 - r0] -- the new clustering's member_cluster, with
+        last_split_stats.n_result_clusters slots --, n_parts uint32[n_clusters], part_id int32[r1 - r0], member_rank int32[r1 - r0],
+        part_order: per slot the int32 array of its returned ids in list order).  ReferenceWouldCrash.index is the slot."""
+        mc, _ = self._merge_args(r0, r1, member_cluster, None)
+        ncl = int(n_clusters)
+        return self._split(lambda *out: N.lib.hmk_clinkage_split(self._h, int(r0), int(r1), _ptr(mc, C.c_uint32), ncl, int(max_shift),
+                                                                 int(shift_penalty), int(threshold), *out), r0, mc, ncl)
+
+    def clinkage_split_from_edges(self, edges, r0, r1, member_cluster, n_clusters):
+        """hmk_clinkage_split_from_edges: the same from a sequence-level edge list (works on a host-only context)."""
+        edges = np.ascontiguousarray(edges, dtype=np.uint64)
+        mc, _ = self._merge_args(r0, r1, member_cluster, None)
+        ncl = int(n_clusters)
+        return self._split(lambda *out: N.lib.hmk_clinkage_split_from_edges(self._h, _ptr(edges, C.c_uint64), edges.size, int(r0), int(r1),
+                                                                            _ptr(mc, C.c_uint32), ncl, *out), r0, mc, ncl)
+
     def greedy_phases(self):
         """hmk_greedy_last_phases: per-phase milliseconds of the last greedy_cluster / greedy_from_edges_dev call."""
         ph = N.GreedyPhases()

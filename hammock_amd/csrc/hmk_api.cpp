@@ -103,7 +103,7 @@ void hmk_destroy(hmk_ctx *ctx) {
         for (DevBuf *b : {&ctx->d_res32, &ctx->d_len, &ctx->d_M, &ctx->d_rows_scratch}) b->release();
         for (DevBuf &b : ctx->sb) b.release();
         ctx->edges.release();
-        for (PinnedBuf *b : {&ctx->h_start, &ctx->h_stage, &ctx->h_merge, &ctx->h_adj}) b->release();
+        for (PinnedBuf *b : {&ctx->h_start, &ctx->h_stage, &ctx->h_merge, &ctx->h_split, &ctx->h_adj}) b->release();
         for (void *h : {(void *)ctx->h_counts, (void *)ctx->h_loop})
             if (h) HMK_QUIET(hipHostFree(h));
         std::vector<hipStream_t> streams(ctx->side, ctx->side + hmk_ctx::N_SIDE);

@@ -90,6 +90,7 @@ enum {
     SB_MERGE_TMP,                                   // ... per slot its feasible (slot, min score) records, at the slot's run offset
     SB_MERGE_CNT, SB_MERGE_OSTART, SB_MERGE_SCR, SB_MERGE_SCAN,   // ... feasible counts, their prefix sums, long-run list, scan scratch
     SB_LINK_TAB, SB_LINK_OUT,                       // the linkage inside given clusters (hmk_linkage.cpp): members by slot + work prefix sums; accumulators
+    SB_SPLIT_SCORES,                                // the split of given clusters (hmk_split.cpp): the slots' dense triangles of int16 scores
     SB_N
 };
 
@@ -213,6 +214,7 @@ struct hmk_ctx {
     PinnedBuf h_stage;   // what the merge uploads after phase 1 (cluster_of, sizes, leftovers, ...)
     PinnedBuf h_adj;     // adjacency rows fetched so far
     PinnedBuf h_merge;   // the cluster-level lists of hmk_merge.cpp (k_merge_compact stores them here)
+    PinnedBuf h_split;   // the score triangles of hmk_split.cpp, copied back in one piece
     unsigned long long *h_loop = nullptr;    // pinned, coherent: progress word of the device-side second loop (written by k_loop_apply)
     unsigned long long *h_counts = nullptr;  // pinned: final segment counts [HMK_EDGE_SHARDS], band snapshot [HMK_EDGE_SHARDS], misc (HC_* below)
     hmk_greedy_phases phases{};
@@ -347,6 +349,10 @@ int build_plan_local_search(hmk_ctx *ctx, PlanLocal &pl, uint32_t q0, uint32_t q
 int build_plan_triangle(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1);
 // the parameter checks of a shifted rectangle (the shift against both ranges, threshold and int16 limits)
 int check_shifted(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
+// ---- hmk_linkage.cpp
+// the parameter checks of a call that scores the pairs inside slots of the members [r0, r1): check_shifted over the range, and the
+// lowest possible score fits int16, the indices 24 bits
+int check_link_scores(hmk_ctx *ctx, int X, int p, int thr, uint32_t r0, uint32_t r1);
 // ---- hmk_assign.cpp
 // the clusters' argument checks of the assignment and the continuation (`what` names the call in the range message):
 // members[c] = slot c's members, size[c] = its Cluster.size()

@@ -1,9 +1,12 @@
-// hmk_linkage.h -- launchers of k_linkage.hip (complete-linkage scores inside given clusters), used by hmk_linkage.cpp.
+// hmk_linkage.h -- launchers of k_linkage.hip (complete-linkage scores inside given clusters), used by hmk_linkage.cpp, and the host
+// tables of the pairs inside given clusters, which hmk_split.cpp (k_split.hip) decodes its work from too.
 #ifndef HMK_LINKAGE_H
 #define HMK_LINKAGE_H
 
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
+
+#include <vector>
 
 namespace hmk {
 
@@ -29,6 +32,24 @@ hipError_t launch_linkage_flat(const uint8_t *res32, const uint8_t *len, const i
 hipError_t launch_linkage_tiled(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const uint32_t *tab, const uint32_t *bslot,
                                 const uint32_t *bmstart, const uint32_t *btstart, uint32_t nb, uint32_t n_tiles, uint32_t r0, int X, int p,
                                 int thr, uint64_t *key, unsigned long long *below, int32_t *member_min, uint32_t *member_below, hipStream_t s);
+
+// The host tables both calls upload, O(members + clusters): the members of the slots of two or more by slot, each slot's in index
+// order, the flat slots' first; per flat / big slot the caller's slot and its members' places in tab; the prefix sums the kernels
+// decode their work from.  One block of 32-bit words h (offsets o_*, in words), the 64-bit tables 8-byte aligned behind the others:
+//   tab | fslot[nf] | fmstart[nf + 1] | bslot[nb] | bmstart[nb + 1] | btstart[nb + 1] | fpstart[nf + 1] (u64) | tbase[nb + 1] (u64)
+// tbase[g]: where big slot g's dense triangle of s (s - 1) / 2 entries begins in an array that holds the flat pair space first
+// (k_split.hip); tbase[nb] = total_pairs.
+struct LinkTables {
+    std::vector<uint32_t> h;
+    uint32_t nf = 0, nb = 0, n_tiles = 0;
+    size_t o_tab = 0, o_fslot = 0, o_fmstart = 0, o_bslot = 0, o_bmstart = 0, o_btstart = 0, o_fpstart = 0, o_tbase = 0;
+    unsigned long long flat_pairs = 0, total_pairs = 0;
+    const unsigned long long *fpstart() const { return reinterpret_cast<const unsigned long long *>(h.data() + o_fpstart); }
+    const unsigned long long *tbase() const { return reinterpret_cast<const unsigned long long *>(h.data() + o_tbase); }
+};
+// members[c]: slot c's member count (check_clusters); member_cluster[nm]: the slot of member r0 + i (hmk_linkage.cpp)
+void build_link_tables(uint32_t r0, uint32_t nm, const uint32_t *member_cluster, uint32_t n_clusters, const std::vector<uint32_t> &members,
+                       LinkTables &T);
 
 }  // namespace hmk
 #endif

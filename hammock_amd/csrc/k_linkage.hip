@@ -11,8 +11,7 @@
 // atomicMin of (score + 32768) << 48 | a << 24 | b: reduced in the wave first, one atomic per wave and slot segment.
 #include <algorithm>
 
-#include "hmk_device.h"
-#include "hmk_linkage.h"
+#include "hmk_link_device.h"
 
 namespace hmk {
 
@@ -29,25 +28,6 @@ __device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int d) {
 __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int d) {
     const uint32_t lo = __shfl_xor((uint32_t)v, d), hi = __shfl_xor((uint32_t)(v >> 32), d);
     return ((uint64_t)hi << 32) | lo;
-}
-
-// largest k in [0, n) with start[k] <= x (start[0] = 0 <= x < start[n])
-template <typename T>
-__device__ __forceinline__ uint32_t run_of(const T *__restrict__ start, uint32_t n, T x) {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (start[mid] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// q = i (i - 1) / 2 + j with j < i: the row of the strict lower triangle that holds entry q
-__device__ __forceinline__ uint32_t tri_row(uint32_t q) {
-    uint32_t i = (uint32_t)((1.0f + sqrtf(1.0f + 8.0f * (float)q)) * 0.5f);
-    while (i > 1 && (uint64_t)i * (i - 1) / 2 > q) i--;
-    while ((uint64_t)(i + 1) * i / 2 <= q) i++;
-    return i;
 }
 
 }  // namespace
@@ -103,17 +83,15 @@ k_linkage_flat(const uint8_t *__restrict__ res32, const uint8_t *__restrict__ le
         int score = INT32_MAX;
         if (valid) {
             f = run_of<unsigned long long>(fpstart, nf, k);
-            const uint32_t q = (uint32_t)(k - fpstart[f]);
-            ib = tri_row(q);
-            ia = q - ib * (ib - 1) / 2;
+            const TriEntry e = tri_entry((uint32_t)(k - fpstart[f]));
+            ib = e.row;
+            ia = e.col;
             mbase = fmstart[f];
             a = tab[mbase + ia];
             b = tab[mbase + ib];   // a < b: the members of a slot are in index order
             if (members && tid == 0) span[0] = mbase;
             if (members && k == k_last) span[1] = fmstart[f + 1];
-            stage_sequence(s1, res32, b);
-            stage_sequence(s2, res32, a);
-            score = shifted_score_literal(M, reinterpret_cast<const uint8_t *>(s1), len[b], reinterpret_cast<const uint8_t *>(s2), len[a], X, p);
+            score = link_pair_score(M, s1, s2, res32, len, a, b, X, p);
         }
         const bool low = valid && score < thr;
         // ---- the slot side: segmented scan over the wave's lanes (the slots of consecutive pairs never decrease)
@@ -189,21 +167,15 @@ k_linkage_tiled(const uint8_t *__restrict__ res32, const uint8_t *__restrict__ l
     const bool members = member_min != nullptr;   // (uniform)
     uint32_t *mine = colseq + tid * SEQ_STRIDE_DW;
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint32_t g = run_of<uint32_t>(btstart, nb, tile);
-        const uint32_t t = tile - btstart[g];
-        uint32_t i = (uint32_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-        while (i > 0 && (uint64_t)i * (i + 1) / 2 > t) i--;
-        while ((uint64_t)(i + 1) * (i + 2) / 2 <= t) i++;
-        const uint32_t j = t - (uint32_t)((uint64_t)i * (i + 1) / 2);
+        uint32_t g, i, j;
+        link_tile_decode(btstart, nb, tile, g, i, j);
         const uint32_t mbase = bmstart[g], s = bmstart[g + 1] - mbase;
         const uint32_t row0 = i * T, col0 = j * T;           // places in the member list; row0 < s
         const uint32_t nrows = min((uint32_t)T, s - row0), ncols = min((uint32_t)T, s - col0);
         __syncthreads();   // the matrix stands; the last tile's rows have been flushed
         if ((uint32_t)tid < nrows) {
             const uint32_t idx = tab[mbase + row0 + tid];
-            const u32x4 *src = reinterpret_cast<const u32x4 *>(res32 + (size_t)idx * 32);
-            reinterpret_cast<u32x4 *>(rowseq)[tid * 2] = src[0];
-            reinterpret_cast<u32x4 *>(rowseq)[tid * 2 + 1] = src[1];
+            link_stage_row(rowseq, tid, res32, idx);
             rowidx[tid] = idx;
             rowlen[tid] = len[idx];
         }

@@ -142,6 +142,8 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "          hammock-hip merge -i <clusters.tsv> [--clusters <other clusters.tsv>] -d <directory> [--skip_singletons] [-m <file>]\n"
               << "                      [-x <int>] [-p <int>] [-g <int>] [--java_hashset <int>] [--device <int>]\n"
               << "          hammock-hip check -i <clusters.tsv> -d <directory> [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [-g <int>]\n"
+              << "                      [--device <int>]\n"
+              << "          hammock-hip split -i <clusters.tsv> -d <directory> [-m <file>] [-x <int>] [-p <int>] [-g <int>] [--java_hashset <int>]\n"
               << "                      [--device <int>]\n\n"
               << "-i, --input <file>\n\tA path to an input file\n\n"
               << "-d, --output_directory <directory>\n\tA directory to store all output files in\n\n"
@@ -162,7 +164,7 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "--best <int>\n\t(search) keep only the best 1..32 hits of each query; (assign, match) report the best 1..32 feasible clusters (default 1)\n\n"
               << "--clusters <file>\n\t(assign, continue, match) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv);\n\t(merge) a second cluster file: its clusters keep their ids, the -i file's are renumbered behind them\n\n"
               << "--skip_singletons\n\t(assign, match, merge) only clusters of more than one unique sequence are candidates;\n\t(check) clusters of one unique sequence are left out of cluster_linkage.tsv\n\n"
-              << "--java_hashset <8|7|6>\n\t(clinkage, merge) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
+              << "--java_hashset <8|7|6>\n\t(clinkage, merge, split) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
 }
 
 std::string labelsToString(bool have, const std::vector<std::string> &labels) {  // List.toString() / "null"
@@ -1211,6 +1213,116 @@ int runCheck(const std::vector<std::string> &args) {
     }
 }
 
+// `hammock-hip split -i clusters.tsv -d dir [-x -p -g] [--java_hashset V]`: splits the clusters of a cluster file into complete-linkage
+// clusters at these parameters -- what acts on check's answer.  hmk_clinkage_split over the file's clusters: per cluster
+// ClinkageSequenceClusterer.cluster (ClinkageSequenceClusterer.java:43-124) on its sequences alone, in file order.  Defaults of
+// -x / -g / -p are check's.  The result list is the source clusters in file order: a cluster that comes back in one part is written as
+// it was read (same id, same member order); the parts of a split cluster follow in list order (:121-123), their members in
+// getSequences() order (:105-106), their ids continuing from the file's largest id in that order.  Writes the stage-1 files of greedy
+// and split_clusters.tsv, one line per resulting cluster.  Exit codes as check: a cluster file the loader rejects is 2.
+int runSplit(const std::vector<std::string> &args) {
+    Options o;
+    parseCommonArgs(args, o);
+    parseModeArgs(args, o, -1);
+    requireOneDevice(o, "split", "a split");
+    requireInput(o);
+    makeOutputDirectory(o, o.parentDir);
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        ContextFuture contextReady = beginRun(o, logger, false);
+        logRunStart(logger, "split", args);
+        logger.logAndStderr("Loading clusters...");
+        MergeInput in;
+        try {
+            in = loadMergeInput(o.inputFileName, std::string());
+            if (in.clusters.empty()) throw FileFormatException("Error. The cluster file holds no clusters.");
+        } catch (const FileFormatException &e) {
+            logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
+            logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
+            return 2;
+        }
+        const std::vector<ClusterPtr> &clusters = in.clusters;
+        if (o.haveLabels) in.labels = FileIOManager::splitChar(o.labelString, ',', true);
+        const std::vector<UniqueSequencePtr> all = sequencesOf(clusters);
+        logger.logAndStderr(std::to_string(clusters.size()) + " clusters of " + std::to_string(all.size()) + " sequences loaded.");
+        requireOccurrences(all, "Error in cluster file");
+        const SequenceListSummary summary = summariseSequences(all);
+        settleShiftAndThreshold(o, logger, summary, summary, summary, "Split");
+        logger.logAndStderr("Parameters: max shift " + std::to_string(o.maxShift) + ", gap penalty " + std::to_string(o.shiftPenalty) + ", threshold " +
+                            std::to_string(o.sequenceClusteringThreshold) + ", java_hashset " + std::to_string(o.javaHashSet));
+
+        std::vector<UniqueSequencePtr> upload;
+        const Candidates cand = appendCandidates(clusters, false, 0, upload);
+        const uint32_t n = (uint32_t)upload.size(), ncl = (uint32_t)cand.slots.size();
+        std::vector<uint32_t> splitCluster(n), nParts(ncl), partStart(ncl + 1);
+        std::vector<int32_t> partId(n), rank(n), partOrder(n);
+        hmk_split_stats stats{};
+        logger.logAndStderr("Splitting...");
+        const auto time0 = std::chrono::steady_clock::now();
+        {
+            const std::shared_ptr<NativeContext> nc = contextReady.get();
+            nc->setSequences(upload, true);
+            int st = hmk_set_java_hashset(nc->get(), o.javaHashSet);
+            if (st) nc->raise(st, nullptr);
+            st = hmk_clinkage_split(nc->get(), 0, n, cand.memberCluster.data(), ncl, o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold,
+                                    splitCluster.data(), nParts.data(), partId.data(), rank.data(), partOrder.data(), partStart.data(), &stats);
+            if (st) nc->raise(st, nullptr);
+        }
+        const long long ms = millisSince(time0);
+        int maxId = INT32_MIN;
+        for (auto &cl : clusters) maxId = std::max(maxId, cl->getId());
+        std::vector<ClusterPtr> result;
+        std::vector<int> sourceOf, partsOf;   // per resulting cluster: its source cluster's id, that cluster's number of parts
+        for (uint32_t c = 0; c < ncl; c++) {   // (every cluster is a candidate: slot c is cluster c, its members upload[partStart[c] ...))
+            if (nParts[c] <= 1) {
+                result.push_back(clusters[c]);
+                sourceOf.push_back(clusters[c]->getId());
+                partsOf.push_back(1);
+                continue;
+            }
+            for (uint32_t t = 0; t < nParts[c]; t++) {
+                const int32_t id = partOrder[partStart[c] + t];
+                std::vector<UniqueSequencePtr> members;
+                for (uint32_t k = partStart[c]; k < partStart[c + 1]; k++) {
+                    if (partId[k] != id) continue;
+                    if (members.size() <= (size_t)rank[k]) members.resize((size_t)rank[k] + 1);
+                    members[rank[k]] = upload[k];
+                }
+                result.push_back(std::make_shared<Cluster>(members, ++maxId));
+                sourceOf.push_back(clusters[c]->getId());
+                partsOf.push_back((int)nParts[c]);
+            }
+        }
+        logger.logAndStderr("Ready. Split time: " + std::to_string(ms));
+        logger.logAndStderr("Clusters of more than one sequence: " + std::to_string(stats.n_multi) + ", pairs scored: " + std::to_string(stats.pairs_scored) +
+                            ", pairs at or above the threshold: " + std::to_string(stats.n_edges) + ", merges: " + std::to_string(stats.merges) +
+                            ", GPU kernels: " + std::to_string(stats.kernel_ms) + " ms, chains: " + std::to_string(stats.chain_ms) + " ms");
+        logger.logAndStderr("Clusters split: " + std::to_string(stats.n_split));
+        logger.logAndStderr("Resulting clusers: " + std::to_string(result.size()));
+        logger.logAndStderr("Saving results to output files...");
+        const std::string seqCsv = o.workingDirectory + "/initial_clusters_sequences.tsv";
+        const std::string orderedCsv = o.workingDirectory + "/initial_clusters_sequences_original_order.tsv";
+        const std::string clustersCsv = o.workingDirectory + "/initial_clusters.tsv";
+        FileIOManager::saveInitialClusters(result, seqCsv, orderedCsv, clustersCsv, in.labels, in.lineOrder);
+        const std::string splitCsv = o.workingDirectory + "/split_clusters.tsv";
+        {
+            std::ofstream out(splitCsv);
+            if (!out) throw HammockException("cannot write " + splitCsv);
+            out << "source_cluster_id\tcluster_id\tunique_size\tsize\tparts\n";
+            for (size_t k = 0; k < result.size(); k++)
+                out << sourceOf[k] << '\t' << result[k]->getId() << '\t' << result[k]->getUniqueSize() << '\t' << result[k]->size() << '\t' << partsOf[k] << '\n';
+        }
+        logger.logAndStderr("Split clustering in: " + clustersCsv);
+        logger.logAndStderr("and: " + seqCsv);
+        logger.logAndStderr("and: " + orderedCsv);
+        logger.logAndStderr("Resulting clusters by source cluster in: " + splitCsv);
+        logger.logWithTime("Program successfully ended.");
+        return 0;
+    } catch (...) {
+        return reportRunError(logger, false);
+    }
+}
+
 // `hammock-hip io-selftest ...`: exposes the loaders / orderings to the CPU test-suite (no GPU involved)
 int ioSelftest(const std::vector<std::string> &args) {
     if (args.size() >= 3 && args[1] == "matrix") {
@@ -1332,6 +1444,7 @@ int main(int argc, char **argv) {
         if (args[0] == "match") return runMatch(args);
         if (args[0] == "merge") return runMerge(args);
         if (args[0] == "check") return runCheck(args);
+        if (args[0] == "split") return runSplit(args);
         if (args[0] == "io-selftest") return ioSelftest(args);
         if (args[0] == "dump-matrix") {   // the default matrix in the text format FileIOManager.loadScoringMatrix reads
             std::cout << "# BLOSUM62 substitution matrix (public NCBI table), 24 x 24, order " << AMINO_ACIDS << "\n"

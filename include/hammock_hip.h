@@ -541,6 +541,68 @@ int hmk_cluster_linkage_shifted(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const ui
                                 uint32_t *min_b, uint64_t *n_below, int32_t *member_min, uint32_t *member_below,
                                 hmk_linkage_stats *stats);
 
+/* ---- splitting given clusters by complete linkage ------------------------------------ */
+
+typedef struct {
+    uint64_t pairs_scored;       /* sum over slots of s(s-1)/2 (0 for hmk_clinkage_split_from_edges: nothing is scored) */
+    uint64_t n_edges;            /* pairs inside a slot scoring >= threshold (_from_edges: the edges it kept) */
+    uint32_t n_multi;            /* slots with two or more members */
+    uint32_t n_split;            /* slots returned in more than one part */
+    uint32_t n_result_clusters;  /* parts of all slots: the n_clusters that goes with split_cluster */
+    uint32_t merges;             /* clusters joined, all chains (ClinkageSequenceClusterer.java:96-111) */
+    int32_t  crash_slot;         /* the slot HMK_ERR_REFERENCE_WOULD_CRASH names, -1 otherwise */
+    int32_t  reserved;
+    double   kernel_ms;          /* device time of the scoring, HIP events */
+    double   chain_ms;           /* host wall time of all chains, their seeding included */
+    double   copy_ms;            /* device time of the triangles' copy to the host, HIP events */
+} hmk_split_stats;
+
+/* Splits given clusters: the reverse of hmk_clinkage_merge.  That call runs the reference's complete-linkage chain between given
+ * clusters and never looks inside one; this one runs it inside each given cluster and never looks between two.  It is what acts
+ * on hmk_cluster_linkage_shifted's answer: a cluster file that fails that check -- a looser threshold, another matrix, another
+ * tool, an edit by hand -- comes back as complete-linkage clusters at these parameters without being clustered from nothing.
+ * Members [r0, r1) of the hmk_set_sequences set with member_cluster and n_clusters as hmk_cluster_linkage_shifted takes them.
+ *   per slot c with the members m_0 < m_1 < ... < m_(s-1): what hmk_clinkage_cluster returns for a set that holds exactly those s
+ *     sequences in that order (ClinkageSequenceClusterer.java:43-124 on the slot alone): the uploaded sizes (Cluster.size(), the
+ *     tie-break), the HashSet order hmk_set_java_hashset selects.
+ *   n_parts[c]             the number of returned clusters of slot c; 1 for a slot of one member
+ *   part_id[m - r0]        the Java id inside the slot's own run: k + 1 for the member at place k left alone, s + 2, s + 3, ...
+ *                          for merged clusters in merge order; may be NULL
+ *   member_rank[m - r0]    the position in the returned Cluster.getSequences(); may be NULL
+ *   part_order[part_start[c] .. part_start[c] + n_parts[c])   the slot's returned ids in list order; part_start[c] = the number of
+ *                          members in slots below c, part_start has n_clusters + 1 entries and part_order r1 - r0; NULL together
+ *                          or not at all
+ *   split_cluster[m - r0]  required: all parts numbered densely, slots in slot order and inside a slot its parts in list order.
+ *                          split_cluster with stats.n_result_clusters is the member_cluster / n_clusters of the new clustering
+ *                          for every other call here: hmk_cluster_linkage_shifted finds no pair below the threshold in it.
+ *   crash parity           a slot whose chain returns to a cluster still on its stack (see hmk_clinkage_cluster) makes the call
+ *                          return HMK_ERR_REFERENCE_WOULD_CRASH; hmk_last_error and stats.crash_slot name the lowest such slot,
+ *                          whatever the number of host threads; the outputs are then unspecified.  An empty range is HMK_OK with
+ *                          nothing written.  The tree-bin case of hmk_clinkage_merge cannot arise: a slot's ids are consecutive.
+ *   checks                 HMK_ERR_BAD_ARG before the device is looked at (a host-only context answers them): every check of
+ *                          hmk_cluster_linkage_shifted (so a slot without members is refused, the matrix must be symmetric, and
+ *                          the scores must fit int16 at both ends: they travel as int16); a null split_cluster or n_parts with a
+ *                          non-empty range; part_order without part_start or the reverse; more than 2^30 pairs inside the slots of
+ *                          one call, sum of s(s-1)/2 -- pass fewer slots per call then, slots are independent.  The bound keeps
+ *                          the score buffer at 2 GiB and the candidate lists at what hmk_clinkage_cluster takes on a dense graph
+ *                          of that many pairs.  Never HMK_ERR_CAPACITY.
+ * Every pair inside a slot is scored and stored, a dense strict lower triangle of int16 per slot (k_split.hip; flat for slots of
+ * few members, tiled for large ones, as the linkage call's kernels); the triangles cross to the host in one piece and the chains
+ * run there, one per slot, on up to 8 threads; the result does not depend on their number.  On a hmk_create_multi context the call
+ * runs on the root device. */
+int hmk_clinkage_split(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_cluster, uint32_t n_clusters,
+                       int max_shift, int shift_penalty, int threshold, uint32_t *split_cluster, uint32_t *n_parts,
+                       int32_t *part_id, int32_t *member_rank, int32_t *part_order, uint32_t *part_start,
+                       hmk_split_stats *stats);
+
+/* The same from a sequence-level edge list as hmk_neighbors_shifted packs it (indices of the uploaded set, each unordered pair
+ * once, any order; edges with an end outside [r0, r1) or with ends in two slots are ignored).  Works on a host-only context
+ * (device = -1).  Checks as hmk_clinkage_split's without those of the scoring parameters. */
+int hmk_clinkage_split_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t n_edges, uint32_t r0, uint32_t r1,
+                                  const uint32_t *member_cluster, uint32_t n_clusters, uint32_t *split_cluster,
+                                  uint32_t *n_parts, int32_t *part_id, int32_t *member_rank, int32_t *part_order,
+                                  uint32_t *part_start, hmk_split_stats *stats);
+
 /* Where the time of the last hmk_greedy_cluster / hmk_greedy_from_edges_dev call of this context went
  * (milliseconds; the span of Hammock.java:406-411 minus the sort).  score_ms and csr_ms are device times (HIP events on
  * the call's stream), the others host wall time.  The parts overlap (phase 1 runs while the rest of the pair space is
