@@ -1,9 +1,24 @@
 // hmk_common.cpp -- what every part of the host side uses: error text, the device check, the 32-byte residue copy of the probes,
 // the context's grow-only device and pinned buffers and the edge buffer (the owners of hmk_ctx.h), the clustering calls' streams and
 // events, the tail's buffer list.
-#include "hmk_ctx.h"
+#include <atomic>
 
-namespace hmk { namespace impl {
+#include "hmk_ctx.h"
+#include "hmk_grid.h"
+
+namespace hmk {
+
+// HMK_TEST_GRID_CAP (hmk_grid.h): one value per process, as the environment is; the launchers have no context to ask
+static std::atomic<int> g_test_grid_cap{0};
+void set_test_grid_cap(int cap) { g_test_grid_cap.store(cap < 1 ? 0 : cap, std::memory_order_relaxed); }
+uint32_t capped_grid(const char *kernel, uint32_t wanted) {
+    const int cap = g_test_grid_cap.load(std::memory_order_relaxed);
+    if (cap < 1 || wanted <= (uint32_t)cap) return wanted;
+    std::fprintf(stderr, "[hmk grid] %s %u -> %d\n", kernel, wanted, cap);
+    return (uint32_t)cap;
+}
+
+namespace impl {
 
 thread_local std::string g_last_error;
 
@@ -36,6 +51,8 @@ void Switches::read() {
     late_buffers_delay_ms = std::max(0, num("HMK_LATE_BUFFERS_DELAY_MS", 0));
     csr_bucket_shift = num("HMK_CSR_BUCKET_SHIFT", 0);
     if (const char *v = getenv("HMK_EDGE_GUESS")) edge_guess = std::strtoull(v, nullptr, 10);
+    test_grid_cap = std::max(0, num("HMK_TEST_GRID_CAP", 0));
+    set_test_grid_cap(test_grid_cap);
 }
 void refresh_switches(hmk_ctx *ctx) {
     ctx->sw.read();

@@ -120,6 +120,7 @@ struct Switches {
     int late_buffers_delay_ms = 0;   // HMK_LATE_BUFFERS_DELAY_MS: hmk_reserve's buffer thread sleeps first (a host where device memory is slow to get)
     int csr_bucket_shift = 0;     // HMK_CSR_BUCKET_SHIFT: rows per bucket = 2^shift in the CSR's dealing pass (the wide buckets of n > 2^21)
     uint64_t edge_guess = 0;      // HMK_EDGE_GUESS: first edge-buffer capacity (forces the overflow / retry path)
+    int test_grid_cap = 0;        // HMK_TEST_GRID_CAP=n, n >= 1: the grid-stride launches of hmk_grid.h get at most n workgroups (0: their own grids)
     void read();
 };
 

@@ -8,6 +8,7 @@
 // Every store here is an ordinary vector store; the counters are vector atomics.
 #include "hmk_device.h"
 #include "k_assign_table.h"
+#include "hmk_grid.h"
 
 namespace hmk {
 
@@ -118,11 +119,12 @@ hipError_t launch_assign_gather(const uint64_t *edges, uint64_t cap_per_shard, c
     uint32_t *cnt = scratch, *cursor = scratch + nq;
     hipError_t e = hipMemsetAsync(scratch, 0, ((size_t)2 * nq + 1) * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
-    const dim3 seg_grid(seg_grid_x(max_count), HMK_EDGE_SHARDS);
-    hipLaunchKernelGGL(k_assign_count, seg_grid, dim3(256), 0, s, edges, cap_per_shard, counts, q0, nq, cnt);
+    const uint32_t seg_x = seg_grid_x(max_count);
+    const dim3 count_grid(capped_grid("k_assign_count", seg_x), HMK_EDGE_SHARDS), scatter_grid(capped_grid("k_assign_scatter", seg_x), HMK_EDGE_SHARDS);
+    hipLaunchKernelGGL(k_assign_count, count_grid, dim3(256), 0, s, edges, cap_per_shard, counts, q0, nq, cnt);
     e = launch_scan_u32(cnt, start, nq, scan_scratch, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_assign_scatter, seg_grid, dim3(256), 0, s, edges, cap_per_shard, counts, q0, nq, r0, nm, member_rank, start, cursor, rec,
+    hipLaunchKernelGGL(k_assign_scatter, scatter_grid, dim3(256), 0, s, edges, cap_per_shard, counts, q0, nq, r0, nm, member_rank, start, cursor, rec,
                        rec_capacity);
     return hipGetLastError();
 }
@@ -137,14 +139,14 @@ hipError_t launch_assign(const uint64_t *edges, uint64_t cap_per_shard, const un
                                         rec_capacity, s);
     if (e != hipSuccess) return e;
     // a wave per new sequence, up to 8 workgroups per CU's worth (256 CUs), the rest grid-stride
-    const uint32_t wave_grid = std::max(1u, std::min((nq + 3) / 4, 2048u));
+    const uint32_t wave_grid = capped_grid("k_assign_wave", std::max(1u, std::min((nq + 3) / 4, 2048u)));
     hipLaunchKernelGGL(k_assign_wave, dim3(wave_grid), dim3(256), 0, s, start, rec, nq, k, LONG_RUN, members_of_rank, slot_of_rank, long_list,
                        long_count, best_cluster, best_score, n_feasible);
     // at most total / (LONG_RUN + 1) runs can be long: no workgroups for runs that cannot exist
     const uint64_t max_long = std::min<uint64_t>(nq, total / (LONG_RUN + 1));
     if (max_long)
-        hipLaunchKernelGGL(k_assign_block, dim3((uint32_t)std::min<uint64_t>(max_long, 1024)), dim3(256), 0, s, start, rec, k, members_of_rank,
-                           slot_of_rank, long_list, long_count, best_cluster, best_score, n_feasible);
+        hipLaunchKernelGGL(k_assign_block, dim3(capped_grid("k_assign_block", (uint32_t)std::min<uint64_t>(max_long, 1024))), dim3(256), 0, s, start, rec, k,
+                           members_of_rank, slot_of_rank, long_list, long_count, best_cluster, best_score, n_feasible);
     return hipGetLastError();
 }
 

@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "hmk_link_device.h"
+#include "hmk_grid.h"
 
 namespace hmk {
 
@@ -260,7 +261,7 @@ hipError_t launch_linkage_init(uint64_t *key, unsigned long long *below, uint32_
                                uint32_t nm, hipStream_t s) {
     const uint32_t n = std::max(n_clusters, member_min ? nm : 0u);
     if (n == 0) return hipSuccess;
-    const uint32_t blocks = std::min<uint32_t>((n + 255) / 256, 4096);
+    const uint32_t blocks = capped_grid("k_linkage_init", std::min<uint32_t>((n + 255) / 256, 4096));
     hipLaunchKernelGGL(k_linkage_init, dim3(blocks), dim3(256), 0, s, key, below, n_clusters, member_min, member_below, nm);
     return hipGetLastError();
 }
@@ -271,7 +272,7 @@ hipError_t launch_linkage_flat(const uint8_t *res32, const uint8_t *len, const i
                                hipStream_t s) {
     if (n_pairs == 0 || nf == 0) return hipSuccess;
     const unsigned long long chunks = (n_pairs + 255) / 256;
-    const uint32_t blocks = (uint32_t)std::min<unsigned long long>(chunks, 65536);
+    const uint32_t blocks = capped_grid("k_linkage_flat", (uint32_t)std::min<unsigned long long>(chunks, 65536));
     hipLaunchKernelGGL(k_linkage_flat, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, tab, fslot, fmstart, fpstart, nf, n_pairs, r0, X, p,
                        thr, key, below, member_min, member_below);
     return hipGetLastError();
@@ -281,7 +282,7 @@ hipError_t launch_linkage_tiled(const uint8_t *res32, const uint8_t *len, const 
                                 const uint32_t *bmstart, const uint32_t *btstart, uint32_t nb, uint32_t n_tiles, uint32_t r0, int X, int p,
                                 int thr, uint64_t *key, unsigned long long *below, int32_t *member_min, uint32_t *member_below, hipStream_t s) {
     if (n_tiles == 0 || nb == 0) return hipSuccess;
-    const uint32_t blocks = std::min<uint32_t>(n_tiles, 65536);
+    const uint32_t blocks = capped_grid("k_linkage_tiled", std::min<uint32_t>(n_tiles, 65536));
     hipLaunchKernelGGL(k_linkage_tiled, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, tab, bslot, bmstart, btstart, nb, n_tiles, r0, X, p,
                        thr, key, below, member_min, member_below);
     return hipGetLastError();

@@ -9,6 +9,7 @@
 // Every store here is an ordinary vector store; the counters are vector atomics.
 #include "hmk_device.h"
 #include "k_assign_table.h"
+#include "hmk_grid.h"
 
 namespace hmk {
 
@@ -167,20 +168,22 @@ hipError_t launch_match(const uint64_t *edges, uint64_t cap_per_shard, const uns
     uint32_t *n_feas = scratch2, *cnt2 = scratch2 + nq, *cursor2 = cnt2 + nb, *long_count2 = cursor2 + nb, *long_list2 = long_count2 + 1;
     e = hipMemsetAsync(cnt2, 0, ((size_t)2 * nb + 1) * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_match_feasible_wave, dim3(wave_grid(nq)), dim3(256), 0, s, start, rec, nq, LONG_RUN, members_of_rank, long_list,
-                       long_count, feas, n_feas);
-    if (std::min<uint64_t>(nq, max_long))
-        hipLaunchKernelGGL(k_match_feasible_block, dim3((uint32_t)std::min<uint64_t>(std::min<uint64_t>(nq, max_long), 1024)), dim3(256), 0, s,
+    hipLaunchKernelGGL(k_match_feasible_wave, dim3(capped_grid("k_match_feasible_wave", wave_grid(nq))), dim3(256), 0, s, start, rec, nq, LONG_RUN,
+                       members_of_rank, long_list, long_count, feas, n_feas);
+    if (const uint32_t n_block = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(nq, max_long), 1024))
+        hipLaunchKernelGGL(k_match_feasible_block, dim3(capped_grid("k_match_feasible_block", n_block)), dim3(256), 0, s,
                            start, rec, members_of_rank, long_list, long_count, feas, n_feas);
     // level 2: the gather into the query clusters' runs (rec is free again: it holds them)
-    hipLaunchKernelGGL(k_match_count, dim3(std::max(1u, std::min((nq + 255) / 256, 1024u))), dim3(256), 0, s, n_feas, query_slot, nq, cnt2);
+    const uint32_t count_grid = capped_grid("k_match_count", std::max(1u, std::min((nq + 255) / 256, 1024u)));
+    hipLaunchKernelGGL(k_match_count, dim3(count_grid), dim3(256), 0, s, n_feas, query_slot, nq, cnt2);
     e = launch_scan_u32(cnt2, start2, nb, scan_scratch, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_match_copy, dim3(wave_grid(nq)), dim3(256), 0, s, start, feas, n_feas, query_slot, nq, start2, cursor2, rec, rec_capacity);
-    hipLaunchKernelGGL(k_match_select_wave, dim3(wave_grid(nb)), dim3(256), 0, s, start2, rec, nb, k, LONG_RUN, query_members, slot_of_rank,
-                       long_list2, long_count2, best_cluster, best_score, n_feasible);
-    if (std::min<uint64_t>(nb, max_long))
-        hipLaunchKernelGGL(k_match_select_block, dim3((uint32_t)std::min<uint64_t>(std::min<uint64_t>(nb, max_long), 1024)), dim3(256), 0, s,
+    hipLaunchKernelGGL(k_match_copy, dim3(capped_grid("k_match_copy", wave_grid(nq))), dim3(256), 0, s, start, feas, n_feas, query_slot, nq, start2, cursor2,
+                       rec, rec_capacity);
+    hipLaunchKernelGGL(k_match_select_wave, dim3(capped_grid("k_match_select_wave", wave_grid(nb))), dim3(256), 0, s, start2, rec, nb, k, LONG_RUN,
+                       query_members, slot_of_rank, long_list2, long_count2, best_cluster, best_score, n_feasible);
+    if (const uint32_t n_block = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(nb, max_long), 1024))
+        hipLaunchKernelGGL(k_match_select_block, dim3(capped_grid("k_match_select_block", n_block)), dim3(256), 0, s,
                            start2, rec, k, query_members, slot_of_rank, long_list2, long_count2, best_cluster, best_score, n_feasible);
     return hipGetLastError();
 }

@@ -10,6 +10,7 @@
 // Every store here is an ordinary vector store; the counters are vector atomics.
 #include "hmk_device.h"
 #include "k_assign_table.h"
+#include "hmk_grid.h"
 
 namespace hmk {
 
@@ -209,16 +210,19 @@ hipError_t launch_merge_graph(bool packed, const uint64_t *start, const void *ad
     uint32_t *long_count = scratch, *long_list = scratch + 1;
     hipError_t e = hipMemsetAsync(long_count, 0, sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_merge_len, dim3(std::max(1u, std::min((nm + 255) / 256, 1024u))), dim3(256), 0, s, start, cl_members, nm, mlen);
+    const uint32_t len_grid = capped_grid("k_merge_len", std::max(1u, std::min((nm + 255) / 256, 1024u)));
+    hipLaunchKernelGGL(k_merge_len, dim3(len_grid), dim3(256), 0, s, start, cl_members, nm, mlen);
     e = launch_scan_u32(mlen, mstart, nm, scan_scratch, s);
     if (e != hipSuccess) return e;
     // at most entries / (LONG_RUN + 1) runs can be long: no workgroups for runs that cannot exist
-    const uint32_t n_block = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(ncl, entries / (LONG_RUN + 1)), 1024);
+    uint32_t n_block = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(ncl, entries / (LONG_RUN + 1)), 1024);
+    const uint32_t n_wave = capped_grid(packed ? "k_merge_wave<true>" : "k_merge_wave<false>", wave_grid(ncl));
+    if (n_block) n_block = capped_grid(packed ? "k_merge_block<true>" : "k_merge_block<false>", n_block);
     if (packed) {
-        hipLaunchKernelGGL(k_merge_wave<true>, dim3(wave_grid(ncl)), dim3(256), 0, s, C, ncl, LONG_RUN, mstart, long_list, long_count, tmp, cnt);
+        hipLaunchKernelGGL(k_merge_wave<true>, dim3(n_wave), dim3(256), 0, s, C, ncl, LONG_RUN, mstart, long_list, long_count, tmp, cnt);
         if (n_block) hipLaunchKernelGGL(k_merge_block<true>, dim3(n_block), dim3(256), 0, s, C, mstart, long_list, long_count, tmp, cnt);
     } else {
-        hipLaunchKernelGGL(k_merge_wave<false>, dim3(wave_grid(ncl)), dim3(256), 0, s, C, ncl, LONG_RUN, mstart, long_list, long_count, tmp, cnt);
+        hipLaunchKernelGGL(k_merge_wave<false>, dim3(n_wave), dim3(256), 0, s, C, ncl, LONG_RUN, mstart, long_list, long_count, tmp, cnt);
         if (n_block) hipLaunchKernelGGL(k_merge_block<false>, dim3(n_block), dim3(256), 0, s, C, mstart, long_list, long_count, tmp, cnt);
     }
     return launch_scan_u32(cnt, ostart, ncl, scan_scratch, s);
@@ -227,7 +231,8 @@ hipError_t launch_merge_graph(bool packed, const uint64_t *start, const void *ad
 hipError_t launch_merge_compact(uint32_t ncl, const uint32_t *cl_start, const uint32_t *mstart, const uint64_t *tmp, const uint32_t *cnt,
                                 const uint32_t *ostart, int thr, uint64_t *out, uint64_t out_capacity, hipStream_t s) {
     if (ncl == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_merge_compact, dim3(wave_grid(ncl)), dim3(256), 0, s, ncl, cl_start, mstart, tmp, cnt, ostart, thr, out, out_capacity);
+    const uint32_t grid = capped_grid("k_merge_compact", wave_grid(ncl));
+    hipLaunchKernelGGL(k_merge_compact, dim3(grid), dim3(256), 0, s, ncl, cl_start, mstart, tmp, cnt, ostart, thr, out, out_capacity);
     return hipGetLastError();
 }
 

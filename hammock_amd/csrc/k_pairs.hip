@@ -1,6 +1,7 @@
 // k_pairs.hip -- one pair per lane, literal loops: the parity probes behind hmk_score_pairs_* and the
 // literal tier of hmk_score_block_* (ShiftedScorer.java:48-95, LocalAlignmentScorer.java:27-86).
 #include "hmk_device.h"
+#include "hmk_grid.h"
 
 namespace hmk {
 
@@ -50,6 +51,7 @@ hipError_t launch_pairs(int scorer, const uint8_t *res32, const uint8_t *len, co
     if (blocks > 65536) blocks = 65536;
     const size_t lds_shift = 2304 + 256 * 2 * SEQ_STRIDE_DW * 4;
     const size_t lds_local = lds_shift + 33 * 256 * 4;
+    blocks = capped_grid(scorer == 0 ? "k_pairs<0>" : "k_pairs<1>", (uint32_t)blocks);
     if (scorer == 0)
         hipLaunchKernelGGL(k_pairs<0>, dim3((uint32_t)blocks), dim3(256), lds_shift, s, res32, len, d_matrix, pi, pj,
                            n_pairs, r0, c0, width, a, b, out, out_shift);

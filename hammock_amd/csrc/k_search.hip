@@ -3,6 +3,7 @@
 // and packed into one block; the best k references of every query selected on the device (count, scan, scatter, select).
 // Every store here is an ordinary vector store; the counters are vector atomics.
 #include "hmk_device.h"
+#include "hmk_grid.h"
 
 namespace hmk {
 
@@ -146,8 +147,8 @@ uint32_t seg_grid_x(uint64_t max_count) {
 
 hipError_t launch_search_compact(const uint64_t *edges, uint64_t cap_per_shard, const unsigned long long *counts, uint64_t max_count,
                                  uint32_t q0, uint32_t nq, uint64_t *out, uint64_t out_capacity, hipStream_t s) {
-    hipLaunchKernelGGL(k_search_compact, dim3(seg_grid_x(max_count), HMK_EDGE_SHARDS), dim3(256), 0, s, edges, cap_per_shard, counts, q0, nq,
-                       out, out_capacity);
+    const dim3 seg_grid(capped_grid("k_search_compact", seg_grid_x(max_count)), HMK_EDGE_SHARDS);
+    hipLaunchKernelGGL(k_search_compact, seg_grid, dim3(256), 0, s, edges, cap_per_shard, counts, q0, nq, out, out_capacity);
     return hipGetLastError();
 }
 
@@ -158,11 +159,12 @@ hipError_t launch_search_best(const uint64_t *edges, uint64_t cap_per_shard, con
     uint32_t *cnt = cnt_cursor, *cursor = cnt_cursor + nq;
     hipError_t e = hipMemsetAsync(cnt_cursor, 0, (size_t)2 * nq * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
-    const dim3 seg_grid(seg_grid_x(max_count), HMK_EDGE_SHARDS);
-    hipLaunchKernelGGL(k_search_count, seg_grid, dim3(256), 0, s, edges, cap_per_shard, counts, q0, nq, cnt);
+    const uint32_t seg_x = seg_grid_x(max_count);
+    const dim3 count_grid(capped_grid("k_search_count", seg_x), HMK_EDGE_SHARDS), scatter_grid(capped_grid("k_search_scatter", seg_x), HMK_EDGE_SHARDS);
+    hipLaunchKernelGGL(k_search_count, count_grid, dim3(256), 0, s, edges, cap_per_shard, counts, q0, nq, cnt);
     e = launch_scan_u32(cnt, start, nq, scan_scratch, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_search_scatter, seg_grid, dim3(256), 0, s, edges, cap_per_shard, counts, q0, nq, start, cursor, keys, keys_capacity);
+    hipLaunchKernelGGL(k_search_scatter, scatter_grid, dim3(256), 0, s, edges, cap_per_shard, counts, q0, nq, start, cursor, keys, keys_capacity);
     hipLaunchKernelGGL(k_search_best_wave, dim3((nq + 3) / 4), dim3(256), 0, s, start, keys, nq, k, LONG_RUN, hit_index, hit_score, n_hits);
     hipLaunchKernelGGL(k_search_best_block, dim3(nq), dim3(256), 0, s, start, keys, nq, k, LONG_RUN, hit_index, hit_score, n_hits);
     return hipGetLastError();

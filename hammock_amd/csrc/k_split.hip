@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "hmk_link_device.h"
+#include "hmk_grid.h"
 #include "hmk_split.h"
 
 namespace hmk {
@@ -104,7 +105,7 @@ hipError_t launch_split_flat(const uint8_t *res32, const uint8_t *len, const int
                              hipStream_t s) {
     if (n_pairs == 0 || nf == 0) return hipSuccess;
     const unsigned long long chunks = (n_pairs + 255) / 256;
-    const uint32_t blocks = (uint32_t)std::min<unsigned long long>(chunks, 65536);
+    const uint32_t blocks = capped_grid("k_split_flat", (uint32_t)std::min<unsigned long long>(chunks, 65536));
     hipLaunchKernelGGL(k_split_flat, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, tab, fmstart, fpstart, nf, n_pairs, X, p, scores);
     return hipGetLastError();
 }
@@ -113,7 +114,8 @@ hipError_t launch_split_tiled(const uint8_t *res32, const uint8_t *len, const in
                               const uint32_t *btstart, const unsigned long long *tbase, uint32_t nb, uint32_t n_tiles, int X, int p,
                               int16_t *scores, hipStream_t s) {
     if (n_tiles == 0 || nb == 0) return hipSuccess;
-    const uint32_t blocks = (uint32_t)std::min<unsigned long long>((unsigned long long)n_tiles * (LINK_TILE / SPLIT_ROWS), 65536);
+    const uint32_t blocks =
+        capped_grid("k_split_tiled", (uint32_t)std::min<unsigned long long>((unsigned long long)n_tiles * (LINK_TILE / SPLIT_ROWS), 65536));
     hipLaunchKernelGGL(k_split_tiled, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, tab, bmstart, btstart, tbase, nb, n_tiles, X, p, scores);
     return hipGetLastError();
 }
