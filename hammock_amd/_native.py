@@ -34,6 +34,7 @@ SYMBOLS = [
     "hmk_clinkage_cluster", "hmk_clinkage_from_edges", "hmk_set_java_hashset", "hmk_reserve",
     "hmk_cluster_pairs_shifted", "hmk_clinkage_merge", "hmk_clinkage_merge_from_edges",
     "hmk_cluster_linkage_shifted", "hmk_clinkage_split", "hmk_clinkage_split_from_edges",
+    "hmk_components_shifted", "hmk_components_from_edges", "hmk_components_from_edges_dev",
 ]
 
 
@@ -85,6 +86,18 @@ class SplitStats(C.Structure):
     _fields_ = [("pairs_scored", C.c_uint64), ("n_edges", C.c_uint64), ("n_multi", C.c_uint32), ("n_split", C.c_uint32),
                 ("n_result_clusters", C.c_uint32), ("merges", C.c_uint32), ("crash_slot", C.c_int32), ("reserved", C.c_int32),
                 ("kernel_ms", C.c_double), ("chain_ms", C.c_double), ("copy_ms", C.c_double)]
+
+
+class ComponentLevel(C.Structure):
+    """hmk_component_level"""
+    _fields_ = [("n_edges", C.c_uint64), ("n_components", C.c_uint32), ("n_singletons", C.c_uint32), ("largest", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class ComponentsStats(C.Structure):
+    """hmk_components_stats"""
+    _fields_ = [("n_edges", C.c_uint64), ("pairs_scored", C.c_uint64), ("n_levels", C.c_uint32), ("n_components", C.c_uint32),
+                ("n_singletons", C.c_uint32), ("largest", C.c_uint32), ("kernel_ms", C.c_double), ("components_ms", C.c_double)]
 
 
 class GreedyPhases(C.Structure):
@@ -165,6 +178,9 @@ def _load():
     L.hmk_clinkage_split.argtypes = [vp, u32, u32, p_u32, u32, i32, i32, i32, p_u32, p_u32, p_i32, p_i32, p_i32, p_u32, C.POINTER(SplitStats)]
     L.hmk_clinkage_split_from_edges.argtypes = [vp, p_u64, u64, u32, u32, p_u32, u32, p_u32, p_u32, p_i32, p_i32, p_i32, p_u32,
                                                 C.POINTER(SplitStats)]
+    L.hmk_components_shifted.argtypes = [vp, i32, i32, i32, i32, p_u32, C.POINTER(ComponentLevel), C.POINTER(ComponentsStats)]
+    L.hmk_components_from_edges.argtypes = [vp, p_u64, u64, i32, i32, p_u32, C.POINTER(ComponentLevel), C.POINTER(ComponentsStats)]
+    L.hmk_components_from_edges_dev.argtypes = [vp, vp, u64, i32, i32, p_u32, C.POINTER(ComponentLevel), C.POINTER(ComponentsStats)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("hmk_destroy", "hmk_last_error", "hmk_last_kernel_ms"):

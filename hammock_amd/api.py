@@ -91,6 +91,11 @@ def pack_edges(x, m, score) -> np.ndarray:
     return (x << np.uint64(40)) | (m << np.uint64(16)) | s
 
 
+# hmk_component_level, one entry per threshold of a components call
+LEVEL_DTYPE = np.dtype([("n_edges", np.uint64), ("n_components", np.uint32), ("n_singletons", np.uint32), ("largest", np.uint32),
+                        ("reserved", np.uint32)])
+
+
 class Context:
     """1:1 wrapper of hmk_ctx.  device >= 0: HIP ordinal; -1: host-only."""
 
@@ -635,6 +640,41 @@ class Context:
         ncl = int(n_clusters)
         return self._split(lambda *out: N.lib.hmk_clinkage_split_from_edges(self._h, _ptr(edges, C.c_uint64), edges.size, int(r0), int(r1),
                                                                             _ptr(mc, C.c_uint32), ncl, *out), r0, mc, ncl)
+
+    # -- connected components of the neighbour graph ---------------------------------------
+    def _components(self, call, threshold, threshold_hi, component, levels):
+        """runs call(threshold, threshold_hi, component, levels, stats) -> (component uint32[n] or None, levels: structured array
+        LEVEL_DTYPE[threshold_hi - threshold + 1] or None); statistics in last_components_stats"""
+        thr = int(threshold)
+        hi = thr if threshold_hi is None else int(threshold_hi)
+        comp = np.zeros(max(self.n, 1), dtype=np.uint32) if component else None
+        lv = np.zeros(min(max(hi - thr + 1, 1), 256), dtype=LEVEL_DTYPE) if levels else None
+        stats = N.ComponentsStats()
+        st = call(thr, hi, _ptr(comp, C.c_uint32) if component else None,
+                  lv.ctypes.data_as(C.POINTER(N.ComponentLevel)) if levels else None, C.byref(stats))
+        if st:
+            self._raise(st)
+        self.last_components_stats = stats
+        return (comp[:self.n] if component else None), lv
+
+    def components_shifted(self, max_shift, shift_penalty, threshold, threshold_hi=None, component=True, levels=True):
+        """hmk_components_shifted: the connected components of the graph {ShiftedScorer score >= t} over the uploaded set, for every
+        t = threshold ... threshold_hi (None: threshold alone) from one scoring pass -> (component uint32[n]: the smallest index in
+        i's component at `threshold`, levels: structured array (LEVEL_DTYPE) with the fields n_edges, n_components, n_singletons,
+        largest, one entry per t).  component=False / levels=False pass NULL for that output and return None for it."""
+        return self._components(lambda thr, hi, *out: N.lib.hmk_components_shifted(self._h, int(max_shift), int(shift_penalty), thr, hi, *out),
+                                threshold, threshold_hi, component, levels)
+
+    def components_from_edges(self, edges, threshold, threshold_hi=None, component=True, levels=True):
+        """hmk_components_from_edges: the same from packed edges, by a sequential union-find on the host (works on a host-only context)."""
+        edges = np.ascontiguousarray(edges, dtype=np.uint64)
+        return self._components(lambda thr, hi, *out: N.lib.hmk_components_from_edges(self._h, _ptr(edges, C.c_uint64), edges.size, thr, hi, *out),
+                                threshold, threshold_hi, component, levels)
+
+    def components_from_edges_dev(self, d_edges_ptr, n_edges, threshold, threshold_hi=None, component=True, levels=True):
+        """hmk_components_from_edges_dev: the same with the packed edges in device memory, through the device kernels."""
+        return self._components(lambda thr, hi, *out: N.lib.hmk_components_from_edges_dev(self._h, C.c_void_p(d_edges_ptr), int(n_edges), thr, hi, *out),
+                                threshold, threshold_hi, component, levels)
 
     def greedy_phases(self):
         """hmk_greedy_last_phases: per-phase milliseconds of the last greedy_cluster / greedy_from_edges_dev call."""

@@ -2,7 +2,8 @@
 // hmk_api.cpp (the extern "C" entry points: argument checks, locking, dispatch), hmk_common.cpp (errors, device, the grow-only
 // buffers and their owners, streams), hmk_sizing.h (the sizing rules, pure functions), hmk_plan.cpp (the neighbour passes' planner),
 // hmk_pass.cpp (launching the passes; the pair and block probes), hmk_cluster.cpp (the single-device clustering calls, CSR pipeline,
-// row hand-over, second-loop driver), hmk_multi.cpp (the same calls on several devices).  Not part of the public ABI.
+// row hand-over, second-loop driver), hmk_multi.cpp (the same calls on several devices), and one file per further call
+// (hmk_search.cpp ... hmk_components.cpp).  Not part of the public ABI.
 #ifndef HMK_CTX_H
 #define HMK_CTX_H
 #include <hip/hip_runtime_api.h>
@@ -91,6 +92,8 @@ enum {
     SB_MERGE_CNT, SB_MERGE_OSTART, SB_MERGE_SCR, SB_MERGE_SCAN,   // ... feasible counts, their prefix sums, long-run list, scan scratch
     SB_LINK_TAB, SB_LINK_OUT,                       // the linkage inside given clusters (hmk_linkage.cpp): members by slot + work prefix sums; accumulators
     SB_SPLIT_SCORES,                                // the split of given clusters (hmk_split.cpp): the slots' dense triangles of int16 scores
+    SB_CC_PARENT, SB_CC_SIZE,                       // connected components (hmk_components.cpp): the union-find's parent[n], members per root
+    SB_CC_STATE, SB_CC_RUNS,                        // ... the levels' results, histogram and run offsets (CcState); the edges' (x, m) by level
     SB_N
 };
 
@@ -467,6 +470,9 @@ int neighbors_grow(hmk_ctx *ctx, uint64_t want_cap, unsigned long long counts[HM
         HIPCHK(ctx, hipMemcpy(counts, ctx->edges.counts, HMK_EDGE_SHARDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         if (max_of(counts) <= ctx->edges.seg_cap()) return HMK_OK;
         cap = sizing::edge_capacity_after_overflow(max_of(counts));   // a segment overflowed: grow and rescore
+        if (ctx->sw.greedy_timing)
+            std::fprintf(stderr, "[hmk] an edge segment overflowed (%llu entries for %llu): %llu entries next, scoring again\n",
+                         (unsigned long long)max_of(counts), (unsigned long long)ctx->edges.seg_cap(), (unsigned long long)cap);
         return ST_RETRY_OVERFLOW;
     };
     st = ST_RETRY_OVERFLOW;

@@ -59,6 +59,8 @@ struct Options {
     std::string clustersFile, database, parentDir;
     bool haveClusters = false, haveDatabase = false, havePenalty = false, skipSingletons = false;
     int best = 0;
+    bool haveScanTo = false;   // components: --scan_to T2, the last threshold of the scan (default: -g alone)
+    int scanTo = 0;
 };
 
 void parseCommonArgs(const std::vector<std::string> &args, Options &o) {  // Hammock.java:824-908
@@ -144,7 +146,9 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "          hammock-hip check -i <clusters.tsv> -d <directory> [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [-g <int>]\n"
               << "                      [--device <int>]\n"
               << "          hammock-hip split -i <clusters.tsv> -d <directory> [-m <file>] [-x <int>] [-p <int>] [-g <int>] [--java_hashset <int>]\n"
-              << "                      [--device <int>]\n\n"
+              << "                      [--device <int>]\n"
+              << "          hammock-hip components -i <sequences> -d <directory> [-g <int>] [--scan_to <int>] [-f fasta|tab] [-m <file>] [-x <int>]\n"
+              << "                      [-p <int>] [-l <labels>] [--device <int>]\n\n"
               << "-i, --input <file>\n\tA path to an input file\n\n"
               << "-d, --output_directory <directory>\n\tA directory to store all output files in\n\n"
               << "-t, --threads <int>\n\tAccepted for compatibility (the GPU path ignores it)\n\n"
@@ -163,6 +167,7 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "--database <file>\n\t(search) the reference sequences every query (-i) is scored against\n\n"
               << "--best <int>\n\t(search) keep only the best 1..32 hits of each query; (assign, match) report the best 1..32 feasible clusters (default 1)\n\n"
               << "--clusters <file>\n\t(assign, continue, match) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv);\n\t(merge) a second cluster file: its clusters keep their ids, the -i file's are renumbered behind them\n\n"
+              << "--scan_to <int>\n\t(components) the last threshold of the scan: component_levels.tsv gets one line per threshold from -g to this one\n\t(at most 255 above -g; default: -g alone)\n\n"
               << "--skip_singletons\n\t(assign, match, merge) only clusters of more than one unique sequence are candidates;\n\t(check) clusters of one unique sequence are left out of cluster_linkage.tsv\n\n"
               << "--java_hashset <8|7|6>\n\t(clinkage, merge, split) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
 }
@@ -185,7 +190,7 @@ long long millisSince(std::chrono::steady_clock::time_point time0) {
 }
 
 // The newer modes' arguments: greedy's (-f -g -x -R -S -p) and their own.  Each parser walks all of args on its own, as the
-// reference's do; only --clusters, --database and --best take their value here.  bestDefault < 0: the mode has no --best.
+// reference's do; only --clusters, --database, --best and --scan_to take their value here.  bestDefault < 0: the mode has no --best.
 void parseModeArgs(const std::vector<std::string> &args, Options &o, int bestDefault) {
     parseGreedyArgs(args, o);
     o.best = std::max(bestDefault, 0);
@@ -196,7 +201,8 @@ void parseModeArgs(const std::vector<std::string> &args, Options &o, int bestDef
         else if (args[i] == "--best" && more && bestDefault >= 0) {
             o.best = javaIntegerDecode(args[++i]);
             if (o.best < 1 || o.best > 32) throw CLIException("Error. --best may be 1 to 32.");
-        } else if (args[i] == "--skip_singletons") o.skipSingletons = true;
+        } else if (args[i] == "--scan_to" && more) { o.scanTo = javaIntegerDecode(args[++i]); o.haveScanTo = true; }
+        else if (args[i] == "--skip_singletons") o.skipSingletons = true;
         else if ((args[i] == "-p" || args[i] == "--gap_penalty") && more) o.havePenalty = true;
     }
 }
@@ -327,6 +333,20 @@ std::vector<UniqueSequencePtr> loadSequences(const Options &o, const std::string
     return o.inputType == "fasta" ? FileIOManager::loadUniqueSequencesFromFasta(file) : FileIOManager::loadUniqueSequencesFromTable(file);
 }
 
+std::vector<UniqueSequencePtr> filterSequencesForLabels(const std::vector<UniqueSequencePtr> &sequences, const std::vector<std::string> &labels) {  // :1661-1675
+    std::vector<UniqueSequencePtr> kept;
+    for (auto &s : sequences) {
+        std::vector<std::pair<std::string, int>> lm;
+        for (auto &label : labels) {
+            bool present = false;
+            const int c = s->labelCount(label, &present);
+            if (present) lm.push_back({label, c});
+        }
+        if (!lm.empty()) kept.push_back(std::make_shared<UniqueSequence>(s->getSequenceString(), lm));
+    }
+    return kept;
+}
+
 std::vector<UniqueSequencePtr> sequencesOf(const std::vector<ClusterPtr> &clusters) {
     std::vector<UniqueSequencePtr> sequences;
     for (auto &cl : clusters) for (auto &s : cl->getSequences()) sequences.push_back(s);
@@ -426,18 +446,8 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
         logger.logAndStderr(std::to_string(sequences.size()) + " unique sequences loaded.");
         SequenceListSummary summary = summariseSequences(sequences);
         logger.logAndStderr(std::to_string(summary.total) + " total sequences loaded.");
-        if (o.haveLabels) {  // filterSequencesForLabels, :1661-1675
-            std::vector<UniqueSequencePtr> kept;
-            for (auto &s : sequences) {
-                std::vector<std::pair<std::string, int>> lm;
-                for (auto &label : labels) {
-                    bool present = false;
-                    const int c = s->labelCount(label, &present);
-                    if (present) lm.push_back({label, c});
-                }
-                if (!lm.empty()) kept.push_back(std::make_shared<UniqueSequence>(s->getSequenceString(), lm));
-            }
-            sequences = kept;
+        if (o.haveLabels) {
+            sequences = filterSequencesForLabels(sequences, labels);
             summary = summariseSequences(sequences);
         }
         logger.logAndStderr(std::to_string(sequences.size()) + " unique sequences after non-specified labels filtered out");
@@ -1323,6 +1333,91 @@ int runSplit(const std::vector<std::string> &args) {
     }
 }
 
+// `hammock-hip components -i X.fa -d dir [-g T] [--scan_to T2] [-x -p -m -f -l]`: the connected components of the neighbour graph
+// {score >= t} for every t = T ... T2 from one scoring pass (hmk_components_shifted).  No cluster any other mode can form at t crosses
+// a component at t (ClinkageClusterScorer.java:36-48), so this is where to read off at which threshold a data set falls apart, and
+// which sequences can never cluster with anything.  Sequences in load order, as clinkage takes them; -x / -g / -p default as in
+// clinkage.  Writes the stage-1 files with the components at T as clusters -- id = 1 + the smallest load-order index, multi-member
+// components first in ascending id, then the singletons in ascending id, members in load order -- so that check, split, merge and
+// assign take the file, and component_levels.tsv: one line per threshold.
+int runComponents(const std::vector<std::string> &args) {
+    Options o;
+    parseCommonArgs(args, o);
+    parseModeArgs(args, o, -1);
+    requireOneDevice(o, "components", "a components scan");
+    requireInput(o);
+    requireFastaOrTab(o, "components");
+    makeOutputDirectory(o, o.parentDir);
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        ContextFuture contextReady = beginRun(o, logger, false);
+        logRunStart(logger, "components", args);
+        std::vector<std::string> labels;
+        if (o.haveLabels) labels = FileIOManager::splitChar(o.labelString, ',', true);
+        logger.logAndStderr("Loading input sequences...");
+        std::vector<UniqueSequencePtr> sequences = loadSequences(o, o.inputFileName);
+        logger.logAndStderr(std::to_string(sequences.size()) + " unique sequences loaded.");
+        if (o.haveLabels) sequences = filterSequencesForLabels(sequences, labels);
+        else labels = FileIOManager::getSortedLabels(sequences);
+        if (sequences.empty()) throw FileFormatException("Error. No sequences (with specified labels) to cluster.");
+        const SequenceListSummary summary = summariseSequences(sequences);
+        settleShiftAndThreshold(o, logger, summary, summary, summary, "Components");
+        const int thr = o.sequenceClusteringThreshold, thrHi = o.haveScanTo ? o.scanTo : thr;
+        if (thrHi < thr || (long long)thrHi - thr > 255)
+            throw CLIException("Error. --scan_to may be the threshold (-g) " + std::to_string(thr) + " up to " + std::to_string((long long)thr + 255) + ".");
+        logger.logAndStderr("Parameters: max shift " + std::to_string(o.maxShift) + ", gap penalty " + std::to_string(o.shiftPenalty) + ", thresholds " +
+                            std::to_string(thr) + " to " + std::to_string(thrHi));
+
+        const uint32_t n = (uint32_t)sequences.size();
+        std::vector<uint32_t> component(n);
+        std::vector<hmk_component_level> levels((size_t)(thrHi - thr) + 1);
+        hmk_components_stats stats{};
+        logger.logAndStderr("Components...");
+        const auto time0 = std::chrono::steady_clock::now();
+        {
+            const std::shared_ptr<NativeContext> nc = contextReady.get();
+            nc->setSequences(sequences, true);
+            const int st = hmk_components_shifted(nc->get(), o.maxShift, o.shiftPenalty, thr, thrHi, component.data(), levels.data(), &stats);
+            if (st) nc->raise(st, nullptr);
+        }
+        logger.logAndStderr("Ready. Components time: " + std::to_string(millisSince(time0)));
+        logger.logAndStderr("Pairs scored: " + std::to_string(stats.pairs_scored) + ", pairs at or above the threshold: " + std::to_string(stats.n_edges) +
+                            ", GPU scoring: " + std::to_string(stats.kernel_ms) + " ms, GPU components: " + std::to_string(stats.components_ms) + " ms");
+        logger.logAndStderr("Components at threshold " + std::to_string(thr) + ": " + std::to_string(stats.n_components) + ", of one sequence: " +
+                            std::to_string(stats.n_singletons) + ", largest: " + std::to_string(stats.largest));
+        // component[i] = the smallest index of i's component: its members follow it, in load order
+        std::vector<std::vector<UniqueSequencePtr>> members(n);
+        for (uint32_t i = 0; i < n; i++) members[component[i]].push_back(sequences[i]);
+        std::vector<ClusterPtr> result;
+        for (int multi = 1; multi >= 0; multi--)
+            for (uint32_t i = 0; i < n; i++)
+                if (!members[i].empty() && (members[i].size() > 1) == (multi == 1)) result.push_back(std::make_shared<Cluster>(members[i], (int)i + 1));
+        logger.logAndStderr("Resulting clusers: " + std::to_string(result.size()));
+        logger.logAndStderr("Saving results to output files...");
+        const std::string seqCsv = o.workingDirectory + "/initial_clusters_sequences.tsv";
+        const std::string orderedCsv = o.workingDirectory + "/initial_clusters_sequences_original_order.tsv";
+        const std::string clustersCsv = o.workingDirectory + "/initial_clusters.tsv";
+        FileIOManager::saveInitialClusters(result, seqCsv, orderedCsv, clustersCsv, labels, sequences);
+        const std::string levelsCsv = o.workingDirectory + "/component_levels.tsv";
+        {
+            std::ofstream out(levelsCsv);
+            if (!out) throw HammockException("cannot write " + levelsCsv);
+            out << "threshold\tedges\tcomponents\tsingletons\tlargest\n";
+            for (size_t l = 0; l < levels.size(); l++)
+                out << thr + (int)l << '\t' << levels[l].n_edges << '\t' << levels[l].n_components << '\t' << levels[l].n_singletons << '\t'
+                    << levels[l].largest << '\n';
+        }
+        logger.logAndStderr("Components as clusters in: " + clustersCsv);
+        logger.logAndStderr("and: " + seqCsv);
+        logger.logAndStderr("and: " + orderedCsv);
+        logger.logAndStderr("Components by threshold in: " + levelsCsv);
+        logger.logWithTime("Program successfully ended.");
+        return 0;
+    } catch (...) {
+        return reportRunError(logger, false);
+    }
+}
+
 // `hammock-hip io-selftest ...`: exposes the loaders / orderings to the CPU test-suite (no GPU involved)
 int ioSelftest(const std::vector<std::string> &args) {
     if (args.size() >= 3 && args[1] == "matrix") {
@@ -1445,6 +1540,7 @@ int main(int argc, char **argv) {
         if (args[0] == "merge") return runMerge(args);
         if (args[0] == "check") return runCheck(args);
         if (args[0] == "split") return runSplit(args);
+        if (args[0] == "components") return runComponents(args);
         if (args[0] == "io-selftest") return ioSelftest(args);
         if (args[0] == "dump-matrix") {   // the default matrix in the text format FileIOManager.loadScoringMatrix reads
             std::cout << "# BLOSUM62 substitution matrix (public NCBI table), 24 x 24, order " << AMINO_ACIDS << "\n"

@@ -603,6 +603,59 @@ int hmk_clinkage_split_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t 
                                   uint32_t *n_parts, int32_t *part_id, int32_t *member_rank, int32_t *part_order,
                                   uint32_t *part_start, hmk_split_stats *stats);
 
+/* ---- connected components of the neighbour graph -------------------------------------- */
+
+typedef struct {
+    uint64_t n_edges;        /* pairs with score >= t */
+    uint32_t n_components;   /* components of the graph {score >= t} */
+    uint32_t n_singletons;   /* components of one member */
+    uint32_t largest;        /* members of the largest component */
+    uint32_t reserved;
+} hmk_component_level;
+
+typedef struct {
+    uint64_t n_edges;        /* edges >= threshold */
+    uint64_t pairs_scored;   /* 0 for the _from_edges forms: nothing is scored */
+    uint32_t n_levels;       /* threshold_hi - threshold + 1 */
+    uint32_t n_components, n_singletons, largest;   /* at `threshold` */
+    double   kernel_ms;      /* the scoring pass, HIP events */
+    double   components_ms;  /* the kernels behind the pass on the device, HIP events (0 for hmk_components_from_edges) */
+} hmk_components_stats;
+
+/* The connected components of the neighbour graph of the whole hmk_set_sequences set, a ~ b iff
+ * ShiftedScorer(matrix, shift_penalty, max_shift).sequenceScore >= t, for every t = threshold ... threshold_hi from ONE scoring
+ * pass at `threshold`.  What a component means to the other calls: ClinkageClusterScorer.clusterScore returns MIN_VALUE + 1 as
+ * soon as one pair of two clusters is below the threshold (ClinkageClusterScorer.java:36-48), so no cluster that the greedy or the
+ * complete-linkage calls here (cluster, assign, continue, match, merge, split) can form at t crosses a component at t, and a
+ * component of one member is a singleton in all of them.  Components are independent inputs for hmk_clinkage_split / _merge.
+ *   component[i]            the smallest index of the uploaded set in i's component at the level `threshold`; may be NULL.  It
+ *                           does not depend on the order of the edges, on the plan's order or on the pass's segments.
+ *   levels[t - threshold]   for t = threshold ... threshold_hi; may be NULL.  threshold_hi == threshold is the single-level call.
+ *   checks                  HMK_ERR_BAD_ARG before the device is looked at (a host-only context answers them): threshold_hi <
+ *                           threshold, threshold_hi - threshold > 255, component and levels both NULL with n > 0, an asymmetric
+ *                           matrix (as hmk_clinkage_cluster).  Then the checks of hmk_neighbors_shifted at `threshold`.  Never
+ *                           HMK_ERR_CAPACITY (the call grows its own scratch).  No sequences: HMK_OK, zeroed levels.
+ * The pass is hmk_neighbors_shifted's (same plan slot, same kernels) into the context's edge buffer; behind it k_components.hip: a
+ * histogram of the edges' levels min(score, threshold_hi) - threshold, the edges dealt into one run per level, and per level from
+ * threshold_hi down one lock-free union-find launch (the larger root is hooked under the smaller), one that flattens the trees and
+ * counts the members per root, one that reads singletons and the largest component off those counts.  A single-level call without
+ * `levels` unites straight from the pass's segments.  Only the levels and one label array cross to the host.  On a
+ * hmk_create_multi context the call runs on the root device. */
+int hmk_components_shifted(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, int threshold_hi,
+                           uint32_t *component, hmk_component_level *levels, hmk_components_stats *stats);
+
+/* The same from packed HMK_EDGE_* edges: each unordered pair once, either orientation, any order; the scores are read from the
+ * edges, an edge with a score below `threshold` is ignored; an index >= n or a self pair is HMK_ERR_BAD_ARG.  A plain sequential
+ * union-find on the host (edges sorted by score, descending, by counting): works on a host-only context, and is the second
+ * implementation the device path is tested against.  No symmetry check: nothing is scored. */
+int hmk_components_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t n_edges, int threshold, int threshold_hi,
+                              uint32_t *component, hmk_component_level *levels, hmk_components_stats *stats);
+
+/* The same with the edges in device memory (the context's device), through the kernels of hmk_components_shifted.  An index >= n
+ * or a self pair is found on the device, before any array is touched with it: HMK_ERR_BAD_ARG. */
+int hmk_components_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n_edges, int threshold, int threshold_hi,
+                                  uint32_t *component, hmk_component_level *levels, hmk_components_stats *stats);
+
 /* Where the time of the last hmk_greedy_cluster / hmk_greedy_from_edges_dev call of this context went
  * (milliseconds; the span of Hammock.java:406-411 minus the sort).  score_ms and csr_ms are device times (HIP events on
  * the call's stream), the others host wall time.  The parts overlap (phase 1 runs while the rest of the pair space is
