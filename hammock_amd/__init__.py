@@ -4,8 +4,8 @@ scoring + LimitedGreedySequenceClusterer), behind the C ABI of
 include/hammock_hip.h.  See DESIGN.md and INTEGRATION.md."""
 from .api import (AMINO_ACIDS, Cluster, Context, DataException, DeviceError, FileFormatException,
                   HammockException, HipClinkageSequenceClusterer, HipGreedySequenceClusterer, LocalAlignmentScorer, ReferenceWouldCrash,
-                  ShiftedScorer, UniqueSequence, edge_fields, encode, pack_edges, pack_sequences)
+                  ShiftedScorer, UniqueSequence, aligned_rows, edge_fields, encode, pack_edges, pack_sequences)
 
 __all__ = ["AMINO_ACIDS", "Cluster", "Context", "DataException", "DeviceError", "FileFormatException",
            "HammockException", "HipClinkageSequenceClusterer", "HipGreedySequenceClusterer", "LocalAlignmentScorer", "ReferenceWouldCrash",
-           "ShiftedScorer", "UniqueSequence", "edge_fields", "encode", "pack_edges", "pack_sequences"]
+           "ShiftedScorer", "UniqueSequence", "aligned_rows", "edge_fields", "encode", "pack_edges", "pack_sequences"]

@@ -35,6 +35,7 @@ SYMBOLS = [
     "hmk_cluster_pairs_shifted", "hmk_clinkage_merge", "hmk_clinkage_merge_from_edges",
     "hmk_cluster_linkage_shifted", "hmk_clinkage_split", "hmk_clinkage_split_from_edges",
     "hmk_components_shifted", "hmk_components_from_edges", "hmk_components_from_edges_dev",
+    "hmk_cluster_align_shifted",
 ]
 
 
@@ -98,6 +99,12 @@ class ComponentsStats(C.Structure):
     """hmk_components_stats"""
     _fields_ = [("n_edges", C.c_uint64), ("pairs_scored", C.c_uint64), ("n_levels", C.c_uint32), ("n_components", C.c_uint32),
                 ("n_singletons", C.c_uint32), ("largest", C.c_uint32), ("kernel_ms", C.c_double), ("components_ms", C.c_double)]
+
+
+class AlignStats(C.Structure):
+    """hmk_align_stats"""
+    _fields_ = [("pairs_scored", C.c_uint64), ("n_multi", C.c_uint32), ("max_width", C.c_uint32), ("launches", C.c_uint32),
+                ("reserved", C.c_uint32), ("kernel_ms", C.c_double)]
 
 
 class GreedyPhases(C.Structure):
@@ -181,6 +188,9 @@ def _load():
     L.hmk_components_shifted.argtypes = [vp, i32, i32, i32, i32, p_u32, C.POINTER(ComponentLevel), C.POINTER(ComponentsStats)]
     L.hmk_components_from_edges.argtypes = [vp, p_u64, u64, i32, i32, p_u32, C.POINTER(ComponentLevel), C.POINTER(ComponentsStats)]
     L.hmk_components_from_edges_dev.argtypes = [vp, vp, u64, i32, i32, p_u32, C.POINTER(ComponentLevel), C.POINTER(ComponentsStats)]
+    p_i64 = C.POINTER(C.c_int64)
+    L.hmk_cluster_align_shifted.argtypes = [vp, u32, u32, p_u32, u32, i32, i32, p_u32, p_i64, p_u32, p_i64, p_i32, p_i32, p_u32,
+                                            C.POINTER(AlignStats)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("hmk_destroy", "hmk_last_error", "hmk_last_kernel_ms"):

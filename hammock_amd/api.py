@@ -91,6 +91,18 @@ def pack_edges(x, m, score) -> np.ndarray:
     return (x << np.uint64(40)) | (m << np.uint64(16)) | s
 
 
+def aligned_rows(seqs, column, width_of_slot):
+    """The aligned rows of Context.cluster_align_shifted's result: per sequence column[k] times '-', the sequence, '-' up to
+    width_of_slot[k] (the width of the sequence's slot: width[member_cluster]).  seqs: strings."""
+    rows = []
+    for s, c, w in zip(seqs, column, width_of_slot):
+        c, w = int(c), int(w)
+        if c + len(s) > w:
+            raise ValueError(f"a sequence of {len(s)} residues at column {c} does not fit a width of {w}")
+        rows.append("-" * c + s + "-" * (w - c - len(s)))
+    return rows
+
+
 # hmk_component_level, one entry per threshold of a components call
 LEVEL_DTYPE = np.dtype([("n_edges", np.uint64), ("n_components", np.uint32), ("n_singletons", np.uint32), ("largest", np.uint32),
                         ("reserved", np.uint32)])
@@ -564,6 +576,32 @@ class Context:
         self.last_linkage_stats = stats
         return (min_score[:ncl], min_a[:ncl], min_b[:ncl], n_below[:ncl],
                 member_min[:mc.size] if members else None, member_below[:mc.size] if members else None)
+
+    def cluster_align_shifted(self, r0, r1, member_cluster, n_clusters, max_shift, shift_penalty, sums=True):
+        """hmk_cluster_align_shifted: a centre-star alignment of given clusters (members [r0, r1), member r in slot
+        member_cluster[r - r0]) around their medoids, in the ungapped model of ShiftedScorer.scoreWithShift; not Clustal Omega's
+        alignment -> (center uint32[n_clusters] -- the member with the largest sum of scores against the others, the smallest index
+        among ties --, center_sum int64[n_clusters], width uint32[n_clusters], member_sum int64[r1 - r0] or None with sums=False,
+        center_score int32[r1 - r0], shift int32[r1 - r0] -- scoreWithShift(seq1 = the centre, seq2 = the member); INT32_MAX and 0
+        for a centre --, column uint32[r1 - r0]).  aligned_rows builds the strings.  Statistics: last_align_stats."""
+        mc, _ = self._merge_args(r0, r1, member_cluster, None)
+        ncl, nm = int(n_clusters), mc.size
+        center = np.zeros(max(ncl, 1), dtype=np.uint32)
+        center_sum = np.zeros(max(ncl, 1), dtype=np.int64)
+        width = np.zeros(max(ncl, 1), dtype=np.uint32)
+        member_sum = np.zeros(max(nm, 1), dtype=np.int64) if sums else None
+        center_score = np.zeros(max(nm, 1), dtype=np.int32)
+        shift = np.zeros(max(nm, 1), dtype=np.int32)
+        column = np.zeros(max(nm, 1), dtype=np.uint32)
+        stats = N.AlignStats()
+        st = N.lib.hmk_cluster_align_shifted(self._h, int(r0), int(r1), _ptr(mc, C.c_uint32), ncl, int(max_shift), int(shift_penalty),
+                                             _ptr(center, C.c_uint32), _ptr(center_sum, C.c_int64), _ptr(width, C.c_uint32),
+                                             _ptr(member_sum, C.c_int64) if sums else None, _ptr(center_score, C.c_int32),
+                                             _ptr(shift, C.c_int32), _ptr(column, C.c_uint32), C.byref(stats))
+        if st:
+            self._raise(st)
+        self.last_align_stats = stats
+        return (center[:ncl], center_sum[:ncl], width[:ncl], member_sum[:nm] if sums else None, center_score[:nm], shift[:nm], column[:nm])
 
     def _merge_out(self, nm, ncl):
         merged = np.full(max(ncl, 1), -1, dtype=np.int32)

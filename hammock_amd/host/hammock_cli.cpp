@@ -147,6 +147,7 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "                      [--device <int>]\n"
               << "          hammock-hip split -i <clusters.tsv> -d <directory> [-m <file>] [-x <int>] [-p <int>] [-g <int>] [--java_hashset <int>]\n"
               << "                      [--device <int>]\n"
+              << "          hammock-hip align -i <clusters.tsv> -d <directory> [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [--device <int>]\n"
               << "          hammock-hip components -i <sequences> -d <directory> [-g <int>] [--scan_to <int>] [-f fasta|tab] [-m <file>] [-x <int>]\n"
               << "                      [-p <int>] [-l <labels>] [--device <int>]\n\n"
               << "-i, --input <file>\n\tA path to an input file\n\n"
@@ -168,7 +169,7 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "--best <int>\n\t(search) keep only the best 1..32 hits of each query; (assign, match) report the best 1..32 feasible clusters (default 1)\n\n"
               << "--clusters <file>\n\t(assign, continue, match) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv);\n\t(merge) a second cluster file: its clusters keep their ids, the -i file's are renumbered behind them\n\n"
               << "--scan_to <int>\n\t(components) the last threshold of the scan: component_levels.tsv gets one line per threshold from -g to this one\n\t(at most 255 above -g; default: -g alone)\n\n"
-              << "--skip_singletons\n\t(assign, match, merge) only clusters of more than one unique sequence are candidates;\n\t(check) clusters of one unique sequence are left out of cluster_linkage.tsv\n\n"
+              << "--skip_singletons\n\t(assign, match, merge) only clusters of more than one unique sequence are candidates;\n\t(check) clusters of one unique sequence are left out of cluster_linkage.tsv;\n\t(align) clusters of one unique sequence are left out of cluster_centers.tsv\n\n"
               << "--java_hashset <8|7|6>\n\t(clinkage, merge, split) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
 }
 
@@ -1333,6 +1334,108 @@ int runSplit(const std::vector<std::string> &args) {
     }
 }
 
+// `hammock-hip align -i clusters.tsv -d dir [-x -p -m] [--skip_singletons]`: shows the clusters of a cluster file -- a centre-star
+// alignment of each around its medoid in the ungapped model of ShiftedScorer.scoreWithShift (hmk_cluster_align_shifted).  Not the
+// Clustal Omega alignment of the reference (ClustalRunner.java:34-66): no gap ever stands inside a peptide.  Defaults of -x / -p are
+// check's (-g is settled as there and logged, but nothing is thresholded).  Writes
+//   initial_clusters_sequences.tsv   the input's rows in line order in the format of writeClusterSequencesToCsv
+//                                    (FileIOManager.java:594-638), the `alignment` column holding every clustered sequence's aligned
+//                                    row (a cluster of one keeps its bare string); every loader drops that column, so the file feeds
+//                                    the other modes unchanged
+//   alignments_initial/<id>.aln      per cluster of more than one sequence, in the shape the reference reads back
+//                                    (FileIOManager.java:761-776, Cluster.java:167-176; the directory's name: Hammock.java:1317):
+//                                    records ">id_k", k from 1 in the cluster's member order as loaded, each followed by its row
+//   cluster_centers.tsv              cluster_id, size (unique sequences), center (the medoid's string), center_sum, width; clusters
+//                                    in file order (--skip_singletons leaves clusters of one unique sequence out)
+// Exit codes as check: a cluster file the loader rejects is 2.
+int runAlign(const std::vector<std::string> &args) {
+    Options o;
+    parseCommonArgs(args, o);
+    parseModeArgs(args, o, -1);
+    requireOneDevice(o, "align", "an alignment");
+    requireInput(o);
+    makeOutputDirectory(o, o.parentDir);
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        ContextFuture contextReady = beginRun(o, logger, false);
+        logRunStart(logger, "align", args);
+        logger.logAndStderr("Loading clusters...");
+        MergeInput in;
+        try {
+            in = loadMergeInput(o.inputFileName, std::string());
+            if (in.clusters.empty()) throw FileFormatException("Error. The cluster file holds no clusters.");
+        } catch (const FileFormatException &e) {
+            logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
+            logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
+            return 2;
+        }
+        const std::vector<ClusterPtr> &clusters = in.clusters;
+        const std::vector<UniqueSequencePtr> all = sequencesOf(clusters);
+        logger.logAndStderr(std::to_string(clusters.size()) + " clusters of " + std::to_string(all.size()) + " sequences loaded.");
+        const SequenceListSummary summary = summariseSequences(all);
+        settleShiftAndThreshold(o, logger, summary, summary, summary, "Align");
+
+        std::vector<UniqueSequencePtr> upload;
+        const Candidates cand = appendCandidates(clusters, false, 0, upload);
+        const uint32_t n = (uint32_t)upload.size(), ncl = (uint32_t)cand.slots.size();
+        std::vector<uint32_t> center(ncl), width(ncl), column(n);
+        std::vector<int64_t> centerSum(ncl);
+        std::vector<int32_t> centerScore(n), shift(n);
+        hmk_align_stats stats{};
+        logger.logAndStderr("Aligning...");
+        const auto time0 = std::chrono::steady_clock::now();
+        {
+            const std::shared_ptr<NativeContext> nc = contextReady.get();
+            nc->setSequences(upload, true);
+            const int st = hmk_cluster_align_shifted(nc->get(), 0, n, cand.memberCluster.data(), ncl, o.maxShift, o.shiftPenalty, center.data(),
+                                                     centerSum.data(), width.data(), nullptr, centerScore.data(), shift.data(), column.data(), &stats);
+            if (st) nc->raise(st, nullptr);
+        }
+        logger.logAndStderr("Ready. Align time: " + std::to_string(millisSince(time0)));
+        logger.logAndStderr("Clusters of more than one sequence: " + std::to_string(stats.n_multi) + ", pairs scored: " + std::to_string(stats.pairs_scored) +
+                            ", widest alignment: " + std::to_string(stats.max_width) + ", GPU kernels: " + std::to_string(stats.kernel_ms) + " ms");
+        logger.logAndStderr("Saving results to output files...");
+        std::unordered_map<const UniqueSequence *, std::string> rows;
+        rows.reserve(n);
+        auto rowOf = [&](uint32_t k) {
+            const std::string &s = upload[k]->getSequenceString();
+            const uint32_t w = width[cand.memberCluster[k]];
+            return std::string(column[k], '-') + s + std::string(w - column[k] - (uint32_t)s.size(), '-');
+        };
+        for (uint32_t k = 0; k < n; k++) rows.emplace(upload[k].get(), rowOf(k));
+        const std::string seqCsv = o.workingDirectory + "/initial_clusters_sequences.tsv", msaDir = o.workingDirectory + "/alignments_initial",
+                          centersCsv = o.workingDirectory + "/cluster_centers.tsv";
+        FileIOManager::writeClusterSequencesToCsv(in.lineOrder, FileIOManager::SequenceClusterIndex(clusters), seqCsv, in.labels, &rows);
+        if (mkdir(msaDir.c_str(), 0777) != 0) throw HammockException("cannot create " + msaDir);
+        {
+            std::ofstream out(centersCsv);
+            if (!out) throw HammockException("cannot write " + centersCsv);
+            out << "cluster_id\tsize\tcenter\tcenter_sum\twidth\n";
+            uint32_t k = 0;   // (every cluster is a candidate: slot c is cluster c, its members follow each other in upload)
+            for (uint32_t c = 0; c < ncl; c++) {
+                const Cluster &cl = *clusters[c];
+                const uint32_t s = (uint32_t)cl.getUniqueSize();
+                if (s > 1) {
+                    const std::string file = msaDir + "/" + std::to_string(cl.getId()) + ".aln";
+                    std::ofstream aln(file);
+                    if (!aln) throw HammockException("cannot write " + file);
+                    for (uint32_t t = 0; t < s; t++) aln << '>' << cl.getId() << '_' << t + 1 << '\n' << rows.at(upload[k + t].get()) << '\n';
+                }
+                if (s > 1 || !o.skipSingletons)
+                    out << cl.getId() << '\t' << s << '\t' << upload[center[c]]->getSequenceString() << '\t' << centerSum[c] << '\t' << width[c] << '\n';
+                k += s;
+            }
+        }
+        logger.logAndStderr("Aligned cluster file in: " + seqCsv);
+        logger.logAndStderr("Alignments in: " + msaDir);
+        logger.logAndStderr("Centres in: " + centersCsv);
+        logger.logWithTime("Program successfully ended.");
+        return 0;
+    } catch (...) {
+        return reportRunError(logger, false);
+    }
+}
+
 // `hammock-hip components -i X.fa -d dir [-g T] [--scan_to T2] [-x -p -m -f -l]`: the connected components of the neighbour graph
 // {score >= t} for every t = T ... T2 from one scoring pass (hmk_components_shifted).  No cluster any other mode can form at t crosses
 // a component at t (ClinkageClusterScorer.java:36-48), so this is where to read off at which threshold a data set falls apart, and
@@ -1541,6 +1644,7 @@ int main(int argc, char **argv) {
         if (args[0] == "check") return runCheck(args);
         if (args[0] == "split") return runSplit(args);
         if (args[0] == "components") return runComponents(args);
+        if (args[0] == "align") return runAlign(args);
         if (args[0] == "io-selftest") return ioSelftest(args);
         if (args[0] == "dump-matrix") {   // the default matrix in the text format FileIOManager.loadScoringMatrix reads
             std::cout << "# BLOSUM62 substitution matrix (public NCBI table), 24 x 24, order " << AMINO_ACIDS << "\n"

@@ -1121,9 +1121,11 @@ public:
 
 // writeClusterSequencesToCsv, FileIOManager.java:594-638.  The `alignment` column: the reference fills
 // it from Clustal Omega output for multi-member clusters (external process, out of scope) and with the
-// bare sequence for singletons (:770-776); members of multi-member clusters get "NA" (:617-618).
+// bare sequence for singletons (:770-776); members of multi-member clusters get "NA" (:617-618) -- or, from the align mode, their
+// row of `alignedRows` (sequence object -> aligned row).
 inline void writeClusterSequencesToCsv(const std::vector<UniqueSequencePtr> &sequences, const SequenceClusterIndex &index,
-                                       const std::string &filePath, const std::vector<std::string> &labels) {
+                                       const std::string &filePath, const std::vector<std::string> &labels,
+                                       const std::unordered_map<const UniqueSequence *, std::string> *alignedRows = nullptr) {
     std::ofstream w(filePath, std::ios::binary);
     if (!w) throw HammockException("java.io.IOException: cannot write " + filePath);
     std::string head = std::string("cluster_id") + CSV_SEPARATOR + "sequence" + CSV_SEPARATOR + "alignment" + CSV_SEPARATOR + "sum";
@@ -1145,7 +1147,12 @@ inline void writeClusterSequencesToCsv(const std::vector<UniqueSequencePtr> &seq
         if (cluster) {
             appendNumber(out, cluster->getId());
             out += CSV_SEPARATOR; out += str; out += CSV_SEPARATOR;
-            if (index.isSingletonAlignment(str, cluster)) out += str; else out += "NA";
+            const std::string *row = nullptr;
+            if (alignedRows) {
+                const auto it = alignedRows->find(seq.get());
+                if (it != alignedRows->end()) row = &it->second;
+            }
+            if (index.isSingletonAlignment(str, cluster)) out += str; else if (row) out += *row; else out += "NA";
             out += CSV_SEPARATOR;
         } else {
             out += "NA"; out += CSV_SEPARATOR; out += str; out += CSV_SEPARATOR; out += "NA"; out += CSV_SEPARATOR;

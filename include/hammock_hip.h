@@ -656,6 +656,53 @@ int hmk_components_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t n_ed
 int hmk_components_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n_edges, int threshold, int threshold_hi,
                                   uint32_t *component, hmk_component_level *levels, hmk_components_stats *stats);
 
+/* ---- aligning given clusters around their medoids --------------------------------------- */
+
+typedef struct {
+    uint64_t pairs_scored;   /* sum over slots of s(s-1)/2, plus one pair per non-centre member of a multi-member slot */
+    uint32_t n_multi;        /* slots with two or more members */
+    uint32_t max_width;      /* the widest alignment of the call */
+    uint32_t launches, reserved;
+    double   kernel_ms;      /* device time, HIP events */
+} hmk_align_stats;
+
+/* A centre-star alignment of every given cluster in the model of the scorer that formed it: ShiftedScorer.scoreWithShift
+ * (ShiftedScorer.java:48-95) is an ungapped alignment of two peptides and its result carries the shift
+ * (AligningScorerResult.getShift()).  The alignment is gap-free inside a peptide and deterministic.  It is NOT the Clustal Omega
+ * alignment the reference builds per cluster (ClustalRunner.java:34-66) and agrees with it only by accident.
+ * Members [r0, r1) of the hmk_set_sequences set with member_cluster and n_clusters as hmk_cluster_linkage_shifted takes them.  There
+ * is no threshold: nothing is thresholded.
+ *   score(a, b)            ShiftedScorer(matrix, shift_penalty, max_shift).sequenceScore(seq1 = the larger index, seq2 = the smaller)
+ *                          (ShiftedScorer.java:48-100): the orientation of hmk_cluster_linkage_shifted
+ *   member_sum[m - r0]     the sum of score(m, b) over the other members b of m's slot; 0 in a slot of one member; may be NULL
+ *   center[c]              the member of slot c with the largest member_sum (the medoid), among ties the smallest index; a slot of one
+ *                          member is its own centre.  center_sum[c] is that member's sum.
+ *   center_score, shift    [m - r0], for a member m other than its slot's centre z: scoreWithShift(seq1 = z, seq2 = m), getScore() /
+ *                          getShift() -- exactly what hmk_score_with_shift returns for i = z, j = m: the first strict maximum in the
+ *                          loop's order (:86-89) and the sign rule of :91-93.  Read through :69-77 and :91-93, residue k of m then
+ *                          stands under residue k + shift of z.  For m = z: shift = 0 and center_score = INT32_MAX (no comparison is
+ *                          made; the convention hmk_cluster_linkage_shifted has for a slot of one member).
+ *   column[m - r0]         shift[m] - (the smallest shift in m's slot, the centre's 0 included)
+ *   width[c]               the maximum over the slot's members of column + length
+ *   the aligned row of m   column times '-', then the peptide, then '-' up to width.  The call builds no strings.
+ *   checks                 HMK_ERR_BAD_ARG before the device is looked at (a host-only context answers them): the range and slot
+ *                          checks of hmk_cluster_linkage_shifted (a slot without members is refused), a null member_cluster with a
+ *                          non-empty range, a null required output, an asymmetric matrix.  Then the checks of hmk_search_shifted over
+ *                          the range that do not concern a threshold: HMK_ERR_SHIFT_TOO_BIG against the shortest length, and scores
+ *                          that fit int16 at both ends as hmk_cluster_linkage_shifted proves them -- which is what bounds the sums:
+ *                          |member_sum| < 2^15 * 2^24 -- and n <= 2^24.  An empty range is HMK_OK with nothing written.  Never
+ *                          HMK_ERR_CAPACITY.  Without a device HMK_ERR_DEVICE: there is no CPU fallback.
+ * Every pair inside a slot is scored once for the sums and every non-centre member once more against its centre, and nothing else
+ * (k_align.hip); the scratch is O(members + clusters), and the centres never leave the device between the kernels.  Only integer
+ * adds, minima and maxima: the result does not depend on the schedule.  On a hmk_create_multi context the call runs on the root
+ * device. */
+int hmk_cluster_align_shifted(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_cluster, uint32_t n_clusters,
+                              int max_shift, int shift_penalty,
+                              uint32_t *center, int64_t *center_sum, uint32_t *width,               /* n_clusters each, required */
+                              int64_t *member_sum,                                                   /* r1 - r0, may be NULL */
+                              int32_t *center_score, int32_t *shift, uint32_t *column,               /* r1 - r0 each, required */
+                              hmk_align_stats *stats);
+
 /* Where the time of the last hmk_greedy_cluster / hmk_greedy_from_edges_dev call of this context went
  * (milliseconds; the span of Hammock.java:406-411 minus the sort).  score_ms and csr_ms are device times (HIP events on
  * the call's stream), the others host wall time.  The parts overlap (phase 1 runs while the rest of the pair space is
