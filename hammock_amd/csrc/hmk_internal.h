@@ -73,8 +73,10 @@ struct NeighborParams {
 // takes its planes' start values from the entry as loaded.  The table therefore belongs to ONE class's cinit, i.e. to the plan's
 // (max shift, penalty, threshold) -- which is what the plan cache is keyed on (build_plan), and a plan frees its table with itself.
 constexpr int KEYTAB_DWORDS = 16;
-// the shapes that run it: one length, one row group per tile, hits cut out in the loop -- only the BASELINE shape for now
-constexpr bool rows_keyed(int x, int d, int cap, bool exact, int g) { return exact && d == 0 && g == 1 && x == 3 && cap == 12; }
+// the shapes that run it: one length, hits cut out in the loop -- only the BASELINE shape for now, with one row group per tile or
+// (a paired plan, hmk_plan.cpp: ROWS_KEY_PAIR_GROUPS) two
+constexpr int ROWS_KEY_PAIR_GROUPS = 2;
+constexpr bool rows_keyed(int x, int d, int cap, bool exact, int g) { return exact && d == 0 && (g == 1 || g == ROWS_KEY_PAIR_GROUPS) && x == 3 && cap == 12; }
 // the two key positions of length l at max shift x: middle positions (paired with every row position by all 2x + 1 planes)
 constexpr int rows_key_pos(int x, int l, int q) { return l / 2 - 1 + q < x ? x : l / 2 - 1 + q; }
 

@@ -20,9 +20,11 @@ hipError_t launch_neighbors_swar(int lbmax, int nw, bool exact, const NeighborPa
 // exact: a set of one length lb (its own instantiation); else the capacity form, rows_cap_for(lb) >= lb.
 bool rows_kernel_available(int X, int la, int lb, bool exact);
 int rows_cap_for(int lb);
-int rows_per_tile_rows(int X, int d, int cap, bool exact);   // rows per tile of that instantiation
+// rows per tile of that instantiation; key_pairs: of its paired form (a key-sorted plan's two row groups behind one column set-up,
+// Plan::key_pairs), 0 where the shape has none
+int rows_per_tile_rows(int X, int d, int cap, bool exact, bool key_pairs = false);
 hipError_t launch_neighbors_rows(int X, int d, int cap, bool exact, const NeighborParams &P, uint32_t tile_base,
-                                 uint32_t n_tiles, hipStream_t s);
+                                 uint32_t n_tiles, bool key_pairs, hipStream_t s);
 hipError_t warm_neighbors_rows_module();
 // the key table of a key-sorted one-length plan (NeighborParams::keytab) from its sorted residues, on the null stream; cinit: its
 // class's TileClass::cinit (the planes' initial lanes, folded into key 0's entries)

@@ -113,7 +113,7 @@ int launch_plan(hmk_ctx *ctx, const Plan &pl, int X, int p, int thr, void *d_edg
         if (g.path == PATH_DIRECT)
             HIPCHK(ctx, launch_neighbors_direct(P, t0, cnt, ctx->d_M.as<int32_t>(), X, p, thr, s));
         else if (g.path == PATH_ROWS)
-            HIPCHK(ctx, launch_neighbors_rows(X, g.nw, g.lbk, pl.rows_exact, P, t0, cnt, s));
+            HIPCHK(ctx, launch_neighbors_rows(X, g.nw, g.lbk, pl.rows_exact, P, t0, cnt, pl.key_pairs, s));
         else
             HIPCHK(ctx, launch_neighbors_swar(g.lbk, g.nw, pl.exact, P, t0, cnt, s));
     }

@@ -70,12 +70,12 @@ void sort_by_length(const hmk_ctx *ctx, uint32_t a0, uint32_t a1, uint32_t b0, u
 using GroupKey = std::tuple<int, int, int>;
 struct KernelChoice { bool rows; int lbk; uint32_t R; GroupKey key; };   // lbk: column capacity; R: rows per tile
 
-KernelChoice choose_kernel(const TileClass &tc, int X, bool use_rows, bool rows_exact, bool exact) {
+KernelChoice choose_kernel(const TileClass &tc, int X, bool use_rows, bool rows_exact, bool exact, bool key_pairs = false) {
     const int la = tc.la, lb = tc.lb;
     KernelChoice k;
     k.rows = use_rows && tc.path == PATH_U8 && la >= lb && (rows_exact || rows_kernel_available(X, la, lb, false));
     k.lbk = k.rows ? (rows_exact ? lb : rows_cap_for(lb)) : exact ? 12 : swar_lbmax_for(lb);
-    k.R = k.rows ? (uint32_t)rows_per_tile_rows(X, la - lb, k.lbk, rows_exact)
+    k.R = k.rows ? (uint32_t)rows_per_tile_rows(X, la - lb, k.lbk, rows_exact, key_pairs)
                  : tc.path == PATH_DIRECT ? 16u : (uint32_t)swar_rows_per_tile(k.lbk, tc.nw, exact);
     k.key = k.rows ? GroupKey((int)PATH_ROWS, la - lb, k.lbk)
                    : GroupKey((int)tc.path, tc.path == PATH_DIRECT ? 0 : (int)tc.nw, tc.path == PATH_DIRECT ? 0 : k.lbk);
@@ -320,7 +320,7 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
     const int want_keys = key_sort_ok ? ctx->sw.key_sort : 0;
     if (pl.valid && pl.X == X && pl.p == p && pl.thr == thr && pl.part == part && pl.n_parts == n_parts &&
         (band_rows < 0 || pl.band_req == band_rows) && pl.no_rows_kernel == ctx->sw.no_rows_kernel && pl.key_sort == want_keys &&
-        pl.row_shared == !ctx->sw.no_row_shared)
+        pl.row_shared == !ctx->sw.no_row_shared && pl.key_row_pairs == ctx->sw.key_row_pairs)
         return HMK_OK;
     free_plan(pl);
     if (band_rows < 0) band_rows = 0;
@@ -446,6 +446,7 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
     // edges in row order (both slower on the sorted order: 10^5 call 4.04 -> 4.44 ms), and shards keep their caller-order rows.
     pl.key_sort = want_keys;
     pl.row_shared = !ctx->sw.no_row_shared;
+    pl.key_row_pairs = ctx->sw.key_row_pairs;
     std::vector<uint32_t> keyrun;
     const int L1 = ctx->min_len;
     const bool key_sorted = pl.key_sort > 0 && pl.rows_exact && !(refine && !all_rows_fit) &&
@@ -476,11 +477,23 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
     // Column runs: long runs amortise the table build (65,536 columns: 3.55 ms for the whole 10^5 pass against
     // 3.60 ms with 16,384), short ones keep the tail of a small launch short (a 1/8 shard: 0.478 ms with 16,384,
     // 0.532 ms with 65,536).  Take the longest run that still leaves ~8 rounds of workgroups (256 CUs x 7).
-    const uint64_t tile_rows = pl.rows_exact ? (uint64_t)rows_per_tile_rows(X, 0, ctx->min_len, true) : use_rows ? 16 : 6;
-    const uint64_t row_groups = (uint64_t)n / tile_rows / n_parts + 1;
-    pl.cols_per_tile = 65536;
-    while (pl.cols_per_tile > 16384 && row_groups * ((uint64_t)n / (2 * pl.cols_per_tile) + 1) < 8 * 1792)
-        pl.cols_per_tile /= 2;
+    auto tiles_about = [&](uint64_t tile_rows, uint32_t cols) { return ((uint64_t)n / tile_rows / n_parts + 1) * ((uint64_t)n / (2 * cols) + 1); };
+    auto cols_for = [&](uint64_t tile_rows) {
+        uint32_t cols = 65536;
+        while (cols > 16384 && tiles_about(tile_rows, cols) < 8 * 1792) cols /= 2;
+        return cols;
+    };
+    // Paired tiles (k_neighbors_rows.h): a key-sorted plan takes 16-row tiles -- two row groups behind one column
+    // set-up -- when the 16-row plan still has KEY_PAIR_MIN_TILES tiles, six rounds of the 2,048 workgroup slots (256 CUs x 8).  The
+    // constant lies just below the smallest plan pairing was measured on (74,041 12-mers, about 13,900 tiles, -1.2 % and
+    // -2.2 % in two sessions; 10^5, about 25,000, -2.3 %); small sets, which do not fill the slots even with 8-row tiles, keep those.  HMK_KEY_ROW_PAIRS=0|1
+    // overrides the rule.
+    constexpr uint64_t KEY_PAIR_MIN_TILES = 6 * 2048;
+    const uint64_t paired_rows = key_sorted ? (uint64_t)rows_per_tile_rows(X, 0, L1, true, true) : 0;
+    pl.key_pairs = paired_rows != 0 && (ctx->sw.key_row_pairs >= 0 ? ctx->sw.key_row_pairs == 1
+                                                                   : tiles_about(paired_rows, cols_for(paired_rows)) >= KEY_PAIR_MIN_TILES);
+    const uint64_t tile_rows = pl.key_pairs ? paired_rows : pl.rows_exact ? (uint64_t)rows_per_tile_rows(X, 0, ctx->min_len, true) : use_rows ? 16 : 6;
+    pl.cols_per_tile = cols_for(tile_rows);
     // (not below 4,096 columns: a tile's dead time -- its chain of dependent loads before the first table read, the flush after
     // the last -- is about four 256-column batches long, and short tiles pay it several times over on every workgroup slot.
     // 10^4 12-mers: 1,024 / 2,048 / 4,096 / 16,384 columns per tile 0.090 / 0.061 / 0.053 / 0.051 ms, although the last leaves
@@ -530,7 +543,7 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
                 if (split < re) ranges.push_back(Range{split, re, tc0});
             }
             for (const Range &rg : ranges) {
-                const KernelChoice k = choose_kernel(rg.tc, X, use_rows, pl.rows_exact, pl.exact);
+                const KernelChoice k = choose_kernel(rg.tc, X, use_rows, pl.rows_exact, pl.exact, pl.key_pairs);
                 const uint32_t cls = add_class(classes, S, rg.tc, k.rows);
                 std::vector<Tile> &dst = grouped[k.key];
                 const bool tri = same && ctx->symmetric;   // triangle: the columns after the first row of a chunk, column > row

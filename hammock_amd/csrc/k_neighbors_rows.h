@@ -55,7 +55,8 @@ constexpr int rows_stage(int x, int d, int cap, bool exact) {
 // groups of 8 rows per tile.  Capacity forms (a length bucket's short column runs): 1 / 2 / 3 / 4 groups measured 4.87 / 4.48 /
 // 4.58 / 4.74 ms on BASELINE config 4a.  One-length shapes: long column runs, one group (2.65-2.67 ms with 1 or 2 at length
 // 12) -- but the short ones, where what a step does once per COLUMN (fetch, offsets) is a quarter of its VALU work and VALU is as
-// busy as the LDS pipe, take two.
+// busy as the LDS pipe, take two.  (Key-sorted 12-mer plans of enough tiles run a second instantiation with two, ROWS_KEY_PAIR_GROUPS
+// in hmk_internal.h: with the key starts and the row-shared reads VALU became the floor there too)
 constexpr int rows_groups(int x, int /*d*/, int cap, bool exact) {
     return !exact ? 2 : rows_inloop(x, cap) ? 1 : 2;
 }
@@ -661,7 +662,9 @@ __device__ __forceinline__ void rows_for_each_group(std::integer_sequence<int, I
 // One tile (the workgroup's).  MODE: what a flush does beside storing the edge (hmk_device.h).  smem: the kernel's ONE static LDS object
 // (rows_lds_bytes of it are used): its base address is a compile-time constant, so table offsets fold into the ds_read immediate.
 // Inlined into its kernel (the flush reads the kernel's arguments through the kernarg pointer: P and tile_base must be the kernel's first two).
-template <int X, int D, int CAP, bool EXACT_LB, int G, int MODE>
+// KEY_FORMS: compile the key-sorted bodies where the shape has them (rows_keyed); the per-length kernels, whose plans are never
+// key-sorted, leave them out of their two-group 12-mer form.
+template <int X, int D, int CAP, bool EXACT_LB, int G, int MODE, bool KEY_FORMS = true>
 __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_t tile_base, uint8_t *smem) {
     using S = RowsShape<X, D, CAP, EXACT_LB, G>;
     constexpr int ND = S::ND, NI = S::NI, NEND = S::NEND, TAB_BYTES = S::TAB_BYTES;
@@ -683,11 +686,14 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
     // 32-bit LDS pointer, wave-uniform (kept in a scalar register: nothing to spill around the flush call)
     HMK_LDS uint32_t *stage = (HMK_LDS uint32_t *)stage_all + __builtin_amdgcn_readfirstlane(tid >> 6) * STAGE_CAP;
 
-    // Key-sorted sets (rows_keyed, P.keyrun set), see the batch loop.  row_shared: the planner found the group's 8 rows equal at both
-    // key positions (Tile::row_shared, a scalar load with the tile): merged entries here, the row-shared bodies below.
-    constexpr bool KEYED = rows_keyed(X, D, CAP, EXACT_LB, G);
+    // Key-sorted sets (rows_keyed, P.keyrun set), see the batch loop.  rs_groups, bit g: the planner found group g's 8 rows equal at
+    // both key positions (Tile::row_shared, a scalar load with the tile): merged entries here, the row-shared bodies below.
+    constexpr bool KEYED = KEY_FORMS && rows_keyed(X, D, CAP, EXACT_LB, G);
     const bool keyed = KEYED && P.keyrun != nullptr;
-    const bool row_shared = keyed && (T.row_shared & 1u) != 0;
+    // (one group: the flag as a bool, as before the paired tiles; two: the word, tested per group -- as bools the two flags cost the
+    // paired kernel three more SGPRs parked in VGPR lanes and 1-3 v_readlane inside every body)
+    const bool rs_first = keyed && (T.row_shared & 1u) != 0;
+    const uint32_t rs_groups = keyed ? T.row_shared : 0u;
 
     build_begin();
     const uint32_t tab_addr = lds_addr(tab);
@@ -710,7 +716,7 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
         // a row-shared group's merged entries (RowsShape::rs_row), in place of row position key_pos(0)'s: the high dword holds
         // key_pos(1)'s cell -- the same expression below, of rows 4-7, which have key_pos(0)'s residue in common with rows 0-3
         if constexpr (KEYED)
-            if (row_shared && k == S::key_pos(0) && h == 1) i = S::key_pos(1);
+            if ((G == 1 ? rs_first : ((rs_groups >> g) & 1u) != 0) && k == S::key_pos(0) && h == 1) i = S::key_pos(1);
         uint32_t v = 0;
         if (i >= 0 && i < la) {
 #pragma unroll
@@ -765,12 +771,13 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
     // planes' start values.  kmode: 0 none, 1 key 0, 3 both keys (wave-uniform).  A key-0 entry already holds the planes' initial
     // lanes (k_rows_keytab): mode 1 takes the loaded registers as they come, mode 3 adds the key-1 entry, one s_add per dword.
     // What depends on the tile only -- the row group's entries, the wave's place in keyrun -- is worked out here, once.
-    static_assert(!KEYED || (G == 1 && 2 * ND <= KEYTAB_DWORDS), "key table entry; one row group per tile");
+    // (two row groups per tile, the 16-row tiles of a paired plan: one column set-up -- fetch, offsets, run words, kmode -- serves both)
+    static_assert(!KEYED || (G <= 2 && 2 * ND <= KEYTAB_DWORDS), "key table entry; at most two row groups per tile");
     // ds_read_b64 per wave-step of the six bodies, windows that share both keys / key 0 / none
     static_assert(!KEYED || (S::body_reads(3, false) == 58 && S::body_reads(1, false) == 65 && S::body_reads(0, false) == 72), "ordinary bodies");
     static_assert(!KEYED || (S::body_reads(3, true) == 54 && S::body_reads(1, true) == 60 && S::body_reads(0, true) == 66), "row-shared bodies");
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t *kt_tile = nullptr, *kr_wave = nullptr;   // keytab of the tile's row group; keyrun of the wave's first column
+    const uint32_t *kt_tile = nullptr, *kr_wave = nullptr;   // keytab of the tile's first row group; keyrun of the wave's first column
     if (keyed) {
         kt_tile = P.keytab + (size_t)(T.row0 >> 3) * (2 * 24 * KEYTAB_DWORDS);
         kr_wave = P.keyrun + 2 * (size_t)(T.col0 + wave * 64);
@@ -813,20 +820,22 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
             if ((uint32_t)(8 * g) >= T.nrows) return;   // wave-uniform
             uint32_t W0[ND], W1[ND];
             if constexpr (KEYED) {
+                const uint32_t *const kt_group = kt_tile + (size_t)g * (2 * 24 * KEYTAB_DWORDS);   // row group (T.row0 >> 3) + g
+                const bool row_shared = G == 1 ? rs_first : (rs_groups & (1u << g)) != 0;   // wave-uniform
                 // (start values in SGPRs: the plane's first add takes them as its scalar operand.  Byte lanes: every partial sum is
                 // <= the plane's final lane <= 255, no carry)
                 uint32_t ks0[ND], ks1[ND];
                 if (kmode == 3) {
                     uint32_t kb0[ND], kb1[ND];
-                    key_entry(kt_tile + (ra.x & 31u) * KEYTAB_DWORDS, ks0, ks1);
-                    key_entry(kt_tile + (24 + (ra.y & 31u)) * KEYTAB_DWORDS, kb0, kb1);
+                    key_entry(kt_group + (ra.x & 31u) * KEYTAB_DWORDS, ks0, ks1);
+                    key_entry(kt_group + (24 + (ra.y & 31u)) * KEYTAB_DWORDS, kb0, kb1);
 #pragma unroll
                     for (int u = 0; u < ND; u++) { ks0[u] += kb0[u]; ks1[u] += kb1[u]; }
                     read_phase_begin(prio);
                     if (row_shared) S::template accumulate<g, 3, true>(off, toff, lbs, ks0, ks1, W0, W1);
                     else S::template accumulate<g, 3>(off, toff, lbs, ks0, ks1, W0, W1);
                 } else if (kmode == 1) {
-                    key_entry(kt_tile + (ra.x & 31u) * KEYTAB_DWORDS, ks0, ks1);
+                    key_entry(kt_group + (ra.x & 31u) * KEYTAB_DWORDS, ks0, ks1);
                     // (no instruction: the loads are waited for HERE, not at the first add inside the read phase)
 #pragma unroll
                     for (int u = 0; u < ND; u++) asm volatile("" : "+s"(ks0[u]), "+s"(ks1[u]));
@@ -962,7 +971,7 @@ __device__ __forceinline__ void rows_lens_pick(const NeighborParams &P, const ui
         rows_tile<X, D, CAPB, false, 2, MODE>(P, tile_base, smem);   // (a length without a form of its own)
     } else {
         if constexpr (rows_lens_has(X, D, CAPB, LB)) {
-            if (lb == LB) { rows_tile<X, D, LB, true, 2, MODE>(P, tile_base, smem); return; }   // wave-uniform
+            if (lb == LB) { rows_tile<X, D, LB, true, 2, MODE, false>(P, tile_base, smem); return; }   // wave-uniform
         }
         rows_lens_pick<X, D, CAPB, MODE, LB + 1>(P, tile_base, smem, lb);
     }

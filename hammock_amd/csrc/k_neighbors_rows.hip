@@ -23,8 +23,9 @@ int rows_part_of(int X, int d, int cap, bool exact) {
 }
 }  // namespace
 
-int rows_per_tile_rows(int X, int d, int cap, bool exact) {
+int rows_per_tile_rows(int X, int d, int cap, bool exact, bool key_pairs) {
     if (rows_part_of(X, d, cap, exact) < 0) return 0;
+    if (key_pairs) return rows_keyed(X, d, cap, exact, ROWS_KEY_PAIR_GROUPS) ? 8 * ROWS_KEY_PAIR_GROUPS : 0;
     return 8 * rows_groups(X, d, cap, exact);
 }
 
@@ -35,10 +36,10 @@ bool rows_kernel_available(int X, int la, int lb, bool exact) {
 }
 
 hipError_t launch_neighbors_rows(int X, int d, int cap, bool exact, const NeighborParams &P, uint32_t tile_base,
-                                 uint32_t n_tiles, hipStream_t s) {
+                                 uint32_t n_tiles, bool key_pairs, hipStream_t s) {
     if (n_tiles == 0) return hipSuccess;
     switch (rows_part_of(X, d, cap, exact)) {
-#define HMK_P(p) case p: return launch_rows_part_##p(X, d, cap, exact, P, tile_base, n_tiles, s);
+#define HMK_P(p) case p: return launch_rows_part_##p(X, d, cap, exact, P, tile_base, n_tiles, key_pairs, s);
         HMK_P(0) HMK_P(1) HMK_P(2) HMK_P(3) HMK_P(4) HMK_P(5) HMK_P(6) HMK_P(7) HMK_P(8) HMK_P(9) HMK_P(10) HMK_P(11) HMK_P(12)
 #undef HMK_P
     }

@@ -13,12 +13,12 @@ namespace {
 // only the shapes of THIS part are instantiated
 template <bool MINE, int X, int D, int CAP, bool EXACT_LB>
 struct RowsLaunch {
-    static hipError_t go(const NeighborParams &, uint32_t, uint32_t, hipStream_t) { return hipErrorInvalidValue; }
+    static hipError_t go(const NeighborParams &, uint32_t, uint32_t, bool, hipStream_t) { return hipErrorInvalidValue; }
 };
 template <int X, int D, int CAP, bool EXACT_LB>
 struct RowsLaunch<true, X, D, CAP, EXACT_LB> {
-    static hipError_t go(const NeighborParams &P, uint32_t tile_base, uint32_t n_tiles, hipStream_t s) {
-        return launch_rows_t<X, D, CAP, EXACT_LB>(P, tile_base, n_tiles, s);
+    static hipError_t go(const NeighborParams &P, uint32_t tile_base, uint32_t n_tiles, bool key_pairs, hipStream_t s) {
+        return launch_rows_t<X, D, CAP, EXACT_LB>(P, tile_base, n_tiles, key_pairs, s);
     }
 };
 }  // namespace
@@ -27,16 +27,16 @@ struct RowsLaunch<true, X, D, CAP, EXACT_LB> {
 #define HMK_CAT(a, b) HMK_CAT2(a, b)
 
 hipError_t HMK_CAT(launch_rows_part_, HMK_ROWS_PART)(int X, int d, int cap, bool exact, const NeighborParams &P, uint32_t tile_base,
-                                                     uint32_t n_tiles, hipStream_t s) {
+                                                     uint32_t n_tiles, bool key_pairs, hipStream_t s) {
     if (exact) {
 #define HMK_F(PV, XV, L) \
-    if (PV == HMK_ROWS_PART && X == XV && d == 0 && cap == L) return RowsLaunch<PV == HMK_ROWS_PART, XV, 0, L, true>::go(P, tile_base, n_tiles, s);
+    if (PV == HMK_ROWS_PART && X == XV && d == 0 && cap == L) return RowsLaunch<PV == HMK_ROWS_PART, XV, 0, L, true>::go(P, tile_base, n_tiles, key_pairs, s);
         HMK_ROWS_EXACT_LIST(HMK_F)
 #undef HMK_F
         return hipErrorInvalidValue;
     }
 #define HMK_C(PV, XV, DV, CAPV) \
-    if (PV == HMK_ROWS_PART && X == XV && d == DV && cap == CAPV) return RowsLaunch<PV == HMK_ROWS_PART, XV, DV, CAPV, false>::go(P, tile_base, n_tiles, s);
+    if (PV == HMK_ROWS_PART && X == XV && d == DV && cap == CAPV) return RowsLaunch<PV == HMK_ROWS_PART, XV, DV, CAPV, false>::go(P, tile_base, n_tiles, key_pairs, s);
     HMK_ROWS_CAP_LIST(HMK_C)
 #undef HMK_C
     return hipErrorInvalidValue;

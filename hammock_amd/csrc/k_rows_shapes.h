@@ -9,9 +9,19 @@ namespace hmk {
 // -----------------------------------------------------------------------------
 // shapes, parts and launchers
 // -----------------------------------------------------------------------------
+// key_pairs: the tiles of a key-sorted plan hold ROWS_KEY_PAIR_GROUPS row groups (hmk_plan.cpp, Plan::key_pairs)
 template <int X, int D, int CAP, bool EXACT_LB>
-static hipError_t launch_rows_t(const NeighborParams &P, uint32_t tile_base, uint32_t n_tiles, hipStream_t s) {
+static hipError_t launch_rows_t(const NeighborParams &P, uint32_t tile_base, uint32_t n_tiles, bool key_pairs, hipStream_t s) {
     constexpr int G = rows_groups(X, D, CAP, EXACT_LB);
+    if constexpr (rows_keyed(X, D, CAP, EXACT_LB, ROWS_KEY_PAIR_GROUPS) && G != ROWS_KEY_PAIR_GROUPS) {
+        if (key_pairs) {   // (the planner pairs plain key-sorted passes only: no degree counters)
+            if (!P.keyrun || P.deg) return hipErrorInvalidValue;
+            hipLaunchKernelGGL((k_neighbors_rows<X, D, CAP, EXACT_LB, ROWS_KEY_PAIR_GROUPS, EDGES_PLAIN>), dim3(n_tiles), dim3(256), 0, s, P, tile_base);
+            return hipGetLastError();
+        }
+    } else if (key_pairs) {
+        return hipErrorInvalidValue;
+    }
     // the flush's mode is a template parameter: with the run-time form the counting branch's registers spill in every mode
     if constexpr (!EXACT_LB && (X == 2 || X == 3)) {   // mixed lengths at the max shifts of sets with mean length 6 .. 13.9: a one-length form per tile (k_neighbors_rows_lens)
         static_assert(G == 2, "the planner gives the capacity groups 16 rows per tile");
@@ -55,7 +65,7 @@ static hipError_t launch_rows_t(const NeighborParams &P, uint32_t tile_base, uin
 
 // one launcher per part (k_rows_part.hip, -DHMK_ROWS_PART=p); hipErrorInvalidValue: no such shape in that part
 #define HMK_ROWS_PART_DECL(p) \
-    hipError_t launch_rows_part_##p(int X, int d, int cap, bool exact, const NeighborParams &P, uint32_t tile_base, uint32_t n_tiles, hipStream_t s);
+    hipError_t launch_rows_part_##p(int X, int d, int cap, bool exact, const NeighborParams &P, uint32_t tile_base, uint32_t n_tiles, bool key_pairs, hipStream_t s);
 HMK_ROWS_PART_DECL(0) HMK_ROWS_PART_DECL(1) HMK_ROWS_PART_DECL(2) HMK_ROWS_PART_DECL(3)
 HMK_ROWS_PART_DECL(4) HMK_ROWS_PART_DECL(5) HMK_ROWS_PART_DECL(6) HMK_ROWS_PART_DECL(7)
 HMK_ROWS_PART_DECL(8) HMK_ROWS_PART_DECL(9) HMK_ROWS_PART_DECL(10) HMK_ROWS_PART_DECL(11) HMK_ROWS_PART_DECL(12)
