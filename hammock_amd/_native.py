@@ -28,7 +28,7 @@ SYMBOLS = [
     "hmk_abi_version", "hmk_last_kernel_ms", "hmk_create", "hmk_create_multi", "hmk_device_count", "hmk_destroy", "hmk_last_error", "hmk_set_sequences",
     "hmk_score_pairs_shifted", "hmk_score_with_shift", "hmk_score_pairs_local", "hmk_score_block_shifted", "hmk_score_block_local",
     "hmk_neighbors_shifted", "hmk_neighbors_local", "hmk_neighbors_shifted_dev", "hmk_compact_edges_dev", "hmk_pack_rows_dev", "hmk_unpack_rows_dev",
-    "hmk_neighbors_last_plan", "hmk_search_shifted", "hmk_search_local", "hmk_search_best_shifted",
+    "hmk_neighbors_last_plan", "hmk_neighbors_last_plan_shared", "hmk_search_shifted", "hmk_search_local", "hmk_search_best_shifted",
     "hmk_assign_shifted", "hmk_assign_local", "hmk_match_clusters_shifted", "hmk_match_clusters_local", "hmk_greedy_continue",
     "hmk_greedy_cluster", "hmk_greedy_from_edges", "hmk_greedy_from_edges_dev", "hmk_greedy_last_phases",
     "hmk_clinkage_cluster", "hmk_clinkage_from_edges", "hmk_set_java_hashset", "hmk_reserve",
@@ -157,6 +157,7 @@ def _load():
     L.hmk_pack_rows_dev.argtypes = [vp, vp, u64, vp, i32, vp, vp, u64, vp]
     L.hmk_unpack_rows_dev.argtypes = [vp, vp, vp, i32, vp, u64, vp]
     L.hmk_neighbors_last_plan.argtypes = [vp, C.POINTER(NeighborStats)]
+    L.hmk_neighbors_last_plan_shared.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.hmk_search_shifted.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, p_u64, u64, p_u64, C.POINTER(NeighborStats)]
     L.hmk_search_local.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, p_u64, u64, p_u64, C.POINTER(NeighborStats)]
     L.hmk_search_best_shifted.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, u32, p_u32, p_i32, p_u32, C.POINTER(NeighborStats)]

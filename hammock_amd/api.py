@@ -458,6 +458,14 @@ class Context:
             self._raise(st)
         return stats
 
+    def last_plan_shared(self):
+        """-> (16-row tiles of the last plan, those whose second group takes the first group's merged key cells)"""
+        paired, shared = C.c_uint32(0), C.c_uint32(0)
+        st = N.lib.hmk_neighbors_last_plan_shared(self._h, C.byref(paired), C.byref(shared))
+        if st:
+            self._raise(st)
+        return int(paired.value), int(shared.value)
+
     # -- greedy ---------------------------------------------------------------------------
     def greedy_cluster(self, max_shift, shift_penalty, threshold, max_clusters):
         """-> (cluster_id int32[n], result_order int32[n_result], GreedyStats)"""

@@ -281,6 +281,16 @@ int hmk_neighbors_last_plan(hmk_ctx *ctx, hmk_neighbor_stats *stats) {
     return HMK_OK;
 }
 
+int hmk_neighbors_last_plan_shared(hmk_ctx *ctx, uint32_t *paired_tiles, uint32_t *run_shared_tiles) {
+    if (!ctx || !paired_tiles || !run_shared_tiles) return fail(ctx, HMK_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    refresh_switches(ctx);
+    if (!ctx->plan.valid) return fail(ctx, HMK_ERR_BAD_ARG, "no neighbour pass has been planned yet");
+    *paired_tiles = ctx->plan.paired_tiles;
+    *run_shared_tiles = ctx->plan.run_shared_tiles;
+    return HMK_OK;
+}
+
 int hmk_neighbors_shifted(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, uint32_t part,
                           uint32_t n_parts, uint64_t *edges, uint64_t capacity, uint64_t *n_edges,
                           hmk_neighbor_stats *stats) {

@@ -108,6 +108,7 @@ struct Switches {
     int key_sort = 2;             // HMK_NO_KEY_SORT: 0, caller order and no key body; HMK_KEY_SORT_KEYS=1: the first key only (A/B runs)
     bool no_row_shared = false;   // HMK_NO_ROW_SHARED: no row group of a key-sorted plan takes the row-shared bodies (A/B runs)
     int key_row_pairs = -1;       // HMK_KEY_ROW_PAIRS=0|1: a key-sorted plan never / always takes 16-row tiles (-1: the planner's size rule)
+    bool no_row_run_share = false;   // HMK_NO_ROW_RUN_SHARE: no 16-row tile's second group takes its merged cells from the first (A/B runs)
     bool adj_8byte = false;       // HMK_ADJ_8BYTE: 8-byte adjacency entries even where 4 bytes hold every score
     bool local_literal = false;   // HMK_LOCAL_LITERAL: LocalAlignmentScorer through the literal DP
     bool local_signed = false;    // HMK_LOCAL_SIGNED: the signed tagged-max form (what gap_open = 0 runs) for every penalty
@@ -151,7 +152,9 @@ struct Plan : PlanArrays {
     int key_sort = 2;              // ... and this one: keys the plan sorts by (0: none; else rows_keyed shapes only)
     bool row_shared = true;        // ... and HMK_NO_ROW_SHARED (false: no tile is flagged row-shared)
     int key_row_pairs = -1;        // ... and HMK_KEY_ROW_PAIRS
+    bool row_run_share = true;     // ... and HMK_NO_ROW_RUN_SHARE (false: no tile is flagged run-shared)
     bool key_pairs = false;        // the plan is key-sorted with 16-row tiles: two row groups per column set-up (k_neighbors_rows.h)
+    uint32_t paired_tiles = 0, run_shared_tiles = 0;   // tiles of a paired plan; those flagged ROWS_RUN_SHARED (hmk_neighbors_last_plan_shared)
     uint32_t *d_keyrun = nullptr;  // NeighborParams::keyrun / keytab (null: the plan is not key-sorted)
     uint32_t *d_keytab = nullptr;
     uint32_t cols_per_tile = 16384;

@@ -39,7 +39,8 @@ struct Tile {
     uint32_t cls;          // index into the TileClass array
     uint32_t diag;         // 1: rows and columns come from the same bucket: keep col > row only
     uint32_t pad0;
-    uint32_t row_shared;   // bit g: group g's 8 rows are all live and equal at both key positions (key-sorted plans, k_neighbors_rows.h)
+    uint32_t row_shared;   // bit g: group g's 8 rows are all live and equal at both key positions (key-sorted plans, k_neighbors_rows.h);
+                           // ROWS_RUN_SHARED: a paired plan's tile whose groups are all row-shared with the same two key residues
 };
 
 struct NeighborParams {
@@ -76,6 +77,7 @@ constexpr int KEYTAB_DWORDS = 16;
 // the shapes that run it: one length, hits cut out in the loop -- only the BASELINE shape for now, with one row group per tile or
 // (a paired plan, hmk_plan.cpp: ROWS_KEY_PAIR_GROUPS) two
 constexpr int ROWS_KEY_PAIR_GROUPS = 2;
+constexpr uint32_t ROWS_RUN_SHARED = 1u << 8;   // Tile::row_shared
 constexpr bool rows_keyed(int x, int d, int cap, bool exact, int g) { return exact && d == 0 && (g == 1 || g == ROWS_KEY_PAIR_GROUPS) && x == 3 && cap == 12; }
 // the two key positions of length l at max shift x: middle positions (paired with every row position by all 2x + 1 planes)
 constexpr int rows_key_pos(int x, int l, int q) { return l / 2 - 1 + q < x ? x : l / 2 - 1 + q; }

@@ -320,7 +320,7 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
     const int want_keys = key_sort_ok ? ctx->sw.key_sort : 0;
     if (pl.valid && pl.X == X && pl.p == p && pl.thr == thr && pl.part == part && pl.n_parts == n_parts &&
         (band_rows < 0 || pl.band_req == band_rows) && pl.no_rows_kernel == ctx->sw.no_rows_kernel && pl.key_sort == want_keys &&
-        pl.row_shared == !ctx->sw.no_row_shared && pl.key_row_pairs == ctx->sw.key_row_pairs)
+        pl.row_shared == !ctx->sw.no_row_shared && pl.key_row_pairs == ctx->sw.key_row_pairs && pl.row_run_share == !ctx->sw.no_row_run_share)
         return HMK_OK;
     free_plan(pl);
     if (band_rows < 0) band_rows = 0;
@@ -447,6 +447,7 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
     pl.key_sort = want_keys;
     pl.row_shared = !ctx->sw.no_row_shared;
     pl.key_row_pairs = ctx->sw.key_row_pairs;
+    pl.row_run_share = !ctx->sw.no_row_run_share;
     std::vector<uint32_t> keyrun;
     const int L1 = ctx->min_len;
     const bool key_sorted = pl.key_sort > 0 && pl.rows_exact && !(refine && !all_rows_fit) &&
@@ -573,9 +574,17 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
                 for (uint32_t r = 1; r < 8 && same; r++) same = keys_at(t.row0 + 8 * g + r) == keys_at(t.row0 + 8 * g);
                 if (same) t.row_shared |= 1u << g;
             }
+            // Run-shared tiles of a paired plan (k_neighbors_rows.h, accumulate_run): 16 live rows, both groups row-shared with the
+            // SAME two key residues -- the second group's merged cells are the first group's, which hands them over in registers.
+            if (pl.key_pairs && pl.row_run_share && t.nrows == 8u * ROWS_KEY_PAIR_GROUPS && (t.row_shared & 3u) == 3u &&
+                keys_at(t.row0 + 8) == keys_at(t.row0))
+                t.row_shared |= ROWS_RUN_SHARED;
         }
         plan_lap("row-shared groups");
     }
+    pl.paired_tiles = pl.key_pairs ? (uint32_t)tiles.size() : 0u;
+    pl.run_shared_tiles = 0;
+    for (const Tile &t : tiles) pl.run_shared_tiles += (t.row_shared & ROWS_RUN_SHARED) ? 1u : 0u;
 
     // ---- device copies ------------------------------------------------------------
     // (+ 16: the row-packed kernel's unaligned tail loads may touch the bytes after the last row)

@@ -262,6 +262,51 @@ struct RowsShape {
         }
         return true;
     }
+    // Run-shared tiles (Tile::row_shared & ROWS_RUN_SHARED: every group of the tile row-shared with the SAME two key residues): a merged
+    // entry depends on (the two key residues, the column's residue) only, so group g >= 1 would read what group 0 just read.  Group 0
+    // runs the LEAD form of the row-shared body: the same reads, and it leaves P[u] = the sum of plane u's merged halves (a broadcast
+    // dword, four equal bytes, that serves both accumulators).  The others run the FOLLOWER: P[u] is ONE operand of plane u in both
+    // chains, then the plane's ordinary reads -- no merged read.  P[u] is a partial sum of a byte lane whose final value classify()
+    // bounds by 255: nothing carries.
+    static constexpr bool run_carried(int u, int skip) { return merged_half(u, skip, true, 0) || merged_half(u, skip, true, 1); }
+    static constexpr int run_carried_planes(int skip) {
+        int n = 0;
+        for (int u = 0; u < ND; u++) n += run_carried(u, skip) ? 1 : 0;
+        return n;
+    }
+    // the lead sums a plane over P[u] instead of the raw halves where that is the shorter chain: both halves and an odd number of
+    // ordinary reads (P's add + (reads + 1) / 2 add3 per dword against (reads + 3) / 2 per dword and P's add on top)
+    static constexpr bool lead_sums_p(int u, int skip) { return merged_half(u, skip, true, 0) && merged_half(u, skip, true, 1) && (rs_plane_reads(u, skip) & 1); }
+    static constexpr int follower_reads(int skip) {
+        int n = 0;
+        for (int u = 0; u < ND; u++) n += rs_plane_reads(u, skip);
+        return n;
+    }
+    // VALU instructions of a body's sums, both dwords (an operand list of n entries takes n / 2 add3 and, n odd, one add, per dword):
+    // role 0 the row-shared body, 1 the lead with the raw halves in every chain, 2 the lead as built, 3 the follower
+    static constexpr int run_body_adds(int skip, int role) {
+        int n = 0;
+        for (int u = 0; u < ND; u++) {
+            const int halves = (merged_half(u, skip, true, 0) ? 1 : 0) + (merged_half(u, skip, true, 1) ? 1 : 0), r = rs_plane_reads(u, skip);
+            const bool via_p = role == 3 || (role == 2 && lead_sums_p(u, skip));
+            const int ops = r + (via_p ? (halves ? 1 : 0) : halves);
+            n += 2 * ((ops + 1) / 2) + ((role == 1 || role == 2) && halves == 2 ? 1 : 0);
+        }
+        return n;
+    }
+    // The follower's proof: every cell (u, j) of the overlap once -- an ordinary read, a key start value, or a half inside P[u]; the
+    // lead puts into P[u] exactly the halves merged_half() names (accumulate_run), each standing for the row position the cell has
+    static constexpr bool follower_covers(int skip) {
+        if (!body_covers(skip, true)) return false;
+        for (int u = 0; u < ND; u++)
+            for (int j = plane_j0(u); j < plane_j1(u); j++) {
+                int n = (ordinary(u, skip, true, j) ? 1 : 0) + (skipped(skip, j) ? 1 : 0);
+                for (int h = 0; h < 2; h++)
+                    if (run_carried(u, skip) && merged_half(u, skip, true, h) && merged_j(u, h) == j) n += (j + u - X == key_pos(h)) ? 1 : 2;
+                if (n != 1) return false;
+            }
+        return true;
+    }
 
     // All shift sums of (8 rows of group GI) x (this lane's column): W0 / W1[u] = the 8 byte lanes of plane u, started at
     // c0 / c1[u] (rows 0-3 / 4-7).  SKIP (EXACT_LB only): key positions left out, see key_pos.  RS: the row-shared form.
@@ -383,6 +428,49 @@ struct RowsShape {
                     W0[u] += e.x; W1[u] += e.y;
                 }
             }
+        }
+    }
+
+    // A group of a run-shared tile (see run_carried): FOLLOW false, the lead (group 0) -- accumulate<GI, SKIP, true> that also leaves
+    // P; FOLLOW true, a follower (any group g >= 1) -- P in, no merged read.  P[u] exists for the planes run_carried() names.
+    template <int GI, int SKIP, bool FOLLOW>
+    static __device__ __forceinline__ void accumulate_run(const uint32_t (&off)[CAP], const uint32_t (&c0)[ND], const uint32_t (&c1)[ND],
+                                                          uint32_t (&W0)[ND], uint32_t (&W1)[ND], uint32_t (&P)[ND]) {
+        static_assert(EXACT_LB && follower_covers(SKIP), "every cell of the overlap exactly once");
+        u32x2 ml = {0u, 0u}, mh = {0u, 0u};
+#pragma unroll
+        for (int u = 0; u < ND; u++) {
+            const bool hi = !FOLLOW && merged_half(u, SKIP, true, 1), lo = !FOLLOW && merged_half(u, SKIP, true, 0);
+            if (hi) {
+                if (merged_reuse(u, SKIP, true)) mh = ml;
+                else mh = rows_table_read<u32x2>(off[merged_j(u, 1)] + (uint32_t)pos_addr(GI, key_pos(0)));
+            }
+            if (lo) ml = rows_table_read<u32x2>(off[merged_j(u, 0)] + (uint32_t)pos_addr(GI, key_pos(0)));
+            if (hi || lo) P[u] = hi && lo ? mh.y + ml.x : hi ? mh.y : ml.x;
+            // the plane's first operands: P[u] (the follower; the lead where lead_sums_p), or the lead's raw halves
+            const bool via_p = run_carried(u, SKIP) && (FOLLOW || lead_sums_p(u, SKIP));
+            const int nh = via_p ? 1 : (hi ? 1 : 0) + (lo ? 1 : 0);
+            const int n = rs_plane_reads(u, SKIP) + nh;
+            uint32_t a0 = c0[u], a1 = c1[u];
+            auto rd = [&](int k) {
+                if (via_p) { if (k-- == 0) return u32x2{P[u], P[u]}; }
+                else {
+                    if (hi && k-- == 0) return u32x2{mh.y, mh.y};
+                    if (lo && k-- == 0) return u32x2{ml.x, ml.x};
+                }
+                const int j = rs_plane_pos(u, SKIP, k);
+                return rows_table_read<u32x2>(off[j] + (uint32_t)pos_addr(GI, j + u - X));
+            };
+            int k = 0;
+            if (n & 1) { const u32x2 e = rd(0); a0 += e.x; a1 += e.y; k = 1; }
+#pragma unroll
+            for (; k + 1 < n; k += 2) {
+                const u32x2 e0 = rd(k), e1 = rd(k + 1);
+                a0 = a0 + e0.x + e1.x; a1 = a1 + e0.y + e1.y;
+            }
+            // (as in the row-shared body: the plane's adds before the next plane's volatile reads)
+            asm volatile("" : "+v"(a0), "+v"(a1));
+            W0[u] = a0; W1[u] = a1;
         }
     }
 };
@@ -775,7 +863,12 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
     static_assert(!KEYED || (G <= 2 && 2 * ND <= KEYTAB_DWORDS), "key table entry; at most two row groups per tile");
     // ds_read_b64 per wave-step of the six bodies, windows that share both keys / key 0 / none
     static_assert(!KEYED || (S::body_reads(3, false) == 58 && S::body_reads(1, false) == 65 && S::body_reads(0, false) == 72), "ordinary bodies");
-    static_assert(!KEYED || (S::body_reads(3, true) == 54 && S::body_reads(1, true) == 60 && S::body_reads(0, true) == 66), "row-shared bodies");
+    static_assert(!KEYED || (S::body_reads(3, true) == 54 && S::body_reads(1, true) == 60 && S::body_reads(0, true) == 66), "row-shared bodies (and the lead of a run-shared tile)");
+    static_assert(!KEYED || (S::follower_reads(3) == 48 && S::follower_reads(1) == 53 && S::follower_reads(0) == 58), "followers of a run-shared tile");
+    static_assert(!KEYED || (S::run_carried_planes(3) == 6 && S::run_carried_planes(1) == 7 && S::run_carried_planes(0) == 7), "dwords a lead hands over");
+    // (VALU instructions of the sums: the lead's as built against the raw halves in every chain, 66 / 73 / 83; the row-shared body's 62 / 68 / 76)
+    static_assert(!KEYED || (S::run_body_adds(3, 2) == 62 && S::run_body_adds(1, 2) == 69 && S::run_body_adds(0, 2) == 75 && S::run_body_adds(3, 3) == 58 &&
+                             S::run_body_adds(1, 3) == 64 && S::run_body_adds(0, 3) == 68), "sums of the lead and the follower");
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t *kt_tile = nullptr, *kr_wave = nullptr;   // keytab of the tile's first row group; keyrun of the wave's first column
     if (keyed) {
@@ -814,6 +907,10 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
         uint32_t off[CAP], toff[S::NT];
         S::offsets_of(words, tw, tab_addr, tab_addr, off, toff);
         const bool look = !DEFER || (bt & 3u) == 3u || bt + 1 == n_batches;   // wave-uniform
+        // a run-shared tile's merged cells, plane by plane: written by group 0 (the lead), read by the groups after it in the SAME step
+        // -- live across group 0's threshold test, append loop and flush call; nothing on any other tile
+        uint32_t Pm[ND];
+        constexpr bool RUNS = KEYED && G >= 2;
 
         auto one_group = [&](auto gt) {
             constexpr int g = decltype(gt)::value;
@@ -832,7 +929,8 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
 #pragma unroll
                     for (int u = 0; u < ND; u++) { ks0[u] += kb0[u]; ks1[u] += kb1[u]; }
                     read_phase_begin(prio);
-                    if (row_shared) S::template accumulate<g, 3, true>(off, toff, lbs, ks0, ks1, W0, W1);
+                    if (RUNS && (rs_groups & ROWS_RUN_SHARED) != 0) S::template accumulate_run<g, 3, (g > 0)>(off, ks0, ks1, W0, W1, Pm);
+                    else if (row_shared) S::template accumulate<g, 3, true>(off, toff, lbs, ks0, ks1, W0, W1);
                     else S::template accumulate<g, 3>(off, toff, lbs, ks0, ks1, W0, W1);
                 } else if (kmode == 1) {
                     key_entry(kt_group + (ra.x & 31u) * KEYTAB_DWORDS, ks0, ks1);
@@ -840,11 +938,13 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
 #pragma unroll
                     for (int u = 0; u < ND; u++) asm volatile("" : "+s"(ks0[u]), "+s"(ks1[u]));
                     read_phase_begin(prio);
-                    if (row_shared) S::template accumulate<g, 1, true>(off, toff, lbs, ks0, ks1, W0, W1);
+                    if (RUNS && (rs_groups & ROWS_RUN_SHARED) != 0) S::template accumulate_run<g, 1, (g > 0)>(off, ks0, ks1, W0, W1, Pm);
+                    else if (row_shared) S::template accumulate<g, 1, true>(off, toff, lbs, ks0, ks1, W0, W1);
                     else S::template accumulate<g, 1>(off, toff, lbs, ks0, ks1, W0, W1);
                 } else {
                     read_phase_begin(prio);
-                    if (row_shared) S::template accumulate<g, 0, true>(off, toff, lbs, ci, ci, W0, W1);
+                    if (RUNS && (rs_groups & ROWS_RUN_SHARED) != 0) S::template accumulate_run<g, 0, (g > 0)>(off, ci, ci, W0, W1, Pm);
+                    else if (row_shared) S::template accumulate<g, 0, true>(off, toff, lbs, ci, ci, W0, W1);
                     else S::template accumulate<g>(off, toff, lbs, ci, ci, W0, W1);
                 }
             } else {

@@ -183,6 +183,9 @@ int hmk_unpack_rows_dev(hmk_ctx *ctx, const void *d_row_start, const void *d_adj
                         uint64_t out_capacity, void *stream);
 /* pairs / tiles of the plan the last hmk_neighbors_shifted[_dev] call used */
 int hmk_neighbors_last_plan(hmk_ctx *ctx, hmk_neighbor_stats *stats);
+/* ... of that plan: its 16-row tiles (0: the plan is not paired) and those of them whose second row group takes the merged cells of
+ * the two key positions from the first (both groups row-shared with the same two key residues; HMK_NO_ROW_RUN_SHARE=1: none) */
+int hmk_neighbors_last_plan_shared(hmk_ctx *ctx, uint32_t *paired_tiles, uint32_t *run_shared_tiles);
 
 /* ---- query-vs-reference search ---------------------------------------------- */
 
