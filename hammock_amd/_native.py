@@ -22,6 +22,7 @@ HMK_ERR_CAPACITY = 6
 HMK_ERR_NO_SEQUENCES = 7
 HMK_EDGE_SHARDS = 64
 HMK_MAX_LEN = 32
+HMK_SURVEY_MAX_BINS = 1024
 
 # every symbol include/hammock_hip.h declares
 SYMBOLS = [
@@ -35,7 +36,7 @@ SYMBOLS = [
     "hmk_cluster_pairs_shifted", "hmk_clinkage_merge", "hmk_clinkage_merge_from_edges",
     "hmk_cluster_linkage_shifted", "hmk_clinkage_split", "hmk_clinkage_split_from_edges",
     "hmk_components_shifted", "hmk_components_from_edges", "hmk_components_from_edges_dev",
-    "hmk_cluster_align_shifted",
+    "hmk_cluster_align_shifted", "hmk_score_survey_shifted",
 ]
 
 
@@ -105,6 +106,13 @@ class AlignStats(C.Structure):
     """hmk_align_stats"""
     _fields_ = [("pairs_scored", C.c_uint64), ("n_multi", C.c_uint32), ("max_width", C.c_uint32), ("launches", C.c_uint32),
                 ("reserved", C.c_uint32), ("kernel_ms", C.c_double)]
+
+
+class SurveyStats(C.Structure):
+    """hmk_survey_stats"""
+    _fields_ = [("pairs_scored", C.c_uint64), ("n_below", C.c_uint64), ("n_above", C.c_uint64), ("n_at_or_above", C.c_uint64),
+                ("score_min", C.c_int32), ("score_max", C.c_int32), ("launches", C.c_uint32), ("reserved", C.c_uint32),
+                ("kernel_ms", C.c_double)]
 
 
 class GreedyPhases(C.Structure):
@@ -192,6 +200,8 @@ def _load():
     p_i64 = C.POINTER(C.c_int64)
     L.hmk_cluster_align_shifted.argtypes = [vp, u32, u32, p_u32, u32, i32, i32, p_u32, p_i64, p_u32, p_i64, p_i32, p_i32, p_u32,
                                             C.POINTER(AlignStats)]
+    L.hmk_score_survey_shifted.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, i32, u32, p_u64, p_i32, p_u32, p_u32,
+                                           C.POINTER(SurveyStats)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("hmk_destroy", "hmk_last_error", "hmk_last_kernel_ms"):

@@ -611,6 +611,27 @@ class Context:
         self.last_align_stats = stats
         return (center[:ncl], center_sum[:ncl], width[:ncl], member_sum[:nm] if sums else None, center_score[:nm], shift[:nm], column[:nm])
 
+    def score_survey_shifted(self, q0, q1, r0, r1, max_shift, shift_penalty, threshold, score_lo=None, n_bins=0, rows=True):
+        """hmk_score_survey_shifted: the pair scores of the triangle inside one range ([q0, q1) == [r0, r1), seq1 = the larger index) or
+        of the rectangle of two disjoint ranges (seq1 = the query), reduced on the device -> (hist uint64[n_bins] -- the pairs scoring
+        score_lo + k -- or None with n_bins=0, (best_score int32[q1 - q0], best_index uint32[q1 - q0] -- the smallest partner attaining
+        it --, degree uint32[q1 - q0] -- the partners at or above the threshold) or None with rows=False, stats); a row without
+        partners has INT32_MIN, UINT32_MAX, 0.  score_lo=None stands for 0.  Statistics also in last_survey_stats."""
+        nb, nq = int(n_bins), max(int(q1) - int(q0), 0)
+        hist = np.zeros(nb, dtype=np.uint64) if nb else None
+        best_score = np.zeros(max(nq, 1), dtype=np.int32) if rows else None
+        best_index = np.zeros(max(nq, 1), dtype=np.uint32) if rows else None
+        degree = np.zeros(max(nq, 1), dtype=np.uint32) if rows else None
+        stats = N.SurveyStats()
+        st = N.lib.hmk_score_survey_shifted(self._h, int(q0), int(q1), int(r0), int(r1), int(max_shift), int(shift_penalty), int(threshold),
+                                            int(score_lo or 0), nb, _ptr(hist, C.c_uint64) if nb else None,
+                                            _ptr(best_score, C.c_int32) if rows else None, _ptr(best_index, C.c_uint32) if rows else None,
+                                            _ptr(degree, C.c_uint32) if rows else None, C.byref(stats))
+        if st:
+            self._raise(st)
+        self.last_survey_stats = stats
+        return hist, ((best_score[:nq], best_index[:nq], degree[:nq]) if rows else None), stats
+
     def _merge_out(self, nm, ncl):
         merged = np.full(max(ncl, 1), -1, dtype=np.int32)
         order = np.full(max(ncl, 1), -1, dtype=np.int32)

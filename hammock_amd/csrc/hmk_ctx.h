@@ -3,7 +3,7 @@
 // buffers and their owners, streams), hmk_sizing.h (the sizing rules, pure functions), hmk_plan.cpp (the neighbour passes' planner),
 // hmk_pass.cpp (launching the passes; the pair and block probes), hmk_cluster.cpp (the single-device clustering calls, CSR pipeline,
 // row hand-over, second-loop driver), hmk_multi.cpp (the same calls on several devices), and one file per further call
-// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp).  Not part of the public ABI.
+// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp).  Not part of the public ABI.
 #ifndef HMK_CTX_H
 #define HMK_CTX_H
 #include <hip/hip_runtime_api.h>
@@ -95,6 +95,7 @@ enum {
     SB_CC_PARENT, SB_CC_SIZE,                       // connected components (hmk_components.cpp): the union-find's parent[n], members per root
     SB_CC_STATE, SB_CC_RUNS,                        // ... the levels' results, histogram and run offsets (CcState); the edges' (x, m) by level
     SB_ALIGN_SLOT, SB_ALIGN_MEMB,                   // the alignment of given clusters (hmk_align.cpp; tables in SB_LINK_TAB): per slot key, extent; per member sum, score, shift
+    SB_SURVEY_ACC, SB_SURVEY_ROWS,                  // the score survey (hmk_survey.cpp): bins, counters, score range; per row key, best score, best index, degree
     SB_N
 };
 

@@ -149,6 +149,8 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "                      [--device <int>]\n"
               << "          hammock-hip align -i <clusters.tsv> -d <directory> [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [--device <int>]\n"
               << "          hammock-hip components -i <sequences> -d <directory> [-g <int>] [--scan_to <int>] [-f fasta|tab] [-m <file>] [-x <int>]\n"
+              << "                      [-p <int>] [-l <labels>] [--device <int>]\n"
+              << "          hammock-hip survey -i <sequences> -d <directory> [-g <int>] [--database <sequences>] [-f fasta|tab] [-m <file>] [-x <int>]\n"
               << "                      [-p <int>] [-l <labels>] [--device <int>]\n\n"
               << "-i, --input <file>\n\tA path to an input file\n\n"
               << "-d, --output_directory <directory>\n\tA directory to store all output files in\n\n"
@@ -165,7 +167,7 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "-L, --cache_size_limit <int>\n\t(clinkage) accepted and logged; has no effect, as in the reference\n\n"
               << "--device <int>\n\tHIP device ordinal (default 0)\n\n"
               << "--devices <int,int,...>\n\tShard the pair space over several GPUs of the node (the first one runs the merge)\n\n"
-              << "--database <file>\n\t(search) the reference sequences every query (-i) is scored against\n\n"
+              << "--database <file>\n\t(search) the reference sequences every query (-i) is scored against;\n\t(survey) score the input against these sequences instead of against itself\n\n"
               << "--best <int>\n\t(search) keep only the best 1..32 hits of each query; (assign, match) report the best 1..32 feasible clusters (default 1)\n\n"
               << "--clusters <file>\n\t(assign, continue, match) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv);\n\t(merge) a second cluster file: its clusters keep their ids, the -i file's are renumbered behind them\n\n"
               << "--scan_to <int>\n\t(components) the last threshold of the scan: component_levels.tsv gets one line per threshold from -g to this one\n\t(at most 255 above -g; default: -g alone)\n\n"
@@ -1521,6 +1523,123 @@ int runComponents(const std::vector<std::string> &args) {
     }
 }
 
+// `hammock-hip survey -i X.fa -d dir [-g T] [--database known.fa] [-x -p -m -f -l]`: what the pair scores of a set look like, before a
+// threshold is chosen for any other mode (hmk_score_survey_shifted): the histogram of the scores, every sequence's best partner and its
+// number of partners at -g.  Without --database the triangle over the input in load order (every unordered pair, as components scores
+// them); with it the input's sequences are the queries and the database's the references (search's rectangle).  -x / -g / -p default as
+// in components (search's lists with --database).  The histogram window is settled here: first the HMK_SURVEY_MAX_BINS scores ending at
+// the longest length x the matrix's largest cell; if a pair fell outside, once more at [score_min, score_max] of the first call.
+int runSurvey(const std::vector<std::string> &args) {
+    Options o;
+    parseCommonArgs(args, o);
+    parseModeArgs(args, o, -1);
+    requireOneDevice(o, "survey", "a survey");
+    requireInput(o);
+    requireFastaOrTab(o, "survey");
+    makeOutputDirectory(o, o.parentDir);
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        ContextFuture contextReady = beginRun(o, logger, false);
+        logRunStart(logger, "survey", args);
+        std::vector<std::string> labels;
+        if (o.haveLabels) labels = FileIOManager::splitChar(o.labelString, ',', true);
+        logger.logAndStderr("Loading input sequences...");
+        std::vector<UniqueSequencePtr> sequences = loadSequences(o, o.inputFileName);
+        logger.logAndStderr(std::to_string(sequences.size()) + " unique sequences loaded.");
+        if (o.haveLabels) sequences = filterSequencesForLabels(sequences, labels);
+        if (sequences.empty()) throw FileFormatException("Error. No sequences (with specified labels) to survey.");
+        std::vector<UniqueSequencePtr> all(sequences);
+        if (o.haveDatabase) {
+            logger.logAndStderr("Loading reference sequences...");
+            const std::vector<UniqueSequencePtr> references = loadSequences(o, o.database);
+            logger.logAndStderr(std::to_string(references.size()) + " unique reference sequences loaded.");
+            if (references.empty()) throw FileFormatException("Error. No reference sequences to survey against.");
+            all.insert(all.end(), references.begin(), references.end());
+        }
+        const SequenceListSummary summary = summariseSequences(all);
+        settleShiftAndThreshold(o, logger, summary, summary, summariseSequences(sequences), "Survey");
+        const int thr = o.sequenceClusteringThreshold;
+        logger.logAndStderr("Parameters: max shift " + std::to_string(o.maxShift) + ", gap penalty " + std::to_string(o.shiftPenalty) + ", threshold " +
+                            std::to_string(thr));
+        int maxCell = INT32_MIN;
+        for (auto &row : FileIOManager::loadScoringMatrix(o.matrixFile)) for (int v : row) maxCell = std::max(maxCell, v);
+
+        const uint32_t nq = (uint32_t)sequences.size(), n = (uint32_t)all.size();
+        const uint32_t r0 = o.haveDatabase ? nq : 0, r1 = o.haveDatabase ? n : nq;
+        std::vector<uint64_t> hist(HMK_SURVEY_MAX_BINS);
+        std::vector<int32_t> bestScore(nq);
+        std::vector<uint32_t> bestIndex(nq), degree(nq);
+        hmk_survey_stats stats{};
+        int lo = summary.maxLength * maxCell - (HMK_SURVEY_MAX_BINS - 1);
+        double kernelMs = 0;
+        logger.logAndStderr("Survey...");
+        const auto time0 = std::chrono::steady_clock::now();
+        {
+            const std::shared_ptr<NativeContext> nc = contextReady.get();
+            nc->setSequences(all, false);
+            int st = hmk_score_survey_shifted(nc->get(), 0, nq, r0, r1, o.maxShift, o.shiftPenalty, thr, lo, HMK_SURVEY_MAX_BINS, hist.data(),
+                                              bestScore.data(), bestIndex.data(), degree.data(), &stats);
+            if (st) nc->raise(st, nullptr);
+            kernelMs = stats.kernel_ms;
+            if (stats.n_below || stats.n_above) {   // a pair outside the window: the scores' own range, if it fits one
+                const long long span = (long long)stats.score_max - stats.score_min + 1;
+                if (span > HMK_SURVEY_MAX_BINS)
+                    throw CLIException("Error. The pair scores span " + std::to_string(span) + " values (" + std::to_string(stats.score_min) + " to " +
+                                       std::to_string(stats.score_max) + "): more than the " + std::to_string(HMK_SURVEY_MAX_BINS) +
+                                       " a survey's histogram holds (HMK_SURVEY_MAX_BINS).");
+                lo = stats.score_min;
+                logger.logAndStderr("Scores outside the first window. Scoring again for the scores " + std::to_string(stats.score_min) + " to " +
+                                    std::to_string(stats.score_max));
+                hmk_survey_stats again{};
+                st = hmk_score_survey_shifted(nc->get(), 0, nq, r0, r1, o.maxShift, o.shiftPenalty, thr, lo, (uint32_t)span, hist.data(), nullptr,
+                                              nullptr, nullptr, &again);
+                if (st) nc->raise(st, nullptr);
+                if (again.n_below || again.n_above || again.score_min != stats.score_min || again.score_max != stats.score_max)
+                    throw HammockException("the second survey call does not repeat the first one's score range");
+                kernelMs += again.kernel_ms;
+            }
+        }
+        logger.logAndStderr("Ready. Survey time: " + std::to_string(millisSince(time0)));
+        logger.logAndStderr("Pairs scored: " + std::to_string(stats.pairs_scored) + ", pairs at or above the threshold: " +
+                            std::to_string(stats.n_at_or_above) + ", GPU kernels: " + std::to_string(kernelMs) + " ms");
+        logger.logAndStderr("Saving results to output files...");
+        const std::string histCsv = o.workingDirectory + "/score_histogram.tsv", nnCsv = o.workingDirectory + "/nearest_neighbors.tsv";
+        {
+            std::ofstream out(histCsv);
+            if (!out) throw HammockException("cannot write " + histCsv);
+            out << "score\tpairs\tpairs_at_or_above\tsequences_best\tsequences_best_at_or_above\n";
+            if (stats.pairs_scored) {
+                const size_t span = (size_t)((long long)stats.score_max - stats.score_min + 1);
+                std::vector<uint64_t> pairs(span), best(span), pairsUp(span), bestUp(span);
+                for (size_t k = 0; k < span; k++) pairs[k] = hist[(size_t)((long long)stats.score_min + (long long)k - lo)];
+                for (uint32_t q = 0; q < nq; q++)
+                    if (bestIndex[q] != 0xFFFFFFFFu) best[(size_t)((long long)bestScore[q] - stats.score_min)]++;
+                uint64_t a = 0, b = 0;
+                for (size_t k = span; k-- > 0;) { a += pairs[k]; b += best[k]; pairsUp[k] = a; bestUp[k] = b; }
+                for (size_t k = 0; k < span; k++)
+                    out << (long long)stats.score_min + (long long)k << '\t' << pairs[k] << '\t' << pairsUp[k] << '\t' << best[k] << '\t' << bestUp[k] << '\n';
+            }
+        }
+        {
+            std::ofstream out(nnCsv);
+            if (!out) throw HammockException("cannot write " + nnCsv);
+            out << "sequence\tbest_partner\tbest_score\tneighbors_at_threshold\n";
+            for (uint32_t q = 0; q < nq; q++) {
+                out << sequences[q]->getSequenceString() << '\t';
+                if (bestIndex[q] == 0xFFFFFFFFu) out << "NA\tNA";
+                else out << all[bestIndex[q]]->getSequenceString() << '\t' << bestScore[q];
+                out << '\t' << degree[q] << '\n';
+            }
+        }
+        logger.logAndStderr("Score histogram in: " + histCsv);
+        logger.logAndStderr("Nearest neighbours in: " + nnCsv);
+        logger.logWithTime("Program successfully ended.");
+        return 0;
+    } catch (...) {
+        return reportRunError(logger, false);
+    }
+}
+
 // `hammock-hip io-selftest ...`: exposes the loaders / orderings to the CPU test-suite (no GPU involved)
 int ioSelftest(const std::vector<std::string> &args) {
     if (args.size() >= 3 && args[1] == "matrix") {
@@ -1645,6 +1764,7 @@ int main(int argc, char **argv) {
         if (args[0] == "split") return runSplit(args);
         if (args[0] == "components") return runComponents(args);
         if (args[0] == "align") return runAlign(args);
+        if (args[0] == "survey") return runSurvey(args);
         if (args[0] == "io-selftest") return ioSelftest(args);
         if (args[0] == "dump-matrix") {   // the default matrix in the text format FileIOManager.loadScoringMatrix reads
             std::cout << "# BLOSUM62 substitution matrix (public NCBI table), 24 x 24, order " << AMINO_ACIDS << "\n"

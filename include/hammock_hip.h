@@ -706,6 +706,50 @@ int hmk_cluster_align_shifted(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint
                               int32_t *center_score, int32_t *shift, uint32_t *column,               /* r1 - r0 each, required */
                               hmk_align_stats *stats);
 
+/* ---- the score survey of a pair space -------------------------------------------------- */
+
+#define HMK_SURVEY_MAX_BINS 1024
+typedef struct {
+    uint64_t pairs_scored;    /* triangle: s(s-1)/2 for s = q1 - q0; rectangle: (q1 - q0)(r1 - r0) */
+    uint64_t n_below;         /* pairs with score <  score_lo          (not in hist) */
+    uint64_t n_above;         /* pairs with score >= score_lo + n_bins (not in hist) */
+    uint64_t n_at_or_above;   /* pairs with score >= threshold */
+    int32_t  score_min, score_max;   /* over the scored pairs; INT32_MAX / INT32_MIN when there are none */
+    uint32_t launches, reserved;
+    double   kernel_ms;       /* HIP events */
+} hmk_survey_stats;
+
+/* What the pair scores of a set look like, before a threshold is chosen for any other call: the histogram of the scores, every
+ * sequence's best partner, every sequence's number of partners at a threshold.  The output is O(n_bins + rows) whatever the density;
+ * every pair is scored once and reduced on the device (k_survey.hip), nothing proportional to the pairs is stored or copied.
+ * The ranges are index ranges of the hmk_set_sequences set.
+ *   triangle  [q0, q1) == [r0, r1): every unordered pair of distinct members, score = ShiftedScorer(matrix, shift_penalty,
+ *             max_shift).sequenceScore(seq1 = the larger index, seq2 = the smaller) -- the orientation of hmk_cluster_linkage_shifted
+ *             and of the neighbour edges.  An asymmetric matrix is HMK_ERR_BAD_ARG, as in that call.
+ *   rectangle disjoint ranges: every (q, r), score = sequenceScore(seq1 = q, seq2 = r) as in hmk_search_shifted; any matrix.
+ *   hist[k]              the pairs with score == score_lo + k, k < n_bins; sum(hist) + n_below + n_above == pairs_scored
+ *   best_score[q - q0]   the maximum over the row's partners: in the triangle all other members (on both sides of the row), in the
+ *                        rectangle the references
+ *   best_index[q - q0]   the smallest partner index attaining it (an index of the uploaded set)
+ *   degree[q - q0]       the partners with score >= threshold (a pair scoring exactly the threshold counts); the triangle has
+ *                        sum(degree) == 2 n_at_or_above, the rectangle sum(degree) == n_at_or_above
+ *                        A row without partners gets INT32_MIN, UINT32_MAX, 0.
+ *   checks               HMK_ERR_BAD_ARG before the device is looked at (a host-only context answers them): ranges outside [0, n) or
+ *                        overlapping in part, n_bins > HMK_SURVEY_MAX_BINS, hist == NULL with n_bins != 0 or the reverse, some but
+ *                        not all of the three row pointers, hist and the row outputs all absent on a non-empty pair space,
+ *                        stats == NULL, an asymmetric matrix with a triangle.  Then the checks of hmk_cluster_align_shifted over the
+ *                        two ranges (none concerns the threshold, which may be any int): HMK_ERR_SHIFT_TOO_BIG against the shortest
+ *                        length, scores that fit int16 at both ends, n <= 2^24.  An empty pair space (one range empty, a triangle of
+ *                        one member) is HMK_OK: hist zeroed, the rows' no-partner values.  Never HMK_ERR_CAPACITY.  Without a
+ *                        device HMK_ERR_DEVICE: there is no CPU fallback.
+ * Only integer adds, minima and maxima: the result does not depend on the schedule, and every call clears its accumulators first.  On
+ * a hmk_create_multi context the call runs on the root device. */
+int hmk_score_survey_shifted(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1,
+                             int max_shift, int shift_penalty, int threshold,
+                             int score_lo, uint32_t n_bins, uint64_t *hist,             /* n_bins; NULL iff n_bins == 0 */
+                             int32_t *best_score, uint32_t *best_index, uint32_t *degree, /* q1 - q0 each; NULL together */
+                             hmk_survey_stats *stats);
+
 /* Where the time of the last hmk_greedy_cluster / hmk_greedy_from_edges_dev call of this context went
  * (milliseconds; the span of Hammock.java:406-411 minus the sort).  score_ms and csr_ms are device times (HIP events on
  * the call's stream), the others host wall time.  The parts overlap (phase 1 runs while the rest of the pair space is
