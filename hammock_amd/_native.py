@@ -36,7 +36,7 @@ SYMBOLS = [
     "hmk_cluster_pairs_shifted", "hmk_clinkage_merge", "hmk_clinkage_merge_from_edges",
     "hmk_cluster_linkage_shifted", "hmk_clinkage_split", "hmk_clinkage_split_from_edges",
     "hmk_components_shifted", "hmk_components_from_edges", "hmk_components_from_edges_dev",
-    "hmk_cluster_align_shifted", "hmk_score_survey_shifted",
+    "hmk_cluster_align_shifted", "hmk_score_survey_shifted", "hmk_cluster_separation_shifted",
 ]
 
 
@@ -113,6 +113,12 @@ class SurveyStats(C.Structure):
     _fields_ = [("pairs_scored", C.c_uint64), ("n_below", C.c_uint64), ("n_above", C.c_uint64), ("n_at_or_above", C.c_uint64),
                 ("score_min", C.c_int32), ("score_max", C.c_int32), ("launches", C.c_uint32), ("reserved", C.c_uint32),
                 ("kernel_ms", C.c_double)]
+
+
+class SeparationStats(C.Structure):
+    """hmk_separation_stats"""
+    _fields_ = [("pairs_scored", C.c_uint64), ("n_misplaced", C.c_uint32), ("n_multi", C.c_uint32), ("n_segments", C.c_uint32),
+                ("launches", C.c_uint32), ("reserved", C.c_uint32), ("kernel_ms", C.c_double)]
 
 
 class GreedyPhases(C.Structure):
@@ -202,6 +208,8 @@ def _load():
                                             C.POINTER(AlignStats)]
     L.hmk_score_survey_shifted.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, i32, u32, p_u64, p_i32, p_u32, p_u32,
                                            C.POINTER(SurveyStats)]
+    L.hmk_cluster_separation_shifted.argtypes = [vp, u32, u32, p_u32, u32, i32, i32, p_i64, p_i64, p_u32, p_u8, p_u32, p_i64,
+                                                 C.POINTER(SeparationStats)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("hmk_destroy", "hmk_last_error", "hmk_last_kernel_ms"):

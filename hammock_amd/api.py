@@ -632,6 +632,33 @@ class Context:
         self.last_survey_stats = stats
         return hist, ((best_score[:nq], best_index[:nq], degree[:nq]) if rows else None), stats
 
+    def cluster_separation_shifted(self, r0, r1, member_cluster, n_clusters, max_shift, shift_penalty, flags=True, clusters=True):
+        """hmk_cluster_separation_shifted: how well given clusters (members [r0, r1), member r in slot member_cluster[r - r0]) are
+        separated -> (own_sum int64[r1 - r0] -- the member's scores against the rest of its slot --, near_sum int64[r1 - r0],
+        near_cluster uint32[r1 - r0] -- of the other slots the one with the largest mean score, the smallest slot among equal means,
+        and the member's sum against it; 0 and UINT32_MAX with one slot --, misplaced uint8[r1 - r0] -- own mean strictly below the
+        nearest mean -- or None with flags=False, cluster_misplaced uint32[n_clusters] and cluster_own_sum int64[n_clusters] or None
+        with clusters=False).  Statistics: last_separation_stats."""
+        mc, _ = self._merge_args(r0, r1, member_cluster, None)
+        ncl, nm = int(n_clusters), mc.size
+        own_sum = np.zeros(max(nm, 1), dtype=np.int64)
+        near_sum = np.zeros(max(nm, 1), dtype=np.int64)
+        near_cluster = np.zeros(max(nm, 1), dtype=np.uint32)
+        misplaced = np.zeros(max(nm, 1), dtype=np.uint8) if flags else None
+        cluster_misplaced = np.zeros(max(ncl, 1), dtype=np.uint32) if clusters else None
+        cluster_own_sum = np.zeros(max(ncl, 1), dtype=np.int64) if clusters else None
+        stats = N.SeparationStats()
+        st = N.lib.hmk_cluster_separation_shifted(self._h, int(r0), int(r1), _ptr(mc, C.c_uint32), ncl, int(max_shift), int(shift_penalty),
+                                                  _ptr(own_sum, C.c_int64), _ptr(near_sum, C.c_int64), _ptr(near_cluster, C.c_uint32),
+                                                  _ptr(misplaced, C.c_uint8) if flags else None,
+                                                  _ptr(cluster_misplaced, C.c_uint32) if clusters else None,
+                                                  _ptr(cluster_own_sum, C.c_int64) if clusters else None, C.byref(stats))
+        if st:
+            self._raise(st)
+        self.last_separation_stats = stats
+        return (own_sum[:nm], near_sum[:nm], near_cluster[:nm], misplaced[:nm] if flags else None,
+                cluster_misplaced[:ncl] if clusters else None, cluster_own_sum[:ncl] if clusters else None)
+
     def _merge_out(self, nm, ncl):
         merged = np.full(max(ncl, 1), -1, dtype=np.int32)
         order = np.full(max(ncl, 1), -1, dtype=np.int32)

@@ -55,6 +55,7 @@ void Switches::read() {
     if (const char *v = getenv("HMK_EDGE_GUESS")) edge_guess = std::strtoull(v, nullptr, 10);
     test_grid_cap = std::max(0, num("HMK_TEST_GRID_CAP", 0));
     set_test_grid_cap(test_grid_cap);
+    test_separation_segment = std::max(0, num("HMK_TEST_SEPARATION_SEGMENT", 0));
 }
 void refresh_switches(hmk_ctx *ctx) {
     ctx->sw.read();

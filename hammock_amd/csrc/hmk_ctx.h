@@ -3,7 +3,7 @@
 // buffers and their owners, streams), hmk_sizing.h (the sizing rules, pure functions), hmk_plan.cpp (the neighbour passes' planner),
 // hmk_pass.cpp (launching the passes; the pair and block probes), hmk_cluster.cpp (the single-device clustering calls, CSR pipeline,
 // row hand-over, second-loop driver), hmk_multi.cpp (the same calls on several devices), and one file per further call
-// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp).  Not part of the public ABI.
+// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp, hmk_separation.cpp).  Not part of the public ABI.
 #ifndef HMK_CTX_H
 #define HMK_CTX_H
 #include <hip/hip_runtime_api.h>
@@ -96,6 +96,7 @@ enum {
     SB_CC_STATE, SB_CC_RUNS,                        // ... the levels' results, histogram and run offsets (CcState); the edges' (x, m) by level
     SB_ALIGN_SLOT, SB_ALIGN_MEMB,                   // the alignment of given clusters (hmk_align.cpp; tables in SB_LINK_TAB): per slot key, extent; per member sum, score, shift
     SB_SURVEY_ACC, SB_SURVEY_ROWS,                  // the score survey (hmk_survey.cpp): bins, counters, score range; per row key, best score, best index, degree
+    SB_SEP_TAB, SB_SEP_REC, SB_SEP_OUT,             // the separation of given clusters (hmk_separation.cpp): partner order + slot tables; per (segment, member) records; per member outputs
     SB_N
 };
 
@@ -128,6 +129,7 @@ struct Switches {
     int csr_bucket_shift = 0;     // HMK_CSR_BUCKET_SHIFT: rows per bucket = 2^shift in the CSR's dealing pass (the wide buckets of n > 2^21)
     uint64_t edge_guess = 0;      // HMK_EDGE_GUESS: first edge-buffer capacity (forces the overflow / retry path)
     int test_grid_cap = 0;        // HMK_TEST_GRID_CAP=n, n >= 1: the grid-stride launches of hmk_grid.h get at most n workgroups (0: their own grids)
+    int test_separation_segment = 0;   // HMK_TEST_SEPARATION_SEGMENT=n, n >= 1: the separation call's segments are n places long (0: sizing::separation_segments)
     void read();
 };
 

@@ -45,5 +45,26 @@ inline uint64_t edge_capacity_after_overflow(uint64_t max_segment_count) {
     return (uint64_t)HMK_EDGE_SHARDS * (mx + mx / 8 + 1024);
 }
 
+// The separation call (hmk_separation.cpp) cuts its cluster-sorted partner order of nm places into segments; a work item is one block
+// of 256 members against one segment.  One segment would give ceil(nm / 256) items -- 391 at 10^5 members on 256 CUs, 14 at 3,383 --
+// so: enough segments for SEPARATION_ITEMS items (sixteen for each of a gfx950's 256 CUs: with four, all of one size and resident at
+// once, the CUs that took a fifth set the time), at most SEPARATION_MAX_SEGMENTS
+// (the scratch is members x segments records), no segment shorter than 256 places (a staged chunk), all segments but the last of one
+// length.  forced_len != 0 replaces the length (HMK_TEST_SEPARATION_SEGMENT: any length >= 1, any number of segments).
+constexpr uint32_t SEPARATION_ITEMS = 4096, SEPARATION_MAX_SEGMENTS = 64, SEPARATION_MIN_SEGMENT = 256;
+struct SeparationSegments { uint32_t length, count; };
+inline SeparationSegments separation_segments(uint32_t nm, uint32_t forced_len) {
+    if (nm == 0) return {0, 0};
+    uint32_t len = forced_len;
+    if (len == 0) {
+        const uint32_t blocks = (nm + 255) / 256;
+        uint32_t want = std::min((SEPARATION_ITEMS + blocks - 1) / blocks, SEPARATION_MAX_SEGMENTS);
+        want = std::max(1u, std::min(want, nm / SEPARATION_MIN_SEGMENT));
+        len = (nm + want - 1) / want;
+    }
+    len = std::min(len, nm);
+    return {len, (nm + len - 1) / len};
+}
+
 } }  // namespace hmk::sizing
 #endif

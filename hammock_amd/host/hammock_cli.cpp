@@ -151,7 +151,9 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "          hammock-hip components -i <sequences> -d <directory> [-g <int>] [--scan_to <int>] [-f fasta|tab] [-m <file>] [-x <int>]\n"
               << "                      [-p <int>] [-l <labels>] [--device <int>]\n"
               << "          hammock-hip survey -i <sequences> -d <directory> [-g <int>] [--database <sequences>] [-f fasta|tab] [-m <file>] [-x <int>]\n"
-              << "                      [-p <int>] [-l <labels>] [--device <int>]\n\n"
+              << "                      [-p <int>] [-l <labels>] [--device <int>]\n"
+              << "          hammock-hip separation -i <clusters.tsv> -d <directory> [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [-l <labels>]\n"
+              << "                      [--device <int>]\n\n"
               << "-i, --input <file>\n\tA path to an input file\n\n"
               << "-d, --output_directory <directory>\n\tA directory to store all output files in\n\n"
               << "-t, --threads <int>\n\tAccepted for compatibility (the GPU path ignores it)\n\n"
@@ -171,7 +173,7 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "--best <int>\n\t(search) keep only the best 1..32 hits of each query; (assign, match) report the best 1..32 feasible clusters (default 1)\n\n"
               << "--clusters <file>\n\t(assign, continue, match) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv);\n\t(merge) a second cluster file: its clusters keep their ids, the -i file's are renumbered behind them\n\n"
               << "--scan_to <int>\n\t(components) the last threshold of the scan: component_levels.tsv gets one line per threshold from -g to this one\n\t(at most 255 above -g; default: -g alone)\n\n"
-              << "--skip_singletons\n\t(assign, match, merge) only clusters of more than one unique sequence are candidates;\n\t(check) clusters of one unique sequence are left out of cluster_linkage.tsv;\n\t(align) clusters of one unique sequence are left out of cluster_centers.tsv\n\n"
+              << "--skip_singletons\n\t(assign, match, merge) only clusters of more than one unique sequence are candidates;\n\t(check) clusters of one unique sequence are left out of cluster_linkage.tsv;\n\t(align) clusters of one unique sequence are left out of cluster_centers.tsv;\n\t(separation) clusters of one unique sequence are neither members nor candidates for the nearest cluster\n\n"
               << "--java_hashset <8|7|6>\n\t(clinkage, merge, split) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
 }
 
@@ -1438,6 +1440,108 @@ int runAlign(const std::vector<std::string> &args) {
     }
 }
 
+// `hammock-hip separation -i clusters.tsv -d dir [-x -p -m -l] [--skip_singletons]`: how well separated the clusters of a cluster file
+// are, and which sequences sit closer to another cluster than to their own (hmk_cluster_separation_shifted): per sequence the mean
+// ShiftedScorer score against the rest of its cluster and against the nearest other cluster -- the largest mean, the first cluster of
+// the file among equal means.  Every unique sequence counts once.  Defaults of -x / -p are check's (-g is settled as there and logged,
+// but nothing is thresholded).  With --skip_singletons clusters of one unique sequence are neither members nor candidates.  Writes
+//   member_separation.tsv    per sequence, clusters in file order, members in cluster order: its cluster, own_sum and own_mean
+//                            (= own_sum / (members - 1)), the nearest cluster with near_sum and near_mean (= near_sum / its members),
+//                            margin = own_mean - near_mean, misplaced (1: own_mean < near_mean, compared exactly)
+//   cluster_separation.tsv   per cluster: members, own_mean over its members (= the sum of their own_sum / (members (members - 1))),
+//                            misplaced members
+// A mean is one double division of two integers, printed %.4f; NA where it is undefined (the own mean of a cluster of one, the nearest
+// columns of a file of one cluster).  Exit codes as check: a cluster file the loader rejects is 2.
+int runSeparation(const std::vector<std::string> &args) {
+    Options o;
+    parseCommonArgs(args, o);
+    parseModeArgs(args, o, -1);
+    requireOneDevice(o, "separation", "a separation");
+    requireInput(o);
+    makeOutputDirectory(o, o.parentDir);
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        ContextFuture contextReady = beginRun(o, logger, false);
+        logRunStart(logger, "separation", args);
+        logger.logAndStderr("Loading clusters...");
+        std::vector<ClusterPtr> clusters;
+        try {
+            clusters = FileIOManager::loadClustersFromCsv(o.inputFileName);
+            if (clusters.empty()) throw FileFormatException("Error. The cluster file holds no clusters.");
+        } catch (const FileFormatException &e) {
+            logger.logAndStderr("Error. Probably wrong input file format? Run with --help for a brief description of command line parameters. Trace: \n");
+            logger.logAndStderr(std::string("cz.krejciadam.hammock.FileFormatException: ") + e.what());
+            return 2;
+        }
+        const std::vector<UniqueSequencePtr> all = sequencesOf(clusters);
+        logger.logAndStderr(std::to_string(clusters.size()) + " clusters of " + std::to_string(all.size()) + " sequences loaded.");
+        const SequenceListSummary summary = summariseSequences(all);
+        settleShiftAndThreshold(o, logger, summary, summary, summary, "Separation");
+
+        std::vector<UniqueSequencePtr> upload;
+        const Candidates cand = appendCandidates(clusters, o.skipSingletons, 0, upload);
+        const uint32_t n = (uint32_t)upload.size(), ncl = (uint32_t)cand.slots.size();
+        std::vector<int64_t> ownSum(n), nearSum(n), clusterOwnSum(ncl);
+        std::vector<uint32_t> nearCluster(n), clusterMisplaced(ncl);
+        std::vector<uint8_t> misplaced(n);
+        hmk_separation_stats stats{};
+        logger.logAndStderr("Separation...");
+        const auto time0 = std::chrono::steady_clock::now();
+        if (n) {
+            const std::shared_ptr<NativeContext> nc = contextReady.get();
+            nc->setSequences(upload, true);
+            const int st = hmk_cluster_separation_shifted(nc->get(), 0, n, cand.memberCluster.data(), ncl, o.maxShift, o.shiftPenalty, ownSum.data(),
+                                                          nearSum.data(), nearCluster.data(), misplaced.data(), clusterMisplaced.data(),
+                                                          clusterOwnSum.data(), &stats);
+            if (st) nc->raise(st, nullptr);
+        }
+        logger.logAndStderr("Ready. Separation time: " + std::to_string(millisSince(time0)));
+        logger.logAndStderr("Clusters: " + std::to_string(ncl) + ", sequences: " + std::to_string(n) + ", pairs scored: " + std::to_string(stats.pairs_scored) +
+                            ", GPU kernels: " + std::to_string(stats.kernel_ms) + " ms");
+        logger.logAndStderr("Saving results to output files...");
+        auto fixed = [](double v) {
+            char text[64];
+            std::snprintf(text, sizeof text, "%.4f", v);
+            return std::string(text);
+        };
+        const std::string membersCsv = o.workingDirectory + "/member_separation.tsv", clustersCsv = o.workingDirectory + "/cluster_separation.tsv";
+        {
+            std::ofstream out(membersCsv);
+            if (!out) throw HammockException("cannot write " + membersCsv);
+            out << "sequence\tcluster_id\tcluster_members\town_sum\town_mean\tnearest_cluster_id\tnearest_members\tnear_sum\tnear_mean\tmargin\tmisplaced\n";
+            for (uint32_t k = 0; k < n; k++) {
+                const Cluster &cl = *clusters[cand.slots[cand.memberCluster[k]]];
+                const int64_t s = (int64_t)cl.getUniqueSize();
+                const bool hasOwn = s > 1, hasNear = nearCluster[k] != UINT32_MAX;
+                const double ownMean = hasOwn ? (double)ownSum[k] / (double)(s - 1) : 0.0;
+                out << upload[k]->getSequenceString() << '\t' << cl.getId() << '\t' << s << '\t' << ownSum[k] << '\t' << (hasOwn ? fixed(ownMean) : "NA");
+                if (!hasNear) { out << "\tNA\tNA\tNA\tNA\tNA\t" << (int)misplaced[k] << '\n'; continue; }
+                const Cluster &near = *clusters[cand.slots[nearCluster[k]]];
+                const double nearMean = (double)nearSum[k] / (double)(int64_t)near.getUniqueSize();
+                out << '\t' << near.getId() << '\t' << near.getUniqueSize() << '\t' << nearSum[k] << '\t' << fixed(nearMean) << '\t'
+                    << (hasOwn ? fixed(ownMean - nearMean) : "NA") << '\t' << (int)misplaced[k] << '\n';
+            }
+        }
+        {
+            std::ofstream out(clustersCsv);
+            if (!out) throw HammockException("cannot write " + clustersCsv);
+            out << "cluster_id\tmembers\town_mean\tmisplaced_members\n";
+            for (uint32_t c = 0; c < ncl; c++) {
+                const Cluster &cl = *clusters[cand.slots[c]];
+                const int64_t s = (int64_t)cl.getUniqueSize();
+                out << cl.getId() << '\t' << s << '\t' << (s > 1 ? fixed((double)clusterOwnSum[c] / (double)(s * (s - 1))) : "NA") << '\t'
+                    << clusterMisplaced[c] << '\n';
+            }
+        }
+        logger.logAndStderr("Sequences in: " + membersCsv);
+        logger.logAndStderr("Clusters in: " + clustersCsv);
+        logger.logAndStderr(std::to_string(stats.n_misplaced) + " of " + std::to_string(n) + " sequences are closer to another cluster than to their own");
+        return 0;
+    } catch (...) {
+        return reportRunError(logger, false);
+    }
+}
+
 // `hammock-hip components -i X.fa -d dir [-g T] [--scan_to T2] [-x -p -m -f -l]`: the connected components of the neighbour graph
 // {score >= t} for every t = T ... T2 from one scoring pass (hmk_components_shifted).  No cluster any other mode can form at t crosses
 // a component at t (ClinkageClusterScorer.java:36-48), so this is where to read off at which threshold a data set falls apart, and
@@ -1765,6 +1869,7 @@ int main(int argc, char **argv) {
         if (args[0] == "components") return runComponents(args);
         if (args[0] == "align") return runAlign(args);
         if (args[0] == "survey") return runSurvey(args);
+        if (args[0] == "separation") return runSeparation(args);
         if (args[0] == "io-selftest") return ioSelftest(args);
         if (args[0] == "dump-matrix") {   // the default matrix in the text format FileIOManager.loadScoringMatrix reads
             std::cout << "# BLOSUM62 substitution matrix (public NCBI table), 24 x 24, order " << AMINO_ACIDS << "\n"

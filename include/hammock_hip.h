@@ -750,6 +750,53 @@ int hmk_score_survey_shifted(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0
                              int32_t *best_score, uint32_t *best_index, uint32_t *degree, /* q1 - q0 each; NULL together */
                              hmk_survey_stats *stats);
 
+/* ---- the separation of given clusters: own cluster against the nearest other one ------------ */
+
+typedef struct {
+    uint64_t pairs_scored;   /* nm (nm - 1) for nm = r1 - r0: the ordered pairs reduced */
+    uint32_t n_misplaced;    /* members with misplaced == 1 (counted whether or not misplaced is given) */
+    uint32_t n_multi;        /* slots with two or more members */
+    uint32_t n_segments;     /* pieces the cluster-sorted partner order was cut into (1: every walk sees whole slots only) */
+    uint32_t launches, reserved;
+    double   kernel_ms;      /* device time, HIP events */
+} hmk_separation_stats;
+
+/* How well separated given clusters are, and which members sit closer to another cluster than to their own: the average-linkage
+ * statistic behind a silhouette.  Members [r0, r1) of the hmk_set_sequences set with member_cluster and n_clusters as
+ * hmk_cluster_linkage_shifted takes them.  There is no threshold: nothing is thresholded.  Members count one each: the uploaded sizes
+ * are not used.  Below, |A| is the number of members of slot A in the range.
+ *   score(a, b)            ShiftedScorer(matrix, shift_penalty, max_shift).sequenceScore(seq1 = the larger index, seq2 = the smaller)
+ *                          (ShiftedScorer.java:48-100): the orientation of hmk_cluster_linkage_shifted, hmk_cluster_align_shifted and
+ *                          the triangle of hmk_score_survey_shifted
+ *   own_sum[m - r0]        for m in slot A: the sum of score(m, b) over the other members b of A; 0 when |A| = 1.  Equal to
+ *                          hmk_cluster_align_shifted's member_sum.
+ *   near_cluster[m - r0]   the nearest other slot: with sum_C = the sum of score(m, b) over b in C for every slot C other than A, the
+ *                          slot with the largest mean sum_C / |C|, among equal means the smallest slot index.  Means are compared
+ *                          exactly, by 64-bit cross-multiplication: |sum_C| <= 2^15 |C|, two slots are disjoint and n <= 2^24, so
+ *                          every product stays below 2^61.  UINT32_MAX with n_clusters == 1.
+ *   near_sum[m - r0]       that slot's sum_C; 0 with n_clusters == 1
+ *   misplaced[m - r0]      1 iff |A| >= 2, another slot exists and own_sum / (|A| - 1) < near_sum / |C| strictly, C the nearest
+ *                          slot, decided by cross-multiplication again; else 0.  A member of a slot of one is never misplaced.  May
+ *                          be NULL.
+ *   cluster_misplaced[c]   the misplaced members of slot c; may be NULL
+ *   cluster_own_sum[c]     the sum of own_sum over the members of slot c; may be NULL
+ *   checks                 HMK_ERR_BAD_ARG before the device is looked at (a host-only context answers them): the range and slot
+ *                          checks of hmk_cluster_linkage_shifted (a slot without members is refused), a null member_cluster with a
+ *                          non-empty range, a null required output, stats == NULL, an asymmetric matrix.  Then the checks of
+ *                          hmk_cluster_align_shifted over the range: HMK_ERR_SHIFT_TOO_BIG against the shortest length, scores that
+ *                          fit int16 at both ends, n <= 2^24.  An empty range is HMK_OK with nothing written.  Never
+ *                          HMK_ERR_CAPACITY.  Without a device HMK_ERR_DEVICE: there is no CPU fallback.
+ * Every ordered pair of distinct members is scored once and added to a running sum per (member, slot) that is closed where the
+ * cluster-sorted partner order leaves the slot (k_separation.hip); no sum per (member, slot) is ever stored: the scratch is
+ * O(members x n_segments + clusters) with n_segments <= 64.  Only integer adds and comparisons, no atomics: the result does not depend
+ * on the grid, the segment length or the schedule.  On a hmk_create_multi context the call runs on the root device. */
+int hmk_cluster_separation_shifted(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_cluster, uint32_t n_clusters,
+                                   int max_shift, int shift_penalty,
+                                   int64_t *own_sum, int64_t *near_sum, uint32_t *near_cluster,       /* r1 - r0 each, required */
+                                   uint8_t *misplaced,                                                 /* r1 - r0, may be NULL */
+                                   uint32_t *cluster_misplaced, int64_t *cluster_own_sum,              /* n_clusters each, may be NULL */
+                                   hmk_separation_stats *stats);
+
 /* Where the time of the last hmk_greedy_cluster / hmk_greedy_from_edges_dev call of this context went
  * (milliseconds; the span of Hammock.java:406-411 minus the sort).  score_ms and csr_ms are device times (HIP events on
  * the call's stream), the others host wall time.  The parts overlap (phase 1 runs while the rest of the pair space is
