@@ -37,6 +37,7 @@ SYMBOLS = [
     "hmk_cluster_linkage_shifted", "hmk_clinkage_split", "hmk_clinkage_split_from_edges",
     "hmk_components_shifted", "hmk_components_from_edges", "hmk_components_from_edges_dev",
     "hmk_cluster_align_shifted", "hmk_score_survey_shifted", "hmk_cluster_separation_shifted",
+    "hmk_greedy_sweep", "hmk_greedy_sweep_from_edges", "hmk_greedy_sweep_from_edges_dev",
 ]
 
 
@@ -119,6 +120,20 @@ class SeparationStats(C.Structure):
     """hmk_separation_stats"""
     _fields_ = [("pairs_scored", C.c_uint64), ("n_misplaced", C.c_uint32), ("n_multi", C.c_uint32), ("n_segments", C.c_uint32),
                 ("launches", C.c_uint32), ("reserved", C.c_uint32), ("kernel_ms", C.c_double)]
+
+
+class GreedyLevel(C.Structure):
+    """hmk_greedy_level"""
+    _fields_ = [("n_edges", C.c_uint64), ("status", C.c_int32), ("crash_case", C.c_int32), ("crash_index", C.c_int32),
+                ("phase1_stop_index", C.c_int32), ("phase1_clusters", C.c_int32), ("phase1_orphans", C.c_int32),
+                ("n_result_clusters", C.c_int32), ("n_multi", C.c_int32), ("n_singletons", C.c_uint32), ("largest", C.c_uint32),
+                ("tail_ms", C.c_double)]
+
+
+class GreedySweepStats(C.Structure):
+    """hmk_greedy_sweep_stats"""
+    _fields_ = [("n_edges", C.c_uint64), ("pairs_scored", C.c_uint64), ("n_levels", C.c_uint32), ("reserved", C.c_uint32),
+                ("kernel_ms", C.c_double), ("deal_ms", C.c_double)]
 
 
 class GreedyPhases(C.Structure):
@@ -210,6 +225,10 @@ def _load():
                                            C.POINTER(SurveyStats)]
     L.hmk_cluster_separation_shifted.argtypes = [vp, u32, u32, p_u32, u32, i32, i32, p_i64, p_i64, p_u32, p_u8, p_u32, p_i64,
                                                  C.POINTER(SeparationStats)]
+    sweep_out = [p_i32, p_i32, p_i32, C.POINTER(GreedyLevel), C.POINTER(GreedySweepStats)]
+    L.hmk_greedy_sweep.argtypes = [vp, i32, i32, i32, i32, i32] + sweep_out
+    L.hmk_greedy_sweep_from_edges.argtypes = [vp, p_u64, u64, i32, i32, i32, i32] + sweep_out
+    L.hmk_greedy_sweep_from_edges_dev.argtypes = [vp, vp, u64, i32, i32, i32, i32] + sweep_out
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("hmk_destroy", "hmk_last_error", "hmk_last_kernel_ms"):

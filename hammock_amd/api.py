@@ -107,6 +107,12 @@ def aligned_rows(seqs, column, width_of_slot):
 LEVEL_DTYPE = np.dtype([("n_edges", np.uint64), ("n_components", np.uint32), ("n_singletons", np.uint32), ("largest", np.uint32),
                         ("reserved", np.uint32)])
 
+# hmk_greedy_level, one entry per threshold of a greedy sweep
+GREEDY_LEVEL_DTYPE = np.dtype([("n_edges", np.uint64), ("status", np.int32), ("crash_case", np.int32), ("crash_index", np.int32),
+                               ("phase1_stop_index", np.int32), ("phase1_clusters", np.int32), ("phase1_orphans", np.int32),
+                               ("n_result_clusters", np.int32), ("n_multi", np.int32), ("n_singletons", np.uint32),
+                               ("largest", np.uint32), ("tail_ms", np.float64)])
+
 
 class Context:
     """1:1 wrapper of hmk_ctx.  device >= 0: HIP ordinal; -1: host-only."""
@@ -769,6 +775,48 @@ class Context:
         """hmk_components_from_edges_dev: the same with the packed edges in device memory, through the device kernels."""
         return self._components(lambda thr, hi, *out: N.lib.hmk_components_from_edges_dev(self._h, C.c_void_p(d_edges_ptr), int(n_edges), thr, hi, *out),
                                 threshold, threshold_hi, component, levels)
+
+    # -- greedy clusterings at a range of thresholds -----------------------------------------
+    def _greedy_sweep(self, call, threshold, threshold_hi, arrays, levels):
+        """runs call(threshold, threshold_hi, cluster_id, result_order, member_rank, levels, stats) ->
+        (levels: structured array GREEDY_LEVEL_DTYPE[n_levels] or None, cluster_id, result_order, member_rank: int32 (n_levels, n)
+        each, or None); statistics in last_sweep_stats.  A level whose status is not 0 is one where the reference would throw: its
+        rows are -1.  result_order's row of a level is valid up to that level's n_result_clusters, -1 behind."""
+        thr = int(threshold)
+        hi = thr if threshold_hi is None else int(threshold_hi)
+        nl = min(max(hi - thr + 1, 1), 256)
+        out = [np.full((nl, max(self.n, 1)), -1, dtype=np.int32) if arrays else None for _ in range(3)]
+        lv = np.zeros(nl, dtype=GREEDY_LEVEL_DTYPE) if levels else None
+        stats = N.GreedySweepStats()
+        st = call(thr, hi, *[_ptr(a, C.c_int32) if arrays else None for a in out],
+                  lv.ctypes.data_as(C.POINTER(N.GreedyLevel)) if levels else None, C.byref(stats))
+        if st:
+            self._raise(st)
+        self.last_sweep_stats = stats
+        if arrays and self.n == 0:
+            out = [a[:, :0] for a in out]
+        return (lv, *out)
+
+    def greedy_sweep(self, max_shift, shift_penalty, threshold, threshold_hi, max_clusters, arrays=True, levels=True):
+        """hmk_greedy_sweep: the greedy clustering of the uploaded set at every t = threshold ... threshold_hi from one scoring pass
+        -> (levels, cluster_id, result_order, member_rank); row t - threshold is what greedy_cluster(..., t, max_clusters) gives.
+        arrays=False / levels=False pass NULL for those outputs and return None for them."""
+        return self._greedy_sweep(lambda thr, hi, *out: N.lib.hmk_greedy_sweep(self._h, int(max_shift), int(shift_penalty), thr, hi,
+                                                                               int(max_clusters), *out),
+                                  threshold, threshold_hi, arrays, levels)
+
+    def greedy_sweep_from_edges(self, edges, symmetric, threshold, threshold_hi, max_clusters, arrays=True, levels=True):
+        """hmk_greedy_sweep_from_edges: the same from packed edges, by the host merge per threshold (works on a host-only context)."""
+        edges = np.ascontiguousarray(edges, dtype=np.uint64)
+        return self._greedy_sweep(lambda thr, hi, *out: N.lib.hmk_greedy_sweep_from_edges(self._h, _ptr(edges, C.c_uint64), edges.size,
+                                                                                          int(bool(symmetric)), thr, hi, int(max_clusters), *out),
+                                  threshold, threshold_hi, arrays, levels)
+
+    def greedy_sweep_from_edges_dev(self, d_edges_ptr, n_edges, symmetric, threshold, threshold_hi, max_clusters, arrays=True, levels=True):
+        """hmk_greedy_sweep_from_edges_dev: the same with the packed edges in device memory, through the device kernels and tails."""
+        return self._greedy_sweep(lambda thr, hi, *out: N.lib.hmk_greedy_sweep_from_edges_dev(self._h, C.c_void_p(d_edges_ptr), int(n_edges),
+                                                                                              int(bool(symmetric)), thr, hi, int(max_clusters), *out),
+                                  threshold, threshold_hi, arrays, levels)
 
     def greedy_phases(self):
         """hmk_greedy_last_phases: per-phase milliseconds of the last greedy_cluster / greedy_from_edges_dev call."""

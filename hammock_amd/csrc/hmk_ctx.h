@@ -3,7 +3,7 @@
 // buffers and their owners, streams), hmk_sizing.h (the sizing rules, pure functions), hmk_plan.cpp (the neighbour passes' planner),
 // hmk_pass.cpp (launching the passes; the pair and block probes), hmk_cluster.cpp (the single-device clustering calls, CSR pipeline,
 // row hand-over, second-loop driver), hmk_multi.cpp (the same calls on several devices), and one file per further call
-// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp, hmk_separation.cpp).  Not part of the public ABI.
+// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp, hmk_separation.cpp, hmk_sweep.cpp).  Not part of the public ABI.
 #ifndef HMK_CTX_H
 #define HMK_CTX_H
 #include <hip/hip_runtime_api.h>
@@ -97,6 +97,7 @@ enum {
     SB_ALIGN_SLOT, SB_ALIGN_MEMB,                   // the alignment of given clusters (hmk_align.cpp; tables in SB_LINK_TAB): per slot key, extent; per member sum, score, shift
     SB_SURVEY_ACC, SB_SURVEY_ROWS,                  // the score survey (hmk_survey.cpp): bins, counters, score range; per row key, best score, best index, degree
     SB_SEP_TAB, SB_SEP_REC, SB_SEP_OUT,             // the separation of given clusters (hmk_separation.cpp): partner order + slot tables; per (segment, member) records; per member outputs
+    SB_SWEEP_RUNS, SB_SWEEP_STATE,                  // the greedy sweep (hmk_sweep.cpp): the pass's whole edges by level, the top level first; histogram, run offsets, prefixes, flag (SweepState)
     SB_N
 };
 

@@ -150,6 +150,8 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "          hammock-hip align -i <clusters.tsv> -d <directory> [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [--device <int>]\n"
               << "          hammock-hip components -i <sequences> -d <directory> [-g <int>] [--scan_to <int>] [-f fasta|tab] [-m <file>] [-x <int>]\n"
               << "                      [-p <int>] [-l <labels>] [--device <int>]\n"
+              << "          hammock-hip sweep -i <sequences> -d <directory> [-g <int>] [--scan_to <int>] [--pick <int>] [-f fasta|tab] [-m <file>]\n"
+              << "                      [-x <int>] [-p <int>] [-R <order>] [-S <int>] [-l <labels>] [--initial_clusters_limit <int>] [--device <int>]\n"
               << "          hammock-hip survey -i <sequences> -d <directory> [-g <int>] [--database <sequences>] [-f fasta|tab] [-m <file>] [-x <int>]\n"
               << "                      [-p <int>] [-l <labels>] [--device <int>]\n"
               << "          hammock-hip separation -i <clusters.tsv> -d <directory> [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [-l <labels>]\n"
@@ -172,7 +174,8 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "--database <file>\n\t(search) the reference sequences every query (-i) is scored against;\n\t(survey) score the input against these sequences instead of against itself\n\n"
               << "--best <int>\n\t(search) keep only the best 1..32 hits of each query; (assign, match) report the best 1..32 feasible clusters (default 1)\n\n"
               << "--clusters <file>\n\t(assign, continue, match) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv);\n\t(merge) a second cluster file: its clusters keep their ids, the -i file's are renumbered behind them\n\n"
-              << "--scan_to <int>\n\t(components) the last threshold of the scan: component_levels.tsv gets one line per threshold from -g to this one\n\t(at most 255 above -g; default: -g alone)\n\n"
+              << "--scan_to <int>\n\t(components) the last threshold of the scan: component_levels.tsv gets one line per threshold from -g to this one\n\t(at most 255 above -g; default: -g alone);\n\t(sweep) the last threshold of the sweep: greedy_levels.tsv gets one line per threshold from -g to this one\n\n"
+              << "--pick <int>\n\t(sweep) the threshold of the sweep whose clustering is written as the stage-1 files (default: -g)\n\n"
               << "--skip_singletons\n\t(assign, match, merge) only clusters of more than one unique sequence are candidates;\n\t(check) clusters of one unique sequence are left out of cluster_linkage.tsv;\n\t(align) clusters of one unique sequence are left out of cluster_centers.tsv;\n\t(separation) clusters of one unique sequence are neither members nor candidates for the nearest cluster\n\n"
               << "--java_hashset <8|7|6>\n\t(clinkage, merge, split) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
 }
@@ -1627,6 +1630,127 @@ int runComponents(const std::vector<std::string> &args) {
     }
 }
 
+// `hammock-hip sweep -i X.fa -d dir -g T --scan_to T2 [--pick P] [greedy's options]`: the greedy clustering at every threshold
+// t = T ... T2 from one scoring pass (hmk_greedy_sweep; LimitedGreedySequenceClusterer.java:22,39-69 once per threshold).  Input
+// loading, ordering and the defaults of -x, -g and --initial_clusters_limit are greedy's own.  Writes greedy_levels.tsv, one line per
+// threshold (how many clusters, how many singletons, the largest cluster, where the reference would throw), and the stage-1 files
+// of the clustering at --pick (default -g): byte for byte what `hammock-hip greedy -g P` writes.  If the reference would throw at
+// P, the levels file is written, the stage-1 files are not, and the message and exit status are greedy's.
+int runSweep(const std::vector<std::string> &args) {
+    Options o;
+    parseCommonArgs(args, o);
+    parseModeArgs(args, o, -1);
+    bool havePick = false;
+    int pick = 0;
+    for (size_t i = 1; i + 1 < args.size(); i++)
+        if (args[i] == "--pick") { pick = javaIntegerDecode(args[++i]); havePick = true; }
+    requireOneDevice(o, "sweep", "a sweep");
+    requireInput(o);
+    makeOutputDirectory(o, o.parentDir);
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        ContextFuture contextReady = beginRun(o, logger, false);
+        std::vector<std::string> labels;
+        if (o.haveLabels) labels = FileIOManager::splitChar(o.labelString, ',', true);
+        if (!(o.inputType == "fasta" || o.inputType == "seq" || o.inputType == "tab"))
+            throw CLIException("Error. Parameter -f value may be either \"fasta\", \"seq\" or \"tab\". No other values are allowed");
+        logRunStart(logger, "sweep", args);
+        // ---- greedy's loading, ordering and defaults (runSequenceClustering) -----------------------------------------------
+        logger.logAndStderr("Loading input sequences...");
+        if (o.inputType == "seq") throw HammockException("Error, this should have been checked.");
+        std::vector<UniqueSequencePtr> sequences = loadSequences(o, o.inputFileName);
+        logger.logAndStderr(std::to_string(sequences.size()) + " unique sequences loaded.");
+        SequenceListSummary summary = summariseSequences(sequences);
+        if (o.haveLabels) {
+            sequences = filterSequencesForLabels(sequences, labels);
+            summary = summariseSequences(sequences);
+        }
+        if (sequences.empty()) throw FileFormatException("Error. No sequences (with specified labels) to cluster.");
+        if (!o.haveLabels) labels = FileIOManager::getSortedLabels(sequences);
+        const std::vector<UniqueSequencePtr> initialSequences(sequences);
+        settleMaxShift(o, logger, summary, summary, "");
+        logger.logAndStderr("Generating input statistics...");
+        FileIOManager::saveInputStatistics(sequences, labels, o.workingDirectory + "/input_statistics.tsv");
+        settleThreshold(o, logger, summary, "Greedy clustering", "");
+        if (!o.haveLimit) {
+            o.initialClustersLimit = (int)javaRound((double)sequences.size() * 0.025);
+            logger.logAndStderr("Initial greedy clusters limit not set. Setting automatically to: " + std::to_string(o.initialClustersLimit));
+        }
+        const int thr = o.sequenceClusteringThreshold, thrHi = o.haveScanTo ? o.scanTo : thr;
+        if (thrHi < thr || (long long)thrHi - thr > 255)
+            throw CLIException("Error. --scan_to may be the threshold (-g) " + std::to_string(thr) + " up to " + std::to_string((long long)thr + 255) + ".");
+        if (!havePick) pick = thr;
+        if (pick < thr || pick > thrHi)
+            throw CLIException("Error. --pick may be a threshold of the sweep, " + std::to_string(thr) + " up to " + std::to_string(thrHi) + ".");
+        logger.logAndStderr("Parameters: max shift " + std::to_string(o.maxShift) + ", gap penalty " + std::to_string(o.shiftPenalty) + ", thresholds " +
+                            std::to_string(thr) + " to " + std::to_string(thrHi) + ", clusters limit " + std::to_string(o.initialClustersLimit) +
+                            ", stage-1 files at " + std::to_string(pick));
+        sortSequences(sequences, o.order, o.seed, labels);
+
+        const size_t n = sequences.size(), nl = (size_t)(thrHi - thr) + 1, row = (size_t)(pick - thr) * n;
+        std::vector<int32_t> cid(nl * n), order(nl * n), rank(nl * n);
+        std::vector<hmk_greedy_level> levels(nl);
+        hmk_greedy_sweep_stats stats{};
+        logger.logAndStderr("Greedy clustering at " + std::to_string(nl) + " thresholds...");
+        const auto time0 = std::chrono::steady_clock::now();
+        {
+            const std::shared_ptr<NativeContext> nc = contextReady.get();
+            nc->setSequences(sequences, true);
+            const int st = hmk_greedy_sweep(nc->get(), o.maxShift, o.shiftPenalty, thr, thrHi, o.initialClustersLimit, cid.data(), order.data(),
+                                            rank.data(), levels.data(), &stats);
+            if (st) nc->raise(st, nullptr);
+        }
+        logger.logAndStderr("Ready. Sweep time: " + std::to_string(millisSince(time0)));
+        double tails = 0;
+        for (const hmk_greedy_level &lv : levels) tails += lv.tail_ms;
+        logger.logAndStderr("Pairs scored: " + std::to_string(stats.pairs_scored) + ", pairs at or above the threshold: " + std::to_string(stats.n_edges) +
+                            ", GPU scoring: " + std::to_string(stats.kernel_ms) + " ms, edges by level: " + std::to_string(stats.deal_ms) +
+                            " ms, clustering tails: " + std::to_string(tails) + " ms");
+        const std::string levelsCsv = o.workingDirectory + "/greedy_levels.tsv";
+        {
+            std::ofstream out(levelsCsv);
+            if (!out) throw HammockException("cannot write " + levelsCsv);
+            out << "threshold\tedges\tstatus\tclusters\tmulti_member\tsingletons\tlargest\tphase1_stop_index\n";
+            for (size_t l = 0; l < nl; l++) {
+                const hmk_greedy_level &lv = levels[l];
+                out << thr + (int)l << '\t' << lv.n_edges << '\t' << (lv.status == HMK_OK ? std::string("ok") : "reference_would_crash:" + std::to_string(lv.crash_case))
+                    << '\t' << lv.n_result_clusters << '\t' << lv.n_multi << '\t' << lv.n_singletons << '\t' << lv.largest << '\t' << lv.phase1_stop_index << '\n';
+            }
+        }
+        logger.logAndStderr("Clusterings by threshold in: " + levelsCsv);
+        const hmk_greedy_level &at = levels[(size_t)(pick - thr)];
+        if (at.status != HMK_OK)   // greedy's own message (hmk_greedy_cluster's error text) and, through reportRunError, its exit status
+            throw NullPointerException("the reference throws NullPointerException here (LimitedGreedySequenceClusterer.java:97/104/108): case " +
+                                       std::to_string(at.crash_case) + " at index " + std::to_string(at.crash_index), at.crash_case, at.crash_index);
+        // the clusters at --pick, as HipGreedySequenceClusterer::cluster builds them from one call's arrays
+        std::vector<uint32_t> first(n + 1, 0);
+        for (size_t k = 0; k < n; k++) first[(size_t)cid[row + k] + 1]++;
+        for (size_t c = 0; c < n; c++) first[c + 1] += first[c];
+        std::vector<uint32_t> slot(n);
+        for (size_t k = 0; k < n; k++) slot[first[(size_t)cid[row + k]] + (size_t)rank[row + k]] = (uint32_t)k;
+        std::vector<ClusterPtr> clusters((size_t)at.n_result_clusters);
+        for (size_t q = 0; q < clusters.size(); q++) {
+            const size_t c = (size_t)order[row + q];
+            std::vector<UniqueSequencePtr> seqs;
+            for (uint32_t e = first[c]; e < first[c + 1]; e++) seqs.push_back(sequences[slot[e]]);
+            clusters[q] = std::make_shared<Cluster>(std::move(seqs), order[row + q]);
+        }
+        logger.logAndStderr("Resulting clusers at threshold " + std::to_string(pick) + ": " + std::to_string(clusters.size()));
+        logger.logAndStderr("Saving results to output files...");
+        const std::string seqCsv = o.workingDirectory + "/initial_clusters_sequences.tsv";
+        const std::string orderedCsv = o.workingDirectory + "/initial_clusters_sequences_original_order.tsv";
+        const std::string clustersCsv = o.workingDirectory + "/initial_clusters.tsv";
+        FileIOManager::saveInitialClusters(clusters, seqCsv, orderedCsv, clustersCsv, labels, initialSequences);
+        logger.logAndStderr("Greedy clustering results in: " + clustersCsv);
+        logger.logAndStderr("and: " + seqCsv);
+        logger.logAndStderr("and: " + orderedCsv);
+        logger.logWithTime("Program successfully ended.");
+        return 0;
+    } catch (...) {
+        return reportRunError(logger, true);
+    }
+}
+
 // `hammock-hip survey -i X.fa -d dir [-g T] [--database known.fa] [-x -p -m -f -l]`: what the pair scores of a set look like, before a
 // threshold is chosen for any other mode (hmk_score_survey_shifted): the histogram of the scores, every sequence's best partner and its
 // number of partners at -g.  Without --database the triangle over the input in load order (every unordered pair, as components scores
@@ -1867,6 +1991,7 @@ int main(int argc, char **argv) {
         if (args[0] == "check") return runCheck(args);
         if (args[0] == "split") return runSplit(args);
         if (args[0] == "components") return runComponents(args);
+        if (args[0] == "sweep") return runSweep(args);
         if (args[0] == "align") return runAlign(args);
         if (args[0] == "survey") return runSurvey(args);
         if (args[0] == "separation") return runSeparation(args);

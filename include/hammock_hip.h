@@ -389,6 +389,64 @@ int hmk_greedy_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n_edge
                               int max_clusters, int32_t *cluster_id, int32_t *result_order,
                               int32_t *member_rank, hmk_greedy_stats *stats);
 
+/* ---- greedy clusterings at a range of thresholds --------------------------------------- */
+
+typedef struct {
+    uint64_t n_edges;            /* pairs with score >= t */
+    int32_t  status;             /* HMK_OK or HMK_ERR_REFERENCE_WOULD_CRASH at this t */
+    int32_t  crash_case, crash_index;
+    int32_t  phase1_stop_index, phase1_clusters, phase1_orphans;
+    int32_t  n_result_clusters, n_multi;     /* as hmk_greedy_stats at this t */
+    uint32_t n_singletons;       /* result clusters of one sequence */
+    uint32_t largest;            /* sequences (not Cluster.size()) in the largest cluster */
+    double   tail_ms;            /* wall time of this level's tail */
+} hmk_greedy_level;
+
+typedef struct {
+    uint64_t n_edges, pairs_scored;   /* edges >= threshold; 0 pairs for the _from_edges forms: nothing is scored */
+    uint32_t n_levels, reserved;      /* threshold_hi - threshold + 1 */
+    double kernel_ms;            /* the scoring pass, HIP events */
+    double deal_ms;              /* the three k_sweep kernels, HIP events (0 for hmk_greedy_sweep_from_edges) */
+} hmk_greedy_sweep_stats;
+
+/* Replaces one LimitedGreedySequenceClusterer(scorer, t, maxClusters).cluster(sequences)
+ * (LimitedGreedySequenceClusterer.java:22,39-69) per threshold t = threshold ... threshold_hi, scorer =
+ * ShiftedScorer(matrix, shift_penalty, max_shift), with ONE scoring pass at `threshold`: the neighbour graph at the lowest threshold
+ * holds every higher threshold's graph, each edge carries its score.
+ *   cluster_id, result_order, member_rank   each [n_levels][n] or NULL; row t - threshold is exactly what
+ *                           hmk_greedy_cluster(..., t, max_clusters, ...) writes (entries of result_order behind the level's
+ *                           n_result_clusters are -1)
+ *   levels[t - threshold]   may be NULL; the fields it shares with hmk_greedy_stats are that call's stats
+ *   a level where the reference would throw: the failure is recorded in that level (status, crash_case, crash_index), its rows
+ *                           are filled with -1, the sweep goes on and returns HMK_OK.  Any other error ends the call.
+ *   checks                  HMK_ERR_BAD_ARG before the device is looked at (a host-only context answers them): threshold_hi <
+ *                           threshold, threshold_hi - threshold > 255, threshold_hi > 32767, levels and all three arrays NULL
+ *                           with n > 0.  Then the checks of hmk_greedy_cluster at `threshold`.  Never HMK_ERR_CAPACITY (the call
+ *                           grows its own scratch).  No sequences: HMK_OK, zeroed levels.
+ * The pass is hmk_neighbors_shifted's (same plan slot, same kernels) into the context's edge buffer; behind it k_sweep.hip: a
+ * histogram of the edges' levels min(score, threshold_hi) - threshold, the whole edges dealt into one run per level with the top
+ * level first, so that the edges with score >= t are a prefix of one buffer; then per level the tail of hmk_greedy_cluster on that
+ * prefix.  On a hmk_create_multi context the call runs on the root device. */
+int hmk_greedy_sweep(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, int threshold_hi, int max_clusters,
+                     int32_t *cluster_id, int32_t *result_order, int32_t *member_rank, hmk_greedy_level *levels,
+                     hmk_greedy_sweep_stats *stats);
+
+/* The same (LimitedGreedySequenceClusterer.java:22,39-69, once per threshold) from packed HMK_EDGE_* edges as
+ * hmk_greedy_from_edges takes them, any order; the scores are read from the edges, an edge with a score below `threshold` is
+ * ignored, one above threshold_hi counts at every level and keeps its score; an index >= n or a self pair is HMK_ERR_BAD_ARG.
+ * On the host: the edges sorted by level by counting, hmk_greedy_from_edges's merge per prefix.  Works on a host-only context, and
+ * is the second implementation the device path is tested against. */
+int hmk_greedy_sweep_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t n_edges, int symmetric, int threshold, int threshold_hi,
+                                int max_clusters, int32_t *cluster_id, int32_t *result_order, int32_t *member_rank,
+                                hmk_greedy_level *levels, hmk_greedy_sweep_stats *stats);
+
+/* The same (LimitedGreedySequenceClusterer.java:22,39-69, once per threshold) with the edges in device memory (the context's
+ * device), through the kernels and tails of hmk_greedy_sweep.  An index >= n or a self pair is found on the device, before any
+ * array is indexed with it: HMK_ERR_BAD_ARG. */
+int hmk_greedy_sweep_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n_edges, int symmetric, int threshold, int threshold_hi,
+                                    int max_clusters, int32_t *cluster_id, int32_t *result_order, int32_t *member_rank,
+                                    hmk_greedy_level *levels, hmk_greedy_sweep_stats *stats);
+
 /* ---- clinkage mode ------------------------------------------------------- */
 
 typedef struct {
