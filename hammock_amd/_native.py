@@ -38,6 +38,7 @@ SYMBOLS = [
     "hmk_components_shifted", "hmk_components_from_edges", "hmk_components_from_edges_dev",
     "hmk_cluster_align_shifted", "hmk_score_survey_shifted", "hmk_cluster_separation_shifted",
     "hmk_greedy_sweep", "hmk_greedy_sweep_from_edges", "hmk_greedy_sweep_from_edges_dev",
+    "hmk_representatives_shifted", "hmk_representatives_from_edges", "hmk_representatives_from_edges_dev",
 ]
 
 
@@ -136,6 +137,19 @@ class GreedySweepStats(C.Structure):
                 ("kernel_ms", C.c_double), ("deal_ms", C.c_double)]
 
 
+class RepresentativeLevel(C.Structure):
+    """hmk_representative_level"""
+    _fields_ = [("n_edges", C.c_uint64), ("n_representatives", C.c_uint32), ("n_isolated", C.c_uint32), ("largest", C.c_uint32),
+                ("n_rounds", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class RepresentativesStats(C.Structure):
+    """hmk_representatives_stats"""
+    _fields_ = [("n_edges", C.c_uint64), ("pairs_scored", C.c_uint64), ("n_levels", C.c_uint32), ("n_representatives", C.c_uint32),
+                ("n_isolated", C.c_uint32), ("largest", C.c_uint32), ("rounds_total", C.c_uint32), ("reserved", C.c_uint32),
+                ("kernel_ms", C.c_double), ("select_ms", C.c_double)]
+
+
 class GreedyPhases(C.Structure):
     """hmk_greedy_phases: where the time of the last greedy call went (milliseconds)."""
     _fields_ = [(k, C.c_double) for k in ("plan_ms", "score_ms", "csr_ms", "wait_rows_ms", "phase1_ms", "precheck_ms", "exchange_ms",
@@ -229,6 +243,10 @@ def _load():
     L.hmk_greedy_sweep.argtypes = [vp, i32, i32, i32, i32, i32] + sweep_out
     L.hmk_greedy_sweep_from_edges.argtypes = [vp, p_u64, u64, i32, i32, i32, i32] + sweep_out
     L.hmk_greedy_sweep_from_edges_dev.argtypes = [vp, vp, u64, i32, i32, i32, i32] + sweep_out
+    rep_out = [p_u32, p_u32, p_i32, C.POINTER(RepresentativeLevel), C.POINTER(RepresentativesStats)]
+    L.hmk_representatives_shifted.argtypes = [vp, i32, i32, i32, i32] + rep_out
+    L.hmk_representatives_from_edges.argtypes = [vp, p_u64, u64, i32, i32] + rep_out
+    L.hmk_representatives_from_edges_dev.argtypes = [vp, vp, u64, i32, i32] + rep_out
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("hmk_destroy", "hmk_last_error", "hmk_last_kernel_ms"):

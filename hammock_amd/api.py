@@ -113,6 +113,10 @@ GREEDY_LEVEL_DTYPE = np.dtype([("n_edges", np.uint64), ("status", np.int32), ("c
                                ("n_result_clusters", np.int32), ("n_multi", np.int32), ("n_singletons", np.uint32),
                                ("largest", np.uint32), ("tail_ms", np.float64)])
 
+# hmk_representative_level, one entry per threshold of a representatives call
+REPRESENTATIVE_LEVEL_DTYPE = np.dtype([("n_edges", np.uint64), ("n_representatives", np.uint32), ("n_isolated", np.uint32),
+                                       ("largest", np.uint32), ("n_rounds", np.uint32), ("reserved", np.uint32, (2,))])
+
 
 class Context:
     """1:1 wrapper of hmk_ctx.  device >= 0: HIP ordinal; -1: host-only."""
@@ -817,6 +821,50 @@ class Context:
         return self._greedy_sweep(lambda thr, hi, *out: N.lib.hmk_greedy_sweep_from_edges_dev(self._h, C.c_void_p(d_edges_ptr), int(n_edges),
                                                                                               int(bool(symmetric)), thr, hi, int(max_clusters), *out),
                                   threshold, threshold_hi, arrays, levels)
+
+    # -- representatives: a non-redundant subset of the set -----------------------------------
+    def _representatives(self, call, threshold, threshold_hi, arrays, levels):
+        """runs call(threshold, threshold_hi, covered_by, nearest, nearest_score, levels, stats) -> (levels: structured array
+        REPRESENTATIVE_LEVEL_DTYPE[n_levels] or None, covered_by uint32, nearest uint32, nearest_score int32: (n_levels, n) each, or
+        None); statistics in last_representatives_stats.  arrays: True, False, or one flag per array."""
+        thr = int(threshold)
+        hi = thr if threshold_hi is None else int(threshold_hi)
+        nl = min(max(hi - thr + 1, 1), 256)
+        want = (bool(arrays),) * 3 if isinstance(arrays, (bool, int)) else tuple(bool(a) for a in arrays)
+        kinds = (np.uint32, np.uint32, np.int32)
+        out = [np.zeros((nl, max(self.n, 1)), dtype=k) if w else None for k, w in zip(kinds, want)]
+        lv = np.zeros(nl, dtype=REPRESENTATIVE_LEVEL_DTYPE) if levels else None
+        stats = N.RepresentativesStats()
+        st = call(thr, hi, _ptr(out[0], C.c_uint32) if want[0] else None, _ptr(out[1], C.c_uint32) if want[1] else None,
+                  _ptr(out[2], C.c_int32) if want[2] else None,
+                  lv.ctypes.data_as(C.POINTER(N.RepresentativeLevel)) if levels else None, C.byref(stats))
+        if st:
+            self._raise(st)
+        self.last_representatives_stats = stats
+        if self.n == 0:
+            out = [a[:, :0] if a is not None else None for a in out]
+        return (lv, *out)
+
+    def representatives_shifted(self, max_shift, shift_penalty, threshold, threshold_hi=None, arrays=True, levels=True):
+        """hmk_representatives_shifted: the representatives of the uploaded set (i is one iff no representative r < i is its
+        neighbour in {ShiftedScorer score >= t}) at every t = threshold ... threshold_hi (None: threshold alone) from one scoring pass
+        -> (levels, covered_by, nearest, nearest_score); row t - threshold: covered_by[i] = i for a representative, else its
+        smallest-index representative neighbour; nearest[i], nearest_score[i] = i, INT32_MAX for a representative, else the
+        representative neighbour with the largest score and that score.  arrays=False / levels=False pass NULL and return None."""
+        return self._representatives(lambda thr, hi, *out: N.lib.hmk_representatives_shifted(self._h, int(max_shift), int(shift_penalty), thr, hi, *out),
+                                     threshold, threshold_hi, arrays, levels)
+
+    def representatives_from_edges(self, edges, threshold, threshold_hi=None, arrays=True, levels=True):
+        """hmk_representatives_from_edges: the same from packed edges read as an undirected graph, by the sequential definition on the
+        host (works on a host-only context)."""
+        edges = np.ascontiguousarray(edges, dtype=np.uint64)
+        return self._representatives(lambda thr, hi, *out: N.lib.hmk_representatives_from_edges(self._h, _ptr(edges, C.c_uint64), edges.size, thr, hi, *out),
+                                     threshold, threshold_hi, arrays, levels)
+
+    def representatives_from_edges_dev(self, d_edges_ptr, n_edges, threshold, threshold_hi=None, arrays=True, levels=True):
+        """hmk_representatives_from_edges_dev: the same with the packed edges in device memory, through the device kernels."""
+        return self._representatives(lambda thr, hi, *out: N.lib.hmk_representatives_from_edges_dev(self._h, C.c_void_p(d_edges_ptr), int(n_edges), thr, hi, *out),
+                                     threshold, threshold_hi, arrays, levels)
 
     def greedy_phases(self):
         """hmk_greedy_last_phases: per-phase milliseconds of the last greedy_cluster / greedy_from_edges_dev call."""

@@ -152,6 +152,8 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "                      [-p <int>] [-l <labels>] [--device <int>]\n"
               << "          hammock-hip sweep -i <sequences> -d <directory> [-g <int>] [--scan_to <int>] [--pick <int>] [-f fasta|tab] [-m <file>]\n"
               << "                      [-x <int>] [-p <int>] [-R <order>] [-S <int>] [-l <labels>] [--initial_clusters_limit <int>] [--device <int>]\n"
+              << "          hammock-hip representatives -i <sequences> -d <directory> [-g <int>] [--scan_to <int>] [-f fasta|tab] [-m <file>]\n"
+              << "                      [-x <int>] [-p <int>] [-R <order>] [-S <int>] [-l <labels>] [--device <int>]\n"
               << "          hammock-hip survey -i <sequences> -d <directory> [-g <int>] [--database <sequences>] [-f fasta|tab] [-m <file>] [-x <int>]\n"
               << "                      [-p <int>] [-l <labels>] [--device <int>]\n"
               << "          hammock-hip separation -i <clusters.tsv> -d <directory> [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [-l <labels>]\n"
@@ -174,7 +176,7 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "--database <file>\n\t(search) the reference sequences every query (-i) is scored against;\n\t(survey) score the input against these sequences instead of against itself\n\n"
               << "--best <int>\n\t(search) keep only the best 1..32 hits of each query; (assign, match) report the best 1..32 feasible clusters (default 1)\n\n"
               << "--clusters <file>\n\t(assign, continue, match) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv);\n\t(merge) a second cluster file: its clusters keep their ids, the -i file's are renumbered behind them\n\n"
-              << "--scan_to <int>\n\t(components) the last threshold of the scan: component_levels.tsv gets one line per threshold from -g to this one\n\t(at most 255 above -g; default: -g alone);\n\t(sweep) the last threshold of the sweep: greedy_levels.tsv gets one line per threshold from -g to this one\n\n"
+              << "--scan_to <int>\n\t(components) the last threshold of the scan: component_levels.tsv gets one line per threshold from -g to this one\n\t(at most 255 above -g; default: -g alone);\n\t(sweep) the last threshold of the sweep: greedy_levels.tsv gets one line per threshold from -g to this one;\n\t(representatives) the last threshold: representative_levels.tsv gets one line per threshold from -g to this one\n\n"
               << "--pick <int>\n\t(sweep) the threshold of the sweep whose clustering is written as the stage-1 files (default: -g)\n\n"
               << "--skip_singletons\n\t(assign, match, merge) only clusters of more than one unique sequence are candidates;\n\t(check) clusters of one unique sequence are left out of cluster_linkage.tsv;\n\t(align) clusters of one unique sequence are left out of cluster_centers.tsv;\n\t(separation) clusters of one unique sequence are neither members nor candidates for the nearest cluster\n\n"
               << "--java_hashset <8|7|6>\n\t(clinkage, merge, split) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
@@ -1751,6 +1753,131 @@ int runSweep(const std::vector<std::string> &args) {
     }
 }
 
+// `hammock-hip representatives -i X.fa -d dir [-g T] [--scan_to T2] [greedy's ordering and scoring options]`: the non-redundant
+// subset of the input at every threshold t = T ... T2 from one scoring pass (hmk_representatives_shifted): in greedy's order a
+// sequence is a representative unless an earlier representative scores >= t with it -- the greedy incremental selection of CD-HIT
+// and UCLUST.  With the default order the most abundant sequence of a family becomes its representative.  Loading, ordering and the
+// defaults of -x and -g are greedy's own.  Writes representative_levels.tsv (one line per threshold), representatives.tsv (one line
+// per sequence at T), representatives.fa (the representatives at T, one record per label, the label's count summed over the
+// sequences nearest to that representative: it loads back through -i with the input's total count) and the stage-1 files with the
+// `nearest` groups at T as clusters -- id = 1 + the representative's place in the order, groups of several sequences first in
+// ascending id, then the single ones, members in the order -- so that check, separation and align take them.
+int runRepresentatives(const std::vector<std::string> &args) {
+    Options o;
+    parseCommonArgs(args, o);
+    parseModeArgs(args, o, -1);
+    requireOneDevice(o, "representatives", "a selection of representatives");
+    requireInput(o);
+    requireFastaOrTab(o, "representatives");
+    makeOutputDirectory(o, o.parentDir);
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        ContextFuture contextReady = beginRun(o, logger, false);
+        logRunStart(logger, "representatives", args);
+        std::vector<std::string> labels;
+        if (o.haveLabels) labels = FileIOManager::splitChar(o.labelString, ',', true);
+        // ---- greedy's loading, ordering and defaults (runSequenceClustering) -----------------------------------------------
+        logger.logAndStderr("Loading input sequences...");
+        std::vector<UniqueSequencePtr> sequences = loadSequences(o, o.inputFileName);
+        logger.logAndStderr(std::to_string(sequences.size()) + " unique sequences loaded.");
+        SequenceListSummary summary = summariseSequences(sequences);
+        if (o.haveLabels) {
+            sequences = filterSequencesForLabels(sequences, labels);
+            summary = summariseSequences(sequences);
+        }
+        if (sequences.empty()) throw FileFormatException("Error. No sequences (with specified labels) to cluster.");
+        if (!o.haveLabels) labels = FileIOManager::getSortedLabels(sequences);
+        const std::vector<UniqueSequencePtr> initialSequences(sequences);
+        settleMaxShift(o, logger, summary, summary, "");
+        settleThreshold(o, logger, summary, "Representatives", "");
+        const int thr = o.sequenceClusteringThreshold, thrHi = o.haveScanTo ? o.scanTo : thr;
+        if (thrHi < thr || (long long)thrHi - thr > 255)
+            throw CLIException("Error. --scan_to may be the threshold (-g) " + std::to_string(thr) + " up to " + std::to_string((long long)thr + 255) + ".");
+        logger.logAndStderr("Parameters: max shift " + std::to_string(o.maxShift) + ", gap penalty " + std::to_string(o.shiftPenalty) + ", thresholds " +
+                            std::to_string(thr) + " to " + std::to_string(thrHi));
+        sortSequences(sequences, o.order, o.seed, labels);
+
+        const size_t n = sequences.size(), nl = (size_t)(thrHi - thr) + 1;
+        std::vector<uint32_t> covered(nl * n), nearest(nl * n);
+        std::vector<int32_t> score(nl * n);
+        std::vector<hmk_representative_level> levels(nl);
+        hmk_representatives_stats stats{};
+        logger.logAndStderr("Representatives at " + std::to_string(nl) + " thresholds...");
+        const auto time0 = std::chrono::steady_clock::now();
+        {
+            const std::shared_ptr<NativeContext> nc = contextReady.get();
+            nc->setSequences(sequences, true);
+            const int st = hmk_representatives_shifted(nc->get(), o.maxShift, o.shiftPenalty, thr, thrHi, covered.data(), nearest.data(), score.data(),
+                                                       levels.data(), &stats);
+            if (st) nc->raise(st, nullptr);
+        }
+        logger.logAndStderr("Ready. Representatives time: " + std::to_string(millisSince(time0)));
+        logger.logAndStderr("Pairs scored: " + std::to_string(stats.pairs_scored) + ", pairs at or above the threshold: " + std::to_string(stats.n_edges) +
+                            ", GPU scoring: " + std::to_string(stats.kernel_ms) + " ms, GPU selection: " + std::to_string(stats.select_ms) + " ms, rounds: " +
+                            std::to_string(stats.rounds_total));
+        logger.logAndStderr("Representatives at threshold " + std::to_string(thr) + ": " + std::to_string(stats.n_representatives) + ", without a neighbour: " +
+                            std::to_string(stats.n_isolated) + ", largest group: " + std::to_string(stats.largest));
+        logger.logAndStderr("Saving results to output files...");
+        const std::string levelsCsv = o.workingDirectory + "/representative_levels.tsv";
+        {
+            std::ofstream out(levelsCsv);
+            if (!out) throw HammockException("cannot write " + levelsCsv);
+            out << "threshold\tedges\trepresentatives\tisolated\tlargest\n";
+            for (size_t l = 0; l < nl; l++)
+                out << thr + (int)l << '\t' << levels[l].n_edges << '\t' << levels[l].n_representatives << '\t' << levels[l].n_isolated << '\t'
+                    << levels[l].largest << '\n';
+        }
+        // the level -g: row 0 of the arrays
+        const std::string perSequence = o.workingDirectory + "/representatives.tsv";
+        {
+            std::ofstream out(perSequence);
+            if (!out) throw HammockException("cannot write " + perSequence);
+            out << "sequence\trepresentative\tcovered_by\tnearest\tscore\n";
+            for (size_t i = 0; i < n; i++) {
+                const bool rep = nearest[i] == i;
+                out << sequences[i]->getSequenceString() << '\t' << (rep ? 1 : 0) << '\t' << sequences[covered[i]]->getSequenceString() << '\t'
+                    << sequences[nearest[i]]->getSequenceString() << '\t' << (rep ? std::string("NA") : std::to_string(score[i])) << '\n';
+            }
+        }
+        std::vector<std::vector<UniqueSequencePtr>> members(n);
+        for (size_t i = 0; i < n; i++) members[nearest[i]].push_back(sequences[i]);
+        const std::string fasta = o.workingDirectory + "/representatives.fa";
+        {
+            std::ofstream out(fasta);
+            if (!out) throw HammockException("cannot write " + fasta);
+            for (size_t i = 0; i < n; i++) {
+                if (members[i].empty()) continue;
+                for (const std::string &label : labels) {
+                    long long count = 0;
+                    for (const UniqueSequencePtr &s : members[i])
+                        for (const auto &e : s->getLabelsMap())
+                            if (e.first == label) count += e.second;
+                    if (count > 0) out << '>' << i + 1 << '|' << count << '|' << label << '\n' << sequences[i]->getSequenceString() << '\n';
+                }
+            }
+        }
+        std::vector<ClusterPtr> result;
+        for (int multi = 1; multi >= 0; multi--)
+            for (size_t i = 0; i < n; i++)
+                if (!members[i].empty() && (members[i].size() > 1) == (multi == 1)) result.push_back(std::make_shared<Cluster>(members[i], (int)i + 1));
+        logger.logAndStderr("Resulting clusers: " + std::to_string(result.size()));
+        const std::string seqCsv = o.workingDirectory + "/initial_clusters_sequences.tsv";
+        const std::string orderedCsv = o.workingDirectory + "/initial_clusters_sequences_original_order.tsv";
+        const std::string clustersCsv = o.workingDirectory + "/initial_clusters.tsv";
+        FileIOManager::saveInitialClusters(result, seqCsv, orderedCsv, clustersCsv, labels, initialSequences);
+        logger.logAndStderr("Representatives by threshold in: " + levelsCsv);
+        logger.logAndStderr("Sequences and their representatives in: " + perSequence);
+        logger.logAndStderr("Representatives in: " + fasta);
+        logger.logAndStderr("Groups as clusters in: " + clustersCsv);
+        logger.logAndStderr("and: " + seqCsv);
+        logger.logAndStderr("and: " + orderedCsv);
+        logger.logWithTime("Program successfully ended.");
+        return 0;
+    } catch (...) {
+        return reportRunError(logger, false);
+    }
+}
+
 // `hammock-hip survey -i X.fa -d dir [-g T] [--database known.fa] [-x -p -m -f -l]`: what the pair scores of a set look like, before a
 // threshold is chosen for any other mode (hmk_score_survey_shifted): the histogram of the scores, every sequence's best partner and its
 // number of partners at -g.  Without --database the triangle over the input in load order (every unordered pair, as components scores
@@ -1992,6 +2119,7 @@ int main(int argc, char **argv) {
         if (args[0] == "split") return runSplit(args);
         if (args[0] == "components") return runComponents(args);
         if (args[0] == "sweep") return runSweep(args);
+        if (args[0] == "representatives") return runRepresentatives(args);
         if (args[0] == "align") return runAlign(args);
         if (args[0] == "survey") return runSurvey(args);
         if (args[0] == "separation") return runSeparation(args);

@@ -717,6 +717,70 @@ int hmk_components_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t n_ed
 int hmk_components_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n_edges, int threshold, int threshold_hi,
                                   uint32_t *component, hmk_component_level *levels, hmk_components_stats *stats);
 
+/* ---- representatives: a non-redundant subset of the set --------------------------------- */
+
+typedef struct {
+    uint64_t n_edges;             /* edges given with score >= t (as the other calls count them: every entry of the list) */
+    uint32_t n_representatives;
+    uint32_t n_isolated;          /* sequences without any neighbour at t (each one is a representative) */
+    uint32_t largest;             /* members of the largest group by `nearest`, its representative included */
+    uint32_t n_rounds;            /* rounds the device needed at this level; 0 for hmk_representatives_from_edges */
+    uint32_t reserved[2];
+} hmk_representative_level;
+
+typedef struct {
+    uint64_t n_edges;             /* edges >= threshold */
+    uint64_t pairs_scored;        /* 0 for the _from_edges forms: nothing is scored */
+    uint32_t n_levels;            /* threshold_hi - threshold + 1 */
+    uint32_t n_representatives, n_isolated, largest;   /* at `threshold` */
+    uint32_t rounds_total;        /* the sum of the levels' n_rounds */
+    uint32_t reserved;
+    double   kernel_ms;           /* the scoring pass, HIP events */
+    double   select_ms;           /* everything behind the pass on the device, the levels' copies included, HIP events (0 for
+                                     hmk_representatives_from_edges) */
+} hmk_representatives_stats;
+
+/* The representatives of the hmk_set_sequences set at every t = threshold ... threshold_hi, from ONE scoring pass at `threshold`:
+ * the greedy incremental selection of CD-HIT and UCLUST on the neighbour graph a ~ b iff ShiftedScorer(matrix, shift_penalty,
+ * max_shift).sequenceScore >= t.  Walk the sequences in caller order; a sequence becomes a representative unless an earlier
+ * representative is its neighbour.  On the graph that is the lexicographically first maximal independent set.  The set is not
+ * monotone in t: every level is decided on its own.
+ *   representative          i is one iff no representative r < i is a neighbour of i, decided for i = 0, 1, 2, ... in order
+ *   covered_by[l][i]        i itself for a representative, else the smallest-index representative among i's neighbours (it is < i)
+ *   nearest[l][i], nearest_score[l][i]   i and INT32_MAX for a representative, else the representative neighbour with the largest
+ *                           score (it may have a larger index than i), among equal scores the smaller index, and that score
+ *   levels[l]               l = t - threshold; the arrays are [n_levels][n], each may be NULL, levels may be NULL
+ *   checks                  HMK_ERR_BAD_ARG before the device is looked at (a host-only context answers them): threshold_hi <
+ *                           threshold, threshold_hi - threshold > 255, threshold_hi > 32767, all four outputs NULL with n > 0, an
+ *                           asymmetric matrix (as hmk_components_shifted).  Then the checks of hmk_neighbors_shifted at `threshold`.
+ *                           Never HMK_ERR_CAPACITY (the call grows its own scratch).  No sequences: HMK_OK, zeroed levels.
+ * The pass is hmk_neighbors_shifted's (same plan slot, same kernels) into the context's edge buffer.  A range is dealt by the
+ * kernels of hmk_greedy_sweep into one run per level with the top level first, so that the edges >= t are a prefix; a single level
+ * reads the pass's segments where they lie.  Per level k_representatives.hip runs synchronous rounds: a marking kernel over the
+ * live edges that only reads the vertices' states, a decision kernel over the vertices; a vertex is decided only once its decision
+ * is forced, so the result and n_rounds do not depend on the grid or the schedule.  The host polls a progress word and keeps one
+ * round in the queue beside the running one.  Two more kernels assign covered_by and nearest.  Only the result arrays cross to the
+ * host.  On a hmk_create_multi context the call runs on the root device. */
+int hmk_representatives_shifted(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, int threshold_hi,
+                                uint32_t *covered_by, uint32_t *nearest, int32_t *nearest_score,
+                                hmk_representative_level *levels, hmk_representatives_stats *stats);
+
+/* The same from packed HMK_EDGE_* edges read as an undirected graph: a pair is adjacent if it appears in either orientation, any
+ * number of times, and its score is the largest it appears with; edges below `threshold` are ignored, one above threshold_hi counts
+ * at every level and keeps its score; an index >= n or a self pair is HMK_ERR_BAD_ARG.  This is the definition written plainly on
+ * the host (lower adjacency by counting, one walk in index order per level, one pass over the edges for covered_by and nearest):
+ * it works on a host-only context, and is the second implementation the device path is tested against.  No symmetry check:
+ * nothing is scored. */
+int hmk_representatives_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t n_edges, int threshold, int threshold_hi,
+                                   uint32_t *covered_by, uint32_t *nearest, int32_t *nearest_score,
+                                   hmk_representative_level *levels, hmk_representatives_stats *stats);
+
+/* The same with the edges in device memory (the context's device), through the kernels of hmk_representatives_shifted.  An index
+ * >= n or a self pair is found on the device, before any array is indexed with it: HMK_ERR_BAD_ARG. */
+int hmk_representatives_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n_edges, int threshold, int threshold_hi,
+                                       uint32_t *covered_by, uint32_t *nearest, int32_t *nearest_score,
+                                       hmk_representative_level *levels, hmk_representatives_stats *stats);
+
 /* ---- aligning given clusters around their medoids --------------------------------------- */
 
 typedef struct {
