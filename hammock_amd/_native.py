@@ -39,6 +39,7 @@ SYMBOLS = [
     "hmk_cluster_align_shifted", "hmk_score_survey_shifted", "hmk_cluster_separation_shifted",
     "hmk_greedy_sweep", "hmk_greedy_sweep_from_edges", "hmk_greedy_sweep_from_edges_dev",
     "hmk_representatives_shifted", "hmk_representatives_from_edges", "hmk_representatives_from_edges_dev",
+    "hmk_density_shifted", "hmk_density_from_edges", "hmk_density_from_edges_dev",
 ]
 
 
@@ -150,6 +151,19 @@ class RepresentativesStats(C.Structure):
                 ("kernel_ms", C.c_double), ("select_ms", C.c_double)]
 
 
+class DensityLevel(C.Structure):
+    """hmk_density_level"""
+    _fields_ = [("n_edges", C.c_uint64), ("n_core", C.c_uint32), ("n_border", C.c_uint32), ("n_noise", C.c_uint32),
+                ("n_clusters", C.c_uint32), ("largest", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DensityStats(C.Structure):
+    """hmk_density_stats"""
+    _fields_ = [("n_edges", C.c_uint64), ("pairs_scored", C.c_uint64), ("n_levels", C.c_uint32), ("min_neighbors", C.c_uint32),
+                ("n_core", C.c_uint32), ("n_border", C.c_uint32), ("n_noise", C.c_uint32), ("n_clusters", C.c_uint32),
+                ("largest", C.c_uint32), ("reserved", C.c_uint32), ("kernel_ms", C.c_double), ("density_ms", C.c_double)]
+
+
 class GreedyPhases(C.Structure):
     """hmk_greedy_phases: where the time of the last greedy call went (milliseconds)."""
     _fields_ = [(k, C.c_double) for k in ("plan_ms", "score_ms", "csr_ms", "wait_rows_ms", "phase1_ms", "precheck_ms", "exchange_ms",
@@ -247,6 +261,10 @@ def _load():
     L.hmk_representatives_shifted.argtypes = [vp, i32, i32, i32, i32] + rep_out
     L.hmk_representatives_from_edges.argtypes = [vp, p_u64, u64, i32, i32] + rep_out
     L.hmk_representatives_from_edges_dev.argtypes = [vp, vp, u64, i32, i32] + rep_out
+    den_out = [p_u32, p_u32, p_u32, C.POINTER(DensityLevel), C.POINTER(DensityStats)]
+    L.hmk_density_shifted.argtypes = [vp, i32, i32, i32, i32, i32] + den_out
+    L.hmk_density_from_edges.argtypes = [vp, p_u64, u64, i32, i32, i32] + den_out
+    L.hmk_density_from_edges_dev.argtypes = [vp, vp, u64, i32, i32, i32] + den_out
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("hmk_destroy", "hmk_last_error", "hmk_last_kernel_ms"):

@@ -117,6 +117,11 @@ GREEDY_LEVEL_DTYPE = np.dtype([("n_edges", np.uint64), ("status", np.int32), ("c
 REPRESENTATIVE_LEVEL_DTYPE = np.dtype([("n_edges", np.uint64), ("n_representatives", np.uint32), ("n_isolated", np.uint32),
                                        ("largest", np.uint32), ("n_rounds", np.uint32), ("reserved", np.uint32, (2,))])
 
+# hmk_density_level, one entry per threshold of a density call
+DENSITY_LEVEL_DTYPE = np.dtype([("n_edges", np.uint64), ("n_core", np.uint32), ("n_border", np.uint32), ("n_noise", np.uint32),
+                                ("n_clusters", np.uint32), ("largest", np.uint32), ("reserved", np.uint32)])
+DENSITY_NOISE = 0xFFFFFFFF   # HMK_DENSITY_NOISE: cluster and anchor of a noise sequence
+
 
 class Context:
     """1:1 wrapper of hmk_ctx.  device >= 0: HIP ordinal; -1: host-only."""
@@ -865,6 +870,50 @@ class Context:
         """hmk_representatives_from_edges_dev: the same with the packed edges in device memory, through the device kernels."""
         return self._representatives(lambda thr, hi, *out: N.lib.hmk_representatives_from_edges_dev(self._h, C.c_void_p(d_edges_ptr), int(n_edges), thr, hi, *out),
                                      threshold, threshold_hi, arrays, levels)
+
+    # -- density clustering: core, border and noise sequences ----------------------------------
+    def _density(self, call, threshold, threshold_hi, min_neighbors, arrays, levels):
+        """runs call(threshold, threshold_hi, min_neighbors, cluster, anchor, degree, levels, stats) -> (levels: structured array
+        DENSITY_LEVEL_DTYPE[n_levels] or None, cluster, degree, anchor: uint32 (n_levels, n) each, or None); statistics in
+        last_density_stats.  arrays: True, False, or one flag per returned array (cluster, degree, anchor)."""
+        thr = int(threshold)
+        hi = thr if threshold_hi is None else int(threshold_hi)
+        nl = min(max(hi - thr + 1, 1), 256)
+        want = (bool(arrays),) * 3 if isinstance(arrays, (bool, int)) else tuple(bool(a) for a in arrays)
+        cluster, degree, anchor = [np.zeros((nl, max(self.n, 1)), dtype=np.uint32) if w else None for w in want]
+        lv = np.zeros(nl, dtype=DENSITY_LEVEL_DTYPE) if levels else None
+        stats = N.DensityStats()
+        st = call(thr, hi, int(min_neighbors), *[_ptr(a, C.c_uint32) if a is not None else None for a in (cluster, anchor, degree)],
+                  lv.ctypes.data_as(C.POINTER(N.DensityLevel)) if levels else None, C.byref(stats))
+        if st:
+            self._raise(st)
+        self.last_density_stats = stats
+        out = [cluster, degree, anchor]
+        if self.n == 0:
+            out = [a[:, :0] if a is not None else None for a in out]
+        return (lv, *out)
+
+    def density_shifted(self, max_shift, shift_penalty, threshold, threshold_hi=None, min_neighbors=3, arrays=True, levels=True):
+        """hmk_density_shifted: density clustering (DBSCAN on the graph {ShiftedScorer score >= t}, independent of any order) of the
+        uploaded set at every t = threshold ... threshold_hi (None: threshold alone) from one scoring pass -> (levels, cluster,
+        degree, anchor); row t - threshold: degree[i] = i's neighbours; i is core iff degree[i] >= min_neighbors; cluster[i] = the
+        smallest core index of i's cluster (core-core edges only), for a border sequence its anchor's cluster, DENSITY_NOISE for
+        noise; anchor[i] = i for a core sequence, for a border one its core neighbour with the largest score (the smaller index
+        among equal scores), DENSITY_NOISE for noise.  arrays=False / levels=False pass NULL and return None."""
+        return self._density(lambda thr, hi, mn, *out: N.lib.hmk_density_shifted(self._h, int(max_shift), int(shift_penalty), thr, hi, mn, *out),
+                             threshold, threshold_hi, min_neighbors, arrays, levels)
+
+    def density_from_edges(self, edges, threshold, threshold_hi=None, min_neighbors=3, arrays=True, levels=True):
+        """hmk_density_from_edges: the same from packed edges (each unordered pair once; a pair given k times counts k times
+        towards both degrees), by the definition on the host (works on a host-only context)."""
+        edges = np.ascontiguousarray(edges, dtype=np.uint64)
+        return self._density(lambda thr, hi, mn, *out: N.lib.hmk_density_from_edges(self._h, _ptr(edges, C.c_uint64), edges.size, thr, hi, mn, *out),
+                             threshold, threshold_hi, min_neighbors, arrays, levels)
+
+    def density_from_edges_dev(self, d_edges_ptr, n_edges, threshold, threshold_hi=None, min_neighbors=3, arrays=True, levels=True):
+        """hmk_density_from_edges_dev: the same with the packed edges in device memory, through the device kernels."""
+        return self._density(lambda thr, hi, mn, *out: N.lib.hmk_density_from_edges_dev(self._h, C.c_void_p(d_edges_ptr), int(n_edges), thr, hi, mn, *out),
+                             threshold, threshold_hi, min_neighbors, arrays, levels)
 
     def greedy_phases(self):
         """hmk_greedy_last_phases: per-phase milliseconds of the last greedy_cluster / greedy_from_edges_dev call."""

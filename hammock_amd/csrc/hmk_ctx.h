@@ -3,7 +3,7 @@
 // buffers and their owners, streams), hmk_sizing.h (the sizing rules, pure functions), hmk_plan.cpp (the neighbour passes' planner),
 // hmk_pass.cpp (launching the passes; the pair and block probes), hmk_cluster.cpp (the single-device clustering calls, CSR pipeline,
 // row hand-over, second-loop driver), hmk_multi.cpp (the same calls on several devices), and one file per further call
-// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp, hmk_separation.cpp, hmk_sweep.cpp, hmk_representatives.cpp).  Not part of the public ABI.
+// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp, hmk_separation.cpp, hmk_sweep.cpp, hmk_representatives.cpp, hmk_density.cpp).  Not part of the public ABI.
 #ifndef HMK_CTX_H
 #define HMK_CTX_H
 #include <hip/hip_runtime_api.h>
@@ -99,6 +99,7 @@ enum {
     SB_SEP_TAB, SB_SEP_REC, SB_SEP_OUT,             // the separation of given clusters (hmk_separation.cpp): partner order + slot tables; per (segment, member) records; per member outputs
     SB_SWEEP_RUNS, SB_SWEEP_STATE,                  // the greedy sweep (hmk_sweep.cpp): the pass's whole edges by level, the top level first; histogram, run offsets, prefixes, flag (SweepState)
     SB_REP_STATE, SB_REP_VERT, SB_REP_LIVE,         // the representatives (hmk_representatives.cpp): the level's counters (RepState); the per-vertex arrays (RepVertex); the two live-edge buffers
+    SB_DEN_STATE, SB_DEN_VERT, SB_DEN_ROWS,         // density clustering (hmk_density.cpp): one record per level and the flag (DenState); the per-vertex arrays (DenVertex); the requested rows of a batch of levels
     SB_N
 };
 

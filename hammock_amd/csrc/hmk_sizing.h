@@ -66,5 +66,19 @@ inline SeparationSegments separation_segments(uint32_t nm, uint32_t forced_len) 
     return {len, (nm + len - 1) / len};
 }
 
+// The density call (hmk_density.cpp) keeps the requested rows (n_arrays of cluster, anchor, degree; 4 bytes per vertex and level) of
+// several levels on the device and brings them back with one copy per array, so that no level waits for the host: as many levels as
+// fit DENSITY_ROWS_BUDGET bytes, at least one, at most the call's n_levels.  21 levels of 10^6 vertices, all three arrays, are one
+// batch (252 MB); 256 levels of them are 22 batches.
+constexpr uint64_t DENSITY_ROWS_BUDGET = 256ull << 20;
+inline uint32_t density_rows_per_batch(uint32_t n, uint32_t n_arrays, uint32_t n_levels) {
+    const uint64_t level_bytes = (uint64_t)n * 4 * n_arrays;
+    if (level_bytes == 0) return std::max(n_levels, 1u);
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_levels, DENSITY_ROWS_BUDGET / level_bytes));
+}
+inline uint64_t density_rows_bytes(uint32_t n, uint32_t n_arrays, uint32_t per_batch) {
+    return std::max<uint64_t>((uint64_t)n * 4 * n_arrays * per_batch, 64);
+}
+
 } }  // namespace hmk::sizing
 #endif

@@ -150,6 +150,8 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "          hammock-hip align -i <clusters.tsv> -d <directory> [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [--device <int>]\n"
               << "          hammock-hip components -i <sequences> -d <directory> [-g <int>] [--scan_to <int>] [-f fasta|tab] [-m <file>] [-x <int>]\n"
               << "                      [-p <int>] [-l <labels>] [--device <int>]\n"
+              << "          hammock-hip density -i <sequences> -d <directory> [-g <int>] [--min_neighbors <int>] [--scan_to <int>] [--pick <int>]\n"
+              << "                      [-f fasta|tab] [-m <file>] [-x <int>] [-p <int>] [-l <labels>] [--device <int>]\n"
               << "          hammock-hip sweep -i <sequences> -d <directory> [-g <int>] [--scan_to <int>] [--pick <int>] [-f fasta|tab] [-m <file>]\n"
               << "                      [-x <int>] [-p <int>] [-R <order>] [-S <int>] [-l <labels>] [--initial_clusters_limit <int>] [--device <int>]\n"
               << "          hammock-hip representatives -i <sequences> -d <directory> [-g <int>] [--scan_to <int>] [-f fasta|tab] [-m <file>]\n"
@@ -176,8 +178,9 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "--database <file>\n\t(search) the reference sequences every query (-i) is scored against;\n\t(survey) score the input against these sequences instead of against itself\n\n"
               << "--best <int>\n\t(search) keep only the best 1..32 hits of each query; (assign, match) report the best 1..32 feasible clusters (default 1)\n\n"
               << "--clusters <file>\n\t(assign, continue, match) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv);\n\t(merge) a second cluster file: its clusters keep their ids, the -i file's are renumbered behind them\n\n"
-              << "--scan_to <int>\n\t(components) the last threshold of the scan: component_levels.tsv gets one line per threshold from -g to this one\n\t(at most 255 above -g; default: -g alone);\n\t(sweep) the last threshold of the sweep: greedy_levels.tsv gets one line per threshold from -g to this one;\n\t(representatives) the last threshold: representative_levels.tsv gets one line per threshold from -g to this one\n\n"
-              << "--pick <int>\n\t(sweep) the threshold of the sweep whose clustering is written as the stage-1 files (default: -g)\n\n"
+              << "--scan_to <int>\n\t(components) the last threshold of the scan: component_levels.tsv gets one line per threshold from -g to this one\n\t(at most 255 above -g; default: -g alone);\n\t(sweep) the last threshold of the sweep: greedy_levels.tsv gets one line per threshold from -g to this one;\n\t(representatives) the last threshold: representative_levels.tsv gets one line per threshold from -g to this one;\n\t(density) the last threshold: density_levels.tsv gets one line per threshold from -g to this one\n\n"
+              << "--pick <int>\n\t(sweep) the threshold of the sweep whose clustering is written as the stage-1 files (default: -g);\n\t(density) the threshold whose clusters are written as density_members.tsv and the stage-1 files (default: -g)\n\n"
+              << "--min_neighbors <int>\n\t(density) a sequence with at least this many neighbours (itself not counted) is core (default 3)\n\n"
               << "--skip_singletons\n\t(assign, match, merge) only clusters of more than one unique sequence are candidates;\n\t(check) clusters of one unique sequence are left out of cluster_linkage.tsv;\n\t(align) clusters of one unique sequence are left out of cluster_centers.tsv;\n\t(separation) clusters of one unique sequence are neither members nor candidates for the nearest cluster\n\n"
               << "--java_hashset <8|7|6>\n\t(clinkage, merge, split) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
 }
@@ -1632,6 +1635,119 @@ int runComponents(const std::vector<std::string> &args) {
     }
 }
 
+// `hammock-hip density -i X.fa -d dir [-g T] [--min_neighbors K] [--scan_to T2] [--pick P] [-x -p -m -f -l]`: density clustering
+// (DBSCAN on the neighbour graph {score >= t}, hmk_density_shifted) for every t = T ... T2 from one scoring pass: a sequence with at
+// least K neighbours is core, clusters are the components of the core sequences, a non-core neighbour of a core sequence is border
+// and joins its best core neighbour's cluster, the rest is noise.  Where `components` chains the motif families together over a few
+// weak bridges, this does not.  Sequences in load order and -x / -g / -p defaults as in components.  Writes density_levels.tsv (one
+// line per threshold), density_members.tsv (every sequence's kind, degree, cluster and anchor at --pick, default -g) and the stage-1
+// files with the clusters at --pick -- id = 1 + the smallest core load-order index, a noise sequence a cluster of its own with id =
+// 1 + its index; clusters of several sequences first in ascending id, then the single ones, members in load order -- so that they
+// load back through --clusters.
+int runDensity(const std::vector<std::string> &args) {
+    Options o;
+    parseCommonArgs(args, o);
+    parseModeArgs(args, o, -1);
+    bool havePick = false;
+    int pick = 0, minNeighbors = 3;
+    for (size_t i = 1; i + 1 < args.size(); i++) {
+        if (args[i] == "--pick") { pick = javaIntegerDecode(args[++i]); havePick = true; }
+        else if (args[i] == "--min_neighbors") minNeighbors = javaIntegerDecode(args[++i]);
+    }
+    if (minNeighbors < 0) throw CLIException("Error. --min_neighbors may not be negative.");
+    requireOneDevice(o, "density", "a density clustering");
+    requireInput(o);
+    requireFastaOrTab(o, "density");
+    makeOutputDirectory(o, o.parentDir);
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        ContextFuture contextReady = beginRun(o, logger, false);
+        logRunStart(logger, "density", args);
+        std::vector<std::string> labels;
+        if (o.haveLabels) labels = FileIOManager::splitChar(o.labelString, ',', true);
+        logger.logAndStderr("Loading input sequences...");
+        std::vector<UniqueSequencePtr> sequences = loadSequences(o, o.inputFileName);
+        logger.logAndStderr(std::to_string(sequences.size()) + " unique sequences loaded.");
+        if (o.haveLabels) sequences = filterSequencesForLabels(sequences, labels);
+        else labels = FileIOManager::getSortedLabels(sequences);
+        if (sequences.empty()) throw FileFormatException("Error. No sequences (with specified labels) to cluster.");
+        const SequenceListSummary summary = summariseSequences(sequences);
+        settleShiftAndThreshold(o, logger, summary, summary, summary, "Density clustering");
+        const int thr = o.sequenceClusteringThreshold, thrHi = o.haveScanTo ? o.scanTo : thr;
+        if (thrHi < thr || (long long)thrHi - thr > 255)
+            throw CLIException("Error. --scan_to may be the threshold (-g) " + std::to_string(thr) + " up to " + std::to_string((long long)thr + 255) + ".");
+        if (!havePick) pick = thr;
+        if (pick < thr || pick > thrHi)
+            throw CLIException("Error. --pick may be a threshold of the scan, " + std::to_string(thr) + " up to " + std::to_string(thrHi) + ".");
+        logger.logAndStderr("Parameters: max shift " + std::to_string(o.maxShift) + ", gap penalty " + std::to_string(o.shiftPenalty) + ", thresholds " +
+                            std::to_string(thr) + " to " + std::to_string(thrHi) + ", min neighbors " + std::to_string(minNeighbors) +
+                            ", members and stage-1 files at " + std::to_string(pick));
+
+        const size_t n = sequences.size(), nl = (size_t)(thrHi - thr) + 1, row = (size_t)(pick - thr) * n;
+        std::vector<uint32_t> cluster(nl * n), anchor(nl * n), degree(nl * n);
+        std::vector<hmk_density_level> levels(nl);
+        hmk_density_stats stats{};
+        logger.logAndStderr("Density clustering at " + std::to_string(nl) + " thresholds...");
+        const auto time0 = std::chrono::steady_clock::now();
+        {
+            const std::shared_ptr<NativeContext> nc = contextReady.get();
+            nc->setSequences(sequences, true);
+            const int st = hmk_density_shifted(nc->get(), o.maxShift, o.shiftPenalty, thr, thrHi, minNeighbors, cluster.data(), anchor.data(), degree.data(),
+                                               levels.data(), &stats);
+            if (st) nc->raise(st, nullptr);
+        }
+        logger.logAndStderr("Ready. Density clustering time: " + std::to_string(millisSince(time0)));
+        logger.logAndStderr("Pairs scored: " + std::to_string(stats.pairs_scored) + ", pairs at or above the threshold: " + std::to_string(stats.n_edges) +
+                            ", GPU scoring: " + std::to_string(stats.kernel_ms) + " ms, GPU density clustering: " + std::to_string(stats.density_ms) + " ms");
+        const hmk_density_level &at = levels[(size_t)(pick - thr)];
+        logger.logAndStderr("At threshold " + std::to_string(pick) + ": core " + std::to_string(at.n_core) + ", border " + std::to_string(at.n_border) +
+                            ", noise " + std::to_string(at.n_noise) + ", clusters " + std::to_string(at.n_clusters) + ", largest: " + std::to_string(at.largest));
+        logger.logAndStderr("Saving results to output files...");
+        const std::string levelsCsv = o.workingDirectory + "/density_levels.tsv";
+        {
+            std::ofstream out(levelsCsv);
+            if (!out) throw HammockException("cannot write " + levelsCsv);
+            out << "threshold\tedges\tcore\tborder\tnoise\tclusters\tlargest\n";
+            for (size_t l = 0; l < nl; l++)
+                out << thr + (int)l << '\t' << levels[l].n_edges << '\t' << levels[l].n_core << '\t' << levels[l].n_border << '\t' << levels[l].n_noise << '\t'
+                    << levels[l].n_clusters << '\t' << levels[l].largest << '\n';
+        }
+        // the level --pick: cluster ids as in the stage-1 files, the anchor as a sequence
+        const std::string membersCsv = o.workingDirectory + "/density_members.tsv";
+        {
+            std::ofstream out(membersCsv);
+            if (!out) throw HammockException("cannot write " + membersCsv);
+            out << "sequence\tkind\tdegree\tcluster\tanchor\n";
+            for (size_t i = 0; i < n; i++) {
+                const uint32_t c = cluster[row + i], a = anchor[row + i];
+                out << sequences[i]->getSequenceString() << '\t' << (c == HMK_DENSITY_NOISE ? "noise" : a == i ? "core" : "border") << '\t' << degree[row + i]
+                    << '\t' << (c == HMK_DENSITY_NOISE ? std::string("NA") : std::to_string(c + 1)) << '\t'
+                    << (a == HMK_DENSITY_NOISE ? std::string("NA") : sequences[a]->getSequenceString()) << '\n';
+            }
+        }
+        std::vector<std::vector<UniqueSequencePtr>> members(n);
+        for (size_t i = 0; i < n; i++) members[cluster[row + i] == HMK_DENSITY_NOISE ? i : cluster[row + i]].push_back(sequences[i]);
+        std::vector<ClusterPtr> result;
+        for (int multi = 1; multi >= 0; multi--)
+            for (size_t i = 0; i < n; i++)
+                if (!members[i].empty() && (members[i].size() > 1) == (multi == 1)) result.push_back(std::make_shared<Cluster>(members[i], (int)i + 1));
+        logger.logAndStderr("Resulting clusers at threshold " + std::to_string(pick) + ": " + std::to_string(result.size()));
+        const std::string seqCsv = o.workingDirectory + "/initial_clusters_sequences.tsv";
+        const std::string orderedCsv = o.workingDirectory + "/initial_clusters_sequences_original_order.tsv";
+        const std::string clustersCsv = o.workingDirectory + "/initial_clusters.tsv";
+        FileIOManager::saveInitialClusters(result, seqCsv, orderedCsv, clustersCsv, labels, sequences);
+        logger.logAndStderr("Density clustering by threshold in: " + levelsCsv);
+        logger.logAndStderr("Sequences, their kind, cluster and anchor in: " + membersCsv);
+        logger.logAndStderr("Clusters (noise as single sequences) in: " + clustersCsv);
+        logger.logAndStderr("and: " + seqCsv);
+        logger.logAndStderr("and: " + orderedCsv);
+        logger.logWithTime("Program successfully ended.");
+        return 0;
+    } catch (...) {
+        return reportRunError(logger, false);
+    }
+}
+
 // `hammock-hip sweep -i X.fa -d dir -g T --scan_to T2 [--pick P] [greedy's options]`: the greedy clustering at every threshold
 // t = T ... T2 from one scoring pass (hmk_greedy_sweep; LimitedGreedySequenceClusterer.java:22,39-69 once per threshold).  Input
 // loading, ordering and the defaults of -x, -g and --initial_clusters_limit are greedy's own.  Writes greedy_levels.tsv, one line per
@@ -2118,6 +2234,7 @@ int main(int argc, char **argv) {
         if (args[0] == "check") return runCheck(args);
         if (args[0] == "split") return runSplit(args);
         if (args[0] == "components") return runComponents(args);
+        if (args[0] == "density") return runDensity(args);
         if (args[0] == "sweep") return runSweep(args);
         if (args[0] == "representatives") return runRepresentatives(args);
         if (args[0] == "align") return runAlign(args);

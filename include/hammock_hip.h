@@ -781,6 +781,74 @@ int hmk_representatives_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64
                                        uint32_t *covered_by, uint32_t *nearest, int32_t *nearest_score,
                                        hmk_representative_level *levels, hmk_representatives_stats *stats);
 
+/* ---- density clustering: core, border and noise sequences ------------------------------- */
+
+#define HMK_DENSITY_NOISE 0xFFFFFFFFu   /* cluster[i] and anchor[i] of a noise sequence */
+
+typedef struct {
+    uint64_t n_edges;             /* edges given with score >= t (every entry of the list) */
+    uint32_t n_core;              /* sequences with at least min_neighbors neighbours at t */
+    uint32_t n_border;            /* not core, next to a core sequence */
+    uint32_t n_noise;             /* the rest: n_core + n_border + n_noise = n */
+    uint32_t n_clusters;          /* connected components of the core sequences under core-core edges */
+    uint32_t largest;             /* members of the largest cluster, core and border */
+    uint32_t reserved;
+} hmk_density_level;
+
+typedef struct {
+    uint64_t n_edges;             /* edges >= threshold */
+    uint64_t pairs_scored;        /* 0 for the _from_edges forms: nothing is scored */
+    uint32_t n_levels;            /* threshold_hi - threshold + 1 */
+    uint32_t min_neighbors;
+    uint32_t n_core, n_border, n_noise, n_clusters, largest;   /* at `threshold` */
+    uint32_t reserved;
+    double   kernel_ms;           /* the scoring pass, HIP events */
+    double   density_ms;          /* everything behind the pass on the device, the copies included, HIP events (0 for
+                                     hmk_density_from_edges) */
+} hmk_density_stats;
+
+/* Density clustering (DBSCAN on the similarity graph) of the hmk_set_sequences set at every t = threshold ... threshold_hi, from
+ * ONE scoring pass at `threshold`.  The graph at t is a ~ b iff ShiftedScorer(matrix, shift_penalty, max_shift).sequenceScore >= t,
+ * the graph of hmk_components_shifted.  Unlike DBSCAN proper the result does not depend on any order:
+ *   degree[l][i]            the edges >= t that touch i (i itself is not counted: min_neighbors = DBSCAN's minPts - 1)
+ *   core                    degree >= min_neighbors
+ *   cluster[l][i]           core: the smallest core index of i's connected component in the subgraph of the core sequences
+ *                           (core-core edges only); border: the cluster of its anchor; noise: HMK_DENSITY_NOISE
+ *   anchor[l][i]            core: i.  Border (not core, at least one core neighbour): the core neighbour with the largest score,
+ *                           among equal scores the smallest index.  Noise (everything else): HMK_DENSITY_NOISE
+ *   levels[l]               l = t - threshold; the arrays are [n_levels][n], each may be NULL, levels may be NULL
+ *   min_neighbors = 0       every sequence is core: cluster is `component` of hmk_components_shifted, n_clusters = n_components
+ *   checks                  HMK_ERR_BAD_ARG before the device is looked at (a host-only context answers them): min_neighbors < 0,
+ *                           threshold_hi < threshold, threshold_hi - threshold > 255, threshold_hi > 32767, all four outputs NULL
+ *                           with n > 0, an asymmetric matrix (as hmk_components_shifted).  Then the checks of
+ *                           hmk_neighbors_shifted at `threshold`.  Never HMK_ERR_CAPACITY (the call grows its own scratch).  No
+ *                           sequences: HMK_OK, zeroed levels.
+ * The pass is hmk_neighbors_shifted's (same plan slot, same kernels) into the context's edge buffer.  A range is dealt by the
+ * kernels of hmk_greedy_sweep into one run per level with the top level first, so that the edges >= t are a prefix; a single level
+ * reads the pass's segments where they lie.  As t falls, degrees, the core set and the set of core-core edges only grow: one
+ * union-find and one anchor key per sequence carry over from the top level down (k_density.hip).  Per level: the level's own edges
+ * add to the degrees; the sequences that turn core are marked; the link kernel reads the level's own edges and every older edge
+ * with an end that turned core at this level (both ends core: union; one: an atomic maximum into the other end's anchor key);
+ * labels and sizes follow.  No host synchronisation between levels; only the levels' block and the requested rows cross to the
+ * host.  On a hmk_create_multi context the call runs on the root device. */
+int hmk_density_shifted(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, int threshold_hi, int min_neighbors,
+                        uint32_t *cluster, uint32_t *anchor, uint32_t *degree, hmk_density_level *levels, hmk_density_stats *stats);
+
+/* The same from packed HMK_EDGE_* edges, by hmk_components_from_edges' contract: each unordered pair once, in either orientation
+ * and any order; edges below `threshold` are ignored, one above threshold_hi counts at every level (and keeps its score where
+ * anchors are compared); an index >= n or a self pair is HMK_ERR_BAD_ARG.  A pair given k times counts k times towards both ends'
+ * degrees (the host and the device form agree on it); for clusters and anchors repetition changes nothing else.  This is the
+ * definition written plainly on the host (degrees per level by counting, a sequential union-find over the core-core edges, one pass
+ * for the anchors): it works on a host-only context, and is the second implementation the device path is tested against.  No
+ * symmetry check: nothing is scored. */
+int hmk_density_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t n_edges, int threshold, int threshold_hi, int min_neighbors,
+                           uint32_t *cluster, uint32_t *anchor, uint32_t *degree, hmk_density_level *levels, hmk_density_stats *stats);
+
+/* The same with the edges in device memory (the context's device), through the kernels of hmk_density_shifted.  An index >= n or a
+ * self pair is found on the device, before any array is indexed with it: HMK_ERR_BAD_ARG. */
+int hmk_density_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n_edges, int threshold, int threshold_hi, int min_neighbors,
+                               uint32_t *cluster, uint32_t *anchor, uint32_t *degree, hmk_density_level *levels, hmk_density_stats *stats);
+
 /* ---- aligning given clusters around their medoids --------------------------------------- */
 
 typedef struct {
