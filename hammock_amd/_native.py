@@ -23,6 +23,8 @@ HMK_ERR_NO_SEQUENCES = 7
 HMK_EDGE_SHARDS = 64
 HMK_MAX_LEN = 32
 HMK_SURVEY_MAX_BINS = 1024
+HMK_PROFILE_SYMBOLS = 21
+HMK_PROFILE_MAX_WIDTH = 96
 
 # every symbol include/hammock_hip.h declares
 SYMBOLS = [
@@ -40,6 +42,7 @@ SYMBOLS = [
     "hmk_greedy_sweep", "hmk_greedy_sweep_from_edges", "hmk_greedy_sweep_from_edges_dev",
     "hmk_representatives_shifted", "hmk_representatives_from_edges", "hmk_representatives_from_edges_dev",
     "hmk_density_shifted", "hmk_density_from_edges", "hmk_density_from_edges_dev",
+    "hmk_cluster_profile",
 ]
 
 
@@ -122,6 +125,20 @@ class SeparationStats(C.Structure):
     """hmk_separation_stats"""
     _fields_ = [("pairs_scored", C.c_uint64), ("n_misplaced", C.c_uint32), ("n_multi", C.c_uint32), ("n_segments", C.c_uint32),
                 ("launches", C.c_uint32), ("reserved", C.c_uint32), ("kernel_ms", C.c_double)]
+
+
+class ProfileParams(C.Structure):
+    """hmk_profile_params"""
+    _fields_ = [("min_ic", C.c_double), ("max_gap_proportion", C.c_double), ("min_conserved_positions", C.c_int32),
+                ("allow_inner_gaps", C.c_int32), ("beta", C.c_double), ("sigma", C.c_double), ("scale", C.c_double),
+                ("frequency", C.c_double * 400), ("background", C.c_double * 20)]
+
+
+class ProfileStats(C.Structure):
+    """hmk_profile_stats"""
+    _fields_ = [("columns", C.c_uint64), ("n_multi", C.c_uint32), ("omitted", C.c_uint32), ("small_members", C.c_uint32),
+                ("large_chunks", C.c_uint32), ("launches", C.c_uint32), ("reserved", C.c_uint32), ("system_kld_match", C.c_double),
+                ("system_kld_all", C.c_double), ("kernel_ms", C.c_double)]
 
 
 class GreedyLevel(C.Structure):
@@ -265,6 +282,9 @@ def _load():
     L.hmk_density_shifted.argtypes = [vp, i32, i32, i32, i32, i32] + den_out
     L.hmk_density_from_edges.argtypes = [vp, p_u64, u64, i32, i32, i32] + den_out
     L.hmk_density_from_edges_dev.argtypes = [vp, vp, u64, i32, i32, i32] + den_out
+    p_f64 = C.POINTER(C.c_double)
+    L.hmk_cluster_profile.argtypes = [vp, u32, u32, p_u32, u32, p_u32, C.POINTER(ProfileParams), p_u32, p_u32, p_u32, p_u8, p_f64, p_f64,
+                                      p_u64, u64, p_u32, p_f64, p_u8, p_f64, p_f64, C.POINTER(ProfileStats)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("hmk_destroy", "hmk_last_error", "hmk_last_kernel_ms"):

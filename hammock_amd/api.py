@@ -103,6 +103,79 @@ def aligned_rows(seqs, column, width_of_slot):
     return rows
 
 
+def load_frequency_matrix(path):
+    """A frequency matrix in the text format FileIOManager.loadFrequencyMatrix reads (FileIOManager.java:90-118): lines starting
+    with '#' are comments, one header line of letters, then one tab-separated row of numbers per letter, in the header's order ->
+    (frequency float64[20, 20] in the order of AMINO_ACIDS, [row letter j][column letter i]: what hmk_profile_params.frequency
+    takes, and the header's letters as a string, which a background file follows)."""
+    letters, rows = None, []
+    with open(path) as fh:
+        for raw in fh:
+            line = raw.rstrip("\r\n")
+            if line.startswith("#") or not line.strip():
+                continue
+            if letters is None:
+                letters = [s.strip()[:1].upper() for s in line.split("\t")]
+                continue
+            try:
+                rows.append([float(s) for s in line.split("\t")])
+            except ValueError:
+                raise FileFormatException(f"{path}: a row of the frequency matrix holds something that is not a number")
+    if letters is None or sorted(letters) != sorted(AMINO_ACIDS[:20]):
+        raise FileFormatException(f"{path}: the header line must name each of the 20 amino acids {AMINO_ACIDS[:20]} once")
+    if len(rows) != 20 or any(len(r) != 20 for r in rows):
+        raise FileFormatException(f"{path}: 20 rows of 20 numbers are expected after the header")
+    pos = [_NAME_TO_NUM[c] for c in letters]
+    freq = np.zeros((20, 20), dtype=np.float64)
+    freq[np.ix_(pos, pos)] = np.asarray(rows, dtype=np.float64)
+    return freq, "".join(letters)
+
+
+def load_background(path, letters=AMINO_ACIDS[:20]):
+    """One line of 20 numbers (tabs or blanks between them, '#' comment lines before it) in the order of `letters` -- the
+    frequency file's header -> float64[20] in the order of AMINO_ACIDS."""
+    with open(path) as fh:
+        lines = [ln for ln in (raw.strip() for raw in fh) if ln and not ln.startswith("#")]
+    try:
+        values = [float(s) for s in lines[0].split()] if len(lines) == 1 else []
+    except ValueError:
+        values = []
+    if len(values) != 20 or len(letters) != 20:
+        raise FileFormatException(f"{path}: one line of 20 numbers is expected")
+    bg = np.zeros(20, dtype=np.float64)
+    bg[[_NAME_TO_NUM[c] for c in letters]] = values
+    return bg
+
+
+def profile_params(frequency, background=None, min_ic=1.2, max_gap_proportion=0.2, min_conserved_positions=0, allow_inner_gaps=False,
+                   beta=200.0, sigma=10.0, scale=2.88539):
+    """hmk_profile_params.  The defaults are the reference's (Hammock.minIc, maxGapProportion; Statistics.java:21-23) but for the
+    background: None stands for 0.05 throughout, the equiprobable model the information content uses.  The reference's own table is
+    Statistics.java:25-28; pass it to get Hammock's numbers."""
+    P = N.ProfileParams()
+    P.min_ic, P.max_gap_proportion = float(min_ic), float(max_gap_proportion)
+    P.min_conserved_positions, P.allow_inner_gaps = int(min_conserved_positions), 1 if allow_inner_gaps else 0
+    P.beta, P.sigma, P.scale = float(beta), float(sigma), float(scale)
+    f = np.ascontiguousarray(np.asarray(frequency, dtype=np.float64).reshape(400))
+    b = np.full(20, 0.05) if background is None else np.ascontiguousarray(np.asarray(background, dtype=np.float64).reshape(20))
+    P.frequency[:] = f.tolist()
+    P.background[:] = b.tolist()
+    return P
+
+
+class ProfileResult:
+    """What Context.cluster_profile returns (hmk_cluster_profile): per slot width, n_conserved, n_match, passes, kld_match_mean,
+    kld_all_mean, col_start[n_clusters + 1]; per column counts[columns, 21], ic, col_flags (None where not asked for); per member
+    kld_match, kld_all; stats (hmk_profile_stats)."""
+    __slots__ = ("width", "n_conserved", "n_match", "passes", "kld_match_mean", "kld_all_mean", "col_start", "counts", "ic", "col_flags",
+                 "kld_match", "kld_all", "stats")
+
+    def match_string(self, c):
+        """slot c's match states, 'M' per match-state column and '.' per other one"""
+        a, b = int(self.col_start[c]), int(self.col_start[c + 1])
+        return "".join("M" if f & 2 else "." for f in self.col_flags[a:b])
+
+
 # hmk_component_level, one entry per threshold of a components call
 LEVEL_DTYPE = np.dtype([("n_edges", np.uint64), ("n_components", np.uint32), ("n_singletons", np.uint32), ("largest", np.uint32),
                         ("reserved", np.uint32)])
@@ -625,6 +698,66 @@ class Context:
             self._raise(st)
         self.last_align_stats = stats
         return (center[:ncl], center_sum[:ncl], width[:ncl], member_sum[:nm] if sums else None, center_score[:nm], shift[:nm], column[:nm])
+
+    def cluster_profile(self, r0, r1, member_cluster, n_clusters, column, params, counts=True, ic=True, flags=True, col_capacity=None):
+        """hmk_cluster_profile: what the reference reads from a cluster's alignment, for given clusters (members [r0, r1), member r
+        in slot member_cluster[r - r0]) under the placement column[r - r0] -- cluster_align_shifted's column, or any ungapped
+        placement -> ProfileResult.  params: profile_params(...).  counts / ic / flags = False: that per-column array is not
+        fetched.  col_capacity=None sizes the per-column arrays from the call's own answer (a refused first call that touches no
+        device); a number is passed on as it is, and BufferError then carries the needed count in .needed."""
+        mc, _ = self._merge_args(r0, r1, member_cluster, None)
+        ncl, nm = int(n_clusters), mc.size
+        col = np.ascontiguousarray(np.asarray(column, dtype=np.int64).ravel())
+        if col.size != nm:
+            raise ValueError(f"column has {col.size} entries for the {nm} members [r0, r1)")
+        if (col < 0).any() or (col > 0xFFFFFFFF).any():
+            raise ValueError("column holds values outside uint32")
+        col = col.astype(np.uint32)
+        R = ProfileResult()
+        R.width = np.zeros(max(ncl, 1), dtype=np.uint32)
+        R.n_conserved = np.zeros(max(ncl, 1), dtype=np.uint32)
+        R.n_match = np.zeros(max(ncl, 1), dtype=np.uint32)
+        R.passes = np.zeros(max(ncl, 1), dtype=np.uint8)
+        R.kld_match_mean = np.zeros(max(ncl, 1), dtype=np.float64)
+        R.kld_all_mean = np.zeros(max(ncl, 1), dtype=np.float64)
+        R.col_start = np.zeros(ncl + 1, dtype=np.uint64)
+        R.kld_match = np.zeros(max(nm, 1), dtype=np.float64)
+        R.kld_all = np.zeros(max(nm, 1), dtype=np.float64)
+        stats = N.ProfileStats()
+        want = counts or ic or flags
+
+        def call(cap):
+            R.counts = np.zeros((max(cap, 1), N.HMK_PROFILE_SYMBOLS), dtype=np.uint32) if counts else None
+            R.ic = np.zeros(max(cap, 1), dtype=np.float64) if ic else None
+            R.col_flags = np.zeros(max(cap, 1), dtype=np.uint8) if flags else None
+            return N.lib.hmk_cluster_profile(self._h, int(r0), int(r1), _ptr(mc, C.c_uint32), ncl, _ptr(col, C.c_uint32), C.byref(params),
+                                             _ptr(R.width, C.c_uint32), _ptr(R.n_conserved, C.c_uint32), _ptr(R.n_match, C.c_uint32),
+                                             _ptr(R.passes, C.c_uint8), _ptr(R.kld_match_mean, C.c_double), _ptr(R.kld_all_mean, C.c_double),
+                                             _ptr(R.col_start, C.c_uint64), cap, _ptr(R.counts, C.c_uint32) if counts else None,
+                                             _ptr(R.ic, C.c_double) if ic else None, _ptr(R.col_flags, C.c_uint8) if flags else None,
+                                             _ptr(R.kld_match, C.c_double), _ptr(R.kld_all, C.c_double), C.byref(stats))
+
+        st = call(int(col_capacity) if col_capacity is not None else 0)
+        if st == N.HMK_ERR_CAPACITY and col_capacity is None and want:
+            st = call(int(stats.columns))
+        if st == N.HMK_ERR_CAPACITY:
+            try:
+                self._raise(st)
+            except BufferError as e:
+                e.needed = int(stats.columns)
+                raise
+        if st:
+            self._raise(st)
+        ncols = int(stats.columns)
+        for name in ("width", "n_conserved", "n_match", "passes", "kld_match_mean", "kld_all_mean"):
+            setattr(R, name, getattr(R, name)[:ncl])
+        R.kld_match, R.kld_all = R.kld_match[:nm], R.kld_all[:nm]
+        R.counts = R.counts[:ncols] if counts else None
+        R.ic = R.ic[:ncols] if ic else None
+        R.col_flags = R.col_flags[:ncols] if flags else None
+        R.stats = stats
+        self.last_profile_stats = stats
+        return R
 
     def score_survey_shifted(self, q0, q1, r0, r1, max_shift, shift_penalty, threshold, score_lo=None, n_bins=0, rows=True):
         """hmk_score_survey_shifted: the pair scores of the triangle inside one range ([q0, q1) == [r0, r1), seq1 = the larger index) or

@@ -56,6 +56,7 @@ void Switches::read() {
     test_grid_cap = std::max(0, num("HMK_TEST_GRID_CAP", 0));
     set_test_grid_cap(test_grid_cap);
     test_separation_segment = std::max(0, num("HMK_TEST_SEPARATION_SEGMENT", 0));
+    profile_large_min = std::max(0, num("HMK_PROFILE_LARGE_MIN", 0));
 }
 void refresh_switches(hmk_ctx *ctx) {
     ctx->sw.read();

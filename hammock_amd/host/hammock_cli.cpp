@@ -148,6 +148,9 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "          hammock-hip split -i <clusters.tsv> -d <directory> [-m <file>] [-x <int>] [-p <int>] [-g <int>] [--java_hashset <int>]\n"
               << "                      [--device <int>]\n"
               << "          hammock-hip align -i <clusters.tsv> -d <directory> [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [--device <int>]\n"
+              << "          hammock-hip profile -i <clusters.tsv> -d <directory> --frequency_matrix <file> [--background <file>] [--min_ic <float>]\n"
+              << "                      [--max_gap_proportion <float>] [--min_conserved_positions <int>] [--max_inner_gaps <int>] [--skip_singletons]\n"
+              << "                      [-m <file>] [-x <int>] [-p <int>] [--device <int>]\n"
               << "          hammock-hip components -i <sequences> -d <directory> [-g <int>] [--scan_to <int>] [-f fasta|tab] [-m <file>] [-x <int>]\n"
               << "                      [-p <int>] [-l <labels>] [--device <int>]\n"
               << "          hammock-hip density -i <sequences> -d <directory> [-g <int>] [--min_neighbors <int>] [--scan_to <int>] [--pick <int>]\n"
@@ -181,7 +184,13 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "--scan_to <int>\n\t(components) the last threshold of the scan: component_levels.tsv gets one line per threshold from -g to this one\n\t(at most 255 above -g; default: -g alone);\n\t(sweep) the last threshold of the sweep: greedy_levels.tsv gets one line per threshold from -g to this one;\n\t(representatives) the last threshold: representative_levels.tsv gets one line per threshold from -g to this one;\n\t(density) the last threshold: density_levels.tsv gets one line per threshold from -g to this one\n\n"
               << "--pick <int>\n\t(sweep) the threshold of the sweep whose clustering is written as the stage-1 files (default: -g);\n\t(density) the threshold whose clusters are written as density_members.tsv and the stage-1 files (default: -g)\n\n"
               << "--min_neighbors <int>\n\t(density) a sequence with at least this many neighbours (itself not counted) is core (default 3)\n\n"
-              << "--skip_singletons\n\t(assign, match, merge) only clusters of more than one unique sequence are candidates;\n\t(check) clusters of one unique sequence are left out of cluster_linkage.tsv;\n\t(align) clusters of one unique sequence are left out of cluster_centers.tsv;\n\t(separation) clusters of one unique sequence are neither members nor candidates for the nearest cluster\n\n"
+              << "--frequency_matrix <file>\n\t(profile) required: a row-normalised frequency matrix q_ij in the format of Hammock's settings/misc/blosum62.freq_rownorm\n\t('#' comment lines, one header line of letters, tab-separated rows); hammock-hip ships no such table\n\n"
+              << "--background <file>\n\t(profile) one line of 20 background probabilities in the letter order of the frequency matrix file (default: 0.05 throughout,\n\tthe equiprobable model the information content uses).  Hammock's own table is the array at Statistics.java:25-28: pass it in a file\n\tto get Hammock's KLD numbers\n\n"
+              << "-k, --min_ic <float>\n\t(profile) minimal information content of a conserved MSA position (default 1.2)\n\n"
+              << "-y, --max_gap_proportion <float [0, 1]>\n\t(profile) maximal proportion of gaps in a conserved MSA position (default 0.2)\n\n"
+              << "-h, --min_conserved_positions <int>\n\t(profile) a cluster passes with at least this many conserved positions (default: a third of the mean sequence length)\n\n"
+              << "-u, --max_inner_gaps <int>\n\t(profile) above 0, non-match positions may lie between match states (default 0)\n\n"
+              << "--skip_singletons\n\t(assign, match, merge) only clusters of more than one unique sequence are candidates;\n\t(check) clusters of one unique sequence are left out of cluster_linkage.tsv;\n\t(align, profile) clusters of one unique sequence are left out of cluster_centers.tsv (profile: and of cluster_profiles.tsv,\n\tposition_profiles.tsv and member_kld.tsv);\n\t(separation) clusters of one unique sequence are neither members nor candidates for the nearest cluster\n\n"
               << "--java_hashset <8|7|6>\n\t(clinkage, merge, split) whose java.util.HashSet iteration order picks the chain starts and orders the result: 8 = Java 8 and\n\tlater (default), 7 = JDK 7u6 and later updates of 7, 6 = JDK 6 and JDK 7 before 7u6\n\n";
 }
 
@@ -1360,20 +1369,128 @@ int runSplit(const std::vector<std::string> &args) {
 //   cluster_centers.tsv              cluster_id, size (unique sequences), center (the medoid's string), center_sum, width; clusters
 //                                    in file order (--skip_singletons leaves clusters of one unique sequence out)
 // Exit codes as check: a cluster file the loader rejects is 2.
-int runAlign(const std::vector<std::string> &args) {
+//
+// `hammock-hip profile -i clusters.tsv -d dir --frequency_matrix F [--background B] [-k/--min_ic 1.2] [-y/--max_gap_proportion 0.2]
+// [-h/--min_conserved_positions n] [-u/--max_inner_gaps 0] [--skip_singletons]` aligns as align does, with the same scorer options,
+// then reads the alignments as the reference reads Clustal's (hmk_cluster_profile): it writes what align writes, and in addition
+//   cluster_profiles.tsv             cluster_id, size, width, conserved, match_states (a string of M / .), passes, kld_match_mean,
+//                                    kld_all_mean; clusters in file order
+//   position_profiles.tsv            cluster_id, column (from 1), gaps, ic, flags (bit 0 conserved, bit 1 match state), the 20 counts
+//   member_kld.tsv                   cluster_id, sequence, kld_match, kld_all; members in the clusters' member order as loaded
+// and logs the two "Final system KLD over ..." lines of Hammock.java:696-697.  Doubles are written with %.17g.  --skip_singletons
+// leaves the clusters of one unique sequence out of all three.  -h defaults to what Hammock.java:1448-1452 computes; -u above 0
+// allows inner gaps (:1337-1341).  A frequency or background file that cannot be read as such is 2, as a bad cluster file.
+struct ProfileOptions {
+    std::string frequencyFile, backgroundFile;
+    bool haveFrequency = false, haveBackground = false, haveMinConserved = false;
+    double minIc = 1.2, maxGapProportion = 0.2;   // Hammock.java: minIc, maxGapProportion
+    int minConservedPositions = 0, maxInnerGaps = 0;
+};
+
+double parseDoubleArg(const std::string &v) {  // Double.parseDouble(args[i + 1].trim())
+    const std::string t = FileIOManager::trim(v);
+    size_t used = 0;
+    double d = 0;
+    try { d = std::stod(t, &used); } catch (const std::exception &) { used = std::string::npos; }
+    if (t.empty() || used != t.size()) throw HammockException("NumberFormatException: For input string: \"" + v + "\"");
+    return d;
+}
+
+ProfileOptions parseProfileArgs(const std::vector<std::string> &args) {  // Hammock.java:1099-1140
+    ProfileOptions po;
+    for (size_t i = 1; i + 1 < args.size(); i++) {
+        const std::string &a = args[i];
+        if (a == "--frequency_matrix") { po.frequencyFile = args[++i]; po.haveFrequency = true; }
+        else if (a == "--background") { po.backgroundFile = args[++i]; po.haveBackground = true; }
+        else if (a == "-k" || a == "--min_ic") po.minIc = parseDoubleArg(args[++i]);
+        else if (a == "-y" || a == "--max_gap_proportion") po.maxGapProportion = parseDoubleArg(args[++i]);
+        else if (a == "-h" || a == "--min_conserved_positions") { po.minConservedPositions = javaIntegerDecode(FileIOManager::trim(args[++i])); po.haveMinConserved = true; }
+        else if (a == "-u" || a == "--max_inner_gaps") po.maxInnerGaps = javaIntegerDecode(args[++i]);
+    }
+    if (!po.haveFrequency) throw CLIException("Error. Parameter frequency matrix (--frequency_matrix) missing with no default.");
+    return po;
+}
+
+// A frequency matrix as FileIOManager.loadFrequencyMatrix reads it (FileIOManager.java:90-118) into hmk_profile_params.frequency
+// ([row letter j][column letter i], in the alphabet's order) -> the header's letters; then the background, one line of 20 numbers in
+// that letter order (0.05 throughout without a file)
+void loadProfileTables(const ProfileOptions &po, hmk_profile_params &P) {
+    std::vector<int> letters;
+    std::vector<std::vector<double>> rows;
+    bool haveHeader = false;
+    auto numbers = [](const std::vector<std::string> &parts, const std::string &file) {
+        std::vector<double> v;
+        for (const std::string &s : parts) {
+            size_t used = 0;
+            double d = 0;
+            try { d = std::stod(s, &used); } catch (const std::exception &) { used = std::string::npos; }
+            if (used != s.size()) throw FileFormatException("Error in file: " + file + ". \"" + s + "\" is not a number.");
+            v.push_back(d);
+        }
+        return v;
+    };
+    for (const std::string &raw : FileIOManager::readLines(po.frequencyFile)) {
+        if (!raw.empty() && raw[0] == '#') continue;
+        const std::vector<std::string> parts = FileIOManager::splitWhitespace(raw);
+        if (parts.empty()) continue;
+        if (!haveHeader) {
+            haveHeader = true;
+            for (const std::string &s : parts) {
+                const char *f = std::strchr(AMINO_ACIDS, (char)std::toupper((unsigned char)s[0]));
+                letters.push_back(f && *f ? (int)(f - AMINO_ACIDS) : 99);
+            }
+            continue;
+        }
+        rows.push_back(numbers(parts, po.frequencyFile));
+    }
+    std::vector<int> sorted = letters;
+    std::sort(sorted.begin(), sorted.end());
+    bool ok = letters.size() == 20 && rows.size() == 20;
+    for (int k = 0; ok && k < 20; k++) ok = sorted[k] == k && rows[k].size() == 20;
+    if (!ok)
+        throw FileFormatException("Error in frequency matrix file: " + po.frequencyFile + ". A header line naming each of the 20 amino acids once "
+                                  "and 20 rows of 20 numbers are expected.");
+    for (int j = 0; j < 20; j++)
+        for (int i = 0; i < 20; i++) P.frequency[letters[j] * 20 + letters[i]] = rows[j][i];
+    for (int k = 0; k < 20; k++) P.background[k] = 0.05;
+    if (po.haveBackground) {
+        std::vector<std::vector<double>> lines;
+        for (const std::string &raw : FileIOManager::readLines(po.backgroundFile)) {
+            if (!raw.empty() && raw[0] == '#') continue;
+            const std::vector<std::string> parts = FileIOManager::splitWhitespace(raw);
+            if (!parts.empty()) lines.push_back(numbers(parts, po.backgroundFile));
+        }
+        if (lines.size() != 1 || lines[0].size() != 20)
+            throw FileFormatException("Error in background file: " + po.backgroundFile + ". One line of 20 numbers is expected.");
+        for (int k = 0; k < 20; k++) P.background[letters[k]] = lines[0][k];
+    }
+}
+
+std::string g17(double v) {
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "%.17g", v);
+    return buf;
+}
+
+int runAlign(const std::vector<std::string> &args, bool profile = false) {
     Options o;
     parseCommonArgs(args, o);
     parseModeArgs(args, o, -1);
-    requireOneDevice(o, "align", "an alignment");
+    const std::string mode = profile ? "profile" : "align";
+    requireOneDevice(o, mode, profile ? "a profile" : "an alignment");
     requireInput(o);
+    ProfileOptions po;
+    if (profile) po = parseProfileArgs(args);
     makeOutputDirectory(o, o.parentDir);
     Logger logger(o.workingDirectory + "/run.log", false);
     try {
         ContextFuture contextReady = beginRun(o, logger, false);
-        logRunStart(logger, "align", args);
+        logRunStart(logger, mode, args);
         logger.logAndStderr("Loading clusters...");
         MergeInput in;
+        hmk_profile_params params{};
         try {
+            if (profile) loadProfileTables(po, params);
             in = loadMergeInput(o.inputFileName, std::string());
             if (in.clusters.empty()) throw FileFormatException("Error. The cluster file holds no clusters.");
         } catch (const FileFormatException &e) {
@@ -1394,7 +1511,25 @@ int runAlign(const std::vector<std::string> &args) {
         std::vector<int64_t> centerSum(ncl);
         std::vector<int32_t> centerScore(n), shift(n);
         hmk_align_stats stats{};
-        logger.logAndStderr("Aligning...");
+        hmk_profile_stats pstats{};
+        std::vector<uint32_t> nConserved, nMatch, counts;
+        std::vector<uint8_t> passes, colFlags;
+        std::vector<double> kldMatchMean, kldAllMean, ic, kldMatch, kldAll;
+        std::vector<uint64_t> colStart;
+        if (profile) {
+            if (!po.haveMinConserved) {                                                               // Hammock.java:524-527, :1448-1452
+                po.minConservedPositions = (int)javaRound(summary.meanLength() / 3);
+                logger.logAndStderr("Minimal number of match states not set. Setting automatically to: " + std::to_string(po.minConservedPositions));
+            }
+            params.min_ic = po.minIc;
+            params.max_gap_proportion = po.maxGapProportion;
+            params.min_conserved_positions = po.minConservedPositions;
+            params.allow_inner_gaps = po.maxInnerGaps > 0 ? 1 : 0;                                    // :1337-1341
+            params.beta = 200;                                                                        // Statistics.java:21-23
+            params.sigma = 10;
+            params.scale = 2.88539;
+        }
+        logger.logAndStderr(profile ? "Aligning and profiling..." : "Aligning...");
         const auto time0 = std::chrono::steady_clock::now();
         {
             const std::shared_ptr<NativeContext> nc = contextReady.get();
@@ -1402,10 +1537,32 @@ int runAlign(const std::vector<std::string> &args) {
             const int st = hmk_cluster_align_shifted(nc->get(), 0, n, cand.memberCluster.data(), ncl, o.maxShift, o.shiftPenalty, center.data(),
                                                      centerSum.data(), width.data(), nullptr, centerScore.data(), shift.data(), column.data(), &stats);
             if (st) nc->raise(st, nullptr);
+            if (profile) {   // the same context, the sequences already there: the alignment's columns are the placement
+                uint64_t columns = 0;
+                for (uint32_t c = 0; c < ncl; c++) columns += width[c];
+                nConserved.resize(ncl); nMatch.resize(ncl); passes.resize(ncl); kldMatchMean.resize(ncl); kldAllMean.resize(ncl);
+                colStart.resize((size_t)ncl + 1); kldMatch.resize(n); kldAll.resize(n);
+                counts.resize(columns * HMK_PROFILE_SYMBOLS); ic.resize(columns); colFlags.resize(columns);
+                std::vector<uint32_t> profileWidth(ncl);
+                const int ps = hmk_cluster_profile(nc->get(), 0, n, cand.memberCluster.data(), ncl, column.data(), &params, profileWidth.data(),
+                                                   nConserved.data(), nMatch.data(), passes.data(), kldMatchMean.data(), kldAllMean.data(),
+                                                   colStart.data(), columns, counts.data(), ic.data(), colFlags.data(), kldMatch.data(),
+                                                   kldAll.data(), &pstats);
+                if (ps) nc->raise(ps, nullptr);
+                if (profileWidth != width) throw HammockException("the profile's widths differ from the alignment's");
+            }
         }
         logger.logAndStderr("Ready. Align time: " + std::to_string(millisSince(time0)));
         logger.logAndStderr("Clusters of more than one sequence: " + std::to_string(stats.n_multi) + ", pairs scored: " + std::to_string(stats.pairs_scored) +
                             ", widest alignment: " + std::to_string(stats.max_width) + ", GPU kernels: " + std::to_string(stats.kernel_ms) + " ms");
+        if (profile) {
+            logger.logAndStderr("Profile columns: " + std::to_string(pstats.columns) + ", GPU kernels: " + std::to_string(pstats.kernel_ms) + " ms");
+            logger.logAndStderr("\nCalculating KLD...");                                             // Hammock.java:681-697
+            if (pstats.omitted > 0)
+                logger.logAndStderr(std::to_string(pstats.omitted) + " clusters omitted from KLD calculation because each of them only contains a single unique sequence.");
+            logger.logAndStderr("Final system KLD over match state MSA positions: " + g17(pstats.system_kld_match));
+            logger.logAndStderr("Final system KLD over all MSA positions: " + g17(pstats.system_kld_all));
+        }
         logger.logAndStderr("Saving results to output files...");
         std::unordered_map<const UniqueSequence *, std::string> rows;
         rows.reserve(n);
@@ -1441,6 +1598,40 @@ int runAlign(const std::vector<std::string> &args) {
         logger.logAndStderr("Aligned cluster file in: " + seqCsv);
         logger.logAndStderr("Alignments in: " + msaDir);
         logger.logAndStderr("Centres in: " + centersCsv);
+        if (profile) {
+            const std::string clustersTsv = o.workingDirectory + "/cluster_profiles.tsv", positionsTsv = o.workingDirectory + "/position_profiles.tsv",
+                              membersTsv = o.workingDirectory + "/member_kld.tsv";
+            std::ofstream cf(clustersTsv), pf(positionsTsv), mf(membersTsv);
+            if (!cf || !pf || !mf) throw HammockException("cannot write the profile files in " + o.workingDirectory);
+            cf << "cluster_id\tsize\twidth\tconserved\tmatch_states\tpasses\tkld_match_mean\tkld_all_mean\n";
+            pf << "cluster_id\tcolumn\tgaps\tic\tflags";
+            for (int a = 0; a < 20; a++) pf << '\t' << AMINO_ACIDS[a];
+            pf << '\n';
+            mf << "cluster_id\tsequence\tkld_match\tkld_all\n";
+            uint32_t k = 0;
+            for (uint32_t c = 0; c < ncl; c++) {
+                const Cluster &cl = *clusters[c];
+                const uint32_t s = (uint32_t)cl.getUniqueSize();
+                if (s > 1 || !o.skipSingletons) {
+                    std::string states;
+                    for (uint64_t g = colStart[c]; g < colStart[c + 1]; g++) states.push_back(colFlags[g] & 2 ? 'M' : '.');
+                    cf << cl.getId() << '\t' << s << '\t' << width[c] << '\t' << nConserved[c] << '\t' << states << '\t' << (int)passes[c] << '\t'
+                       << g17(kldMatchMean[c]) << '\t' << g17(kldAllMean[c]) << '\n';
+                    for (uint64_t g = colStart[c]; g < colStart[c + 1]; g++) {
+                        const uint32_t *cnt = counts.data() + g * HMK_PROFILE_SYMBOLS;
+                        pf << cl.getId() << '\t' << g - colStart[c] + 1 << '\t' << cnt[20] << '\t' << g17(ic[g]) << '\t' << (int)colFlags[g];
+                        for (int a = 0; a < 20; a++) pf << '\t' << cnt[a];
+                        pf << '\n';
+                    }
+                    for (uint32_t t = 0; t < s; t++)
+                        mf << cl.getId() << '\t' << upload[k + t]->getSequenceString() << '\t' << g17(kldMatch[k + t]) << '\t' << g17(kldAll[k + t]) << '\n';
+                }
+                k += s;
+            }
+            logger.logAndStderr("Cluster profiles in: " + clustersTsv);
+            logger.logAndStderr("Position profiles in: " + positionsTsv);
+            logger.logAndStderr("Member KLDs in: " + membersTsv);
+        }
         logger.logWithTime("Program successfully ended.");
         return 0;
     } catch (...) {
@@ -2238,6 +2429,7 @@ int main(int argc, char **argv) {
         if (args[0] == "sweep") return runSweep(args);
         if (args[0] == "representatives") return runRepresentatives(args);
         if (args[0] == "align") return runAlign(args);
+        if (args[0] == "profile") return runAlign(args, true);
         if (args[0] == "survey") return runSurvey(args);
         if (args[0] == "separation") return runSeparation(args);
         if (args[0] == "io-selftest") return ioSelftest(args);

@@ -987,6 +987,96 @@ int hmk_cluster_separation_shifted(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const
                                    uint32_t *cluster_misplaced, int64_t *cluster_own_sum,              /* n_clusters each, may be NULL */
                                    hmk_separation_stats *stats);
 
+/* ---- the profile of given clusters: column counts, information content, match states, KLD ---- */
+
+#define HMK_PROFILE_SYMBOLS 21     /* the 20 residues in the alphabet's order, then the gap */
+#define HMK_PROFILE_MAX_WIDTH 96
+typedef struct {
+    double  min_ic, max_gap_proportion;        /* Hammock.minIc 1.2, maxGapProportion 0.2 */
+    int32_t min_conserved_positions, allow_inner_gaps;
+    double  beta, sigma, scale;                /* Statistics.java:21-23: 200, 10, 2.88539 */
+    double  frequency[20 * 20];                /* [observed j][scored i], as loadFrequencyMatrix (FileIOManager.java:90-118) reads a
+                                                * row-normalised q_ij file: row j of the file, column i */
+    double  background[20];                    /* the divisor of Statistics.java:267, per scored letter */
+} hmk_profile_params;
+
+typedef struct {
+    uint64_t columns;            /* the sum of width[] over all slots: what col_capacity must hold (set with HMK_ERR_CAPACITY too) */
+    uint32_t n_multi;            /* slots with two or more members */
+    uint32_t omitted;            /* slots of one member, left out of the system means (Hammock.java:684-692) */
+    uint32_t small_members;      /* members counted by the form for small slots (a lane per member) */
+    uint32_t large_chunks;       /* chunks of the form for large slots (one workgroup step each) */
+    uint32_t launches, reserved;
+    double   system_kld_match;   /* Statistics.getMeanSystemKld(paths, false), Hammock.java:694; NaN (0.0 / 0) without a multi-member slot */
+    double   system_kld_all;     /* ... (paths, true), :695 */
+    double   kernel_ms;          /* device time, HIP events */
+} hmk_profile_stats;
+
+/* What the reference reads from a cluster's alignment, for every given cluster at once.  Members [r0, r1) of the hmk_set_sequences
+ * set with member_cluster and n_clusters as hmk_cluster_linkage_shifted takes them.  The call takes a placement, not a scorer:
+ * column[m - r0] is where member m's first residue stands in its slot's alignment -- what hmk_cluster_align_shifted returns, or any
+ * ungapped placement of the caller's.  Below, slot c has s members.
+ *   rows                   the aligned row of m is column gaps, then the peptide, then gaps up to width[c]
+ *   width[c]               the maximum over the slot's members of column + length
+ *   col_start[c]           where slot c's columns begin in the per-column arrays; col_start[n_clusters] = stats->columns
+ *   counts[col][sym]       the rows of the slot with symbol sym in that column (FileIOManager.getPositionLetterCounts, :1221-1247);
+ *                          HMK_PROFILE_SYMBOLS words per column, the gap is symbol 20.  May be NULL.
+ *   ic[col]                FileIOManager.getInformationContents (:1195-1211): -1.0 unless (gaps + 0.0) / s <= max_gap_proportion
+ *                          (:1204), else getInformationContent (:1421-1439): -(log(0.05) / log(2)) + the sum over the non-gap symbols
+ *                          present of p * (log(p) / log(2)), p = count / (s - gaps), the sum in symbol order.  May be NULL.
+ *   col_flags[col]         bit 0, conserved: ic >= min_ic (:1271, :1281).  Bit 1, match state (defineMatchStates, :1265-1300): bit 0
+ *                          if allow_inner_gaps, else every column from the slot's first to its last conserved one (:1277-1297).  May
+ *                          be NULL.
+ *   n_conserved, n_match   [c] the columns of the slot with bit 0 / with bit 1
+ *   passes[c]              n_conserved >= min_conserved_positions (checkConservedStates, :1172-1181, which always counts with inner
+ *                          gaps allowed; used at Hammock.java:1683)
+ *   kld_all, kld_match     [m - r0] Statistics.getPeptideKld (:238-273) of m's row against its own slot's counts, over all columns
+ *                          and over the match-state columns only.  Per column, left to right: skipped where m has a gap (:249-252);
+ *                          m's own letter is taken out of the counts (:253-254); sum = s - 1 (:258-261); skipped if what remains is
+ *                          only gaps (:262-265); else with a = m's letter, fj = count_j / sum over the 20 residues (the gaps stay
+ *                          inside sum, :277-280, :285), g = the sum in symbol order of fj * frequency[j][a] (:283-289),
+ *                          fi = count_a / sum (0 where m was the only one: the letter lives on the pseudocount alone),
+ *                          Q = ((sum - 1) * fi + beta * g) / ((sum - 1) + beta) (:296), and the column adds
+ *                          log(Q / background[a]) * (sum / (sum + sigma)) * scale (:267-269).  0.0 for the member of a slot of one.
+ *   kld_match_mean[c], kld_all_mean[c]
+ *                          the slot's sum in member index order / s (getMeanClusterKld, :194-197); 0.0 for a slot of one
+ *   stats->system_kld_*    the sum over the members of multi-member slots, in member index order, / their number
+ *                          (getMeanSystemKld, :178-184, over the paths of Hammock.java:684-692); stats->omitted counts the slots of
+ *                          one member left out
+ *   summation order        symbols in symbol order, columns left to right, members in index order.  This is not the iteration order
+ *                          of the JVM's HashMap and no bit parity with the Java's doubles is claimed.  The device functions are
+ *                          compiled without contraction: the operations are the ones written above.
+ *   the decision           ic >= min_ic is made once, on the device; col_flags, n_conserved, n_match, passes and kld_match all
+ *                          follow that one decision.  It can be a tie in exact arithmetic: ten members, one letter twice and eight
+ *                          letters once, have log2 20 - 0.2 log2 5 - 0.8 log2 10 = 1.2 exactly, the reference's default minIc; which
+ *                          side the doubles fall on is rounding (and, in the Java, map order).
+ *   determinism            counts are integer sums; ic is computed by one lane per column, a member's KLDs by one lane in column
+ *                          order: every output is bit-identical between calls and between grids.
+ *   checks                 HMK_ERR_BAD_ARG before the device is looked at (a host-only context answers them): the range and slot
+ *                          checks of hmk_cluster_linkage_shifted (a slot without members is refused), a null member_cluster or column
+ *                          with a non-empty range, a null required output, params or stats, column + length > HMK_PROFILE_MAX_WIDTH,
+ *                          a non-finite min_ic, max_gap_proportion outside [0, 1], negative min_conserved_positions, and beta, sigma,
+ *                          scale, any frequency or background entry that is not finite and > 0.  Then
+ *                          HMK_ERR_REFERENCE_WOULD_CRASH for a residue code >= 20 (B, Z, X, *) in the range: frequencyMatrix.get()
+ *                          is null for it at Statistics.java:286.  Then HMK_ERR_CAPACITY with stats->columns set when col_capacity
+ *                          < the sum of the widths.  An empty range is HMK_OK: col_start[0] = 0, nothing else written.  Without a
+ *                          device HMK_ERR_DEVICE: there is no CPU fallback.
+ * hmk_cluster_align_shifted cannot produce a width above HMK_PROFILE_MAX_WIDTH: the shift loop of scoreWithShift runs over
+ * [-max_shift, max_shift + diff] with max_shift < the shorter length, so a shift lies in [-31, 31], column <= 62 and width <= 94.
+ * Scratch is O(members + columns); the masks never leave the device between the kernels (k_profile.hip).  On a hmk_create_multi
+ * context the call runs on the root device. */
+int hmk_cluster_profile(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_cluster, uint32_t n_clusters,
+                        const uint32_t *column,                                                         /* r1 - r0 */
+                        const hmk_profile_params *params,
+                        uint32_t *width, uint32_t *n_conserved, uint32_t *n_match, uint8_t *passes,     /* n_clusters each, required */
+                        double *kld_match_mean, double *kld_all_mean,                                   /* n_clusters each, required */
+                        uint64_t *col_start,                                                            /* n_clusters + 1, required */
+                        uint64_t col_capacity,                                                          /* columns the next three hold */
+                        uint32_t *counts,                                                               /* x HMK_PROFILE_SYMBOLS, may be NULL */
+                        double *ic, uint8_t *col_flags,                                                 /* may be NULL */
+                        double *kld_match, double *kld_all,                                             /* r1 - r0 each, required */
+                        hmk_profile_stats *stats);
+
 /* Where the time of the last hmk_greedy_cluster / hmk_greedy_from_edges_dev call of this context went
  * (milliseconds; the span of Hammock.java:406-411 minus the sort).  score_ms and csr_ms are device times (HIP events on
  * the call's stream), the others host wall time.  The parts overlap (phase 1 runs while the rest of the pair space is
