@@ -25,6 +25,8 @@ HMK_MAX_LEN = 32
 HMK_SURVEY_MAX_BINS = 1024
 HMK_PROFILE_SYMBOLS = 21
 HMK_PROFILE_MAX_WIDTH = 96
+HMK_TARGET_MAX_LEN = 1 << 20
+HMK_SCAN_ALL_WINDOWS = 1
 
 # every symbol include/hammock_hip.h declares
 SYMBOLS = [
@@ -42,7 +44,7 @@ SYMBOLS = [
     "hmk_greedy_sweep", "hmk_greedy_sweep_from_edges", "hmk_greedy_sweep_from_edges_dev",
     "hmk_representatives_shifted", "hmk_representatives_from_edges", "hmk_representatives_from_edges_dev",
     "hmk_density_shifted", "hmk_density_from_edges", "hmk_density_from_edges_dev",
-    "hmk_cluster_profile",
+    "hmk_cluster_profile", "hmk_set_targets", "hmk_scan_shifted",
 ]
 
 
@@ -139,6 +141,17 @@ class ProfileStats(C.Structure):
     _fields_ = [("columns", C.c_uint64), ("n_multi", C.c_uint32), ("omitted", C.c_uint32), ("small_members", C.c_uint32),
                 ("large_chunks", C.c_uint32), ("launches", C.c_uint32), ("reserved", C.c_uint32), ("system_kld_match", C.c_double),
                 ("system_kld_all", C.c_double), ("kernel_ms", C.c_double)]
+
+
+class ScanHit(C.Structure):
+    """hmk_scan_hit"""
+    _fields_ = [("query", C.c_uint32), ("target", C.c_uint32), ("score", C.c_int32), ("offset", C.c_int32)]
+
+
+class ScanStats(C.Structure):
+    """hmk_scan_stats"""
+    _fields_ = [("n_hits", C.c_uint64), ("windows_scored", C.c_uint64), ("window_hits", C.c_uint64), ("windows_packed", C.c_uint64),
+                ("windows_literal", C.c_uint64), ("n_tiles", C.c_uint32), ("launches", C.c_uint32), ("kernel_ms", C.c_double)]
 
 
 class GreedyLevel(C.Structure):
@@ -285,6 +298,8 @@ def _load():
     p_f64 = C.POINTER(C.c_double)
     L.hmk_cluster_profile.argtypes = [vp, u32, u32, p_u32, u32, p_u32, C.POINTER(ProfileParams), p_u32, p_u32, p_u32, p_u8, p_f64, p_f64,
                                       p_u64, u64, p_u32, p_f64, p_u8, p_f64, p_f64, C.POINTER(ProfileStats)]
+    L.hmk_set_targets.argtypes = [vp, p_u8, p_u64, u32]
+    L.hmk_scan_shifted.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, u32, C.POINTER(ScanHit), u64, p_u32, p_u64, C.POINTER(ScanStats)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("hmk_destroy", "hmk_last_error", "hmk_last_kernel_ms"):

@@ -51,6 +51,9 @@ class ReferenceWouldCrash(HammockException):
         self.index = index
 
 
+SCAN_HIT_DTYPE = np.dtype([("query", np.uint32), ("target", np.uint32), ("score", np.int32), ("offset", np.int32)])
+
+
 def _ptr(arr, ctype):
     return arr.ctypes.data_as(C.POINTER(ctype))
 
@@ -374,6 +377,52 @@ class Context:
     def search_local(self, q0, q1, r0, r1, gap_open, gap_extend, threshold, capacity=None):
         """The same with LocalAlignmentScorer(seq1 = query, seq2 = reference) -> (edges uint64[n_edges], NeighborStats)"""
         return self._search(N.lib.hmk_search_local, q0, q1, r0, r1, gap_open, gap_extend, threshold, capacity)
+
+    # -- scanning peptides along long targets ---------------------------------------------
+    def set_targets(self, seqs=None, residues=None, offsets=None):
+        """The second resident set: targets of HMK_MAX_LEN + 1 .. HMK_TARGET_MAX_LEN residues (strings or uint8 arrays, or
+        concatenated residues with uint64 offsets[n + 1]).  Independent of set_sequences; an empty list clears them."""
+        if residues is None:
+            arrs = [encode(s) if isinstance(s, str) else np.asarray(s, dtype=np.uint8) for s in (seqs or [])]
+            offsets = np.zeros(len(arrs) + 1, dtype=np.uint64)
+            if arrs:
+                offsets[1:] = np.cumsum([len(a) for a in arrs])
+            residues = np.concatenate(arrs) if arrs else np.zeros(0, dtype=np.uint8)
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(len(offsets) - 1, 0)
+        st = N.lib.hmk_set_targets(self._h, _ptr(residues, C.c_uint8) if n else None, _ptr(offsets, C.c_uint64) if n else None, n)
+        if st:
+            self._raise(st)
+        self.n_targets = n
+        self._target_offsets = offsets.copy() if n else np.zeros(1, dtype=np.uint64)
+        return self
+
+    def scan_shifted(self, q0, q1, t0, t1, max_shift, shift_penalty, threshold, all_windows=False, coverage=False, capacity=None):
+        """Queries [q0, q1) slid along targets [t0, t1) as scoreWithShift(seq1 = query, seq2 = target) slides them
+        -> (hits, ScanStats) or, with coverage, (hits, ScanStats, coverage_count uint32[], coverage_size uint64[]) per residue of
+        the targets in the range.  hits: structured array (query, target, score, offset), one record per pair whose best window
+        reaches the threshold (the smallest offset among ties) or, with all_windows, per window that does; order unspecified."""
+        stats = N.ScanStats()
+        off = getattr(self, "_target_offsets", np.zeros(1, dtype=np.uint64))
+        total = int(off[t1] - off[t0]) if coverage and 0 <= t0 <= t1 < len(off) else 0
+        cc = np.zeros(max(total, 1), dtype=np.uint32) if coverage else None
+        cs = np.zeros(max(total, 1), dtype=np.uint64) if coverage else None
+        cap = int(capacity) if capacity is not None else 1 << 16
+        flags = N.HMK_SCAN_ALL_WINDOWS if all_windows else 0
+        for attempt in (0, 1):   # at most one retry, with the count the first call reported
+            buf = np.zeros(max(cap, 1), dtype=SCAN_HIT_DTYPE)
+            st = N.lib.hmk_scan_shifted(self._h, int(q0), int(q1), int(t0), int(t1), int(max_shift), int(shift_penalty), int(threshold),
+                                        flags, buf.ctypes.data_as(C.POINTER(N.ScanHit)), cap,
+                                        _ptr(cc, C.c_uint32) if coverage else None, _ptr(cs, C.c_uint64) if coverage else None,
+                                        C.byref(stats))
+            if st == N.HMK_ERR_CAPACITY and capacity is None and attempt == 0 and int(stats.n_hits) > cap:
+                cap = int(stats.n_hits)
+                continue
+            if st:
+                self._raise(st, stats)
+            hits = buf[:stats.n_hits].copy()
+            return (hits, stats, cc[:total], cs[:total]) if coverage else (hits, stats)
 
     def search_best_shifted(self, q0, q1, r0, r1, max_shift, shift_penalty, threshold, k):
         """The best k (1..32) references of every query with score >= threshold, by score descending, then reference

@@ -57,6 +57,7 @@ void Switches::read() {
     set_test_grid_cap(test_grid_cap);
     test_separation_segment = std::max(0, num("HMK_TEST_SEPARATION_SEGMENT", 0));
     profile_large_min = std::max(0, num("HMK_PROFILE_LARGE_MIN", 0));
+    no_scan_packed = flag("HMK_NO_SCAN_PACKED");
 }
 void refresh_switches(hmk_ctx *ctx) {
     ctx->sw.read();

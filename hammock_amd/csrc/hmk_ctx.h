@@ -3,7 +3,7 @@
 // buffers and their owners, streams), hmk_sizing.h (the sizing rules, pure functions), hmk_plan.cpp (the neighbour passes' planner),
 // hmk_pass.cpp (launching the passes; the pair and block probes), hmk_cluster.cpp (the single-device clustering calls, CSR pipeline,
 // row hand-over, second-loop driver), hmk_multi.cpp (the same calls on several devices), and one file per further call
-// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp, hmk_separation.cpp, hmk_sweep.cpp, hmk_representatives.cpp, hmk_density.cpp, hmk_profile.cpp).  Not part of the public ABI.
+// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp, hmk_separation.cpp, hmk_sweep.cpp, hmk_representatives.cpp, hmk_density.cpp, hmk_profile.cpp, hmk_scan.cpp).  Not part of the public ABI.
 #ifndef HMK_CTX_H
 #define HMK_CTX_H
 #include <hip/hip_runtime_api.h>
@@ -101,6 +101,10 @@ enum {
     SB_REP_STATE, SB_REP_VERT, SB_REP_LIVE,         // the representatives (hmk_representatives.cpp): the level's counters (RepState); the per-vertex arrays (RepVertex); the two live-edge buffers
     SB_DEN_STATE, SB_DEN_VERT, SB_DEN_ROWS,         // density clustering (hmk_density.cpp): one record per level and the flag (DenState); the per-vertex arrays (DenVertex); the requested rows of a batch of levels
     SB_PROF_IN, SB_PROF_COLS, SB_PROF_OUT,          // the profile of given clusters (hmk_profile.cpp; tables in SB_LINK_TAB): tables and inputs per member and slot; per column ic, counts, flags; per member KLDs, per slot conserved count, first, last
+    SB_SCAN_TRES, SB_SCAN_TOFF,                     // the scan along targets (hmk_scan.cpp): the targets' residues and offsets
+    SB_SCAN_PLAN, SB_SCAN_TAB, SB_SCAN_SIZES,       // ... query list, runs and chunks of a call; the runs' tables; the sequences' sizes
+    SB_SCAN_HITS, SB_SCAN_CNT,                      // ... the window hits; the pass's and the reduction's counters
+    SB_SCAN_HASH, SB_SCAN_PAIRS, SB_SCAN_COV,       // ... pair mode's table of (pair, best window) and its records; the two coverage arrays
     SB_N
 };
 
@@ -134,6 +138,7 @@ struct Switches {
     uint64_t edge_guess = 0;      // HMK_EDGE_GUESS: first edge-buffer capacity (forces the overflow / retry path)
     int test_grid_cap = 0;        // HMK_TEST_GRID_CAP=n, n >= 1: the grid-stride launches of hmk_grid.h get at most n workgroups (0: their own grids)
     int test_separation_segment = 0;   // HMK_TEST_SEPARATION_SEGMENT=n, n >= 1: the separation call's segments are n places long (0: sizing::separation_segments)
+    bool no_scan_packed = false;  // HMK_NO_SCAN_PACKED: hmk_scan_shifted scores every class with the literal form (tests/test_scan.py)
     int profile_large_min = 0;    // HMK_PROFILE_LARGE_MIN=n, n >= 2: hmk_cluster_profile counts slots of n members or more in LDS (0: PROFILE_LARGE_MIN, hmk_profile.h)
     void read();
 };
@@ -200,6 +205,12 @@ struct hmk_ctx {
     bool has_sizes = false;
     std::vector<uint8_t> len;
     int min_len = 0, max_len = 0;
+
+    // hmk_set_targets: the second resident set (hmk_scan.cpp); the device copy (SB_SCAN_TRES / SB_SCAN_TOFF) is made at the first scan
+    uint32_t n_targets = 0;
+    std::vector<uint8_t> tres;
+    std::vector<uint64_t> toff;
+    bool targets_on_device = false;
 
     DevBuf d_res32, d_len;   // uint8: the probes' padded residues and lengths (ensure_res32)
     DevBuf d_M;              // int32: the matrix

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "hmk_internal.h"
+#include "hmk_scan.h"
 
 namespace hmk {
 
@@ -197,6 +198,23 @@ hipError_t launch_merge_graph(bool packed, const uint64_t *start, const void *ad
                               uint64_t *scan_scratch, hipStream_t s);
 hipError_t launch_merge_compact(uint32_t ncl, const uint32_t *cl_start, const uint32_t *mstart, const uint64_t *tmp, const uint32_t *cnt,
                                 const uint32_t *ostart, int thr, uint64_t *out, uint64_t out_capacity, hipStream_t s);
+
+// ---- the scan of peptides along long targets (k_scan.hip; lists, parameter block and class rule in hmk_scan.h)
+// the runs' tables E[group][position][column] (8 biased bytes per entry) from the residues
+hipError_t launch_scan_tables(const ScanParams &P, uint64_t *tables, hipStream_t s);
+// the two scoring forms over (chunk, run): the byte lanes for the runs [run0, run0 + n_runs_m) of length m (6..20), the int32 sums
+// for every class the byte lanes do not take; both append to P.hits and count in *P.count
+hipError_t launch_scan_packed(int m, const ScanParams &P, uint32_t run0, uint32_t n_runs_m, hipStream_t s);
+hipError_t launch_scan_literal(const ScanParams &P, hipStream_t s);
+// pair mode: the best window of every (query, target) among `n` window hits through a table of `slots` (a power of two >= 2 n)
+// keys and values, both zeroed by the caller; then the table's entries as records (*count = how many)
+hipError_t launch_scan_pairs(const hmk_scan_hit *hits, uint64_t n, uint32_t q0, uint32_t t0, uint32_t nt, int X,
+                             unsigned long long *keys, unsigned long long *vals, uint64_t slots, hmk_scan_hit *out, uint64_t out_cap,
+                             unsigned long long *count, hipStream_t s);
+// coverage of `n` records: difference arrays (zeroed by the caller, `total` entries each, indexed toff[t] - toff[t0] + position),
+// then an inclusive scan per target in place.  len: the sequences' lengths; sizes: their sizes or null (1 each)
+hipError_t launch_scan_coverage(const hmk_scan_hit *recs, uint64_t n, const uint8_t *len, const int32_t *sizes, const uint64_t *toff,
+                                uint32_t t0, uint32_t nt, uint32_t *cov_count, unsigned long long *cov_size, hipStream_t s);
 
 // force the deferred load of the code objects a clustering call launches from (hmk_create)
 hipError_t warm_neighbors_module();

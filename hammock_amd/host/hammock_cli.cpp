@@ -6,7 +6,7 @@
 //
 // Extra flags that the reference does not have: --device <k> (HIP ordinal, default 0) and --devices a,b,.. (several
 // GPUs of the node behind one context, the first is the root: hmk_create_multi).
-// Extra modes that the reference does not have: search, assign, match, continue and merge (runSearch, runAssign, ...), each described
+// Extra modes that the reference does not have: search, assign, match, continue, merge, ... and scan (runSearch, runAssign, ...), each described
 // above its run function.  Every run function is a list of the shared steps below (parseModeArgs ... writeRankedTable) and what is its own.
 #include <deque>
 #include <future>
@@ -21,6 +21,7 @@
 #include <malloc.h>
 
 #include "hammock_host.hpp"
+#include "hammock_targets.hpp"
 
 using namespace hammock;
 
@@ -161,6 +162,8 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "                      [-x <int>] [-p <int>] [-R <order>] [-S <int>] [-l <labels>] [--device <int>]\n"
               << "          hammock-hip survey -i <sequences> -d <directory> [-g <int>] [--database <sequences>] [-f fasta|tab] [-m <file>] [-x <int>]\n"
               << "                      [-p <int>] [-l <labels>] [--device <int>]\n"
+              << "          hammock-hip scan -i <peptides> --targets <proteins.fa> -d <directory> [-g <int>] [-x <int>] [-p <int>] [--all_windows]\n"
+              << "                      [-f fasta|tab] [-m <file>] [--device <int>]\n"
               << "          hammock-hip separation -i <clusters.tsv> -d <directory> [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [-l <labels>]\n"
               << "                      [--device <int>]\n\n"
               << "-i, --input <file>\n\tA path to an input file\n\n"
@@ -179,6 +182,8 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "--device <int>\n\tHIP device ordinal (default 0)\n\n"
               << "--devices <int,int,...>\n\tShard the pair space over several GPUs of the node (the first one runs the merge)\n\n"
               << "--database <file>\n\t(search) the reference sequences every query (-i) is scored against;\n\t(survey) score the input against these sequences instead of against itself\n\n"
+              << "--targets <file>\n\t(scan) the long sequences (an antigen, a proteome) the peptides of -i are slid along: a FASTA file whose sequences may\n\tspan lines, named by the header up to the first white space, never merged; 33 to 1,048,576 residues each\n\n"
+              << "--all_windows\n\t(scan) one line per window at or above -g instead of one per (peptide, target) with its best window\n\n"
               << "--best <int>\n\t(search) keep only the best 1..32 hits of each query; (assign, match) report the best 1..32 feasible clusters (default 1)\n\n"
               << "--clusters <file>\n\t(assign, continue, match) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv);\n\t(merge) a second cluster file: its clusters keep their ids, the -i file's are renumbered behind them\n\n"
               << "--scan_to <int>\n\t(components) the last threshold of the scan: component_levels.tsv gets one line per threshold from -g to this one\n\t(at most 255 above -g; default: -g alone);\n\t(sweep) the last threshold of the sweep: greedy_levels.tsv gets one line per threshold from -g to this one;\n\t(representatives) the last threshold: representative_levels.tsv gets one line per threshold from -g to this one;\n\t(density) the last threshold: density_levels.tsv gets one line per threshold from -g to this one\n\n"
@@ -2303,10 +2308,140 @@ int runSurvey(const std::vector<std::string> &args) {
 }
 
 // `hammock-hip io-selftest ...`: exposes the loaders / orderings to the CPU test-suite (no GPU involved)
+// `hammock-hip scan -i peptides.fa --targets proteins.fa -d dir ...`: where on the targets do the peptides sit?  Every peptide of -i
+// slides along every target as scoreWithShift(seq1 = peptide, seq2 = target) slides it (ShiftedScorer.java:67-85; hmk_scan_shifted):
+// one line per (peptide, target) whose best window reaches -g -- or, with --all_windows, per window that does -- to
+// <dir>/scan_hits.tsv, the coverage of the targets' residues by those lines to target_coverage.tsv (targets with a hit only), one line
+// per target to target_summary.tsv.  Rows are sorted by (target, offset, peptide in load order): two runs write the same bytes.
+// Defaults: -x and -g as greedy derives them from the peptides (Hammock.java:394-397, 1421-1434), -p 0.
+int runScan(const std::vector<std::string> &args) {
+    Options o;
+    parseCommonArgs(args, o);
+    parseModeArgs(args, o, -1);
+    std::string targetsFile;
+    bool allWindows = false;
+    for (size_t i = 1; i < args.size(); i++) {
+        if (args[i] == "--targets" && args.size() > i + 1) targetsFile = args[++i];
+        else if (args[i] == "--all_windows") allWindows = true;
+    }
+    requireOneDevice(o, "scan", "a scan");
+    requireInput(o);
+    if (targetsFile.empty()) throw CLIException("Error. Parameter targets file (--targets) missing with no default.");
+    requireFastaOrTab(o, "scan");
+    makeOutputDirectory(o, o.parentDir);
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        ContextFuture contextReady = beginRun(o, logger, false);
+        logRunStart(logger, "scan", args);
+        logger.logAndStderr("Loading peptides...");
+        const std::vector<UniqueSequencePtr> peptides = loadSequences(o, o.inputFileName);
+        logger.logAndStderr(std::to_string(peptides.size()) + " unique peptides loaded.");
+        if (peptides.empty()) throw FileFormatException("Error. No peptides to scan with.");
+        requireOccurrences(peptides, "Error in file " + o.inputFileName);
+        logger.logAndStderr("Loading targets...");
+        TargetSet targets;
+        try {
+            targets = loadTargetsFromFasta(targetsFile, HMK_MAX_LEN + 1, HMK_TARGET_MAX_LEN);
+        } catch (const TargetFormatError &e) {
+            throw FileFormatException(e.what());
+        }
+        logger.logAndStderr(std::to_string(targets.size()) + " targets loaded, " + std::to_string(targets.residues.size()) + " residues.");
+        if (targets.size() == 0) throw FileFormatException("Error. No targets to scan.");
+        const SequenceListSummary summary = summariseSequences(peptides);
+        settleShiftAndThreshold(o, logger, summary, summary, summary, "Scan");
+
+        const std::shared_ptr<NativeContext> nc = contextReady.get();
+        hmk_ctx *c = nc->get();
+        nc->setSequences(peptides, true);
+        const uint32_t nq = (uint32_t)peptides.size(), nt = (uint32_t)targets.size();
+        int st = hmk_set_targets(c, targets.residues.data(), targets.offsets.data(), nt);
+        if (st) nc->raise(st, nullptr);
+        logger.logAndStderr("Scanning...");
+        const auto time0 = std::chrono::steady_clock::now();
+        std::vector<hmk_scan_hit> hits(1 << 16);
+        std::vector<uint32_t> covCount(targets.residues.size());
+        std::vector<uint64_t> covSize(targets.residues.size());
+        hmk_scan_stats stats{};
+        const uint32_t flags = allWindows ? HMK_SCAN_ALL_WINDOWS : 0u;
+        st = hmk_scan_shifted(c, 0, nq, 0, nt, o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold, flags, hits.data(), hits.size(),
+                              covCount.data(), covSize.data(), &stats);
+        if (st == HMK_ERR_CAPACITY) {
+            hits.resize(stats.n_hits);
+            st = hmk_scan_shifted(c, 0, nq, 0, nt, o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold, flags, hits.data(), hits.size(),
+                                  covCount.data(), covSize.data(), &stats);
+        }
+        if (st) nc->raise(st, nullptr);
+        hits.resize(stats.n_hits);
+        std::sort(hits.begin(), hits.end(), [](const hmk_scan_hit &a, const hmk_scan_hit &b) {
+            return a.target != b.target ? a.target < b.target : a.offset != b.offset ? a.offset < b.offset : a.query < b.query;
+        });
+        logger.logAndStderr("Ready. Scan time: " + std::to_string(millisSince(time0)));
+        logger.logAndStderr("Windows scored: " + std::to_string(stats.windows_scored) + " (" + std::to_string(stats.windows_packed) + " on byte lanes), windows at or above the threshold: " +
+                            std::to_string(stats.window_hits) + ", hits reported: " + std::to_string(stats.n_hits) + ", GPU kernels: " +
+                            std::to_string(stats.kernel_ms) + " ms");
+        const std::string hitsFile = o.workingDirectory + "/scan_hits.tsv", coverageFile = o.workingDirectory + "/target_coverage.tsv",
+                          summaryFile = o.workingDirectory + "/target_summary.tsv";
+        struct PerTarget { uint64_t hits = 0; int best = INT_MIN; std::unordered_set<uint32_t> peptides; };
+        std::vector<PerTarget> per(nt);
+        {
+            std::ofstream out(hitsFile);
+            if (!out) throw HammockException("cannot write " + hitsFile);
+            out << "peptide\tcount\ttarget\tstart\tscore\tsegment\n";
+            for (const hmk_scan_hit &h : hits) {
+                const std::string &pep = peptides[h.query]->getSequenceString();
+                const int64_t n = (int64_t)targets.length(h.target);
+                std::string segment;
+                for (int64_t i = 0; i < (int64_t)pep.size(); i++) {
+                    const int64_t pos = (int64_t)h.offset + i;
+                    segment.push_back(pos >= 0 && pos < n ? AMINO_ACIDS[targets.residues[targets.offsets[h.target] + (uint64_t)pos]] : '-');
+                }
+                out << pep << '\t' << peptides[h.query]->size() << '\t' << targets.names[h.target] << '\t' << h.offset + 1 << '\t' << h.score << '\t'
+                    << segment << '\n';
+                PerTarget &pt = per[h.target];
+                pt.hits++;
+                pt.best = std::max(pt.best, (int)h.score);
+                pt.peptides.insert(h.query);
+            }
+        }
+        {
+            std::ofstream cov(coverageFile), sum(summaryFile);
+            if (!cov) throw HammockException("cannot write " + coverageFile);
+            if (!sum) throw HammockException("cannot write " + summaryFile);
+            cov << "target\tposition\tresidue\thits\tcount\n";
+            sum << "target\tlength\thits\tpeptides\tbest_score\tcovered_positions\n";
+            for (uint32_t t = 0; t < nt; t++) {
+                uint64_t covered = 0;
+                for (uint64_t k = targets.offsets[t]; k < targets.offsets[t + 1]; k++) {
+                    covered += covCount[k] != 0;
+                    if (per[t].hits)
+                        cov << targets.names[t] << '\t' << k - targets.offsets[t] + 1 << '\t' << AMINO_ACIDS[targets.residues[k]] << '\t' << covCount[k] << '\t'
+                            << covSize[k] << '\n';
+                }
+                sum << targets.names[t] << '\t' << targets.length(t) << '\t' << per[t].hits << '\t' << per[t].peptides.size() << '\t'
+                    << (per[t].hits ? std::to_string(per[t].best) : std::string("NA")) << '\t' << covered << '\n';
+            }
+        }
+        logger.logAndStderr("Scan results in: " + hitsFile + ", " + coverageFile + ", " + summaryFile);
+        logger.logWithTime("Program successfully ended.");
+        return 0;
+    } catch (...) {
+        return reportRunError(logger, false);
+    }
+}
+
 int ioSelftest(const std::vector<std::string> &args) {
     if (args.size() >= 3 && args[1] == "matrix") {
         for (auto &row : FileIOManager::loadScoringMatrix(args[2])) {
             for (size_t c = 0; c < row.size(); c++) std::cout << (c ? " " : "") << row[c];
+            std::cout << "\n";
+        }
+        return 0;
+    }
+    if (args.size() >= 3 && args[1] == "targets") {  // targets <fasta>: what `scan --targets` loads, one "name<TAB>length<TAB>letters" per record
+        const TargetSet set = loadTargetsFromFasta(args[2], HMK_MAX_LEN + 1, HMK_TARGET_MAX_LEN);
+        for (size_t t = 0; t < set.size(); t++) {
+            std::cout << set.names[t] << "\t" << set.length(t) << "\t";
+            for (uint64_t k = set.offsets[t]; k < set.offsets[t + 1]; k++) std::cout << AMINO_ACIDS[set.residues[k]];
             std::cout << "\n";
         }
         return 0;
@@ -2357,7 +2492,7 @@ int ioSelftest(const std::vector<std::string> &args) {
             for (auto &s : cl->getSequences()) std::cout << cl->getId() << "\t" << s->getSequenceString() << "\t" << s->size() << "\n";
         return 0;
     }
-    std::cerr << "usage: hammock-hip io-selftest matrix <file> | sequences <fasta|tab> <file> <order> [seed] | "
+    std::cerr << "usage: hammock-hip io-selftest matrix <file> | targets <fasta> | sequences <fasta|tab> <file> <order> [seed] | "
                  "writers <fasta|tab> <file> <order> <seed> <clusters.tsv> <out dir> | clusters <cluster file>\n";
     return 2;
 }
@@ -2432,6 +2567,7 @@ int main(int argc, char **argv) {
         if (args[0] == "profile") return runAlign(args, true);
         if (args[0] == "survey") return runSurvey(args);
         if (args[0] == "separation") return runSeparation(args);
+        if (args[0] == "scan") return runScan(args);
         if (args[0] == "io-selftest") return ioSelftest(args);
         if (args[0] == "dump-matrix") {   // the default matrix in the text format FileIOManager.loadScoringMatrix reads
             std::cout << "# BLOSUM62 substitution matrix (public NCBI table), 24 x 24, order " << AMINO_ACIDS << "\n"

@@ -1077,6 +1077,65 @@ int hmk_cluster_profile(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *
                         double *kld_match, double *kld_all,                                             /* r1 - r0 each, required */
                         hmk_profile_stats *stats);
 
+/* ---- scanning peptides along long targets ----------------------------------------- */
+
+/* A second resident set: the TARGETS, sequences longer than any peptide the library takes (an antigen, a proteome), which the
+ * sequences of hmk_set_sequences are scanned along (hmk_scan_shifted).  Residues concatenated in the alphabet's codes 0..23,
+ * offsets[n_targets + 1]; everything is copied.  Targets and sequences are independent: either call may come first, neither
+ * disturbs the other; the next call replaces the targets, n_targets = 0 clears them.  A host-only context stores them and
+ * answers the checks.  HMK_ERR_BAD_ARG for: a target length outside [HMK_MAX_LEN + 1, HMK_TARGET_MAX_LEN] (a target is by
+ * definition the longer sequence, so seq1 = peptide is always the shorter one and the equal-length role swap of
+ * ShiftedScorer.java:51-57 cannot occur; shorter "targets" are sequences, hmk_search_shifted serves them), a residue code
+ * >= 24, offsets that do not start at 0 or do not ascend, more than 2^31 - 1 residues in all, a null pointer with
+ * n_targets > 0.  On a hmk_create_multi context the targets live on the root device. */
+#define HMK_TARGET_MAX_LEN (1u << 20)
+int hmk_set_targets(hmk_ctx *ctx, const uint8_t *residues, const uint64_t *offsets, uint32_t n_targets);
+
+typedef struct { uint32_t query, target; int32_t score, offset; } hmk_scan_hit;   /* 16 bytes */
+typedef struct {
+    uint64_t n_hits;            /* records returned (or needed, with HMK_ERR_CAPACITY) */
+    uint64_t windows_scored;    /* sum over (q, t) of d + 2X + 1 */
+    uint64_t window_hits;       /* windows at or above the threshold, before any reduction per pair */
+    uint64_t windows_packed;    /* of windows_scored: scored by the byte-lane form */
+    uint64_t windows_literal;   /* ... by the plain int32 form */
+    uint32_t n_tiles, launches;
+    double   kernel_ms;         /* HIP events, scoring (a pass repeated into a larger scratch included) + reduction + coverage */
+} hmk_scan_stats;
+
+#define HMK_SCAN_ALL_WINDOWS 1u
+/* Where do the peptides sit on the targets?  Queries [q0, q1) of the hmk_set_sequences set slide along targets [t0, t1) of the
+ * hmk_set_targets set as ShiftedScorer(matrix, shift_penalty, max_shift).scoreWithShift(seq1 = query, seq2 = target) slides
+ * them (ShiftedScorer.java:48-95).  With m, n the two lengths, d = n - m, X = max_shift, p = shift_penalty, the WINDOW SCORE
+ * w(q, t, s) of every offset s in [-X, d + X] (:67) is the sum of the cells M[q[i]][t[i + s]] over the overlap (:69-77; the
+ * matrix index is [peptide residue][target residue]) + d p (:79) + 2 p (-s) for s < 0 (:80-82) or 2 p (s - d) for s > d
+ * (:83-85).  `offset` = s is where the peptide's residue 0 stands on the target (negative: it hangs over the start);
+ * AligningScorerResult.getShift() is -offset (:91-93).
+ *   flags = 0              pair mode, the reference's sequenceScore: one record per pair (q, t) whose best window reaches the
+ *                          threshold, with that maximum and the SMALLEST s attaining it (the first strict maximum, :86-89).
+ *                          The window hits never reach the host.
+ *   HMK_SCAN_ALL_WINDOWS   window mode: one record per (q, t, s) with w >= threshold; repeats on a target show as several.
+ *   hits, capacity         record order unspecified.  HMK_ERR_CAPACITY with stats->n_hits = the number needed when `capacity`
+ *                          is too small; the call grows its own device scratch.
+ *   coverage_count, coverage_size   may be NULL; per residue position of the targets [t0, t1), indexed offsets[t] - offsets[t0]
+ *                          + position: the number of returned records (of the call's mode) whose window covers the position
+ *                          (positions max(s, 0) .. min(s + m, n) - 1), and the sum of those records' peptides' sizes as
+ *                          uploaded (UniqueSequence.size(); 1 each without sizes), in 64 bits.  Summed on the device.
+ *   checks                 answered before the device is looked at (a host-only context answers them): HMK_ERR_BAD_ARG for a
+ *                          null stats, null hits with capacity > 0, unknown flag bits, max_shift < 0, a threshold outside
+ *                          [-30000, 30000], |p| (HMK_TARGET_MAX_LEN + 2X) + 32 max|M| not below 2^30; HMK_ERR_NO_SEQUENCES
+ *                          without a sequence set, or without targets when t1 > t0; HMK_ERR_BAD_ARG for ranges outside the two
+ *                          sets; HMK_ERR_SHIFT_TOO_BIG when max_shift >= the shortest length in [q0, q1) (:59-62).  An empty
+ *                          range on either side: HMK_OK, 0 records, zeroed coverage.  Then, without a device, HMK_ERR_DEVICE.
+ *   stats                  the counters above; windows_packed + windows_literal = windows_scored.  Two bit-exact kernels score:
+ *                          byte lanes (peptide lengths 6..20, max_shift <= 5, where the lane-range proof holds for the group
+ *                          of peptides and the target's length) and plain int32 sums (everything else).
+ * On a hmk_create_multi context the scan runs on the root device. */
+int hmk_scan_shifted(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t t0, uint32_t t1,
+                     int max_shift, int shift_penalty, int threshold, uint32_t flags,
+                     hmk_scan_hit *hits, uint64_t capacity,
+                     uint32_t *coverage_count, uint64_t *coverage_size,   /* per residue of targets [t0, t1), may be NULL */
+                     hmk_scan_stats *stats);
+
 /* Where the time of the last hmk_greedy_cluster / hmk_greedy_from_edges_dev call of this context went
  * (milliseconds; the span of Hammock.java:406-411 minus the sort).  score_ms and csr_ms are device times (HIP events on
  * the call's stream), the others host wall time.  The parts overlap (phase 1 runs while the rest of the pair space is
