@@ -42,6 +42,7 @@ SYMBOLS = [
     "hmk_components_shifted", "hmk_components_from_edges", "hmk_components_from_edges_dev",
     "hmk_cluster_align_shifted", "hmk_score_survey_shifted", "hmk_cluster_separation_shifted",
     "hmk_greedy_sweep", "hmk_greedy_sweep_from_edges", "hmk_greedy_sweep_from_edges_dev",
+    "hmk_greedy_orders", "hmk_greedy_orders_from_edges",
     "hmk_representatives_shifted", "hmk_representatives_from_edges", "hmk_representatives_from_edges_dev",
     "hmk_density_shifted", "hmk_density_from_edges", "hmk_density_from_edges_dev",
     "hmk_cluster_profile", "hmk_set_targets", "hmk_scan_shifted",
@@ -168,6 +169,22 @@ class GreedySweepStats(C.Structure):
                 ("kernel_ms", C.c_double), ("deal_ms", C.c_double)]
 
 
+class GreedyOrder(C.Structure):
+    """hmk_greedy_order"""
+    _fields_ = [("status", C.c_int32), ("crash_case", C.c_int32), ("crash_index", C.c_int32),
+                ("phase1_stop_index", C.c_int32), ("phase1_clusters", C.c_int32), ("phase1_orphans", C.c_int32),
+                ("n_result_clusters", C.c_int32), ("n_multi", C.c_int32), ("n_singletons", C.c_uint32), ("largest", C.c_uint32),
+                ("pairs_together", C.c_uint64), ("pairs_with_first", C.c_uint64), ("tail_ms", C.c_double)]
+
+
+class GreedyOrdersStats(C.Structure):
+    """hmk_greedy_orders_stats"""
+    _fields_ = [("n_edges", C.c_uint64), ("pairs_scored", C.c_uint64), ("n_orders", C.c_uint32), ("n_valid", C.c_uint32),
+                ("pairs_ever", C.c_uint64), ("pairs_always", C.c_uint64), ("n_consensus", C.c_uint32),
+                ("n_consensus_singletons", C.c_uint32), ("consensus_largest", C.c_uint32), ("reserved", C.c_uint32),
+                ("kernel_ms", C.c_double), ("relabel_ms", C.c_double), ("support_ms", C.c_double)]
+
+
 class RepresentativeLevel(C.Structure):
     """hmk_representative_level"""
     _fields_ = [("n_edges", C.c_uint64), ("n_representatives", C.c_uint32), ("n_isolated", C.c_uint32), ("largest", C.c_uint32),
@@ -287,6 +304,10 @@ def _load():
     L.hmk_greedy_sweep.argtypes = [vp, i32, i32, i32, i32, i32] + sweep_out
     L.hmk_greedy_sweep_from_edges.argtypes = [vp, p_u64, u64, i32, i32, i32, i32] + sweep_out
     L.hmk_greedy_sweep_from_edges_dev.argtypes = [vp, vp, u64, i32, i32, i32, i32] + sweep_out
+    orders_tail = [p_u32, u32, u32, p_i32, p_i32, p_i32, C.POINTER(GreedyOrder), p_u32, p_u32, p_u32, p_u64, u64, p_u64,
+                   C.POINTER(GreedyOrdersStats)]
+    L.hmk_greedy_orders.argtypes = [vp, i32, i32, i32, i32] + orders_tail
+    L.hmk_greedy_orders_from_edges.argtypes = [vp, p_u64, u64, i32, i32] + orders_tail
     rep_out = [p_u32, p_u32, p_i32, C.POINTER(RepresentativeLevel), C.POINTER(RepresentativesStats)]
     L.hmk_representatives_shifted.argtypes = [vp, i32, i32, i32, i32] + rep_out
     L.hmk_representatives_from_edges.argtypes = [vp, p_u64, u64, i32, i32] + rep_out

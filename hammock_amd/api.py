@@ -189,6 +189,23 @@ GREEDY_LEVEL_DTYPE = np.dtype([("n_edges", np.uint64), ("status", np.int32), ("c
                                ("n_result_clusters", np.int32), ("n_multi", np.int32), ("n_singletons", np.uint32),
                                ("largest", np.uint32), ("tail_ms", np.float64)])
 
+# hmk_greedy_order, one entry per order of a greedy orders call
+GREEDY_ORDER_DTYPE = np.dtype([("status", np.int32), ("crash_case", np.int32), ("crash_index", np.int32),
+                               ("phase1_stop_index", np.int32), ("phase1_clusters", np.int32), ("phase1_orphans", np.int32),
+                               ("n_result_clusters", np.int32), ("n_multi", np.int32), ("n_singletons", np.uint32),
+                               ("largest", np.uint32), ("pairs_together", np.uint64), ("pairs_with_first", np.uint64),
+                               ("tail_ms", np.float64)])
+
+
+class OrdersResult:
+    """What Context.greedy_orders returns (hmk_greedy_orders): per_order (GREEDY_ORDER_DTYPE[n_orders]); cluster_id, result_order,
+    member_rank (int32 (n_orders, n), by uploaded index, clusters named by their seed's uploaded index); partners_always,
+    partners_ever, consensus (uint32[n]); support_edges (packed, the support in the score field); stats (hmk_greedy_orders_stats).
+    None where an output was not asked for."""
+    __slots__ = ("per_order", "cluster_id", "result_order", "member_rank", "partners_always", "partners_ever", "consensus",
+                 "support_edges", "stats")
+
+
 # hmk_representative_level, one entry per threshold of a representatives call
 REPRESENTATIVE_LEVEL_DTYPE = np.dtype([("n_edges", np.uint64), ("n_representatives", np.uint32), ("n_isolated", np.uint32),
                                        ("largest", np.uint32), ("n_rounds", np.uint32), ("reserved", np.uint32, (2,))])
@@ -1008,6 +1025,68 @@ class Context:
         return self._greedy_sweep(lambda thr, hi, *out: N.lib.hmk_greedy_sweep_from_edges_dev(self._h, C.c_void_p(d_edges_ptr), int(n_edges),
                                                                                               int(bool(symmetric)), thr, hi, int(max_clusters), *out),
                                   threshold, threshold_hi, arrays, levels)
+
+    # -- greedy clusterings under many orders of the set ---------------------------------------
+    def _greedy_orders(self, call, orders, min_support, arrays, per_order, support, support_capacity):
+        """runs call(orders, n_orders, min_support, cluster_id, result_order, member_rank, per_order, partners_always, partners_ever,
+        consensus, support_edges, capacity, n_support_edges, stats) -> OrdersResult; statistics also in last_orders_stats."""
+        n = self.n
+        orders = np.ascontiguousarray(orders, dtype=np.uint32)
+        if orders.ndim == 1:
+            orders = orders.reshape(1, -1)
+        if orders.ndim != 2 or orders.shape[1] != n:
+            raise ValueError(f"orders must be (n_orders, {n}): one permutation of the uploaded set per row")
+        k = orders.shape[0]
+        rows = [np.full((k, max(n, 1)), -1, dtype=np.int32) if arrays else None for _ in range(3)]
+        po = np.zeros(max(k, 1), dtype=GREEDY_ORDER_DTYPE) if per_order else None
+        pa, pe, cons = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+        stats = N.GreedyOrdersStats()
+        need = C.c_uint64(0)
+        cap = 0 if not support else max(4 * n, 1024) if support_capacity is None else int(support_capacity)
+        for attempt in range(2):
+            sup = np.zeros(max(cap, 1), dtype=np.uint64) if support else None
+            st = call(_ptr(orders, C.c_uint32) if orders.size or k else None, k, int(min_support),
+                      *[_ptr(a, C.c_int32) if arrays else None for a in rows],
+                      po.ctypes.data_as(C.POINTER(N.GreedyOrder)) if per_order else None,
+                      _ptr(pa, C.c_uint32), _ptr(pe, C.c_uint32), _ptr(cons, C.c_uint32),
+                      _ptr(sup, C.c_uint64) if support else None, cap, C.byref(need), C.byref(stats))
+            if st == N.HMK_ERR_CAPACITY and support_capacity is None and attempt == 0 and int(need.value) > cap:
+                cap = int(need.value)
+                continue
+            break
+        self.last_orders_needed = int(need.value)
+        if st:
+            self._raise(st)
+        self.last_orders_stats = stats
+        r = OrdersResult()
+        r.per_order = po[:k] if per_order else None
+        r.cluster_id, r.result_order, r.member_rank = [a[:, :n] if arrays else None for a in rows]
+        r.partners_always, r.partners_ever, r.consensus = pa[:n], pe[:n], cons[:n]
+        r.support_edges = sup[:int(need.value)] if support else None
+        r.stats = stats
+        return r
+
+    def greedy_orders(self, max_shift, shift_penalty, threshold, max_clusters, orders, min_support=0, arrays=True, per_order=True,
+                      support=True, support_capacity=None):
+        """hmk_greedy_orders: the greedy clustering of the uploaded set under every order of `orders` (uint32 (n_orders, n): row k
+        names the uploaded index standing at each position of order k) from ONE scoring pass -> OrdersResult.  Rows are indexed by
+        uploaded index and name a cluster by the uploaded index of its seed; an order whose status is not 0 is one where the
+        reference would throw: its rows are -1 and it takes no part in the supports.  support_edges: every pair that shares a cluster
+        in at least one valid order, packed (edge_fields), the support in the score field.  consensus: the components of the pairs
+        with support >= min_support (0: every valid order).  arrays=False / per_order=False / support=False pass NULL for those
+        outputs; support_capacity: the exact capacity to pass (BufferError when it is too small; last_orders_needed says how many)."""
+        return self._greedy_orders(lambda *tail: N.lib.hmk_greedy_orders(self._h, int(max_shift), int(shift_penalty), int(threshold),
+                                                                         int(max_clusters), *tail),
+                                   orders, min_support, arrays, per_order, support, support_capacity)
+
+    def greedy_orders_from_edges(self, edges, threshold, max_clusters, orders, min_support=0, arrays=True, per_order=True, support=True,
+                                 support_capacity=None):
+        """hmk_greedy_orders_from_edges: the same from packed edges (each unordered pair once, either orientation), by plain host code
+        (works on a host-only context)."""
+        edges = np.ascontiguousarray(edges, dtype=np.uint64)
+        return self._greedy_orders(lambda *tail: N.lib.hmk_greedy_orders_from_edges(self._h, _ptr(edges, C.c_uint64), edges.size,
+                                                                                    int(threshold), int(max_clusters), *tail),
+                                   orders, min_support, arrays, per_order, support, support_capacity)
 
     # -- representatives: a non-redundant subset of the set -----------------------------------
     def _representatives(self, call, threshold, threshold_hi, arrays, levels):

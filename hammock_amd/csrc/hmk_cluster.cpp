@@ -134,7 +134,8 @@ bool device_second_loop(hmk_ctx *ctx, hipStream_t S, const LoopIn &in, std::vect
     if (r == hipSuccess) r = ctx->h_stage.ensure((size_t)std::max<size_t>(nl, 1) * 4 + 64, 0);
     if (r == hipSuccess) r = hipHostGetDevicePointer((void **)&d_jslot, ctx->h_stage.p, 0);
     if (r == hipSuccess) r = ensure_buf(ctx, SB_LCOUNT, 64);
-    if (r == hipSuccess && ctx->has_sizes) r = ensure_buf(ctx, SB_SEQSZ, (size_t)n * 4);
+    const int32_t *seq_sizes = tail_sizes(ctx);
+    if (r == hipSuccess && seq_sizes) r = ensure_buf(ctx, SB_SEQSZ, (size_t)n * 4);
     if (r != hipSuccess) return false;
     // subscriber lists (count into FIRST as scratch, scan, fill, sort by leftover)
     r = hipMemsetAsync(buf<void>(ctx, SB_FIRST), 0, (size_t)ncl * 4, S);
@@ -153,8 +154,8 @@ bool device_second_loop(hmk_ctx *ctx, hipStream_t S, const LoopIn &in, std::vect
                                               buf<uint32_t>(ctx, SB_SUBSTART), d_clcursor, nl, buf<uint32_t>(ctx, SB_ACTIVE),
                                               buf<uint32_t>(ctx, SB_DIRTY), buf<uint32_t>(ctx, SB_LCOUNT), d_taken,
                                               buf<uint8_t>(ctx, SB_STATUS), d_jslot, S);
-    if (r == hipSuccess && ctx->has_sizes)
-        r = hipMemcpyAsync(buf<void>(ctx, SB_SEQSZ), ctx->sizes.data(), (size_t)n * 4, hipMemcpyHostToDevice, S);
+    if (r == hipSuccess && seq_sizes)
+        r = hipMemcpyAsync(buf<void>(ctx, SB_SEQSZ), seq_sizes, (size_t)n * 4, hipMemcpyHostToDevice, S);
     uint32_t rounds = 0;
     bool done = false;
     // a second first/accept pass per round saves a third of the rounds; it pays once a round's apply and eval are big enough
@@ -202,7 +203,7 @@ bool device_second_loop(hmk_ctx *ctx, hipStream_t S, const LoopIn &in, std::vect
                               buf<uint32_t>(ctx, SB_ACTIVE), buf<uint32_t>(ctx, SB_DIRTY), rounds, d_first, d_taken, d_clcursor,
                               ncl, accept_passes, buf<uint32_t>(ctx, SB_ACCEPTED), d_jslot,
                               buf<uint32_t>(ctx, SB_SUBSTART), buf<uint64_t>(ctx, SB_SUBS), buf<void>(ctx, SB_JOINED),
-                              ctx->has_sizes ? buf<int32_t>(ctx, SB_SEQSZ) : nullptr, buf<uint32_t>(ctx, SB_LCOUNT), ctx->h_loop, sw.loop_chain, S);
+                              seq_sizes ? buf<int32_t>(ctx, SB_SEQSZ) : nullptr, buf<uint32_t>(ctx, SB_LCOUNT), ctx->h_loop, sw.loop_chain, S);
         rounds++;
     };
     if (nl == 0 || ncl == 0) {
@@ -378,14 +379,14 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
             HIPCHK(ctx, ensure_buf(ctx, SB_FSTART, (size_t)n * 4));
             HIPCHK(ctx, ensure_buf(ctx, SB_TRCNT, (size_t)R1 * BandPack::TR_PER_ROW * 4));
             HIPCHK(ctx, ensure_buf(ctx, SB_TRSTART, ((size_t)R1 * BandPack::TR_PER_ROW + 1) * 4));
-            if (ctx->has_sizes) HIPCHK(ctx, ensure_buf(ctx, SB_SEQSZ, (size_t)n * 4));
+            if (tail_sizes(ctx)) HIPCHK(ctx, ensure_buf(ctx, SB_SEQSZ, (size_t)n * 4));
         }
         // (the fills first: they run beside the band launch, whose end the rest waits for)
         HIPCHK(ctx, hipMemsetAsync(buf<void>(ctx, SB_BDEG), 0, (size_t)R1 * 4, C));
         HIPCHK(ctx, hipMemsetAsync(buf<void>(ctx, SB_BCURSOR), 0, (size_t)R1 * 8, C));
         if (prepared) {
             HIPCHK(ctx, hipMemsetAsync(buf<void>(ctx, SB_FDEG), 0, (size_t)n * 12 + 16, C));   // (+ the totals and the list allocator's counter)
-            if (ctx->has_sizes) HIPCHK(ctx, hipMemcpyAsync(buf<void>(ctx, SB_SEQSZ), ctx->sizes.data(), (size_t)n * 4, hipMemcpyHostToDevice, C));
+            if (tail_sizes(ctx)) HIPCHK(ctx, hipMemcpyAsync(buf<void>(ctx, SB_SEQSZ), tail_sizes(ctx), (size_t)n * 4, hipMemcpyHostToDevice, C));
         }
         HIPCHK(ctx, hipStreamWaitEvent(C, ctx->ev_band, 0));
         HIPCHK(ctx, launch_csr_degree_scan(src.band_segs, n, R1, symmetric, buf<uint32_t>(ctx, SB_BDEG), buf<uint64_t>(ctx, SB_BSTART),
@@ -506,7 +507,7 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
             uint32_t *d_fdeg = buf<uint32_t>(ctx, SB_FDEG), *d_fcur = d_fdeg + n, *d_totals = d_fdeg + 3 * (size_t)n;
             if (e == hipSuccess)
                 e = launch_band_prepare(buf<uint64_t>(ctx, SB_BSTART), buf<uint32_t>(ctx, SB_BCURSOR), buf<void>(ctx, SB_BADJ), R1, (uint64_t)entries, n, FAR_T,
-                                        BandPack::TR_PER_ROW, ctx->has_sizes ? buf<int32_t>(ctx, SB_SEQSZ) : nullptr, buf<uint32_t>(ctx, SB_BNCNT),
+                                        BandPack::TR_PER_ROW, tail_sizes(ctx) ? buf<int32_t>(ctx, SB_SEQSZ) : nullptr, buf<uint32_t>(ctx, SB_BNCNT),
                                         buf<uint32_t>(ctx, SB_BNUP), buf<uint32_t>(ctx, SB_BNSTART), buf<uint32_t>(ctx, SB_BFTOP), buf<uint8_t>(ctx, SB_BFMORE),
                                         d_fdeg, d_fcur, d_totals, buf<uint32_t>(ctx, SB_FSTART), buf<uint32_t>(ctx, SB_FADJ),
                                         buf<uint32_t>(ctx, SB_TRCNT), buf<uint32_t>(ctx, SB_TRSTART), cap, (uint32_t *)(db + o_nstart), (uint32_t *)(db + o_nup),
@@ -788,7 +789,7 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
     GreedyTimes times{};
     hooks.times = &times;
     std::string err;
-    const int32_t *szs = ctx->has_sizes ? ctx->sizes.data() : nullptr;
+    const int32_t *szs = tail_sizes(ctx);
     if (src.clink) {
         // clinkage mode: the chain needs every row; fetch the whole adjacency, then run it on the host
         int cst = HMK_OK;

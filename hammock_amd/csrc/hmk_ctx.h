@@ -3,7 +3,7 @@
 // buffers and their owners, streams), hmk_sizing.h (the sizing rules, pure functions), hmk_plan.cpp (the neighbour passes' planner),
 // hmk_pass.cpp (launching the passes; the pair and block probes), hmk_cluster.cpp (the single-device clustering calls, CSR pipeline,
 // row hand-over, second-loop driver), hmk_multi.cpp (the same calls on several devices), and one file per further call
-// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp, hmk_separation.cpp, hmk_sweep.cpp, hmk_representatives.cpp, hmk_density.cpp, hmk_profile.cpp, hmk_scan.cpp).  Not part of the public ABI.
+// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp, hmk_separation.cpp, hmk_sweep.cpp, hmk_representatives.cpp, hmk_density.cpp, hmk_profile.cpp, hmk_scan.cpp, hmk_orders.cpp).  Not part of the public ABI.
 #ifndef HMK_CTX_H
 #define HMK_CTX_H
 #include <hip/hip_runtime_api.h>
@@ -105,6 +105,8 @@ enum {
     SB_SCAN_PLAN, SB_SCAN_TAB, SB_SCAN_SIZES,       // ... query list, runs and chunks of a call; the runs' tables; the sequences' sizes
     SB_SCAN_HITS, SB_SCAN_CNT,                      // ... the window hits; the pass's and the reduction's counters
     SB_SCAN_HASH, SB_SCAN_PAIRS, SB_SCAN_COV,       // ... pair mode's table of (pair, best window) and its records; the two coverage arrays
+    SB_ORD_EDGES, SB_ORD_STATE, SB_ORD_POS,         // the greedy clusterings under many orders (hmk_orders.cpp): the pass's edges renamed into one order; sums, counters, flag (OrdersState); the order's inverse permutation
+    SB_ORD_IDS, SB_ORD_SUPPORT, SB_ORD_PARTNERS,    // ... the valid orders' cluster ids, transposed; the support edges; partners ever [n], always [n]
     SB_N
 };
 
@@ -203,6 +205,9 @@ struct hmk_ctx {
     std::vector<uint32_t> off;
     std::vector<int32_t> sizes;
     bool has_sizes = false;
+    // hmk_greedy_orders (hmk_orders.cpp): while one order's tail runs, Cluster.size() per row IN THAT ORDER -- what the tail reads
+    // instead of `sizes` (tail_sizes below).  Null outside such a tail; `sizes` itself is never touched.
+    const int32_t *sizes_view = nullptr;
     std::vector<uint8_t> len;
     int min_len = 0, max_len = 0;
 
@@ -342,6 +347,9 @@ struct EdgeSource {
     std::function<int()> before_band, before_full;
 };
 
+// Cluster.size() per row as the clustering tail reads it: the context's sizes, or the permuted view of the order whose tail is
+// running (hmk_ctx::sizes_view); null: every sequence counts once
+inline const int32_t *tail_sizes(const hmk_ctx *ctx) { return ctx->sizes_view ? ctx->sizes_view : ctx->has_sizes ? ctx->sizes.data() : nullptr; }
 // ---- hmk_common.cpp
 void refresh_switches(hmk_ctx *ctx);              // the root's and its peers' (under the context's lock, once per entry-point call)
 GreedyOptions greedy_options(const hmk_ctx *ctx);

@@ -11,6 +11,7 @@
 #include <deque>
 #include <future>
 #include <map>
+#include <unordered_map>
 #include <unordered_set>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -158,6 +159,8 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "                      [-f fasta|tab] [-m <file>] [-x <int>] [-p <int>] [-l <labels>] [--device <int>]\n"
               << "          hammock-hip sweep -i <sequences> -d <directory> [-g <int>] [--scan_to <int>] [--pick <int>] [-f fasta|tab] [-m <file>]\n"
               << "                      [-x <int>] [-p <int>] [-R <order>] [-S <int>] [-l <labels>] [--initial_clusters_limit <int>] [--device <int>]\n"
+              << "          hammock-hip orders -i <sequences> -d <directory> [-R <order>] [--random_orders <int>] [-S <int>] [--min_support <int>] [--pairs]\n"
+              << "                      [-g <int>] [-f fasta|tab] [-m <file>] [-x <int>] [-p <int>] [-l <labels>] [--initial_clusters_limit <int>] [--device <int>]\n"
               << "          hammock-hip representatives -i <sequences> -d <directory> [-g <int>] [--scan_to <int>] [-f fasta|tab] [-m <file>]\n"
               << "                      [-x <int>] [-p <int>] [-R <order>] [-S <int>] [-l <labels>] [--device <int>]\n"
               << "          hammock-hip survey -i <sequences> -d <directory> [-g <int>] [--database <sequences>] [-f fasta|tab] [-m <file>] [-x <int>]\n"
@@ -188,6 +191,9 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "--clusters <file>\n\t(assign, continue, match) the existing clusters, a cluster file as greedy writes it (initial_clusters_sequences.tsv);\n\t(merge) a second cluster file: its clusters keep their ids, the -i file's are renumbered behind them\n\n"
               << "--scan_to <int>\n\t(components) the last threshold of the scan: component_levels.tsv gets one line per threshold from -g to this one\n\t(at most 255 above -g; default: -g alone);\n\t(sweep) the last threshold of the sweep: greedy_levels.tsv gets one line per threshold from -g to this one;\n\t(representatives) the last threshold: representative_levels.tsv gets one line per threshold from -g to this one;\n\t(density) the last threshold: density_levels.tsv gets one line per threshold from -g to this one\n\n"
               << "--pick <int>\n\t(sweep) the threshold of the sweep whose clustering is written as the stage-1 files (default: -g);\n\t(density) the threshold whose clusters are written as density_members.tsv and the stage-1 files (default: -g)\n\n"
+              << "--random_orders <int>\n\t(orders) how many random orders are clustered beside the -R order, 0 to 255 (default 9): order k is -R random with the seed\n\t-S + k - 1\n\n"
+              << "--min_support <int>\n\t(orders) the consensus clusters are the components of the pairs that share a cluster in at least this many valid orders\n\t(default 0: in every valid order)\n\n"
+              << "--pairs\n\t(orders) also write pair_support.tsv: every pair that shares a cluster in at least one order, with its support\n\n"
               << "--min_neighbors <int>\n\t(density) a sequence with at least this many neighbours (itself not counted) is core (default 3)\n\n"
               << "--frequency_matrix <file>\n\t(profile) required: a row-normalised frequency matrix q_ij in the format of Hammock's settings/misc/blosum62.freq_rownorm\n\t('#' comment lines, one header line of letters, tab-separated rows); hammock-hip ships no such table\n\n"
               << "--background <file>\n\t(profile) one line of 20 background probabilities in the letter order of the frequency matrix file (default: 0.05 throughout,\n\tthe equiprobable model the information content uses).  Hammock's own table is the array at Statistics.java:25-28: pass it in a file\n\tto get Hammock's KLD numbers\n\n"
@@ -2065,6 +2071,194 @@ int runSweep(const std::vector<std::string> &args) {
     }
 }
 
+// `hammock-hip orders -i X.fa -d dir [-R order] [--random_orders N] [-S seed] [--min_support S] [--pairs] [greedy's options]`: the
+// greedy clustering under 1 + N orders of the input from one scoring pass (hmk_greedy_orders;
+// LimitedGreedySequenceClusterer.java:22,39-69 once per order), and which of its clusters belong to the data rather than to the
+// order.  The set is uploaded in the -R order (default size): order 0 is the identity, byte for byte what `hammock-hip greedy`
+// clusters; orders 1..N (default 9) are -R random with the seeds S, S + 1, ...: each exactly the list `hammock-hip greedy -R random
+// -S seed` clusters.  Loading and the defaults of -x, -g and --initial_clusters_limit are greedy's own.  Writes order_levels.tsv (one
+// line per order), sequence_support.tsv (one line per sequence: its cluster in order 0, how many sequences share a cluster with it
+// in every valid order and in at least one, its consensus cluster), with --pairs pair_support.tsv (every pair that shares a cluster
+// in at least one order), and the stage-1 files with the consensus clusters -- the components of the pairs together in at least
+// --min_support valid orders (default: all of them); id = 1 + the smallest place in the upload order, clusters of several sequences
+// first in ascending id, then the single ones, members in upload order -- so that check, separation and align take them.
+int runOrders(const std::vector<std::string> &args) {
+    Options o;
+    parseCommonArgs(args, o);
+    parseModeArgs(args, o, -1);
+    int randomOrders = 9, minSupport = 0;
+    bool pairs = false;
+    for (size_t i = 1; i < args.size(); i++) {
+        const bool more = args.size() > i + 1;
+        if (args[i] == "--random_orders" && more) randomOrders = javaIntegerDecode(args[++i]);
+        else if (args[i] == "--min_support" && more) minSupport = javaIntegerDecode(args[++i]);
+        else if (args[i] == "--pairs") pairs = true;
+    }
+    requireOneDevice(o, "orders", "an orders run");
+    requireInput(o);
+    if (randomOrders < 0 || randomOrders > 255) throw CLIException("Error. --random_orders may be 0 to 255.");
+    if (minSupport < 0 || minSupport > randomOrders + 1)
+        throw CLIException("Error. --min_support may be 0 (every valid order) up to the number of orders, " + std::to_string(randomOrders + 1) + ".");
+    makeOutputDirectory(o, o.parentDir);
+    Logger logger(o.workingDirectory + "/run.log", false);
+    try {
+        ContextFuture contextReady = beginRun(o, logger, false);
+        std::vector<std::string> labels;
+        if (o.haveLabels) labels = FileIOManager::splitChar(o.labelString, ',', true);
+        if (!(o.inputType == "fasta" || o.inputType == "seq" || o.inputType == "tab"))
+            throw CLIException("Error. Parameter -f value may be either \"fasta\", \"seq\" or \"tab\". No other values are allowed");
+        logRunStart(logger, "orders", args);
+        // ---- greedy's loading and defaults (runSequenceClustering) -----------------------------------------------------------
+        logger.logAndStderr("Loading input sequences...");
+        if (o.inputType == "seq") throw HammockException("Error, this should have been checked.");
+        std::vector<UniqueSequencePtr> sequences = loadSequences(o, o.inputFileName);
+        logger.logAndStderr(std::to_string(sequences.size()) + " unique sequences loaded.");
+        SequenceListSummary summary = summariseSequences(sequences);
+        if (o.haveLabels) {
+            sequences = filterSequencesForLabels(sequences, labels);
+            summary = summariseSequences(sequences);
+        }
+        if (sequences.empty()) throw FileFormatException("Error. No sequences (with specified labels) to cluster.");
+        if (!o.haveLabels) labels = FileIOManager::getSortedLabels(sequences);
+        const std::vector<UniqueSequencePtr> initialSequences(sequences);
+        settleMaxShift(o, logger, summary, summary, "");
+        logger.logAndStderr("Generating input statistics...");
+        FileIOManager::saveInputStatistics(sequences, labels, o.workingDirectory + "/input_statistics.tsv");
+        settleThreshold(o, logger, summary, "Greedy clustering", "");
+        if (!o.haveLimit) {
+            o.initialClustersLimit = (int)javaRound((double)sequences.size() * 0.025);
+            logger.logAndStderr("Initial greedy clusters limit not set. Setting automatically to: " + std::to_string(o.initialClustersLimit));
+        }
+        const int thr = o.sequenceClusteringThreshold;
+        const size_t n = sequences.size(), nOrders = (size_t)randomOrders + 1;
+        logger.logAndStderr("Parameters: max shift " + std::to_string(o.maxShift) + ", gap penalty " + std::to_string(o.shiftPenalty) + ", threshold " +
+                            std::to_string(thr) + ", clusters limit " + std::to_string(o.initialClustersLimit) + ", orders: " + o.order + " and " +
+                            std::to_string(randomOrders) + " random from seed " + std::to_string(o.seed) + ", min support " +
+                            (minSupport ? std::to_string(minSupport) : std::string("every valid order")));
+        sortSequences(sequences, o.order, o.seed, labels);
+        // the orders: row 0 the upload order itself, row k the list -R random -S (seed + k - 1) hands to the clusterer
+        std::vector<uint32_t> orders(nOrders * n);
+        std::vector<std::string> orderNames(nOrders);
+        {
+            std::unordered_map<const UniqueSequence *, uint32_t> place;
+            for (size_t i = 0; i < n; i++) {
+                place[sequences[i].get()] = (uint32_t)i;
+                orders[i] = (uint32_t)i;
+            }
+            orderNames[0] = o.order + (o.order == "random" ? ":" + std::to_string(o.seed) : "");
+            for (size_t k = 1; k < nOrders; k++) {
+                std::vector<UniqueSequencePtr> shuffled(initialSequences);
+                const int seed = (int)((long long)o.seed + (long long)k - 1);
+                sortSequences(shuffled, "random", seed, labels);
+                for (size_t i = 0; i < n; i++) orders[k * n + i] = place[shuffled[i].get()];
+                orderNames[k] = "random:" + std::to_string(seed);
+            }
+        }
+
+        std::vector<int32_t> cid(nOrders * n);
+        std::vector<hmk_greedy_order> perOrder(nOrders);
+        std::vector<uint32_t> always(n), ever(n), consensus(n);
+        std::vector<uint64_t> support;
+        uint64_t nSupport = 0;
+        hmk_greedy_orders_stats stats{};
+        logger.logAndStderr("Greedy clustering under " + std::to_string(nOrders) + " orders...");
+        const auto time0 = std::chrono::steady_clock::now();
+        {
+            const std::shared_ptr<NativeContext> nc = contextReady.get();
+            nc->setSequences(sequences, true);
+            for (int attempt = 0; attempt < 2; attempt++) {   // (with --pairs: once more when the first room was too small)
+                if (pairs) support.resize(std::max<uint64_t>(nSupport, 16 * (uint64_t)n));
+                const int st = hmk_greedy_orders(nc->get(), o.maxShift, o.shiftPenalty, thr, o.initialClustersLimit, orders.data(), (uint32_t)nOrders,
+                                                 (uint32_t)minSupport, cid.data(), nullptr, nullptr, perOrder.data(), always.data(), ever.data(),
+                                                 consensus.data(), pairs ? support.data() : nullptr, pairs ? support.size() : 0, &nSupport, &stats);
+                if (st == HMK_ERR_CAPACITY && attempt == 0) continue;
+                if (st) nc->raise(st, nullptr);
+                break;
+            }
+        }
+        logger.logAndStderr("Ready. Orders time: " + std::to_string(millisSince(time0)));
+        double tails = 0;
+        for (const hmk_greedy_order &po : perOrder) tails += po.tail_ms;
+        logger.logAndStderr("Pairs scored: " + std::to_string(stats.pairs_scored) + ", pairs at or above the threshold: " + std::to_string(stats.n_edges) +
+                            ", GPU scoring: " + std::to_string(stats.kernel_ms) + " ms, relabel: " + std::to_string(stats.relabel_ms) +
+                            " ms, relabel and clustering tails: " + std::to_string(tails) + " ms, support and consensus: " +
+                            std::to_string(stats.support_ms) + " ms");
+        logger.logAndStderr("Valid orders: " + std::to_string(stats.n_valid) + " of " + std::to_string(stats.n_orders) + ", pairs together in at least one: " +
+                            std::to_string(stats.pairs_ever) + ", in every one: " + std::to_string(stats.pairs_always));
+        logger.logAndStderr("Consensus clusters: " + std::to_string(stats.n_consensus) + ", of one sequence: " + std::to_string(stats.n_consensus_singletons) +
+                            ", largest: " + std::to_string(stats.consensus_largest));
+        logger.logAndStderr("Saving results to output files...");
+        const std::string levelsCsv = o.workingDirectory + "/order_levels.tsv";
+        {
+            std::ofstream out(levelsCsv);
+            if (!out) throw HammockException("cannot write " + levelsCsv);
+            out << "order\tstatus\tclusters\tmulti_member\tsingletons\tlargest\tpairs_together\tpairs_together_with_order_0\n";
+            for (size_t k = 0; k < nOrders; k++) {
+                const hmk_greedy_order &po = perOrder[k];
+                out << orderNames[k] << '\t' << (po.status == HMK_OK ? std::string("ok") : "reference_would_crash:" + std::to_string(po.crash_case)) << '\t'
+                    << po.n_result_clusters << '\t' << po.n_multi << '\t' << po.n_singletons << '\t' << po.largest << '\t' << po.pairs_together << '\t';
+                // (pairs_with_first counts against the first VALID order: it is order 0's column only while order 0 is valid)
+                if (perOrder[0].status == HMK_OK) out << po.pairs_with_first << '\n';
+                else out << "NA\n";
+            }
+        }
+        const std::string perSequence = o.workingDirectory + "/sequence_support.tsv";
+        {
+            std::ofstream out(perSequence);
+            if (!out) throw HammockException("cannot write " + perSequence);
+            out << "sequence\tcluster_in_order_0\tpartners_always\tpartners_ever\tconsensus_cluster\n";
+            for (size_t i = 0; i < n; i++)
+                out << sequences[i]->getSequenceString() << '\t' << (cid[i] < 0 ? std::string("NA") : std::to_string(cid[i] + 1)) << '\t' << always[i] << '\t'
+                    << ever[i] << '\t' << consensus[i] + 1 << '\n';
+        }
+        const std::string byOrder = o.workingDirectory + "/order_clusters.tsv";
+        {
+            std::ofstream out(byOrder);
+            if (!out) throw HammockException("cannot write " + byOrder);
+            out << "sequence";
+            for (size_t k = 0; k < nOrders; k++) out << '\t' << orderNames[k];
+            out << '\n';
+            for (size_t i = 0; i < n; i++) {   // a cluster is named by its seed: 1 + the seed's place in the upload order
+                out << sequences[i]->getSequenceString();
+                for (size_t k = 0; k < nOrders; k++) out << '\t' << (cid[k * n + i] < 0 ? std::string("NA") : std::to_string(cid[k * n + i] + 1));
+                out << '\n';
+            }
+        }
+        const std::string pairCsv = o.workingDirectory + "/pair_support.tsv";
+        if (pairs) {
+            std::sort(support.begin(), support.begin() + (long)nSupport);   // (the call's order is unspecified: by first, then second sequence)
+            std::ofstream out(pairCsv);
+            if (!out) throw HammockException("cannot write " + pairCsv);
+            out << "sequence_1\tsequence_2\tsupport\tvalid_orders\n";
+            for (uint64_t e = 0; e < nSupport; e++)
+                out << sequences[HMK_EDGE_X(support[e])]->getSequenceString() << '\t' << sequences[HMK_EDGE_M(support[e])]->getSequenceString() << '\t'
+                    << HMK_EDGE_SCORE(support[e]) << '\t' << stats.n_valid << '\n';
+        }
+        std::vector<std::vector<UniqueSequencePtr>> members(n);
+        for (size_t i = 0; i < n; i++) members[consensus[i]].push_back(sequences[i]);
+        std::vector<ClusterPtr> result;
+        for (int multi = 1; multi >= 0; multi--)
+            for (size_t i = 0; i < n; i++)
+                if (!members[i].empty() && (members[i].size() > 1) == (multi == 1)) result.push_back(std::make_shared<Cluster>(members[i], (int)i + 1));
+        logger.logAndStderr("Resulting clusers: " + std::to_string(result.size()));
+        const std::string seqCsv = o.workingDirectory + "/initial_clusters_sequences.tsv";
+        const std::string orderedCsv = o.workingDirectory + "/initial_clusters_sequences_original_order.tsv";
+        const std::string clustersCsv = o.workingDirectory + "/initial_clusters.tsv";
+        FileIOManager::saveInitialClusters(result, seqCsv, orderedCsv, clustersCsv, labels, initialSequences);
+        logger.logAndStderr("Clusterings by order in: " + levelsCsv);
+        logger.logAndStderr("Sequences and their support in: " + perSequence);
+        logger.logAndStderr("Sequences and their cluster in every order in: " + byOrder);
+        if (pairs) logger.logAndStderr("Pairs and their support in: " + pairCsv);
+        logger.logAndStderr("Consensus clusters in: " + clustersCsv);
+        logger.logAndStderr("and: " + seqCsv);
+        logger.logAndStderr("and: " + orderedCsv);
+        logger.logWithTime("Program successfully ended.");
+        return 0;
+    } catch (...) {
+        return reportRunError(logger, false);
+    }
+}
+
 // `hammock-hip representatives -i X.fa -d dir [-g T] [--scan_to T2] [greedy's ordering and scoring options]`: the non-redundant
 // subset of the input at every threshold t = T ... T2 from one scoring pass (hmk_representatives_shifted): in greedy's order a
 // sequence is a representative unless an earlier representative scores >= t with it -- the greedy incremental selection of CD-HIT
@@ -2562,6 +2756,7 @@ int main(int argc, char **argv) {
         if (args[0] == "components") return runComponents(args);
         if (args[0] == "density") return runDensity(args);
         if (args[0] == "sweep") return runSweep(args);
+        if (args[0] == "orders") return runOrders(args);
         if (args[0] == "representatives") return runRepresentatives(args);
         if (args[0] == "align") return runAlign(args);
         if (args[0] == "profile") return runAlign(args, true);

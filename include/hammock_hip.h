@@ -447,6 +447,82 @@ int hmk_greedy_sweep_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t 
                                     int max_clusters, int32_t *cluster_id, int32_t *result_order, int32_t *member_rank,
                                     hmk_greedy_level *levels, hmk_greedy_sweep_stats *stats);
 
+/* ---- greedy clusterings under many orders of the set: order stability -------------------- */
+
+typedef struct {
+    int32_t  status;             /* HMK_OK or HMK_ERR_REFERENCE_WOULD_CRASH in this order */
+    int32_t  crash_case, crash_index;        /* as hmk_greedy_stats; crash_index is a position of THIS order */
+    int32_t  phase1_stop_index, phase1_clusters, phase1_orphans;
+    int32_t  n_result_clusters, n_multi;     /* as hmk_greedy_stats in this order */
+    uint32_t n_singletons;       /* result clusters of one sequence */
+    uint32_t largest;            /* sequences (not Cluster.size()) in the largest cluster */
+    uint64_t pairs_together;     /* unordered pairs inside one cluster in this order = the sum of C(members, 2) over its clusters */
+    uint64_t pairs_with_first;   /* of those, also together in the first valid order */
+    double   tail_ms;            /* wall time of this order's relabel and tail */
+} hmk_greedy_order;
+
+typedef struct {
+    uint64_t n_edges, pairs_scored;   /* edges >= threshold; 0 pairs for the _from_edges form: nothing is scored */
+    uint32_t n_orders, n_valid;       /* valid = orders in which the reference does not throw */
+    uint64_t pairs_ever, pairs_always;   /* pairs with support >= 1 / == n_valid */
+    uint32_t n_consensus, n_consensus_singletons, consensus_largest, reserved;
+    double kernel_ms;            /* the scoring pass, HIP events */
+    double relabel_ms;           /* all k_orders_relabel launches, HIP events */
+    double support_ms;           /* k_orders_support and the consensus kernels, HIP events (the three: 0 for the _from_edges form) */
+} hmk_greedy_orders_stats;
+
+/* Replaces one LimitedGreedySequenceClusterer(scorer, threshold, maxClusters).cluster(list k)
+ * (LimitedGreedySequenceClusterer.java:22,39-69) per order k, scorer = ShiftedScorer(matrix, shift_penalty, max_shift), with ONE
+ * scoring pass: list k = the uploaded set in order k with its sizes, i.e. what UniqueSequence.sortSequences would hand over under
+ * another -R.  The greedy clustering depends on the order by construction (:39-120); the scores do not.
+ *   orders[k][pos]         uploaded index of the sequence standing at position pos of order k; every row a permutation of [0, n);
+ *                          1 <= n_orders <= 256
+ *   cluster_id, result_order, member_rank   each [n_orders][n] or NULL, indexed by UPLOADED index, clusters named by the uploaded
+ *                          index of their seed: cluster_id[k][i] = seed of i's cluster, result_order[k][j] = seed of the j-th returned
+ *                          cluster (-1 behind n_result_clusters), member_rank[k][i] as in hmk_greedy_cluster.  The reference's id of
+ *                          a cluster is its seed's position in order k: with pos_k = the inverse of orders[k], pos_k[cluster_id[k][i]].
+ *                          For the identity order the rows and the shared stats fields are exactly hmk_greedy_cluster's; for any
+ *                          order they are that call's result on the permuted upload, mapped back.
+ *   per_order[k]           may be NULL.  An order where the reference would throw is recorded there (status, crash_case,
+ *                          crash_index), its rows are -1, it takes no part in anything below; the call goes on and returns HMK_OK.
+ *   support                support(i, j) = the valid orders in which i and j share a cluster.  With complete linkage every pair
+ *                          inside a cluster is an edge of the neighbour graph at `threshold`, so the support lives on the edge list.
+ *   support_edges          every pair with support >= 1 once, as HMK_EDGE_*: x < m (uploaded indices), the support (<= 256) in the
+ *                          score field, order unspecified -- a valid input of hmk_components_from_edges with a support level as its
+ *                          threshold.  NULL: none returned, no error.  HMK_ERR_CAPACITY when `capacity` is too small (every other
+ *                          output is written); *n_support_edges (may be NULL) = the number needed, in either case.
+ *   partners_ever[i], partners_always[i]   the j with support(i, j) >= 1 / == n_valid
+ *   consensus[i]           smallest uploaded index in i's component of the graph of the pairs with support >= min_support;
+ *                          min_support 0 means n_valid.  At n_valid the components are exactly the meet of the valid partitions
+ *                          ("together in every order" is an equivalence relation); below that the consensus is SINGLE linkage over
+ *                          the support: two sequences may share a consensus cluster without ever having shared a cluster.  A level
+ *                          above n_valid is reached by no pair.  Without a valid order every sequence is alone, the partner counts 0.
+ *   checks                 HMK_ERR_BAD_ARG before the device is looked at (a host-only context answers them): n_orders outside
+ *                          1 .. 256, NULL orders or stats, a row that is no permutation, min_support > n_orders, NULL support_edges
+ *                          with capacity > 0, every output NULL with n > 0, an asymmetric matrix (the orientation of an equal-length
+ *                          pair's score depends on who comes first, ShiftedScorer.java:51-57, and the pass scores one).  Then the
+ *                          checks of hmk_greedy_cluster at `threshold`.  No sequences: HMK_OK, zeroed outputs.
+ * The pass is hmk_neighbors_shifted's (same plan slot, same kernels) into the context's edge buffer; behind it k_orders.hip: per order
+ * the edges renamed to the order's positions and the tail of hmk_greedy_cluster on them (Cluster.size() through a permuted view: the
+ * sequences are not uploaded again, the context's sizes are not touched), once the supports over the original edges with the cluster
+ * ids transposed, then k_components.hip's union-find over the support edges.  On a hmk_create_multi context the call runs on the
+ * root device. */
+int hmk_greedy_orders(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, int max_clusters,
+                      const uint32_t *orders, uint32_t n_orders, uint32_t min_support,
+                      int32_t *cluster_id, int32_t *result_order, int32_t *member_rank, hmk_greedy_order *per_order,
+                      uint32_t *partners_always, uint32_t *partners_ever, uint32_t *consensus,
+                      uint64_t *support_edges, uint64_t capacity, uint64_t *n_support_edges, hmk_greedy_orders_stats *stats);
+
+/* The same from packed HMK_EDGE_* edges: each unordered pair once, either orientation, any order; the scores are read from the
+ * edges, an edge below `threshold` is ignored, an index >= n or a self pair is HMK_ERR_BAD_ARG.  Plain host code: relabel,
+ * hmk_greedy_from_edges's merge per order, supports by a loop, a sequential union-find.  Works on a host-only context, and is the
+ * second implementation the device path is tested against. */
+int hmk_greedy_orders_from_edges(hmk_ctx *ctx, const uint64_t *edges, uint64_t n_edges, int threshold, int max_clusters,
+                                 const uint32_t *orders, uint32_t n_orders, uint32_t min_support,
+                                 int32_t *cluster_id, int32_t *result_order, int32_t *member_rank, hmk_greedy_order *per_order,
+                                 uint32_t *partners_always, uint32_t *partners_ever, uint32_t *consensus,
+                                 uint64_t *support_edges, uint64_t capacity, uint64_t *n_support_edges, hmk_greedy_orders_stats *stats);
+
 /* ---- clinkage mode ------------------------------------------------------- */
 
 typedef struct {
