@@ -112,7 +112,21 @@ struct RowsShape {
 
     // the column's residue words as they lie in memory (zero for a lane without a column); tw: the last X residues, wherever
     // the column ends (capacity form only: unaligned dword loads; the array is padded)
-    static __device__ __forceinline__ void load_words(const uint8_t *rowp, bool live, int lbs, uint32_t (&words)[LPADW], uint32_t (&tw)[TWN]) {
+    // all_live (wave-uniform): every lane has a column -- nothing to zero, no bounds compare, the load runs under the wave's own mask.
+    // (Its address goes through an empty asm: left alone the compiler folds the two loads back into ONE masked load behind the
+    // zeroing moves, with all_live or-ed into the mask.)
+    static __device__ __forceinline__ void load_words(const uint8_t *rowp, bool live, bool all_live, int lbs, uint32_t (&words)[LPADW], uint32_t (&tw)[TWN]) {
+        if constexpr (EXACT_LB && LPADW == 4) {
+            if (all_live) {
+                uint64_t p = (uint64_t)(uintptr_t)rowp;
+                asm volatile("" : "+v"(p));
+                const u32x4 v0 = *reinterpret_cast<const __attribute__((address_space(1))) u32x4 *>(p);   // (global, not flat)
+                words[0] = v0.x; words[1] = v0.y; words[2] = v0.z; words[3] = v0.w;
+#pragma unroll
+                for (int q = 0; q < TWN; q++) tw[q] = 0;
+                return;
+            }
+        }
 #pragma unroll
         for (int q = 0; q < LPADW; q++) words[q] = 0;
 #pragma unroll
@@ -189,7 +203,7 @@ struct RowsShape {
     static __device__ __forceinline__ void offsets(const uint8_t *rowp, bool live, int lbs, uint32_t base, uint32_t tbase,
                                                    uint32_t (&off)[CAP], uint32_t (&toff)[NT]) {
         uint32_t words[LPADW], tw[TWN];
-        load_words(rowp, live, lbs, words, tw);
+        load_words(rowp, live, false, lbs, words, tw);
         offsets_of(words, tw, base, tbase, off, toff);
     }
 
@@ -887,12 +901,15 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
             k0[ND - 1] = a.x; k1[ND - 1] = a.y;
         }
     };
+    using No = std::false_type;
+    using Yes = std::true_type;
+    constexpr bool RUNS = KEYED && G >= 2;
     for (uint32_t bt = 0; bt < n_batches; bt++) {
         const uint32_t colrel = bt * 256 + tid;
         const uint32_t col = T.col0 + colrel;
         // (the column's words are asked for first: the key's scalar loads below are two dependent round trips)
         uint32_t words[S::LPADW], tw[S::TWN];
-        S::load_words(res_sorted + (size_t)col * lpad_s, col < col_end, lbs, words, tw);
+        S::load_words(res_sorted + (size_t)col * lpad_s, col < col_end, RUNS && interior, lbs, words, tw);
         int kmode = 0;
         u32x2 ra;   // the run words of the wave's first column (read where kmode != 0 only)
         if constexpr (KEYED) {
@@ -910,125 +927,235 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
         // a run-shared tile's merged cells, plane by plane: written by group 0 (the lead), read by the groups after it in the SAME step
         // -- live across group 0's threshold test, append loop and flush call; nothing on any other tile
         uint32_t Pm[ND];
-        constexpr bool RUNS = KEYED && G >= 2;
 
-        auto one_group = [&](auto gt) {
-            constexpr int g = decltype(gt)::value;
-            if ((uint32_t)(8 * g) >= T.nrows) return;   // wave-uniform
-            uint32_t W0[ND], W1[ND];
-            if constexpr (KEYED) {
+        if constexpr (RUNS) {
+            // Paired tiles.  kmode belongs to the step's 64 columns, not to the group: ONE switch stands around both groups, and inside
+            // it one test of the tile's flag.  A lead and its follower lie in one straight line -- Pm crosses no join -- and both groups
+            // of a run-shared tile have 8 live rows: no row test, literal row masks.
+            static_assert(INLOOP && !DEFER && !TWO, "paired tiles: an in-loop shape");
+            // The body of group g under window mode KM (0 none, 1 key 0, 3 both keys; compile time): its key entries and its reads.
+            // RUN (compile time): the tile is run-shared -- the lead (g == 0) or a follower.
+            auto body = [&](auto gt, auto kt, auto rt, uint32_t (&W0)[ND], uint32_t (&W1)[ND]) __attribute__((always_inline)) {
+                constexpr int g = decltype(gt)::value, KM = decltype(kt)::value;
+                constexpr bool RUN = decltype(rt)::value;
                 const uint32_t *const kt_group = kt_tile + (size_t)g * (2 * 24 * KEYTAB_DWORDS);   // row group (T.row0 >> 3) + g
-                const bool row_shared = G == 1 ? rs_first : (rs_groups & (1u << g)) != 0;   // wave-uniform
+                [[maybe_unused]] const bool row_shared = (rs_groups & (1u << g)) != 0;   // wave-uniform
                 // (start values in SGPRs: the plane's first add takes them as its scalar operand.  Byte lanes: every partial sum is
                 // <= the plane's final lane <= 255, no carry)
                 uint32_t ks0[ND], ks1[ND];
-                if (kmode == 3) {
+                if constexpr (KM == 3) {
                     uint32_t kb0[ND], kb1[ND];
                     key_entry(kt_group + (ra.x & 31u) * KEYTAB_DWORDS, ks0, ks1);
                     key_entry(kt_group + (24 + (ra.y & 31u)) * KEYTAB_DWORDS, kb0, kb1);
 #pragma unroll
                     for (int u = 0; u < ND; u++) { ks0[u] += kb0[u]; ks1[u] += kb1[u]; }
-                    read_phase_begin(prio);
-                    if (RUNS && (rs_groups & ROWS_RUN_SHARED) != 0) S::template accumulate_run<g, 3, (g > 0)>(off, ks0, ks1, W0, W1, Pm);
-                    else if (row_shared) S::template accumulate<g, 3, true>(off, toff, lbs, ks0, ks1, W0, W1);
-                    else S::template accumulate<g, 3>(off, toff, lbs, ks0, ks1, W0, W1);
-                } else if (kmode == 1) {
+                } else if constexpr (KM == 1) {
                     key_entry(kt_group + (ra.x & 31u) * KEYTAB_DWORDS, ks0, ks1);
                     // (no instruction: the loads are waited for HERE, not at the first add inside the read phase)
 #pragma unroll
                     for (int u = 0; u < ND; u++) asm volatile("" : "+s"(ks0[u]), "+s"(ks1[u]));
-                    read_phase_begin(prio);
-                    if (RUNS && (rs_groups & ROWS_RUN_SHARED) != 0) S::template accumulate_run<g, 1, (g > 0)>(off, ks0, ks1, W0, W1, Pm);
-                    else if (row_shared) S::template accumulate<g, 1, true>(off, toff, lbs, ks0, ks1, W0, W1);
-                    else S::template accumulate<g, 1>(off, toff, lbs, ks0, ks1, W0, W1);
-                } else {
-                    read_phase_begin(prio);
-                    if (RUNS && (rs_groups & ROWS_RUN_SHARED) != 0) S::template accumulate_run<g, 0, (g > 0)>(off, ci, ci, W0, W1, Pm);
-                    else if (row_shared) S::template accumulate<g, 0, true>(off, toff, lbs, ci, ci, W0, W1);
-                    else S::template accumulate<g>(off, toff, lbs, ci, ci, W0, W1);
                 }
-            } else {
+                const uint32_t (&s0)[ND] = KM != 0 ? ks0 : ci;
+                const uint32_t (&s1)[ND] = KM != 0 ? ks1 : ci;
                 read_phase_begin(prio);
-                S::template accumulate<g>(off, toff, lbs, ci, ci, W0, W1);
-            }
-            read_phase_end(prio);
-
-            // ---- threshold test: some (row, shift) lane has its top bit set <=> score >= threshold ----
-            uint32_t o0 = W0[0], o1 = W1[0];
+                if constexpr (RUN) S::template accumulate_run<g, KM, (g > 0)>(off, s0, s1, W0, W1, Pm);
+                else if (row_shared) S::template accumulate<g, KM, true>(off, toff, lbs, s0, s1, W0, W1);
+                else S::template accumulate<g, KM>(off, toff, lbs, s0, s1, W0, W1);
+                read_phase_end(prio);
+            };
+            // Threshold test, hit mask, append loop and flush call of group g (one_group below, with two differences).  FULL (compile
+            // time): the group has 8 live rows.  The hit word's halves are swapped -- rows 0-3 in the bits 8r + 3, rows 4-7 in 8r + 7
+            // -- so that bit q stands for row (q >> 3) | (q & 4).
+            auto hits = [&](auto gt, auto ft, const uint32_t (&W0)[ND], const uint32_t (&W1)[ND]) __attribute__((always_inline)) {
+                constexpr int g = decltype(gt)::value;
+                constexpr bool FULL = decltype(ft)::value;
+                uint32_t o0 = W0[0], o1 = W1[0];
 #pragma unroll
-            for (int u = 1; u < ND; u++) { o0 |= W0[u]; o1 |= W1[u]; }
-            if constexpr (!DEFER)
+                for (int u = 1; u < ND; u++) { o0 |= W0[u]; o1 |= W1[u]; }
                 if (__ballot(((o0 | o1) & 0x80808080u) != 0) == 0) return;
-            // ---- rare path (a hit somewhere in the wave): every lane appends ITS hits, one per turn ----
-            // hm: bit 8r + 7 set <=> row r of the group (r < 4) reached the threshold for this lane's column, bit 8r + 3 <=> row
-            // 4 + r.  The rows beyond the tile's last start at the initial lane value, which may itself have the top bit set:
-            // rm0 / rm1 (wave-uniform) leave them out.
-            const uint32_t rows_here = T.nrows - 8 * g;
-            const uint32_t rm0 = rows_here >= 4 ? 0x80808080u : 0x80808080u & ((1u << (8 * rows_here)) - 1u);
-            const uint32_t rm1 = rows_here >= 8 ? 0x80808080u : rows_here <= 4 ? 0u : 0x80808080u & ((1u << (8 * (rows_here - 4))) - 1u);
-            uint32_t hm = (o0 & rm0) | ((o1 & rm1) >> 4);
-            if (!interior) {  // wave-uniform: only edge tiles filter
-                if (col >= col_end) hm = 0;
-                if (T.diag != 0) {
-                    const int k = (int)col - (int)(T.row0 + 8 * g);   // the row this column IS, relative to the group
-                    if (T.diag == 1) {   // triangle: keep rows r with column > row, i.e. r < k
-                        const int k0 = k < 0 ? 0 : k > 4 ? 4 : k, k1 = k < 4 ? 0 : k > 8 ? 4 : k - 4;
-                        hm &= (k0 >= 4 ? 0x80808080u : 0x80808080u & ((1u << (8 * k0)) - 1u)) |
-                              (k1 >= 4 ? 0x08080808u : 0x08080808u & ((1u << (8 * k1)) - 1u));
-                    } else if (k >= 0 && k < 8) {   // full square minus the diagonal
-                        hm &= ~(k < 4 ? 0x80u << (8 * k) : 0x08u << (8 * (k - 4)));
+                uint32_t rm0 = 0x80808080u, rm1 = 0x80808080u;
+                if constexpr (!FULL) {
+                    const uint32_t rows_here = T.nrows - 8 * g;
+                    rm0 = rows_here >= 4 ? 0x80808080u : 0x80808080u & ((1u << (8 * rows_here)) - 1u);
+                    rm1 = rows_here >= 8 ? 0x80808080u : rows_here <= 4 ? 0u : 0x80808080u & ((1u << (8 * (rows_here - 4))) - 1u);
+                }
+                uint32_t hm = ((o0 & rm0) >> 4) | (o1 & rm1);
+                if (!interior) {  // wave-uniform: only edge tiles filter
+                    if (col >= col_end) hm = 0;
+                    if (T.diag != 0) {
+                        const int k = (int)col - (int)(T.row0 + 8 * g);   // the row this column IS, relative to the group
+                        if (T.diag == 1) {   // triangle: keep rows r with column > row, i.e. r < k
+                            const int k0 = k < 0 ? 0 : k > 4 ? 4 : k, k1 = k < 4 ? 0 : k > 8 ? 4 : k - 4;
+                            hm &= (k0 >= 4 ? 0x08080808u : 0x08080808u & ((1u << (8 * k0)) - 1u)) |
+                                  (k1 >= 4 ? 0x80808080u : 0x80808080u & ((1u << (8 * k1)) - 1u));
+                        } else if (k >= 0 && k < 8) {   // full square minus the diagonal
+                            hm &= ~(k < 4 ? 0x08u << (8 * k) : 0x80u << (8 * (k - 4)));
+                        }
                     }
                 }
-            }
-            if constexpr (DEFER) {
-                // history: this step's bits stay at 3 mod 4, the earlier steps' move down by one per step
-                acc[g] = (acc[g] >> 1) | hm;
-                if (!look) return;
-                hm = acc[g];
-                acc[g] = 0;
-                if (__ballot(hm != 0) == 0) return;
-            }
-            // (the flush sits OUTSIDE the append loop: the rescoring kind needs most of the register file; inside the loop the
-            // compiler kept the loop's state in scratch memory for every turn of it)
-            for (;;) {
-                bool full = false;
                 for (;;) {
-                    const bool any = hm != 0;
-                    const uint64_t mask = __ballot(any);
-                    if (mask == 0) break;
-                    if (cnt + cnt_hi > (uint32_t)(STAGE_CAP - 64)) { full = true; break; }   // keep room for one wave of hits
-                    if (any) {
-                        const uint32_t q = (uint32_t)__builtin_ctz(hm);
-                        if constexpr (INLOOP) {
-                            // the hit's row r (bit 8r + 7: row r; bit 8r + 3: row 4 + r) is byte r of every plane's register pair:
-                            // one v_perm_b32 per plane (selector byte 0 = r: 0-3 pick from the low dword, 4-7 from the high one;
-                            // the other selector bytes give zero), the largest of them is the pair's lane = 128 - threshold + score
-                            const uint32_t r = (q >> 3) + 4u - (q & 4u);
-                            const uint32_t sel = 0x0c0c0c00u | r;
+                    bool full = false;
+                    for (;;) {
+                        const bool any = hm != 0;
+                        const uint64_t mask = __ballot(any);
+                        if (mask == 0) break;
+                        if (cnt > (uint32_t)(STAGE_CAP - 64)) { full = true; break; }   // keep room for one wave of hits
+                        if (any) {
+                            const uint32_t q = (uint32_t)__builtin_ctz(hm);
+                            const uint32_t r = (q >> 3) | (q & 4u);
+                            const uint32_t sel = 0x0c0c0c00u | r;   // (byte r of every plane's register pair, see one_group)
                             uint32_t mx = __builtin_amdgcn_perm(W1[0], W0[0], sel);
 #pragma unroll
                             for (int u = 1; u < ND; u++) mx = max(mx, __builtin_amdgcn_perm(W1[u], W0[u], sel));
                             stage[cnt + mbcnt64(mask)] = colrel | ((uint32_t)(8 * g) + r) << 16 | (mx - 128u) << 24;
-                        } else {
-                            // the record: this step's column | the hit's bit << 16 | group << 21.  Which row and which of the quad's
-                            // steps the bit stands for is worked out by the flush, where all 64 lanes have a record: here a turn
-                            // runs for the few lanes that still have a hit, and every instruction of it costs the wave a VALU slot
-                            const uint32_t rec = (colrel | (uint32_t)g << 21) | q << 16;
-                            if constexpr (TWO && g == 1) stage[(uint32_t)(STAGE_CAP - 1) - (cnt_hi + mbcnt64(mask))] = rec;
-                            else stage[cnt + mbcnt64(mask)] = rec;
                         }
-                        hm &= hm - 1u;   // clear the lowest set bit
+                        hm &= hm - 1u;   // clear the lowest set bit, in every lane -- outside the masked region: 0 & (0 - 1) = 0
+                        cnt += (uint32_t)__popcll(mask);
                     }
-                    if constexpr (TWO && g == 1) cnt_hi += (uint32_t)__popcll(mask);
-                    else cnt += (uint32_t)__popcll(mask);
+                    if (!full) break;
+                    flush_stage_rows<X, D, CAP, EXACT_LB, G, MODE>(stage, cnt, cnt_hi, tab_addr, ka_lo, ka_hi);
+                    cnt = 0;
                 }
-                if (!full) break;
-                flush_stage_rows<X, D, CAP, EXACT_LB, G, MODE>(stage, cnt, cnt_hi, tab_addr, ka_lo, ka_hi);
-                cnt = 0;
-                cnt_hi = 0;
-            }
-        };
-        rows_for_each_group(std::make_integer_sequence<int, G>{}, one_group);
+            };
+            constexpr auto groups_seq = std::make_integer_sequence<int, G>{};
+            auto both = [&](auto kt) __attribute__((always_inline)) {
+                if ((rs_groups & ROWS_RUN_SHARED) != 0) {
+                    rows_for_each_group(groups_seq, [&](auto gt) __attribute__((always_inline)) {
+                        uint32_t W0[ND], W1[ND];
+                        body(gt, kt, Yes{}, W0, W1);
+                        hits(gt, Yes{}, W0, W1);
+                    });
+                } else {
+                    rows_for_each_group(groups_seq, [&](auto gt) __attribute__((always_inline)) {
+                        if ((uint32_t)(8 * decltype(gt)::value) >= T.nrows) return;   // wave-uniform
+                        uint32_t W0[ND], W1[ND];
+                        body(gt, kt, No{}, W0, W1);
+                        hits(gt, No{}, W0, W1);
+                    });
+                }
+            };
+            if (kmode == 3) both(std::integral_constant<int, 3>{});
+            else if (kmode == 1) both(std::integral_constant<int, 1>{});
+            else both(std::integral_constant<int, 0>{});
+        } else {
+            auto one_group = [&](auto gt) {
+                constexpr int g = decltype(gt)::value;
+                if ((uint32_t)(8 * g) >= T.nrows) return;   // wave-uniform
+                uint32_t W0[ND], W1[ND];
+                if constexpr (KEYED) {
+                    const uint32_t *const kt_group = kt_tile + (size_t)g * (2 * 24 * KEYTAB_DWORDS);   // row group (T.row0 >> 3) + g
+                    const bool row_shared = G == 1 ? rs_first : (rs_groups & (1u << g)) != 0;   // wave-uniform
+                    // (start values in SGPRs: the plane's first add takes them as its scalar operand.  Byte lanes: every partial sum is
+                    // <= the plane's final lane <= 255, no carry)
+                    uint32_t ks0[ND], ks1[ND];
+                    if (kmode == 3) {
+                        uint32_t kb0[ND], kb1[ND];
+                        key_entry(kt_group + (ra.x & 31u) * KEYTAB_DWORDS, ks0, ks1);
+                        key_entry(kt_group + (24 + (ra.y & 31u)) * KEYTAB_DWORDS, kb0, kb1);
+#pragma unroll
+                        for (int u = 0; u < ND; u++) { ks0[u] += kb0[u]; ks1[u] += kb1[u]; }
+                        read_phase_begin(prio);
+                        if (RUNS && (rs_groups & ROWS_RUN_SHARED) != 0) S::template accumulate_run<g, 3, (g > 0)>(off, ks0, ks1, W0, W1, Pm);
+                        else if (row_shared) S::template accumulate<g, 3, true>(off, toff, lbs, ks0, ks1, W0, W1);
+                        else S::template accumulate<g, 3>(off, toff, lbs, ks0, ks1, W0, W1);
+                    } else if (kmode == 1) {
+                        key_entry(kt_group + (ra.x & 31u) * KEYTAB_DWORDS, ks0, ks1);
+                        // (no instruction: the loads are waited for HERE, not at the first add inside the read phase)
+#pragma unroll
+                        for (int u = 0; u < ND; u++) asm volatile("" : "+s"(ks0[u]), "+s"(ks1[u]));
+                        read_phase_begin(prio);
+                        if (RUNS && (rs_groups & ROWS_RUN_SHARED) != 0) S::template accumulate_run<g, 1, (g > 0)>(off, ks0, ks1, W0, W1, Pm);
+                        else if (row_shared) S::template accumulate<g, 1, true>(off, toff, lbs, ks0, ks1, W0, W1);
+                        else S::template accumulate<g, 1>(off, toff, lbs, ks0, ks1, W0, W1);
+                    } else {
+                        read_phase_begin(prio);
+                        if (RUNS && (rs_groups & ROWS_RUN_SHARED) != 0) S::template accumulate_run<g, 0, (g > 0)>(off, ci, ci, W0, W1, Pm);
+                        else if (row_shared) S::template accumulate<g, 0, true>(off, toff, lbs, ci, ci, W0, W1);
+                        else S::template accumulate<g>(off, toff, lbs, ci, ci, W0, W1);
+                    }
+                } else {
+                    read_phase_begin(prio);
+                    S::template accumulate<g>(off, toff, lbs, ci, ci, W0, W1);
+                }
+                read_phase_end(prio);
+
+                // ---- threshold test: some (row, shift) lane has its top bit set <=> score >= threshold ----
+                uint32_t o0 = W0[0], o1 = W1[0];
+#pragma unroll
+                for (int u = 1; u < ND; u++) { o0 |= W0[u]; o1 |= W1[u]; }
+                if constexpr (!DEFER)
+                    if (__ballot(((o0 | o1) & 0x80808080u) != 0) == 0) return;
+                // ---- rare path (a hit somewhere in the wave): every lane appends ITS hits, one per turn ----
+                // hm: bit 8r + 7 set <=> row r of the group (r < 4) reached the threshold for this lane's column, bit 8r + 3 <=> row
+                // 4 + r.  The rows beyond the tile's last start at the initial lane value, which may itself have the top bit set:
+                // rm0 / rm1 (wave-uniform) leave them out.
+                const uint32_t rows_here = T.nrows - 8 * g;
+                const uint32_t rm0 = rows_here >= 4 ? 0x80808080u : 0x80808080u & ((1u << (8 * rows_here)) - 1u);
+                const uint32_t rm1 = rows_here >= 8 ? 0x80808080u : rows_here <= 4 ? 0u : 0x80808080u & ((1u << (8 * (rows_here - 4))) - 1u);
+                uint32_t hm = (o0 & rm0) | ((o1 & rm1) >> 4);
+                if (!interior) {  // wave-uniform: only edge tiles filter
+                    if (col >= col_end) hm = 0;
+                    if (T.diag != 0) {
+                        const int k = (int)col - (int)(T.row0 + 8 * g);   // the row this column IS, relative to the group
+                        if (T.diag == 1) {   // triangle: keep rows r with column > row, i.e. r < k
+                            const int k0 = k < 0 ? 0 : k > 4 ? 4 : k, k1 = k < 4 ? 0 : k > 8 ? 4 : k - 4;
+                            hm &= (k0 >= 4 ? 0x80808080u : 0x80808080u & ((1u << (8 * k0)) - 1u)) |
+                                  (k1 >= 4 ? 0x08080808u : 0x08080808u & ((1u << (8 * k1)) - 1u));
+                        } else if (k >= 0 && k < 8) {   // full square minus the diagonal
+                            hm &= ~(k < 4 ? 0x80u << (8 * k) : 0x08u << (8 * (k - 4)));
+                        }
+                    }
+                }
+                if constexpr (DEFER) {
+                    // history: this step's bits stay at 3 mod 4, the earlier steps' move down by one per step
+                    acc[g] = (acc[g] >> 1) | hm;
+                    if (!look) return;
+                    hm = acc[g];
+                    acc[g] = 0;
+                    if (__ballot(hm != 0) == 0) return;
+                }
+                // (the flush sits OUTSIDE the append loop: the rescoring kind needs most of the register file; inside the loop the
+                // compiler kept the loop's state in scratch memory for every turn of it)
+                for (;;) {
+                    bool full = false;
+                    for (;;) {
+                        const bool any = hm != 0;
+                        const uint64_t mask = __ballot(any);
+                        if (mask == 0) break;
+                        if (cnt + cnt_hi > (uint32_t)(STAGE_CAP - 64)) { full = true; break; }   // keep room for one wave of hits
+                        if (any) {
+                            const uint32_t q = (uint32_t)__builtin_ctz(hm);
+                            if constexpr (INLOOP) {
+                                // the hit's row r (bit 8r + 7: row r; bit 8r + 3: row 4 + r) is byte r of every plane's register pair:
+                                // one v_perm_b32 per plane (selector byte 0 = r: 0-3 pick from the low dword, 4-7 from the high one;
+                                // the other selector bytes give zero), the largest of them is the pair's lane = 128 - threshold + score
+                                const uint32_t r = (q >> 3) + 4u - (q & 4u);
+                                const uint32_t sel = 0x0c0c0c00u | r;
+                                uint32_t mx = __builtin_amdgcn_perm(W1[0], W0[0], sel);
+#pragma unroll
+                                for (int u = 1; u < ND; u++) mx = max(mx, __builtin_amdgcn_perm(W1[u], W0[u], sel));
+                                stage[cnt + mbcnt64(mask)] = colrel | ((uint32_t)(8 * g) + r) << 16 | (mx - 128u) << 24;
+                            } else {
+                                // the record: this step's column | the hit's bit << 16 | group << 21.  Which row and which of the quad's
+                                // steps the bit stands for is worked out by the flush, where all 64 lanes have a record: here a turn
+                                // runs for the few lanes that still have a hit, and every instruction of it costs the wave a VALU slot
+                                const uint32_t rec = (colrel | (uint32_t)g << 21) | q << 16;
+                                if constexpr (TWO && g == 1) stage[(uint32_t)(STAGE_CAP - 1) - (cnt_hi + mbcnt64(mask))] = rec;
+                                else stage[cnt + mbcnt64(mask)] = rec;
+                            }
+                            hm &= hm - 1u;   // clear the lowest set bit
+                        }
+                        if constexpr (TWO && g == 1) cnt_hi += (uint32_t)__popcll(mask);
+                        else cnt += (uint32_t)__popcll(mask);
+                    }
+                    if (!full) break;
+                    flush_stage_rows<X, D, CAP, EXACT_LB, G, MODE>(stage, cnt, cnt_hi, tab_addr, ka_lo, ka_hi);
+                    cnt = 0;
+                    cnt_hi = 0;
+                }
+            };
+            rows_for_each_group(std::make_integer_sequence<int, G>{}, one_group);
+        }
         kr_wave += 2 * 256;
     }
     flush_stage_rows<X, D, CAP, EXACT_LB, G, MODE>(stage, cnt, cnt_hi, tab_addr, ka_lo, ka_hi);
