@@ -32,6 +32,7 @@ HMK_SCAN_ALL_WINDOWS = 1
 SYMBOLS = [
     "hmk_abi_version", "hmk_last_kernel_ms", "hmk_create", "hmk_create_multi", "hmk_device_count", "hmk_destroy", "hmk_last_error", "hmk_set_sequences",
     "hmk_score_pairs_shifted", "hmk_score_with_shift", "hmk_score_pairs_local", "hmk_score_block_shifted", "hmk_score_block_local",
+    "hmk_score_pairs_global", "hmk_score_block_global", "hmk_neighbors_global", "hmk_search_global",
     "hmk_neighbors_shifted", "hmk_neighbors_local", "hmk_neighbors_shifted_dev", "hmk_compact_edges_dev", "hmk_pack_rows_dev", "hmk_unpack_rows_dev",
     "hmk_neighbors_last_plan", "hmk_neighbors_last_plan_shared", "hmk_search_shifted", "hmk_search_local", "hmk_search_best_shifted",
     "hmk_assign_shifted", "hmk_assign_local", "hmk_match_clusters_shifted", "hmk_match_clusters_local", "hmk_greedy_continue",
@@ -251,11 +252,14 @@ def _load():
     L.hmk_set_sequences.argtypes = [vp, p_u8, p_u32, p_i32, u32]
     L.hmk_score_pairs_shifted.argtypes = [vp, p_u32, p_u32, u64, i32, i32, p_i32]
     L.hmk_score_pairs_local.argtypes = [vp, p_u32, p_u32, u64, i32, i32, p_i32]
+    L.hmk_score_pairs_global.argtypes = [vp, p_u32, p_u32, u64, i32, i32, p_i32]
     L.hmk_score_with_shift.argtypes = [vp, p_u32, p_u32, u64, i32, i32, p_i32, p_i32]
     L.hmk_score_block_shifted.argtypes = [vp, u32, u32, u32, u32, i32, i32, p_i32]
     L.hmk_score_block_local.argtypes = [vp, u32, u32, u32, u32, i32, i32, p_i32]
+    L.hmk_score_block_global.argtypes = [vp, u32, u32, u32, u32, i32, i32, p_i32]
     L.hmk_neighbors_shifted.argtypes = [vp, i32, i32, i32, u32, u32, p_u64, u64, p_u64, C.POINTER(NeighborStats)]
     L.hmk_neighbors_local.argtypes = [vp, i32, i32, i32, u32, u32, p_u64, u64, p_u64, C.POINTER(NeighborStats)]
+    L.hmk_neighbors_global.argtypes = [vp, i32, i32, i32, u32, u32, p_u64, u64, p_u64, C.POINTER(NeighborStats)]
     L.hmk_neighbors_shifted_dev.argtypes = [vp, i32, i32, i32, u32, u32, vp, u64, vp, vp]
     L.hmk_compact_edges_dev.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp]
     L.hmk_pack_rows_dev.argtypes = [vp, vp, u64, vp, i32, vp, vp, u64, vp]
@@ -264,6 +268,7 @@ def _load():
     L.hmk_neighbors_last_plan_shared.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.hmk_search_shifted.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, p_u64, u64, p_u64, C.POINTER(NeighborStats)]
     L.hmk_search_local.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, p_u64, u64, p_u64, C.POINTER(NeighborStats)]
+    L.hmk_search_global.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, p_u64, u64, p_u64, C.POINTER(NeighborStats)]
     L.hmk_search_best_shifted.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, u32, p_u32, p_i32, p_u32, C.POINTER(NeighborStats)]
     L.hmk_assign_shifted.argtypes = [vp, u32, u32, u32, u32, p_u32, p_i32, u32, i32, i32, i32, u32, p_u32, p_i32, p_u32,
                                      C.POINTER(NeighborStats)]

@@ -319,6 +319,11 @@ class Context:
     def score_pairs_local(self, i, j, gap_open, gap_extend):
         return self._pairs(N.lib.hmk_score_pairs_local, i, j, gap_open, gap_extend)
 
+    def score_pairs_global(self, i, j, gap_open, gap_extend):
+        """GlobalAlignmentScorer: out[k] = global(seq1 = i[k], seq2 = j[k]), Gotoh's global alignment score with the affine gap
+        gap_open + (k - 1) gap_extend (penalties added; -127 <= gap_open <= gap_extend <= 0), end gaps charged."""
+        return self._pairs(N.lib.hmk_score_pairs_global, i, j, gap_open, gap_extend)
+
     def _block(self, fn, r0, r1, c0, c1, a, b):
         out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), dtype=np.int32)
         st = fn(self._h, r0, r1, c0, c1, int(a), int(b), _ptr(out, C.c_int32))
@@ -332,16 +337,18 @@ class Context:
     def score_block_local(self, r0, r1, c0, c1, gap_open, gap_extend):
         return self._block(N.lib.hmk_score_block_local, r0, r1, c0, c1, gap_open, gap_extend)
 
+    def score_block_global(self, r0, r1, c0, c1, gap_open, gap_extend):
+        return self._block(N.lib.hmk_score_block_global, r0, r1, c0, c1, gap_open, gap_extend)
+
     # -- neighbour graph ----------------------------------------------------------------
-    def neighbors_shifted(self, max_shift, shift_penalty, threshold, part=0, n_parts=1, capacity=None):
-        """-> (edges uint64[n_edges], NeighborStats)"""
+    def _neighbors(self, fn, a, b, threshold, part, n_parts, capacity):
+        """an all-vs-all pass into a host buffer, grown to the needed count on HMK_ERR_CAPACITY unless the caller fixed the capacity"""
         stats = N.NeighborStats()
         n_edges = C.c_uint64(0)
         cap = int(capacity) if capacity is not None else 1 << 20
         while True:
             buf = np.empty(max(cap, 1), dtype=np.uint64)
-            st = N.lib.hmk_neighbors_shifted(self._h, int(max_shift), int(shift_penalty), int(threshold), part, n_parts,
-                                             _ptr(buf, C.c_uint64), cap, C.byref(n_edges), C.byref(stats))
+            st = fn(self._h, int(a), int(b), int(threshold), part, n_parts, _ptr(buf, C.c_uint64), cap, C.byref(n_edges), C.byref(stats))
             if st == N.HMK_ERR_CAPACITY and capacity is None and int(n_edges.value) > cap:
                 cap = int(n_edges.value)
                 continue
@@ -349,21 +356,18 @@ class Context:
                 self._raise(st)
             return buf[:n_edges.value].copy(), stats
 
+    def neighbors_shifted(self, max_shift, shift_penalty, threshold, part=0, n_parts=1, capacity=None):
+        """-> (edges uint64[n_edges], NeighborStats)"""
+        return self._neighbors(N.lib.hmk_neighbors_shifted, max_shift, shift_penalty, threshold, part, n_parts, capacity)
+
     def neighbors_local(self, gap_open, gap_extend, threshold, part=0, n_parts=1, capacity=None):
         """LocalAlignmentScorer, all ordered pairs >= threshold -> (edges uint64[n_edges], NeighborStats)"""
-        stats = N.NeighborStats()
-        n_edges = C.c_uint64(0)
-        cap = int(capacity) if capacity is not None else 1 << 20
-        while True:
-            buf = np.empty(max(cap, 1), dtype=np.uint64)
-            st = N.lib.hmk_neighbors_local(self._h, int(gap_open), int(gap_extend), int(threshold), part, n_parts,
-                                           _ptr(buf, C.c_uint64), cap, C.byref(n_edges), C.byref(stats))
-            if st == N.HMK_ERR_CAPACITY and capacity is None and int(n_edges.value) > cap:
-                cap = int(n_edges.value)
-                continue
-            if st:
-                self._raise(st)
-            return buf[:n_edges.value].copy(), stats
+        return self._neighbors(N.lib.hmk_neighbors_local, gap_open, gap_extend, threshold, part, n_parts, capacity)
+
+    def neighbors_global(self, gap_open, gap_extend, threshold, part=0, n_parts=1, capacity=None):
+        """GlobalAlignmentScorer, pairs >= threshold -> (edges uint64[n_edges], NeighborStats): each unordered pair once (x < m)
+        under a symmetric matrix, else all ordered pairs with score(seq1 = m, seq2 = x)"""
+        return self._neighbors(N.lib.hmk_neighbors_global, gap_open, gap_extend, threshold, part, n_parts, capacity)
 
     # -- query-vs-reference search ------------------------------------------------------
     # Upload queries and references together once -- set_sequences(queries + references) -- and search the two index ranges:
@@ -394,6 +398,10 @@ class Context:
     def search_local(self, q0, q1, r0, r1, gap_open, gap_extend, threshold, capacity=None):
         """The same with LocalAlignmentScorer(seq1 = query, seq2 = reference) -> (edges uint64[n_edges], NeighborStats)"""
         return self._search(N.lib.hmk_search_local, q0, q1, r0, r1, gap_open, gap_extend, threshold, capacity)
+
+    def search_global(self, q0, q1, r0, r1, gap_open, gap_extend, threshold, capacity=None):
+        """The same with GlobalAlignmentScorer(seq1 = query, seq2 = reference) -> (edges uint64[n_edges], NeighborStats)"""
+        return self._search(N.lib.hmk_search_global, q0, q1, r0, r1, gap_open, gap_extend, threshold, capacity)
 
     # -- scanning peptides along long targets ---------------------------------------------
     def set_targets(self, seqs=None, residues=None, offsets=None):

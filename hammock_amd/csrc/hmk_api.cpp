@@ -199,6 +199,12 @@ int hmk_score_pairs_local(hmk_ctx *ctx, const uint32_t *i, const uint32_t *j, ui
     return score_pairs(ctx, 1, i, j, n_pairs, gap_open, gap_extend, out);
 }
 
+int hmk_score_pairs_global(hmk_ctx *ctx, const uint32_t *i, const uint32_t *j, uint64_t n_pairs, int gap_open,
+                           int gap_extend, int32_t *out) {
+    if (!ctx) return fail(nullptr, HMK_ERR_BAD_ARG, "null context");
+    return score_pairs(ctx, SCORER_GLOBAL, i, j, n_pairs, gap_open, gap_extend, out);
+}
+
 int hmk_score_block_shifted(hmk_ctx *ctx, uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1, int max_shift,
                             int shift_penalty, int32_t *out) {
     if (!ctx) return fail(nullptr, HMK_ERR_BAD_ARG, "null context");
@@ -209,6 +215,12 @@ int hmk_score_block_local(hmk_ctx *ctx, uint32_t r0, uint32_t r1, uint32_t c0, u
                           int gap_extend, int32_t *out) {
     if (!ctx) return fail(nullptr, HMK_ERR_BAD_ARG, "null context");
     return score_block(ctx, 1, r0, r1, c0, c1, gap_open, gap_extend, out);
+}
+
+int hmk_score_block_global(hmk_ctx *ctx, uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1, int gap_open,
+                           int gap_extend, int32_t *out) {
+    if (!ctx) return fail(nullptr, HMK_ERR_BAD_ARG, "null context");
+    return score_block(ctx, SCORER_GLOBAL, r0, r1, c0, c1, gap_open, gap_extend, out);
 }
 
 int hmk_neighbors_shifted_dev(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, uint32_t part,
@@ -333,6 +345,39 @@ int hmk_neighbors_local(hmk_ctx *ctx, int gap_open, int gap_extend, int threshol
         stats->n_edges = total;
         stats->pairs_scored = ctx->plan_local.pairs;
         stats->n_tiles = ctx->plan_local.n_tiles;
+        stats->kernel_ms = ms;
+    }
+    if (total > capacity) return fail(ctx, HMK_ERR_CAPACITY, "edge buffer too small: " + std::to_string(total) + " needed");
+    if (total && !edges) return fail(ctx, HMK_ERR_BAD_ARG, "null edge buffer");
+    return ctx->edges.fetch(ctx, counts, edges);
+}
+
+int hmk_neighbors_global(hmk_ctx *ctx, int gap_open, int gap_extend, int threshold, uint32_t part, uint32_t n_parts,
+                         uint64_t *edges, uint64_t capacity, uint64_t *n_edges, hmk_neighbor_stats *stats) {
+    if (!ctx) return fail(nullptr, HMK_ERR_BAD_ARG, "null context");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    refresh_switches(ctx);
+    if (!n_edges) return fail(ctx, HMK_ERR_BAD_ARG, "n_edges must not be null");
+    int st = check_global_fits(ctx, gap_open, gap_extend, threshold);
+    if (st) return st;
+    // a symmetric matrix: every unordered pair once (the triangle plan); else all ordered pairs, the local pass's plan
+    PlanLocal &pl = ctx->symmetric ? ctx->plan_global : ctx->plan_local;
+    unsigned long long counts[HMK_EDGE_SHARDS];
+    double ms = 0;
+    st = neighbors_grow(ctx, capacity, counts, &ms, [&](uint64_t *d_edges, uint64_t cap, unsigned long long *d_counts) {
+        const int rc = build_plan_local(ctx, pl, part, n_parts, ctx->symmetric);
+        if (rc) return rc;
+        return launch_plan_local(ctx, pl, SCORER_GLOBAL, gap_open, gap_extend, threshold, d_edges, cap, d_counts, nullptr);
+    });
+    if (st) return st;
+    const uint64_t total = total_of(counts);
+    *n_edges = total;
+    if (stats) {
+        *stats = hmk_neighbor_stats{};
+        stats->n_edges = total;
+        stats->pairs_scored = pl.pairs;
+        stats->n_tiles = pl.n_tiles;
+        stats->symmetric = pl.triangle ? 1u : 0u;
         stats->kernel_ms = ms;
     }
     if (total > capacity) return fail(ctx, HMK_ERR_CAPACITY, "edge buffer too small: " + std::to_string(total) + " needed");

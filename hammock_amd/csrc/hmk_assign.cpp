@@ -76,7 +76,7 @@ int cluster_pass(hmk_ctx *ctx, bool local, Plan &pl, PlanLocal &pll, int a, int 
     double ms = 0;
     st = neighbors_grow(ctx, 0, counts, &ms, [&](uint64_t *d_edges, uint64_t cap, unsigned long long *d_counts) {
         return !local ? launch_plan(ctx, pl, a, b, thr, d_edges, cap, d_counts, nullptr)
-                      : launch_plan_local(ctx, pll, a, b, thr, d_edges, cap, d_counts, nullptr);
+                      : launch_plan_local(ctx, pll, SCORER_LOCAL, a, b, thr, d_edges, cap, d_counts, nullptr);
     });
     if (st) return st;
     *total = total_of(counts);

@@ -183,6 +183,7 @@ struct Plan : PlanArrays {
 struct PlanLocal : PlanArrays {
     bool valid = false;
     uint32_t part = 0, n_parts = 1;
+    bool triangle = false;   // unordered pairs only (a symmetric GlobalAlignmentScorer pass): classes la <= lb, column > row on la == lb
     uint32_t n_tiles = 0;
     uint64_t pairs = 0;
     uint32_t q0 = 0, q1 = 0, r0 = 0, r1 = 0;   // a search plan (build_plan_local_search): its query and reference ranges
@@ -222,6 +223,7 @@ struct hmk_ctx {
 
     Plan plan;
     PlanLocal plan_local;
+    PlanLocal plan_global;         // hmk_neighbors_global under a symmetric matrix: the triangle (every other global pass takes the local plans)
     Plan plan_search;              // the query-vs-reference searches' plans: cached apart from the all-vs-all ones, so that
     PlanLocal plan_local_search;   // searches and clustering calls on one context do not rebuild each other's
     Plan plan_assign;              // the assignments' plans (hmk_assign.cpp: members = the search's queries): cached apart too
@@ -378,7 +380,9 @@ void classify(const hmk_ctx *ctx, int la, int lb, int X, int p, int thr, TileCla
               long long *u8_row_limit = nullptr);
 // key_sort_ok: a plain single-part pass (no band, no degree counters) that may take the key-sorted order
 int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_parts, int64_t band_rows = -1, bool key_sort_ok = false);
-int build_plan_local(hmk_ctx *ctx, uint32_t part, uint32_t n_parts);
+// all ordered pairs of the set (LocalAlignmentScorer; GlobalAlignmentScorer under an asymmetric matrix), or (triangle) every
+// unordered pair once, into the plan slot `pl`
+int build_plan_local(hmk_ctx *ctx, PlanLocal &pl, uint32_t part, uint32_t n_parts, bool triangle = false);
 // the rectangle queries [q0, q1) x references [r0, r1) (disjoint, non-empty) into the plan slot `pl` (the search's, the
 // assignment's, ... own)
 int build_plan_search(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
@@ -419,7 +423,12 @@ int launch_plan(hmk_ctx *ctx, const Plan &pl, int X, int p, int thr, void *d_edg
 bool local_enc(const hmk_ctx *ctx, int gap_open, int gap_extend);
 bool local_literal(const hmk_ctx *ctx, int gap_open, int gap_extend);
 int check_local_fits(hmk_ctx *ctx, int gap_open, int gap_extend, int thr);
-int launch_plan_local(hmk_ctx *ctx, const PlanLocal &pl, int gap_open, int gap_extend, int thr, uint64_t *d_edges, uint64_t capacity,
+// the gapped scorers of the PlanLocal passes (launch_pairs' numbering)
+enum { SCORER_LOCAL = 1, SCORER_GLOBAL = 2 };
+// GlobalAlignmentScorer's argument checks (made before the device is looked at): -127 <= gap_open <= gap_extend <= 0, the
+// threshold within [-30000, 30000], 32 * max(0, max M) <= 32767
+int check_global_fits(hmk_ctx *ctx, int gap_open, int gap_extend, int thr);
+int launch_plan_local(hmk_ctx *ctx, const PlanLocal &pl, int scorer, int gap_open, int gap_extend, int thr, uint64_t *d_edges, uint64_t capacity,
                       unsigned long long *d_counts, hipStream_t stream);
 int neighbors_internal(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_parts, uint64_t want_cap,
                        unsigned long long counts[HMK_EDGE_SHARDS], double *kernel_ms);

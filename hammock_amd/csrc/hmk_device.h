@@ -99,6 +99,62 @@ __device__ __forceinline__ int local_score_literal(const int *M, const uint8_t *
     return global_max;                                                                 // :85
 }
 
+// GlobalAlignmentScorer (hammock_hip.h: hmk_score_pairs_global): Gotoh's global alignment with affine gaps, end gaps
+// charged like inner ones; seq1 = lines, seq2 = columns, penalties are added (<= 0).
+//     H[0][0] = 0, H[0][j] = E[0][j] = open + (j - 1) ext, H[i][0] = F[i][0] = open + (i - 1) ext, E[i][0] = F[0][j] = -inf
+//     E[i][j] = max(E[i][j-1] + ext, H[i][j-1] + open),  F[i][j] = max(F[i-1][j] + ext, H[i-1][j] + open)
+//     H[i][j] = max(H[i-1][j-1] + M[seq1[i-1]][seq2[j-1]], E[i][j], F[i][j]),  score = H[len1][len2]
+// -inf is a sentinel far below every real value (H >= the all-gap alignment >= -8,128 for penalties >= -127 and lengths <= 32)
+// that one more penalty cannot wrap.
+constexpr int GLOBAL_NEG_INF = -(1 << 28);
+
+// The literal form: all arithmetic in int32.  One DP line lives in LDS as row[col * stride], H in the low and F in the high
+// int16 half of a cell: the host admits only 32 * max(0, max M) <= 32767 (the int16 score of a packed edge), every real H / F
+// is >= -8,128 - 2 * 127, and -inf is stored as -32768 -- still below every real candidate after one more penalty.
+__device__ __forceinline__ int global_score_literal(const int *M, const uint8_t *seq1, int len1, const uint8_t *seq2, int len2,
+                                                    int gap_open, int gap_extend, uint32_t *row, int stride) {
+    auto cell = [](int h, int f) { return ((uint32_t)h & 0xFFFFu) | ((uint32_t)max(f, -32768) << 16); };
+    row[0] = cell(0, GLOBAL_NEG_INF);
+    for (int col = 1; col <= len2; col++) row[col * stride] = cell(gap_open + (col - 1) * gap_extend, GLOBAL_NEG_INF);
+    for (int line = 1; line <= len1; line++) {
+        const int a = seq1[line - 1] * 24;
+        int diag_h = (int)(int16_t)row[0];                        // H[line-1][0]
+        int left_h = gap_open + (line - 1) * gap_extend;          // H[line][0]
+        int e = GLOBAL_NEG_INF;                                   // E[line][0]
+        row[0] = cell(left_h, left_h);                            // F[line][0] = H[line][0]
+        for (int col = 1; col <= len2; col++) {
+            const uint32_t upc = row[col * stride];
+            const int up_h = (int)(int16_t)upc, up_f = (int)upc >> 16;
+            e = max(e + gap_extend, left_h + gap_open);
+            const int f = max(up_f + gap_extend, up_h + gap_open);
+            const int h = max(diag_h + M[a + seq2[col - 1]], max(e, f));
+            row[col * stride] = cell(h, f);
+            diag_h = up_h;
+            left_h = h;
+        }
+    }
+    return (int)(int16_t)row[len2 * stride];
+}
+
+// query profiles of R rows into LDS: entry (r, c, iq) = four int8 (score * scale) for lines 4 iq .. 4 iq + 3;
+// -128 for the pad residue (c == 24) and for lines beyond the row's length
+template <int R>
+__device__ __forceinline__ void build_profiles(uint32_t *q, const int8_t *m8, const uint8_t *rowres, const int *row_len,
+                                               uint32_t nrows, int scale, int tid) {
+    for (int e = tid; e < R * 25 * 8; e += 256) {
+        const int r = e / 200, rem = e - r * 200, c = rem >> 3, iq = rem & 7;
+        const int l1 = (uint32_t)r < nrows ? row_len[r] : 0;
+        uint32_t dw = 0;
+        for (int k = 0; k < 4; k++) {
+            const int i = iq * 4 + k;
+            int v = -128;
+            if (i < l1 && c < 24) v = m8[rowres[r * 32 + i] * 24 + c] * scale;
+            dw |= ((uint32_t)v & 0xFFu) << (8 * k);
+        }
+        q[e] = dw;
+    }
+}
+
 // per-lane LDS staging of one sequence: 9-dword stride keeps the byte reads of
 // the 64 lanes on different banks
 constexpr int SEQ_STRIDE_DW = 9;

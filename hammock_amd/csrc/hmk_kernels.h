@@ -34,7 +34,8 @@ hipError_t launch_rows_keytab(const uint8_t *res_sorted, uint32_t lpad, uint32_t
 hipError_t launch_neighbors_direct(const NeighborParams &P, uint32_t tile_base, uint32_t n_tiles,
                                    const int32_t *d_matrix, int max_shift, int shift_penalty, int threshold,
                                    hipStream_t s);
-// scorer 0: ShiftedScorer(a = maxShift, b = shiftPenalty); 1: LocalAlignmentScorer(a = gapOpen, b = gapExtend).
+// scorer 0: ShiftedScorer(a = maxShift, b = shiftPenalty); 1: LocalAlignmentScorer(a = gapOpen, b = gapExtend);
+// 2: GlobalAlignmentScorer(a = gapOpen, b = gapExtend).
 // pi == nullptr: dense block mode, pair k = (r0 + k / width, c0 + k % width).
 hipError_t launch_probe_spin(unsigned long long *when, long long ticks, hipStream_t s);   // when[0] / [1]: start / end, 100 MHz wall clock
 hipError_t launch_pairs(int scorer, const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix,
@@ -49,6 +50,11 @@ hipError_t launch_neighbors_local(int lbmax, bool enc, bool force_signed, bool f
 // the same pass with the literal DP: any gap penalties, any matrix range
 hipError_t launch_neighbors_local_literal(const NeighborParams &P, uint32_t tile_base, uint32_t n_tiles, const int32_t *d_matrix,
                                           int gap_open, int gap_extend, int threshold, hipStream_t s);
+
+// GlobalAlignmentScorer on the same tiles (k_global.hip), thresholded: the register-resident DP, or (literal: a matrix entry
+// outside +-127) global_score_literal; lbmax: the set's longest sequence
+hipError_t launch_neighbors_global(int lbmax, bool literal, const NeighborParams &P, uint32_t tile_base, uint32_t n_tiles,
+                                   const int32_t *d_matrix, int gap_open, int gap_extend, int threshold, hipStream_t s);
 
 // edge segments -> CSR (start[row_limit + 1], adj[]) on the device; rows at and beyond row_limit are left out
 // (row_limit = n: the whole graph).  deg: zeroed uint32[row_limit]; cursor: zeroed uint32[2 row_limit], whose first half

@@ -1,5 +1,5 @@
 // hmk_pass.cpp -- launching the neighbour passes (neighbors_dev_locked: groups, side streams, band / rest), the host-buffer
-// form that grows its edge buffer (neighbors_grow), the LocalAlignmentScorer pass, the pair and block probes.
+// form that grows its edge buffer (neighbors_grow), the LocalAlignmentScorer / GlobalAlignmentScorer passes, the pair and block probes.
 #include "hmk_ctx.h"
 
 namespace hmk { namespace impl {
@@ -144,9 +144,9 @@ int neighbors_local_dev_locked(hmk_ctx *ctx, int gap_open, int gap_extend, int t
     if (st) return st;
     st = check_local_fits(ctx, gap_open, gap_extend, thr);
     if (st) return st;
-    st = build_plan_local(ctx, part, n_parts);
+    st = build_plan_local(ctx, ctx->plan_local, part, n_parts);
     if (st) return st;
-    return launch_plan_local(ctx, ctx->plan_local, gap_open, gap_extend, thr, d_edges, capacity, d_counts, stream);
+    return launch_plan_local(ctx, ctx->plan_local, SCORER_LOCAL, gap_open, gap_extend, thr, d_edges, capacity, d_counts, stream);
 }
 
 // the striped register kernels take gap penalties <= 0 and int8 matrix entries; anything else (the reference imposes
@@ -165,9 +165,25 @@ int check_local_fits(hmk_ctx *ctx, int gap_open, int gap_extend, int thr) {
     return HMK_OK;
 }
 
-int launch_plan_local(hmk_ctx *ctx, const PlanLocal &pl, int gap_open, int gap_extend, int thr, uint64_t *d_edges, uint64_t capacity,
+// GlobalAlignmentScorer: the recurrence is the maximum over all alignments only for gap_open <= gap_extend <= 0; the edge scores
+// travel as int16 (the lowest one, the all-gap alignment, is >= -8,128 by the penalty bound)
+int check_global_fits(hmk_ctx *ctx, int gap_open, int gap_extend, int thr) {
+    if (gap_open < -127 || gap_open > gap_extend || gap_extend > 0)
+        return fail(ctx, HMK_ERR_BAD_ARG, "GlobalAlignmentScorer needs -127 <= gap_open <= gap_extend <= 0, found " + std::to_string(gap_open) +
+                                           " / " + std::to_string(gap_extend));
+    if (thr < -30000 || thr > 30000) return fail(ctx, HMK_ERR_BAD_ARG, "threshold outside [-30000, 30000]");
+    const long long top = 32LL * std::max(0, ctx->max_m);
+    if (top > 32767)
+        return fail(ctx, HMK_ERR_BAD_ARG, "scores up to " + std::to_string(top) + " are possible with this matrix: they do not fit the int16 score "
+                                           "of a packed edge");
+    return HMK_OK;
+}
+
+// the launch of a built PlanLocal with one of the gapped scorers.  GlobalAlignmentScorer on a triangle plan (a symmetric matrix)
+// stores each unordered pair as (min, max); every other pass stores m = row = seq1.
+int launch_plan_local(hmk_ctx *ctx, const PlanLocal &pl, int scorer, int gap_open, int gap_extend, int thr, uint64_t *d_edges, uint64_t capacity,
                       unsigned long long *d_counts, hipStream_t stream) {
-    const bool literal = local_literal(ctx, gap_open, gap_extend);
+    const bool literal = scorer == SCORER_LOCAL && local_literal(ctx, gap_open, gap_extend);
     HIPCHK(ctx, hipMemsetAsync(d_counts, 0, HMK_EDGE_SHARDS * sizeof(unsigned long long), stream));
     NeighborParams P{};
     P.res_sorted = pl.d_res_sorted;
@@ -180,9 +196,12 @@ int launch_plan_local(hmk_ctx *ctx, const PlanLocal &pl, int gap_open, int gap_e
     P.cap_per_shard = capacity / HMK_EDGE_SHARDS;
     P.n_tiles = pl.n_tiles;
     P.lpad = 32;
-    P.symmetric = 0;
-    P.row_is_m = 1;
-    if (literal)
+    P.symmetric = pl.triangle ? 1u : 0u;
+    P.row_is_m = pl.triangle ? 0u : 1u;
+    if (scorer == SCORER_GLOBAL)   // the register DP holds the matrix as int8 profiles
+        HIPCHK(ctx, launch_neighbors_global(ctx->max_len, ctx->min_m < -127 || ctx->max_m > 127, P, 0, pl.n_tiles, ctx->d_M.as<int32_t>(), gap_open,
+                                            gap_extend, thr, stream));
+    else if (literal)
         HIPCHK(ctx, launch_neighbors_local_literal(P, 0, pl.n_tiles, ctx->d_M.as<int32_t>(), gap_open, gap_extend, thr, stream));
     else
         HIPCHK(ctx, launch_neighbors_local(ctx->max_len, local_enc(ctx, gap_open, gap_extend), ctx->sw.local_signed, ctx->sw.local_no_pk, P, 0, pl.n_tiles,
@@ -220,7 +239,9 @@ int score_pairs(hmk_ctx *ctx, int scorer, const uint32_t *i, const uint32_t *j, 
                 int32_t *out, int32_t *out_shift) {
     std::lock_guard<std::mutex> lock(ctx->mu);
     refresh_switches(ctx);
-    int st = need_device(ctx);
+    int st = scorer == SCORER_GLOBAL ? check_global_fits(ctx, a, b, 0) : HMK_OK;
+    if (st) return st;
+    st = need_device(ctx);
     if (st) return st;
     if (scorer == 0 && a < 0) return fail(ctx, HMK_ERR_BAD_ARG, "max_shift must be >= 0");
     st = check_pairs(ctx, i, j, n_pairs, scorer == 0, a);
@@ -261,7 +282,9 @@ int score_block(hmk_ctx *ctx, int scorer, uint32_t r0, uint32_t r1, uint32_t c0,
                 int32_t *out) {
     std::lock_guard<std::mutex> lock(ctx->mu);
     refresh_switches(ctx);
-    int st = need_device(ctx);
+    int st = scorer == SCORER_GLOBAL ? check_global_fits(ctx, a, b, 0) : HMK_OK;
+    if (st) return st;
+    st = need_device(ctx);
     if (st) return st;
     if (ctx->n == 0) return fail(ctx, HMK_ERR_NO_SEQUENCES, "no sequences set (hmk_set_sequences)");
     if (r0 > r1 || c0 > c1 || r1 > ctx->n || c1 > ctx->n) return fail(ctx, HMK_ERR_BAD_ARG, "block outside [0, n)");

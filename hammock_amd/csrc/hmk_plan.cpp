@@ -1,7 +1,7 @@
 // hmk_plan.cpp -- the planner of every neighbour pass.  The steps all plans share (length sort, kernel choice per class, the tiles
 // of a row chunk, launch-group order, device copies, parameter checks); score bounds and lane classes (classify); the builders:
 // build_plan (all-vs-all: triangle or full square), build_plan_search / build_plan_triangle (the rectangle of two ranges, the
-// triangle of one), build_plan_local and build_plan_local_search (the LocalAlignmentScorer passes).
+// triangle of one), build_plan_local and build_plan_local_search (the LocalAlignmentScorer and GlobalAlignmentScorer passes).
 #include "hmk_ctx.h"
 
 namespace hmk { namespace impl {
@@ -256,7 +256,7 @@ void free_plans(hmk_ctx *ctx) {
     for (Plan *pl : {&ctx->plan, &ctx->plan_search, &ctx->plan_assign, &ctx->plan_match, &ctx->plan_continue, &ctx->plan_continue_tri,
                      &ctx->plan_merge})
         free_plan(*pl);
-    for (PlanLocal *pl : {&ctx->plan_local, &ctx->plan_local_search, &ctx->plan_local_assign, &ctx->plan_local_match}) free_plan_local(*pl);
+    for (PlanLocal *pl : {&ctx->plan_local, &ctx->plan_global, &ctx->plan_local_search, &ctx->plan_local_assign, &ctx->plan_local_match}) free_plan_local(*pl);
 }
 
 // Lane layout of one (row length, column length) class; see DESIGN.md "SWAR tables".
@@ -718,8 +718,9 @@ int build_plan_triangle(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t 
 // ---- LocalAlignmentScorer passes: tiles of ordered (row length, column length) classes, 16 rows (the local kernels' rows per
 // tile) against full column runs; sequences in 32-byte rows ------------------------------------------------------------------
 // rows = the buckets bq, columns = br of the sorted order `perm`; `self`: both are the same set, no sequence is paired with itself
+// (2: all ordered pairs; 1: every unordered pair once -- the classes la <= lb, column > row where la == lb)
 static int finish_plan_local(hmk_ctx *ctx, PlanLocal &pl, const Buckets &bq, const Buckets &br, const std::vector<uint32_t> &perm,
-                             uint32_t cols, uint32_t part, uint32_t n_parts, bool self) {
+                             uint32_t cols, uint32_t part, uint32_t n_parts, uint32_t self) {
     std::vector<TileClass> classes;
     std::vector<Tile> tiles;
     constexpr uint32_t R = 16;
@@ -728,7 +729,7 @@ static int finish_plan_local(hmk_ctx *ctx, PlanLocal &pl, const Buckets &bq, con
     for (int la = 1; la <= HMK_MAX_LEN; la++) {          // rows = seq1 (lines)
         const uint32_t rb = bq[la], re = bq[la + 1];
         if (rb == re) continue;
-        for (int lb = 1; lb <= HMK_MAX_LEN; lb++) {      // columns = seq2
+        for (int lb = self == 1 ? la : 1; lb <= HMK_MAX_LEN; lb++) {      // columns = seq2
             const uint32_t cb = br[lb], ce = br[lb + 1];
             if (cb == ce) continue;
             TileClass tc{};
@@ -738,7 +739,8 @@ static int finish_plan_local(hmk_ctx *ctx, PlanLocal &pl, const Buckets &bq, con
             classes.push_back(tc);
             for (uint32_t r0 = rb; r0 < re; r0 += R) {
                 if ((row_chunk_counter++ % n_parts) != part) continue;
-                pl.pairs += emit_tiles(tiles, cls, r0, std::min(R, re - r0), cb, ce, cols, false, self && la == lb ? 2u : 0u);
+                // (triangle: the columns after the chunk's first row)
+                pl.pairs += emit_tiles(tiles, cls, r0, std::min(R, re - r0), self == 1 && la == lb ? r0 + 1 : cb, ce, cols, false, la == lb ? self : 0u);
             }
         }
     }
@@ -747,9 +749,8 @@ static int finish_plan_local(hmk_ctx *ctx, PlanLocal &pl, const Buckets &bq, con
     return upload_plan(ctx, pl, perm, 32, 0, 1, classes, tiles);
 }
 
-int build_plan_local(hmk_ctx *ctx, uint32_t part, uint32_t n_parts) {
-    PlanLocal &pl = ctx->plan_local;
-    if (pl.valid && pl.part == part && pl.n_parts == n_parts) return HMK_OK;
+int build_plan_local(hmk_ctx *ctx, PlanLocal &pl, uint32_t part, uint32_t n_parts, bool triangle) {
+    if (pl.valid && pl.part == part && pl.n_parts == n_parts && pl.triangle == triangle) return HMK_OK;
     free_plan_local(pl);
     const uint32_t n = ctx->n;
     if (n == 0) return fail(ctx, HMK_ERR_NO_SEQUENCES, "no sequences set (hmk_set_sequences)");
@@ -757,8 +758,9 @@ int build_plan_local(hmk_ctx *ctx, uint32_t part, uint32_t n_parts) {
     Buckets bucket, none;
     std::vector<uint32_t> perm;
     sort_by_length(ctx, 0, n, 0, 0, bucket, none, perm);
-    const int st = finish_plan_local(ctx, pl, bucket, bucket, perm, 16384, part, n_parts, true);
+    const int st = finish_plan_local(ctx, pl, bucket, bucket, perm, 16384, part, n_parts, triangle ? 1u : 2u);
     if (st) return st;
+    pl.triangle = triangle;
     pl.valid = true;
     return HMK_OK;
 }
@@ -776,7 +778,7 @@ int build_plan_local_search(hmk_ctx *ctx, PlanLocal &pl, uint32_t q0, uint32_t q
     // column runs of up to 16,384 (build_plan_local), shorter while the rectangle would not fill the GPU once (few queries)
     uint32_t cols = 16384;
     while (cols > 1024 && row_chunks * (((uint64_t)(r1 - r0) + cols - 1) / cols) < 4 * 1792) cols /= 2;
-    const int st = finish_plan_local(ctx, pl, bq, br, perm, cols, 0, 1, false);
+    const int st = finish_plan_local(ctx, pl, bq, br, perm, cols, 0, 1, 0u);
     if (st) return st;
     pl.q0 = q0; pl.q1 = q1; pl.r0 = r0; pl.r1 = r1;
     pl.valid = true;

@@ -1,5 +1,5 @@
 // hmk_search.cpp -- query-vs-reference search: queries [q0, q1) against references [r0, r1) of the hmk_set_sequences set, two
-// disjoint ranges.  The passes over the rectangle's plans (hmk_plan.cpp: build_plan_search, build_plan_local_search), the query-side
+// disjoint ranges, with any of the three scorers.  The passes over the rectangle's plans (hmk_plan.cpp: build_plan_search, build_plan_local_search), the query-side
 // orientation and best-k selection on the device (k_search.hip), the extern "C" entry points.
 #include "hmk_ctx.h"
 
@@ -7,7 +7,7 @@ namespace hmk { namespace impl {
 
 namespace {
 
-enum { SEARCH_SHIFTED = 0, SEARCH_LOCAL = 1 };
+enum { SEARCH_SHIFTED = 0, SEARCH_LOCAL = SCORER_LOCAL, SEARCH_GLOBAL = SCORER_GLOBAL };   // (the gapped ones: launch_plan_local's numbering)
 
 // the argument checks every search makes before it looks at the device (a host-only context answers them too)
 int check_ranges(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1) {
@@ -25,7 +25,7 @@ int search_pass(hmk_ctx *ctx, int scorer, int a, int b, int thr, uint32_t q0, ui
     if (st) return st;
     st = neighbors_grow(ctx, want_cap, counts, ms, [&](uint64_t *d_edges, uint64_t cap, unsigned long long *d_counts) {
         return scorer == SEARCH_SHIFTED ? launch_plan(ctx, ctx->plan_search, a, b, thr, d_edges, cap, d_counts, nullptr)
-                                        : launch_plan_local(ctx, ctx->plan_local_search, a, b, thr, d_edges, cap, d_counts, nullptr);
+                                        : launch_plan_local(ctx, ctx->plan_local_search, scorer, a, b, thr, d_edges, cap, d_counts, nullptr);
     });
     if (st) return st;
     const uint64_t total = total_of(counts);
@@ -51,6 +51,8 @@ int search_edges(hmk_ctx *ctx, int scorer, uint32_t q0, uint32_t q1, uint32_t r0
     int st = check_ranges(ctx, q0, q1, r0, r1);
     if (st) return st;
     *n_edges = 0;
+    if (scorer == SEARCH_GLOBAL) st = check_global_fits(ctx, a, b, thr);   // (before the device is looked at, like the ranges)
+    if (st) return st;
     st = need_device(ctx);
     if (st) return st;
     hmk_neighbor_stats S{};
@@ -59,7 +61,7 @@ int search_edges(hmk_ctx *ctx, int scorer, uint32_t q0, uint32_t q1, uint32_t r0
         if (stats) *stats = S;
         return HMK_OK;
     }
-    st = scorer == SEARCH_SHIFTED ? check_shifted(ctx, a, b, thr, q0, q1, r0, r1) : check_local_fits(ctx, a, b, thr);
+    st = scorer == SEARCH_SHIFTED ? check_shifted(ctx, a, b, thr, q0, q1, r0, r1) : scorer == SEARCH_LOCAL ? check_local_fits(ctx, a, b, thr) : HMK_OK;
     if (st) return st;
     unsigned long long counts[HMK_EDGE_SHARDS];
     double ms = 0;
@@ -91,6 +93,11 @@ int hmk_search_shifted(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint
 int hmk_search_local(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, int gap_open, int gap_extend, int threshold,
                      uint64_t *edges, uint64_t capacity, uint64_t *n_edges, hmk_neighbor_stats *stats) {
     return search_edges(ctx, SEARCH_LOCAL, q0, q1, r0, r1, gap_open, gap_extend, threshold, edges, capacity, n_edges, stats);
+}
+
+int hmk_search_global(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, int gap_open, int gap_extend, int threshold,
+                      uint64_t *edges, uint64_t capacity, uint64_t *n_edges, hmk_neighbor_stats *stats) {
+    return search_edges(ctx, SEARCH_GLOBAL, q0, q1, r0, r1, gap_open, gap_extend, threshold, edges, capacity, n_edges, stats);
 }
 
 int hmk_search_best_shifted(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1, int max_shift, int shift_penalty,

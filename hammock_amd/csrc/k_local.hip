@@ -104,25 +104,6 @@ __device__ __forceinline__ int sw_row(uint32_t row_q_addr, int strips, int ncols
     }
 }
 
-// query profiles of R rows into LDS: entry (r, c, iq) = four int8 (score * scale) for lines 4 iq .. 4 iq + 3;
-// -128 for the pad residue (c == 24) and for lines beyond the row's length
-template <int R>
-__device__ __forceinline__ void build_profiles(uint32_t *q, const int8_t *m8, const uint8_t *rowres, const int *row_len,
-                                               uint32_t nrows, int scale, int tid) {
-    for (int e = tid; e < R * 25 * 8; e += 256) {
-        const int r = e / 200, rem = e - r * 200, c = rem >> 3, iq = rem & 7;
-        const int l1 = (uint32_t)r < nrows ? row_len[r] : 0;
-        uint32_t dw = 0;
-        for (int k = 0; k < 4; k++) {
-            const int i = iq * 4 + k;
-            int v = -128;
-            if (i < l1 && c < 24) v = m8[rowres[r * 32 + i] * 24 + c] * scale;
-            dw |= ((uint32_t)v & 0xFFu) << (8 * k);
-        }
-        q[e] = dw;
-    }
-}
-
 // -----------------------------------------------------------------------------
 // k_local_block: LocalAlignmentScorer for a dense block, register-resident DP
 // -----------------------------------------------------------------------------

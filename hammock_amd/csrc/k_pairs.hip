@@ -1,11 +1,11 @@
 // k_pairs.hip -- one pair per lane, literal loops: the parity probes behind hmk_score_pairs_* and the
-// literal tier of hmk_score_block_* (ShiftedScorer.java:48-95, LocalAlignmentScorer.java:27-86).
+// literal tier of hmk_score_block_* (ShiftedScorer.java:48-95, LocalAlignmentScorer.java:27-86, GlobalAlignmentScorer).
 #include "hmk_device.h"
 #include "hmk_grid.h"
 
 namespace hmk {
 
-template <int SCORER>  // 0 shifted, 1 local
+template <int SCORER>  // 0 shifted, 1 local, 2 global
 __global__ void __launch_bounds__(256)
 k_pairs(const uint8_t *__restrict__ res32, const uint8_t *__restrict__ len, const int32_t *__restrict__ Mg,
         const uint32_t *__restrict__ pi, const uint32_t *__restrict__ pj, uint64_t n_pairs,
@@ -14,7 +14,7 @@ k_pairs(const uint8_t *__restrict__ res32, const uint8_t *__restrict__ len, cons
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     int *M = reinterpret_cast<int *>(smem);                                   // 576 dwords
     uint32_t *seqs = reinterpret_cast<uint32_t *>(smem + 2304);               // 256 * 2 * 9 dwords
-    uint32_t *dp = seqs + 256 * 2 * SEQ_STRIDE_DW;                            // local: 33 * 256 dwords
+    uint32_t *dp = seqs + 256 * 2 * SEQ_STRIDE_DW;                            // local, global: 33 * 256 dwords
     const int tid = threadIdx.x;
     for (int e = tid; e < 576; e += 256) M[e] = Mg[e];
     __syncthreads();
@@ -33,9 +33,12 @@ k_pairs(const uint8_t *__restrict__ res32, const uint8_t *__restrict__ len, cons
             score = shifted_score_literal(M, reinterpret_cast<const uint8_t *>(s1), l1,
                                           reinterpret_cast<const uint8_t *>(s2), l2, a, b, &shift);
             if (out_shift) out_shift[k] = shift;
-        } else
+        } else if (SCORER == 1)
             score = local_score_literal(M, reinterpret_cast<const uint8_t *>(s1), l1,
                                         reinterpret_cast<const uint8_t *>(s2), l2, a, b, dp + tid, 256);
+        else
+            score = global_score_literal(M, reinterpret_cast<const uint8_t *>(s1), l1,
+                                         reinterpret_cast<const uint8_t *>(s2), l2, a, b, dp + tid, 256);
         out[k] = score;
     }
 }
@@ -51,12 +54,15 @@ hipError_t launch_pairs(int scorer, const uint8_t *res32, const uint8_t *len, co
     if (blocks > 65536) blocks = 65536;
     const size_t lds_shift = 2304 + 256 * 2 * SEQ_STRIDE_DW * 4;
     const size_t lds_local = lds_shift + 33 * 256 * 4;
-    blocks = capped_grid(scorer == 0 ? "k_pairs<0>" : "k_pairs<1>", (uint32_t)blocks);
+    blocks = capped_grid(scorer == 0 ? "k_pairs<0>" : scorer == 1 ? "k_pairs<1>" : "k_pairs<2>", (uint32_t)blocks);
     if (scorer == 0)
         hipLaunchKernelGGL(k_pairs<0>, dim3((uint32_t)blocks), dim3(256), lds_shift, s, res32, len, d_matrix, pi, pj,
                            n_pairs, r0, c0, width, a, b, out, out_shift);
-    else
+    else if (scorer == 1)
         hipLaunchKernelGGL(k_pairs<1>, dim3((uint32_t)blocks), dim3(256), lds_local, s, res32, len, d_matrix, pi, pj,
+                           n_pairs, r0, c0, width, a, b, out, out_shift);
+    else
+        hipLaunchKernelGGL(k_pairs<2>, dim3((uint32_t)blocks), dim3(256), lds_local, s, res32, len, d_matrix, pi, pj,
                            n_pairs, r0, c0, width, a, b, out, out_shift);
     return hipGetLastError();
 }

@@ -63,6 +63,9 @@ struct Options {
     int best = 0;
     bool haveScanTo = false;   // components: --scan_to T2, the last threshold of the scan (default: -g alone)
     int scanTo = 0;
+    // search, greedy: --scorer shifted|global (parseScorerArgs); global: GlobalAlignmentScorer with --gap_open / --gap_extend
+    bool haveScorer = false, globalScorer = false;
+    int gapOpen = -5, gapExtend = -1;
 };
 
 void parseCommonArgs(const std::vector<std::string> &args, Options &o) {  // Hammock.java:824-908
@@ -132,11 +135,43 @@ void parseClinkageArgs(const std::vector<std::string> &args, Options &o) {  // H
     }
 }
 
+// search, greedy: --scorer shifted|global, --gap_open, --gap_extend.  With the global scorer the shift parameters have no meaning
+// (-x, -p are errors), the penalties must satisfy the library's condition, and the pass runs on one device.
+void parseScorerArgs(const std::vector<std::string> &args, Options &o) {
+    bool shiftArgs = false;
+    for (size_t i = 1; i < args.size(); i++) {
+        const std::string &a = args[i];
+        const bool more = args.size() > i + 1;
+        if (a == "--scorer" && more) {
+            const std::string &name = args[++i];
+            if (name != "shifted" && name != "global") throw CLIException("Error. --scorer may be either \"shifted\" or \"global\".");
+            o.haveScorer = true;
+            o.globalScorer = name == "global";
+        } else if (a == "--gap_open" && more) o.gapOpen = javaIntegerDecode(args[++i]);
+        else if (a == "--gap_extend" && more) o.gapExtend = javaIntegerDecode(args[++i]);
+        else if (a == "-x" || a == "--max_shift" || a == "-p" || a == "--gap_penalty") shiftArgs = true;
+    }
+    if (!o.globalScorer) return;
+    if (shiftArgs) throw CLIException("Error. -x (--max_shift) and -p (--gap_penalty) have no meaning with --scorer global (--gap_open, --gap_extend).");
+    if (o.gapOpen < -127 || o.gapOpen > o.gapExtend || o.gapExtend > 0)
+        throw CLIException("Error. --scorer global needs -127 <= --gap_open <= --gap_extend <= 0.");
+    if (!o.devices.empty()) throw CLIException("Error. --devices is not available with --scorer global (the pass runs on one device, --device).");
+}
+
+void logScorer(const Options &o, const Logger &logger) {   // (only when --scorer was given: every other run logs as before)
+    if (!o.haveScorer) return;
+    logger.logAndStderr(o.globalScorer ? "Scorer: global (global alignment, affine gap). Gap open penalty: " + std::to_string(o.gapOpen) +
+                                             ", gap extend penalty: " + std::to_string(o.gapExtend)
+                                       : std::string("Scorer: shifted"));
+}
+
 void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
     std::cerr << "\nhammock-hip: MI355X-native greedy and clinkage modes of Hammock version " << VERSION << "\n\n"
               << "Synopsis: hammock-hip <greedy|clinkage> <param1> <param2> ...\n"
+              << "          hammock-hip greedy ... [--scorer shifted|global] [--gap_open <int>] [--gap_extend <int>]\n"
               << "          hammock-hip search -i <queries> --database <references> -d <directory> [-f fasta|tab] [-m <file>] [-x <int>]\n"
-              << "                      [-p <int>] [-g <int>] [--best <int>] [--device <int>]\n"
+              << "                      [-p <int>] [-g <int>] [--best <int>] [--scorer shifted|global] [--gap_open <int>] [--gap_extend <int>]\n"
+              << "                      [--device <int>]\n"
               << "          hammock-hip assign -i <new sequences> --clusters <initial_clusters_sequences.tsv> -d <directory> [--best <int>]\n"
               << "                      [--skip_singletons] [-f fasta|tab] [-m <file>] [-x <int>] [-p <int>] [-g <int>] [--device <int>]\n"
               << "          hammock-hip continue -i <new sequences> --clusters <initial_clusters_sequences.tsv> -d <directory> [-f fasta|tab]\n"
@@ -182,6 +217,9 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "-S, --seed <int>\n\tA seed to make random processes deterministic (if -R random is in use)\n\n"
               << "--initial_clusters_limit <int>\n\tThe max. number of clusters resulting from gredy clustering\n\n"
               << "-L, --cache_size_limit <int>\n\t(clinkage) accepted and logged; has no effect, as in the reference\n\n"
+              << "--scorer <[shifted,global]>\n\t(search, greedy) the pair score: shifted (default) = ShiftedScorer with -x and -p; global = the optimal global\n\talignment score of the two whole sequences under the matrix with an affine gap (end gaps charged); -x and -p are errors with it.\n\tsearch then writes the columns query, target, score\n\n"
+              << "--gap_open <int>\n\t(--scorer global) the penalty added for the first position of a gap (default -5); -127 <= --gap_open <= --gap_extend <= 0\n\n"
+              << "--gap_extend <int>\n\t(--scorer global) the penalty added for every further position of a gap (default -1)\n\n"
               << "--device <int>\n\tHIP device ordinal (default 0)\n\n"
               << "--devices <int,int,...>\n\tShard the pair space over several GPUs of the node (the first one runs the merge)\n\n"
               << "--database <file>\n\t(search) the reference sequences every query (-i) is scored against;\n\t(survey) score the input against these sequences instead of against itself\n\n"
@@ -330,10 +368,14 @@ int reportRunError(const Logger &logger, bool clustering) {
 
 // Hammock.java:803-811 after a limit the reference does not have.  clamp: the list whose longest sequence must fit the kernels and
 // whose shortest one bounds the shift; mean: the list whose mean length sets the default.
-void settleMaxShift(Options &o, const Logger &logger, const SequenceListSummary &clamp, const SequenceListSummary &mean, const std::string &note) {
+void requireKernelLengths(const SequenceListSummary &clamp) {
     if (clamp.maxLength > HMK_MAX_LEN)   // say so here instead of failing inside the clusterer
         throw HammockException("Error. The longest sequence has " + std::to_string(clamp.maxLength) + " amino acids; the GPU kernels of hammock-hip "
                                "take sequences of up to " + std::to_string(HMK_MAX_LEN) + " (Hammock's domain is 7-20).");
+}
+
+void settleMaxShift(Options &o, const Logger &logger, const SequenceListSummary &clamp, const SequenceListSummary &mean, const std::string &note) {
+    requireKernelLengths(clamp);
     if (!o.haveMaxShift) {
         o.maxShift = checkMaxShift(clamp, (int)javaRound(mean.meanLength() / 4));
         logger.logAndStderr("Max shift not set. Setting automatically to: " + std::to_string(o.maxShift) + note);
@@ -431,7 +473,7 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
     Options o;
     parseCommonArgs(args, o);
     if (clinkage) parseClinkageArgs(args, o);
-    else parseGreedyArgs(args, o);
+    else { parseGreedyArgs(args, o); parseScorerArgs(args, o); }
     requireInput(o);
     makeOutputDirectory(o, o.parentDir);
     Logger logger(o.workingDirectory + "/run.log", false);
@@ -464,7 +506,11 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
                               (o.haveThreshold ? std::to_string(o.sequenceClusteringThreshold) : std::string("null")) +
                               "\n-x, --max_shift " + (o.haveMaxShift ? std::to_string(o.maxShift) : std::string("null")) +
                               "\n-p, --gap_penalty " + std::to_string(o.shiftPenalty) + "\n-R, --order " + o.order +
-                              "\n-S, --seed " + std::to_string(o.seed) + "\n\n");
+                              "\n-S, --seed " + std::to_string(o.seed) +
+                              (o.haveScorer ? std::string("\n--scorer ") + (o.globalScorer ? "global" : "shifted") + "\n--gap_open " +
+                                                  std::to_string(o.gapOpen) + "\n--gap_extend " + std::to_string(o.gapExtend)
+                                            : std::string()) +
+                              "\n\n");
 
         // ---- loadInputSequences, :749-787 -----------------------------------------------------------
         const auto timeStart = std::chrono::steady_clock::now();
@@ -489,8 +535,9 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
         if (sequences.empty()) throw FileFormatException("Error. No sequences (with specified labels) to cluster.");
         // the sequence count is known: the context's buffers (24 GB at 10^6) are sized on another thread while this one goes on
         // to the labels, the statistics, the sort and the upload
-        std::future<void> reserved = std::async(std::launch::async, [contextReady, cliLap, count = (uint32_t)sequences.size()]() {
+        std::future<void> reserved = std::async(std::launch::async, [contextReady, cliLap, count = (uint32_t)sequences.size(), global = o.globalScorer]() {
             try {   // (a device error is reported by the clustering call)
+                if (global) return;   // (hmk_greedy_from_edges merges on the host: nothing to reserve)
                 hmk_ctx *c = contextReady.get()->get();
                 cliLap("hmk_reserve begins");
                 (void)hmk_reserve(c, count);
@@ -501,7 +548,9 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
         // ---- runGreedyClustering, :392-437 ------------------------------------------------------------
         if (!o.haveLabels) labels = FileIOManager::getSortedLabels(sequences);                 // :796-798
         const std::vector<UniqueSequencePtr> initialSequences(sequences);                       // :800-801
-        settleMaxShift(o, logger, summary, summary, "");                                        // :803-811
+        if (o.globalScorer) requireKernelLengths(summary);   // (the shift has no part in this scorer)
+        else settleMaxShift(o, logger, summary, summary, "");                                   // :803-811
+        logScorer(o, logger);
         cliLap("labels, lengths, max shift");
         logger.logAndStderr("Generating input statistics...");
         FileIOManager::saveInputStatistics(sequences, labels, inputStatistics);                 // :814-816
@@ -512,8 +561,12 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
             logger.logAndStderr("Initial greedy clusters limit not set. Setting automatically to: " +
                                 std::to_string(o.initialClustersLimit));
         }
-        auto scorer = std::make_shared<ShiftedScorer>(contextReady.get(), o.shiftPenalty, o.maxShift);  // :402 (get() rethrows a device error)
-        HipGreedySequenceClusterer clusterer(scorer, o.sequenceClusteringThreshold, o.initialClustersLimit);  // :403
+        std::shared_ptr<ShiftedScorer> scorer;   // (--scorer global: none)
+        if (!o.globalScorer) scorer = std::make_shared<ShiftedScorer>(contextReady.get(), o.shiftPenalty, o.maxShift);  // :402 (get() rethrows a device error)
+        HipGreedySequenceClusterer clusterer = o.globalScorer
+            ? HipGreedySequenceClusterer(std::make_shared<GlobalAlignmentScorer>(contextReady.get(), o.gapOpen, o.gapExtend),
+                                         o.sequenceClusteringThreshold, o.initialClustersLimit)
+            : HipGreedySequenceClusterer(scorer, o.sequenceClusteringThreshold, o.initialClustersLimit);  // :403
         HipClinkageSequenceClusterer clinkageClusterer(scorer, o.sequenceClusteringThreshold);                // :459
 
         cliLap("GPU context ready");
@@ -569,10 +622,13 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
 // order.  Each file is loaded and deduplicated on its own (FileIOManager.loadUniqueSequencesFrom*), so one peptide may be on
 // both sides.  Defaults: -x as greedy's over the union of both files (Hammock.java:803-811,1421-1434), -g = round(1.7 x the mean
 // query length) (:394-397), -p 0.  --best K: only the best K hits of each query (hmk_search_best_shifted).
+// --scorer global: GlobalAlignmentScorer(--gap_open, --gap_extend) through hmk_search_global instead; no -x / -p, the columns are
+// query, target, score, and --best K cuts each query's sorted hits to K.
 int runSearch(const std::vector<std::string> &args) {
     Options o;
     parseCommonArgs(args, o);
     parseModeArgs(args, o, 0);
+    parseScorerArgs(args, o);
     requireOneDevice(o, "search", "a search");
     requireInput(o);
     if (!o.haveDatabase) throw CLIException("Error. Parameter reference file (--database) missing with no default.");
@@ -592,7 +648,13 @@ int runSearch(const std::vector<std::string> &args) {
         std::vector<UniqueSequencePtr> all(queries);
         all.insert(all.end(), references.begin(), references.end());
         const SequenceListSummary summary = summariseSequences(all);
-        settleShiftAndThreshold(o, logger, summary, summary, summariseSequences(queries), "Search");
+        if (o.globalScorer) {   // (the shift parameters have no part in this scorer)
+            requireKernelLengths(summary);
+            settleThreshold(o, logger, summariseSequences(queries), "Search", "");
+        } else {
+            settleShiftAndThreshold(o, logger, summary, summary, summariseSequences(queries), "Search");
+        }
+        logScorer(o, logger);
 
         const std::shared_ptr<NativeContext> nc = contextReady.get();
         hmk_ctx *c = nc->get();
@@ -603,7 +665,25 @@ int runSearch(const std::vector<std::string> &args) {
         // hits[q] = (score, reference index in load order)
         std::vector<std::vector<std::pair<int, uint32_t>>> hits(nq);
         hmk_neighbor_stats stats{};
-        if (best) {
+        auto byScoreThenReference = [](const std::pair<int, uint32_t> &a, const std::pair<int, uint32_t> &b) {
+            return a.first != b.first ? a.first > b.first : a.second < b.second;
+        };
+        if (o.globalScorer) {   // global(seq1 = query, seq2 = reference); --best K: each query's sorted hits cut to K
+            std::vector<uint64_t> edges(1 << 20);
+            uint64_t n_edges = 0;
+            int st = hmk_search_global(c, 0, nq, nq, n, o.gapOpen, o.gapExtend, o.sequenceClusteringThreshold, edges.data(), edges.size(), &n_edges, &stats);
+            if (st == HMK_ERR_CAPACITY) {
+                edges.resize(n_edges);
+                st = hmk_search_global(c, 0, nq, nq, n, o.gapOpen, o.gapExtend, o.sequenceClusteringThreshold, edges.data(), edges.size(), &n_edges, &stats);
+            }
+            if (st) nc->raise(st, nullptr);
+            for (uint64_t k = 0; k < n_edges; k++)
+                hits[HMK_EDGE_M(edges[k])].push_back({HMK_EDGE_SCORE(edges[k]), HMK_EDGE_X(edges[k]) - nq});
+            for (auto &h : hits) {
+                std::sort(h.begin(), h.end(), byScoreThenReference);
+                if (best && h.size() > best) h.resize(best);
+            }
+        } else if (best) {
             std::vector<uint32_t> index((size_t)nq * best), count(nq);
             std::vector<int32_t> score((size_t)nq * best);
             const int st = hmk_search_best_shifted(c, 0, nq, nq, n, o.maxShift, o.shiftPenalty, o.sequenceClusteringThreshold, best,
@@ -624,17 +704,14 @@ int runSearch(const std::vector<std::string> &args) {
             if (st) nc->raise(st, nullptr);
             for (uint64_t k = 0; k < n_edges; k++)
                 hits[HMK_EDGE_M(edges[k])].push_back({HMK_EDGE_SCORE(edges[k]), HMK_EDGE_X(edges[k]) - nq});
-            for (auto &h : hits)
-                std::sort(h.begin(), h.end(), [](const std::pair<int, uint32_t> &a, const std::pair<int, uint32_t> &b) {
-                    return a.first != b.first ? a.first > b.first : a.second < b.second;
-                });
+            for (auto &h : hits) std::sort(h.begin(), h.end(), byScoreThenReference);
         }
         // AligningScorerResult.getShift() of scoreWithShift(seq1 = query, seq2 = target), for the hits only
         std::vector<uint32_t> pi, pj;
         for (uint32_t q = 0; q < nq; q++)
             for (auto &h : hits[q]) { pi.push_back(q); pj.push_back(nq + h.second); }
         std::vector<int32_t> sc(pi.size()), shift(pi.size());
-        if (!pi.empty()) {
+        if (!pi.empty() && !o.globalScorer) {
             const int st = hmk_score_with_shift(c, pi.data(), pj.data(), pi.size(), o.maxShift, o.shiftPenalty, sc.data(), shift.data());
             if (st) nc->raise(st, nullptr);
         }
@@ -645,12 +722,13 @@ int runSearch(const std::vector<std::string> &args) {
         {
             std::ofstream out(hitsFile);
             if (!out) throw HammockException("cannot write " + hitsFile);
-            out << "query\ttarget\tscore\tshift\n";
+            out << (o.globalScorer ? "query\ttarget\tscore\n" : "query\ttarget\tscore\tshift\n");
             size_t k = 0;
             for (uint32_t q = 0; q < nq; q++)
                 for (auto &h : hits[q]) {
-                    out << queries[q]->getSequenceString() << '\t' << references[h.second]->getSequenceString() << '\t' << h.first << '\t'
-                        << shift[k] << '\n';
+                    out << queries[q]->getSequenceString() << '\t' << references[h.second]->getSequenceString() << '\t' << h.first;
+                    if (!o.globalScorer) out << '\t' << shift[k];
+                    out << '\n';
                     k++;
                 }
         }

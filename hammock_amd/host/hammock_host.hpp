@@ -11,6 +11,7 @@
 //   SequenceScorer / AligningSequenceScorer / SequenceClusterer   (interfaces)
 //   ShiftedScorer             ShiftedScorer.java:12          sequenceScore runs on the GPU
 //   LocalAlignmentScorer      LocalAlignmentScorer.java:10   sequenceScore runs on the GPU
+//   GlobalAlignmentScorer     (no counterpart)               global alignment score with an affine gap, on the GPU
 //   HipGreedySequenceClusterer  drop-in for LimitedGreedySequenceClusterer.java:17
 //   FileIOManager             loaders / stage-1 writers, FileIOManager.java
 //   Logger                    Logger.java
@@ -499,19 +500,65 @@ public:
     }
 };
 
+// ---- GlobalAlignmentScorer: no counterpart in the reference (hammock_hip.h, hmk_score_pairs_global) ------------------
+// The optimal score of a global alignment of two whole sequences with the affine gap gapOpen + (k - 1) gapExtend (penalties
+// added, -127 <= gapOpen <= gapExtend <= 0), end gaps charged; seq1 = lines, seq2 = columns of the matrix.
+class GlobalAlignmentScorer : public SequenceScorer {
+    std::shared_ptr<NativeContext> ctx_;
+    int gapOpenPenalty_, gapExtendPenalty_;
+public:
+    GlobalAlignmentScorer(const std::vector<std::vector<int>> &scoringMatrix, int gapOpenPenalty, int gapExtendPenalty, int device = 0)
+        : ctx_(std::make_shared<NativeContext>(scoringMatrix, device)), gapOpenPenalty_(gapOpenPenalty),
+          gapExtendPenalty_(gapExtendPenalty) {}
+    // over a context that already exists
+    GlobalAlignmentScorer(std::shared_ptr<NativeContext> context, int gapOpenPenalty, int gapExtendPenalty)
+        : ctx_(std::move(context)), gapOpenPenalty_(gapOpenPenalty), gapExtendPenalty_(gapExtendPenalty) {}
+    int sequenceScore(const UniqueSequencePtr &seq1, const UniqueSequencePtr &seq2) override {
+        ctx_->setSequences({seq1, seq2}, false);
+        const uint32_t i = 0, j = 1;
+        int32_t score = 0;
+        const int st = hmk_score_pairs_global(ctx_->get(), &i, &j, 1, gapOpenPenalty_, gapExtendPenalty_, &score);
+        if (st) ctx_->raise(st, nullptr);
+        return score;
+    }
+    int getGapOpenPenalty() const { return gapOpenPenalty_; }
+    int getGapExtendPenalty() const { return gapExtendPenalty_; }
+    const std::shared_ptr<NativeContext> &native() const { return ctx_; }
+};
+
 // ---- HipGreedySequenceClusterer: LimitedGreedySequenceClusterer.java:17-121 on the GPU ----------------------
 class HipGreedySequenceClusterer : public SequenceClusterer {
     std::shared_ptr<ShiftedScorer> scorer_;
+    std::shared_ptr<GlobalAlignmentScorer> global_;   // set: the neighbour graph comes from hmk_neighbors_global
     int threshold_, maxClusters_;
+    // GlobalAlignmentScorer: the thresholded pairs (the buffer grown on HMK_ERR_CAPACITY), then the greedy merge over them
+    int clusterGlobal(int32_t *cid, int32_t *order, int32_t *rank) {
+        hmk_ctx *c = global_->native()->get();
+        const int open = global_->getGapOpenPenalty(), extend = global_->getGapExtendPenalty();
+        std::vector<uint64_t> edges(1 << 20);
+        uint64_t n_edges = 0;
+        hmk_neighbor_stats ns{};
+        int st = hmk_neighbors_global(c, open, extend, threshold_, 0, 1, edges.data(), edges.size(), &n_edges, &ns);
+        if (st == HMK_ERR_CAPACITY) {
+            edges.resize(n_edges);
+            st = hmk_neighbors_global(c, open, extend, threshold_, 0, 1, edges.data(), edges.size(), &n_edges, &ns);
+        }
+        if (st) return st;
+        st = hmk_greedy_from_edges(c, edges.data(), n_edges, (int)ns.symmetric, threshold_, maxClusters_, cid, order, rank, &stats);
+        stats.neighbors_ms = ns.kernel_ms;
+        return st;
+    }
 public:
     hmk_greedy_stats stats{};
     // same constructor shape as LimitedGreedySequenceClusterer(sequenceScorer, threshold, maxClusters), :22-26
     HipGreedySequenceClusterer(std::shared_ptr<ShiftedScorer> sequenceScorer, int threshold, int maxClusters)
         : scorer_(std::move(sequenceScorer)), threshold_(threshold), maxClusters_(maxClusters) {}
+    HipGreedySequenceClusterer(std::shared_ptr<GlobalAlignmentScorer> sequenceScorer, int threshold, int maxClusters)
+        : global_(std::move(sequenceScorer)), threshold_(threshold), maxClusters_(maxClusters) {}
     // cluster(List<UniqueSequence>) -> List<Cluster>, :39-69: clusters in creation order (id = index of the
     // seed), then the remaining singletons; members in Cluster.getSequences() insertion order.
     std::vector<ClusterPtr> cluster(const std::vector<UniqueSequencePtr> &sequences) override {
-        const auto &nc = scorer_->native();
+        const auto &nc = global_ ? global_->native() : scorer_->native();
         const bool timing = std::getenv("HMK_CLI_TIMING") != nullptr;
         auto t0 = std::chrono::steady_clock::now();
         auto lap = [&](const char *what) {
@@ -524,10 +571,11 @@ public:
         lap("upload");
         const size_t n = sequences.size();
         std::vector<int32_t> cid(std::max<size_t>(n, 1)), order(std::max<size_t>(n, 1)), rank(std::max<size_t>(n, 1));
-        const int st = hmk_greedy_cluster(nc->get(), scorer_->getMaxShift(), scorer_->getShiftPenalty(), threshold_,
-                                          maxClusters_, cid.data(), order.data(), rank.data(), &stats);
+        const int st = global_ ? clusterGlobal(cid.data(), order.data(), rank.data())
+                               : hmk_greedy_cluster(nc->get(), scorer_->getMaxShift(), scorer_->getShiftPenalty(), threshold_,
+                                                    maxClusters_, cid.data(), order.data(), rank.data(), &stats);
         if (st) nc->raise(st, &stats);
-        lap("hmk_greedy_cluster");
+        lap(global_ ? "hmk_neighbors_global + hmk_greedy_from_edges" : "hmk_greedy_cluster");
         // members of every cluster in insertion order: a cluster's id is the index of its seed (< n), ranks are 0 .. size - 1
         std::vector<uint32_t> first(n + 1, 0);
         for (size_t k = 0; k < n; k++) first[(size_t)cid[k] + 1]++;

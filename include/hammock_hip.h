@@ -112,11 +112,33 @@ int hmk_score_with_shift(hmk_ctx *ctx, const uint32_t *i, const uint32_t *j, uin
  * (LocalAlignmentScorer.java:27-86); i = seq1 = lines, j = seq2 = columns. */
 int hmk_score_pairs_local(hmk_ctx *ctx, const uint32_t *i, const uint32_t *j, uint64_t n_pairs,
                           int gap_open, int gap_extend, int32_t *out);
+/* GlobalAlignmentScorer: the optimal score of a global alignment of two whole sequences under the matrix with an affine gap
+ * (Gotoh); the reference has no counterpart.  With n = |seq1|, m = |seq2|:
+ *     H[0][0] = 0
+ *     H[0][j] = E[0][j] = gap_open + (j - 1) gap_extend      H[i][0] = F[i][0] = gap_open + (i - 1) gap_extend
+ *     E[i][0] = F[0][j] = -infinity
+ *     E[i][j] = max(E[i][j-1] + gap_extend, H[i][j-1] + gap_open)
+ *     F[i][j] = max(F[i-1][j] + gap_extend, H[i-1][j] + gap_open)
+ *     H[i][j] = max(H[i-1][j-1] + M[seq1[i-1]][seq2[j-1]], E[i][j], F[i][j])          score = H[n][m]
+ * Penalties are ADDED (LocalAlignmentScorer's convention): a gap of length k costs gap_open + (k - 1) gap_extend, end gaps
+ * like inner ones.  Arguments: -127 <= gap_open <= gap_extend <= 0 (under it the recurrence is the maximum over all
+ * alignments; gap_open > gap_extend is not defined) and 32 * max(0, largest matrix entry) <= 32767, else HMK_ERR_BAD_ARG --
+ * answered before the device is looked at (a host-only context answers them too), as are the thresholds' [-30000, 30000]
+ * in the two edge calls below.  The lowest score, the all-gap alignment, is >= -8,128.  A symmetric matrix gives a symmetric
+ * score; a 0 / -1 matrix with penalties -1 / -1 gives minus the Levenshtein distance.
+ * Out of scope: assign, match and best-k forms with this scorer; multi-device sharding beyond part / n_parts; the
+ * alignments themselves (traceback).
+ * out[k] = global(seq1 = i[k], seq2 = j[k]). */
+int hmk_score_pairs_global(hmk_ctx *ctx, const uint32_t *i, const uint32_t *j, uint64_t n_pairs,
+                           int gap_open, int gap_extend, int32_t *out);
 /* Dense block: out[(r - r0) * (c1 - c0) + (c - c0)] = score(r, c), r0<=r<r1, c0<=c<c1. */
 int hmk_score_block_shifted(hmk_ctx *ctx, uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1,
                             int max_shift, int shift_penalty, int32_t *out);
 int hmk_score_block_local(hmk_ctx *ctx, uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1,
                           int gap_open, int gap_extend, int32_t *out);
+/* ... = global(seq1 = r, seq2 = c) (hmk_score_pairs_global) */
+int hmk_score_block_global(hmk_ctx *ctx, uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1,
+                           int gap_open, int gap_extend, int32_t *out);
 
 /* ---- all-vs-all thresholded neighbour graph (the hot kernel) ------------ */
 
@@ -152,6 +174,15 @@ int hmk_neighbors_shifted(hmk_ctx *ctx, int max_shift, int shift_penalty, int th
 int hmk_neighbors_local(hmk_ctx *ctx, int gap_open, int gap_extend, int threshold, uint32_t part,
                         uint32_t n_parts, uint64_t *edges, uint64_t capacity, uint64_t *n_edges,
                         hmk_neighbor_stats *stats);
+
+/* The same for GlobalAlignmentScorer (hmk_score_pairs_global), edges with the contract of hmk_neighbors_shifted: under a
+ * symmetric matrix each unordered pair with global >= threshold once, x < m, and only those pairs are scored
+ * (stats->pairs_scored = n (n - 1) / 2 over all parts, stats->symmetric = 1); otherwise ALL ORDERED pairs, score =
+ * global(seq1 = m, seq2 = x).  Register-resident DP for matrices within +-127, the literal DP on the same tiles otherwise.
+ * Parts are dealt by row chunk as in hmk_neighbors_local.  stats: n_edges, pairs_scored, n_tiles, symmetric, kernel_ms. */
+int hmk_neighbors_global(hmk_ctx *ctx, int gap_open, int gap_extend, int threshold, uint32_t part,
+                         uint32_t n_parts, uint64_t *edges, uint64_t capacity, uint64_t *n_edges,
+                         hmk_neighbor_stats *stats);
 
 /* Device-resident form: asynchronous on `stream` (a hipStream_t, may be NULL),
  * no host synchronisation.  d_edges: device buffer of `capacity` uint64,
@@ -213,6 +244,11 @@ int hmk_search_shifted(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint
 int hmk_search_local(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1,
                      int gap_open, int gap_extend, int threshold,
                      uint64_t *edges, uint64_t capacity, uint64_t *n_edges, hmk_neighbor_stats *stats);
+/* The same for global(seq1 = q, seq2 = r) (hmk_score_pairs_global): ranges and checks as hmk_search_local, the argument
+ * checks of hmk_neighbors_global; ALWAYS m = query and x = reference. */
+int hmk_search_global(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1,
+                      int gap_open, int gap_extend, int threshold,
+                      uint64_t *edges, uint64_t capacity, uint64_t *n_edges, hmk_neighbor_stats *stats);
 /* The best k (1 <= k <= 32) references of every query among those with score(q, r) >= threshold (scores as in
  * hmk_search_shifted), by score descending, then reference index ascending, selected on the device (the edge list never
  * travels to the host): hit_index[(q - q0) * k + t], hit_score[(q - q0) * k + t], n_hits[q - q0] = how many are valid;
