@@ -34,7 +34,7 @@ SYMBOLS = [
     "hmk_score_pairs_shifted", "hmk_score_with_shift", "hmk_score_pairs_local", "hmk_score_block_shifted", "hmk_score_block_local",
     "hmk_score_pairs_global", "hmk_score_block_global", "hmk_neighbors_global", "hmk_search_global",
     "hmk_neighbors_shifted", "hmk_neighbors_local", "hmk_neighbors_shifted_dev", "hmk_compact_edges_dev", "hmk_pack_rows_dev", "hmk_unpack_rows_dev",
-    "hmk_neighbors_last_plan", "hmk_neighbors_last_plan_shared", "hmk_search_shifted", "hmk_search_local", "hmk_search_best_shifted",
+    "hmk_neighbors_last_plan", "hmk_neighbors_last_plan_shared", "hmk_neighbors_last_plan_tables", "hmk_search_shifted", "hmk_search_local", "hmk_search_best_shifted",
     "hmk_assign_shifted", "hmk_assign_local", "hmk_match_clusters_shifted", "hmk_match_clusters_local", "hmk_greedy_continue",
     "hmk_greedy_cluster", "hmk_greedy_from_edges", "hmk_greedy_from_edges_dev", "hmk_greedy_last_phases",
     "hmk_clinkage_cluster", "hmk_clinkage_from_edges", "hmk_set_java_hashset", "hmk_reserve",
@@ -266,6 +266,7 @@ def _load():
     L.hmk_unpack_rows_dev.argtypes = [vp, vp, vp, i32, vp, u64, vp]
     L.hmk_neighbors_last_plan.argtypes = [vp, C.POINTER(NeighborStats)]
     L.hmk_neighbors_last_plan_shared.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.hmk_neighbors_last_plan_tables.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.hmk_search_shifted.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, p_u64, u64, p_u64, C.POINTER(NeighborStats)]
     L.hmk_search_local.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, p_u64, u64, p_u64, C.POINTER(NeighborStats)]
     L.hmk_search_global.argtypes = [vp, u32, u32, u32, u32, i32, i32, i32, p_u64, u64, p_u64, C.POINTER(NeighborStats)]

@@ -628,6 +628,14 @@ class Context:
             self._raise(st)
         return int(paired.value), int(shared.value)
 
+    def last_plan_tables(self):
+        """-> (tiles of the last plan that copy their tables from the plan, bytes of device memory those tables take)"""
+        tiles, nbytes = C.c_uint32(0), C.c_uint64(0)
+        st = N.lib.hmk_neighbors_last_plan_tables(self._h, C.byref(tiles), C.byref(nbytes))
+        if st:
+            self._raise(st)
+        return int(tiles.value), int(nbytes.value)
+
     # -- greedy ---------------------------------------------------------------------------
     def greedy_cluster(self, max_shift, shift_penalty, threshold, max_clusters):
         """-> (cluster_id int32[n], result_order int32[n_result], GreedyStats)"""

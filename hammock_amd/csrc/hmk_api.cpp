@@ -303,6 +303,16 @@ int hmk_neighbors_last_plan_shared(hmk_ctx *ctx, uint32_t *paired_tiles, uint32_
     return HMK_OK;
 }
 
+int hmk_neighbors_last_plan_tables(hmk_ctx *ctx, uint32_t *table_tiles, uint64_t *table_bytes) {
+    if (!ctx || !table_tiles || !table_bytes) return fail(ctx, HMK_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    refresh_switches(ctx);
+    if (!ctx->plan.valid) return fail(ctx, HMK_ERR_BAD_ARG, "no neighbour pass has been planned yet");
+    *table_tiles = ctx->plan.table_tiles;
+    *table_bytes = ctx->plan.table_bytes;
+    return HMK_OK;
+}
+
 int hmk_neighbors_shifted(hmk_ctx *ctx, int max_shift, int shift_penalty, int threshold, uint32_t part,
                           uint32_t n_parts, uint64_t *edges, uint64_t capacity, uint64_t *n_edges,
                           hmk_neighbor_stats *stats) {

@@ -34,6 +34,7 @@ void Switches::read() {
     no_row_shared = flag("HMK_NO_ROW_SHARED");
     key_row_pairs = getenv("HMK_KEY_ROW_PAIRS") ? (num("HMK_KEY_ROW_PAIRS", 0) != 0 ? 1 : 0) : -1;
     no_row_run_share = flag("HMK_NO_ROW_RUN_SHARE");
+    no_tile_tables = flag("HMK_NO_TILE_TABLES");
     adj_8byte = flag("HMK_ADJ_8BYTE");
     local_literal = flag("HMK_LOCAL_LITERAL");
     local_signed = flag("HMK_LOCAL_SIGNED");

@@ -121,6 +121,7 @@ struct Switches {
     bool no_row_shared = false;   // HMK_NO_ROW_SHARED: no row group of a key-sorted plan takes the row-shared bodies (A/B runs)
     int key_row_pairs = -1;       // HMK_KEY_ROW_PAIRS=0|1: a key-sorted plan never / always takes 16-row tiles (-1: the planner's size rule)
     bool no_row_run_share = false;   // HMK_NO_ROW_RUN_SHARE: no 16-row tile's second group takes its merged cells from the first (A/B runs)
+    bool no_tile_tables = false;  // HMK_NO_TILE_TABLES: every tile of a key-sorted plan builds its table in LDS, none copies the plan's (A/B runs)
     bool adj_8byte = false;       // HMK_ADJ_8BYTE: 8-byte adjacency entries even where 4 bytes hold every score
     bool local_literal = false;   // HMK_LOCAL_LITERAL: LocalAlignmentScorer through the literal DP
     bool local_signed = false;    // HMK_LOCAL_SIGNED: the signed tagged-max form (what gap_open = 0 runs) for every penalty
@@ -168,9 +169,12 @@ struct Plan : PlanArrays {
     bool row_shared = true;        // ... and HMK_NO_ROW_SHARED (false: no tile is flagged row-shared)
     int key_row_pairs = -1;        // ... and HMK_KEY_ROW_PAIRS
     bool row_run_share = true;     // ... and HMK_NO_ROW_RUN_SHARE (false: no tile is flagged run-shared)
+    bool tile_tables = true;       // ... and HMK_NO_TILE_TABLES (false: no tile is flagged ROWS_TILE_TABLE, the group records' tables stay unwritten)
     bool key_pairs = false;        // the plan is key-sorted with 16-row tiles: two row groups per column set-up (k_neighbors_rows.h)
     uint32_t paired_tiles = 0, run_shared_tiles = 0;   // tiles of a paired plan; those flagged ROWS_RUN_SHARED (hmk_neighbors_last_plan_shared)
-    uint32_t *d_keyrun = nullptr;  // NeighborParams::keyrun / keytab (null: the plan is not key-sorted)
+    uint32_t table_tiles = 0;      // tiles flagged ROWS_TILE_TABLE, and the bytes of their tables inside d_keytab (hmk_neighbors_last_plan_tables)
+    uint64_t table_bytes = 0;
+    uint32_t *d_keyrun = nullptr;  // NeighborParams::keyrun / keytab (null: the plan is not key-sorted); keytab holds the tile tables too
     uint32_t *d_keytab = nullptr;
     uint32_t cols_per_tile = 16384;
     uint8_t *d_mb = nullptr;

@@ -62,7 +62,8 @@ struct NeighborParams {
     uint32_t *deg;       // total degrees -- or, with deg_m_offset = n, upper counts (the edge's smaller end) in deg[0, n) and lower counts in deg[n, 2n)
     uint32_t deg_m_offset;   // the larger end m of a symmetric edge counts into deg[deg_m_offset + m] (0: one counter per row)
     // optional (null: no key sort): a key-sorted one-length plan (hmk_plan.cpp, rows_keyed).  keyrun[2 s], keyrun[2 s + 1]: run id << 5 |
-    // residue of sorted position s at key position 0 / of the key pair; keytab: KEYTAB_DWORDS per (row group, key, residue)
+    // residue of sorted position s at key position 0 / of the key pair; keytab: one record of KEYGROUP_DWORDS per row group -- KEYTAB_DWORDS
+    // per (key, residue), then the group's tile table (ROWS_TILE_TABLE)
     const uint32_t *keyrun;
     const uint32_t *keytab;
 };
@@ -78,6 +79,16 @@ constexpr int KEYTAB_DWORDS = 16;
 // (a paired plan, hmk_plan.cpp: ROWS_KEY_PAIR_GROUPS) two
 constexpr int ROWS_KEY_PAIR_GROUPS = 2;
 constexpr uint32_t ROWS_RUN_SHARED = 1u << 8;   // Tile::row_shared
+// Tile tables of a key-sorted plan: behind a row group's key entries lie the bytes the tile's table build writes
+// into LDS for that group -- 12 row positions x 24 residues x 8 rows, merged entries at key position 0 where the group is
+// row-shared, zero bytes for a row at or past n -- built once per plan (k_rows_rowtab); a tile flagged ROWS_TILE_TABLE copies them
+// instead of building them.  One record per row group: KEYGROUP_DWORDS, the key entries first.  No field of NeighborParams: one
+// more moves the registers of every row kernel (the argument block is parked in VGPR lanes around the flush call).
+constexpr uint32_t ROWS_TILE_TABLE = 1u << 9;   // Tile::row_shared: the group records of this plan hold the tile tables
+constexpr int ROWTAB_POSITIONS = 12;
+constexpr int ROWTAB_DWORDS = ROWTAB_POSITIONS * 24 * 2;
+constexpr int KEYGROUP_KEY_DWORDS = 2 * 24 * KEYTAB_DWORDS;
+constexpr int KEYGROUP_DWORDS = KEYGROUP_KEY_DWORDS + ROWTAB_DWORDS;
 constexpr bool rows_keyed(int x, int d, int cap, bool exact, int g) { return exact && d == 0 && (g == 1 || g == ROWS_KEY_PAIR_GROUPS) && x == 3 && cap == 12; }
 // the two key positions of length l at max shift x: middle positions (paired with every row position by all 2x + 1 planes)
 constexpr int rows_key_pos(int x, int l, int q) { return l / 2 - 1 + q < x ? x : l / 2 - 1 + q; }

@@ -31,6 +31,10 @@ hipError_t warm_neighbors_rows_module();
 // class's TileClass::cinit (the planes' initial lanes, folded into key 0's entries)
 hipError_t launch_rows_keytab(const uint8_t *res_sorted, uint32_t lpad, uint32_t n, const uint8_t *mb, int case_b, int X, int L,
                               const uint32_t (&cinit)[8], uint32_t *keytab, uint32_t n_groups);
+// ... and the tile tables behind the key entries (hmk_internal.h, ROWS_TILE_TABLE; length ROWTAB_POSITIONS only); row_shared: the planner
+// flags row-shared groups (Plan::row_shared) -- the kernel finds them by the planner's rule
+hipError_t launch_rows_rowtab(const uint8_t *res_sorted, uint32_t lpad, uint32_t n, const uint8_t *mb, int case_b, int X, int L,
+                              bool row_shared, uint32_t *keytab, uint32_t n_groups);
 hipError_t launch_neighbors_direct(const NeighborParams &P, uint32_t tile_base, uint32_t n_tiles,
                                    const int32_t *d_matrix, int max_shift, int shift_penalty, int threshold,
                                    hipStream_t s);

@@ -320,7 +320,8 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
     const int want_keys = key_sort_ok ? ctx->sw.key_sort : 0;
     if (pl.valid && pl.X == X && pl.p == p && pl.thr == thr && pl.part == part && pl.n_parts == n_parts &&
         (band_rows < 0 || pl.band_req == band_rows) && pl.no_rows_kernel == ctx->sw.no_rows_kernel && pl.key_sort == want_keys &&
-        pl.row_shared == !ctx->sw.no_row_shared && pl.key_row_pairs == ctx->sw.key_row_pairs && pl.row_run_share == !ctx->sw.no_row_run_share)
+        pl.row_shared == !ctx->sw.no_row_shared && pl.key_row_pairs == ctx->sw.key_row_pairs && pl.row_run_share == !ctx->sw.no_row_run_share &&
+        pl.tile_tables == !ctx->sw.no_tile_tables)
         return HMK_OK;
     free_plan(pl);
     if (band_rows < 0) band_rows = 0;
@@ -448,6 +449,7 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
     pl.row_shared = !ctx->sw.no_row_shared;
     pl.key_row_pairs = ctx->sw.key_row_pairs;
     pl.row_run_share = !ctx->sw.no_row_run_share;
+    pl.tile_tables = !ctx->sw.no_tile_tables;
     std::vector<uint32_t> keyrun;
     const int L1 = ctx->min_len;
     const bool key_sorted = pl.key_sort > 0 && pl.rows_exact && !(refine && !all_rows_fit) &&
@@ -582,6 +584,15 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
         }
         plan_lap("row-shared groups");
     }
+    // Tile tables (hmk_internal.h, ROWS_TILE_TABLE): what a tile's table build writes depends on the sorted residues, the matrix and the
+    // group's row-shared flag only -- the same in every pass on this plan, and about eleven tiles per row group build it again in each.  The
+    // plan builds the tables once, below, and every tile copies its groups'.  (One class, chunks from position 0 in steps of 8 or 16 rows:
+    // group g of a tile is row group (row0 >> 3) + g.)
+    const bool tile_tables = key_sorted && pl.tile_tables && L1 == ROWTAB_POSITIONS;
+    if (tile_tables)
+        for (Tile &t : tiles) t.row_shared |= ROWS_TILE_TABLE;
+    pl.table_tiles = tile_tables ? (uint32_t)tiles.size() : 0u;
+    pl.table_bytes = tile_tables ? (uint64_t)((n + 7) / 8) * ROWTAB_DWORDS * 4 : 0u;
     pl.paired_tiles = pl.key_pairs ? (uint32_t)tiles.size() : 0u;
     pl.run_shared_tiles = 0;
     for (const Tile &t : tiles) pl.run_shared_tiles += (t.row_shared & ROWS_RUN_SHARED) ? 1u : 0u;
@@ -596,12 +607,15 @@ int build_plan(hmk_ctx *ctx, int X, int p, int thr, uint32_t part, uint32_t n_pa
         // key those are; a key-sorted plan has the one class of its one length)
         if (classes.size() != 1) return fail(ctx, HMK_ERR_DEVICE, "key-sorted plan with more than one class");
         const uint32_t n_groups = (n + 7) / 8;
-        const size_t tab_dwords = (size_t)n_groups * 2 * HMK_ALPHABET * KEYTAB_DWORDS;
+        const size_t tab_dwords = (size_t)n_groups * KEYGROUP_DWORDS;
         HIPCHK(ctx, hipMalloc((void **)&pl.d_keyrun, keyrun.size() * 4));
         HIPCHK(ctx, hipMemcpy(pl.d_keyrun, keyrun.data(), keyrun.size() * 4, hipMemcpyHostToDevice));
         HIPCHK(ctx, hipMalloc((void **)&pl.d_keytab, tab_dwords * 4));
         HIPCHK(ctx, launch_rows_keytab(pl.d_res_sorted, (uint32_t)pl.lpad, n, pl.d_mb, classes.at(0).case_b, X, L1, classes.at(0).cinit, pl.d_keytab,
                                        n_groups));
+        if (tile_tables)
+            HIPCHK(ctx, launch_rows_rowtab(pl.d_res_sorted, (uint32_t)pl.lpad, n, pl.d_mb, classes.at(0).case_b, X, L1, pl.row_shared, pl.d_keytab,
+                                           n_groups));
         HIPCHK(ctx, hipStreamSynchronize(nullptr));
     }
     pl.X = X; pl.p = p; pl.thr = thr; pl.part = part; pl.n_parts = n_parts;

@@ -799,6 +799,22 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
 
     build_begin();
     const uint32_t tab_addr = lds_addr(tab);
+    // Tile tables (hmk_internal.h, ROWS_TILE_TABLE): the plan built the group's table bytes once (k_rows_rowtab); the tile copies
+    // them, 16 bytes per lane and turn, behind ONE barrier -- no matrix, no row residues, no gather.  (The in-loop shapes' flush
+    // reads the stage alone: nothing after this point reads mb or rowres.)  A group the tile does not have gets zero bytes.
+    constexpr bool TABLED = KEYED && MODE == EDGES_PLAIN;   // (a counting pass is never key-sorted: its kernels stay as they were)
+    static_assert(!TABLED || (S::GROUP_STEP == ROWTAB_DWORDS * 4 && TAB_BYTES == G * ROWTAB_DWORDS * 4 && NEND == 0), "the plan's tile table is the LDS table of one group");
+    if (TABLED && keyed && (T.row_shared & ROWS_TILE_TABLE) != 0) {
+        constexpr int PIECES = ROWTAB_DWORDS / 4;   // 16-byte pieces per group
+        const uint32_t *const rt_tile = P.keytab + (size_t)(T.row0 >> 3) * KEYGROUP_DWORDS + KEYGROUP_KEY_DWORDS;
+        for (int e = tid; e < G * PIECES; e += 256) {
+            const int g = e / PIECES, q = e - g * PIECES;
+            u32x4 v = {0, 0, 0, 0};
+            if ((uint32_t)(8 * g) < T.nrows) v = *reinterpret_cast<const u32x4 *>(rt_tile + (size_t)g * KEYGROUP_DWORDS + 4 * q);
+            *reinterpret_cast<u32x4 *>(tab + 16 * e) = v;
+        }
+        __syncthreads();
+    } else {
     for (int e = tid; e < 576; e += 256) mb[e] = P.mb[e];
     for (int e = tid; e < R * 32; e += 256) {
         const int r = e >> 5, k = e & 31;
@@ -833,6 +849,7 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
         *reinterpret_cast<uint32_t *>(tab + dst + c * 8 + h * 4) = v;
     }
     __syncthreads();
+    }
     build_end();
 
     // initial lanes: every byte of plane u starts at g + penalty(s) - bias * cells(s) (TileClass::cinit, one byte per shift)
@@ -886,7 +903,7 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t *kt_tile = nullptr, *kr_wave = nullptr;   // keytab of the tile's first row group; keyrun of the wave's first column
     if (keyed) {
-        kt_tile = P.keytab + (size_t)(T.row0 >> 3) * (2 * 24 * KEYTAB_DWORDS);
+        kt_tile = P.keytab + (size_t)(T.row0 >> 3) * KEYGROUP_DWORDS;
         kr_wave = P.keyrun + 2 * (size_t)(T.col0 + wave * 64);
     }
     // one key entry, whole: rows 0-3 / 4-7 of every plane
@@ -938,7 +955,7 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
             auto body = [&](auto gt, auto kt, auto rt, uint32_t (&W0)[ND], uint32_t (&W1)[ND]) __attribute__((always_inline)) {
                 constexpr int g = decltype(gt)::value, KM = decltype(kt)::value;
                 constexpr bool RUN = decltype(rt)::value;
-                const uint32_t *const kt_group = kt_tile + (size_t)g * (2 * 24 * KEYTAB_DWORDS);   // row group (T.row0 >> 3) + g
+                const uint32_t *const kt_group = kt_tile + (size_t)g * KEYGROUP_DWORDS;   // row group (T.row0 >> 3) + g
                 [[maybe_unused]] const bool row_shared = (rs_groups & (1u << g)) != 0;   // wave-uniform
                 // (start values in SGPRs: the plane's first add takes them as its scalar operand.  Byte lanes: every partial sum is
                 // <= the plane's final lane <= 255, no carry)
@@ -1043,7 +1060,7 @@ __device__ __forceinline__ void rows_tile(const NeighborParams &P, const uint32_
                 if ((uint32_t)(8 * g) >= T.nrows) return;   // wave-uniform
                 uint32_t W0[ND], W1[ND];
                 if constexpr (KEYED) {
-                    const uint32_t *const kt_group = kt_tile + (size_t)g * (2 * 24 * KEYTAB_DWORDS);   // row group (T.row0 >> 3) + g
+                    const uint32_t *const kt_group = kt_tile + (size_t)g * KEYGROUP_DWORDS;   // row group (T.row0 >> 3) + g
                     const bool row_shared = G == 1 ? rs_first : (rs_groups & (1u << g)) != 0;   // wave-uniform
                     // (start values in SGPRs: the plane's first add takes them as its scalar operand.  Byte lanes: every partial sum is
                     // <= the plane's final lane <= 255, no carry)

@@ -1,5 +1,5 @@
 // k_neighbors_rows.hip -- which row-packed instantiation (k_neighbors_rows.h) a (max shift, lengths) class runs, and the
-// dispatch to the part (k_rows_part.hip) that holds it; the key table of a key-sorted plan.
+// dispatch to the part (k_rows_part.hip) that holds it; the key entries and tile tables of a key-sorted plan.
 #include "k_rows_shapes.h"
 
 namespace hmk {
@@ -73,7 +73,39 @@ __global__ void __launch_bounds__(256) k_rows_keytab(const uint8_t *__restrict__
         }
     }
     if (q == 0 && u <= 2 * X) v += ((cinit.w[u >> 2] >> ((u & 3) * 8)) & 0xFFu) * 0x01010101u;
-    keytab[e] = v;
+    keytab[(size_t)g * KEYGROUP_DWORDS + e % KEYGROUP_KEY_DWORDS] = v;   // (the group's record: key entries, then its tile table)
+}
+
+// One thread per tile-table dword (hmk_internal.h, ROWS_TILE_TABLE): group g, row position k, residue c, half h = byte t: cell(row 8g + 4h
+// + t, k, c) + bias, zero for a row at or past n -- the dword rows_tile's build writes at pos_addr(g, k) + 8c + 4h.  A row-shared group,
+// by the planner's own rule (row_shared set: 8 live rows, equal at both key positions), holds its merged entries: at key position 0 the
+// high dword is key position 1's.
+__global__ void __launch_bounds__(256) k_rows_rowtab(const uint8_t *__restrict__ res_sorted, uint32_t lpad, uint32_t n,
+                                                     const uint8_t *__restrict__ mb, int case_b, int X, int L, int row_shared,
+                                                     uint32_t *__restrict__ keytab, uint32_t n_groups) {
+    const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (uint64_t)n_groups * ROWTAB_DWORDS) return;
+    const uint32_t g = (uint32_t)(e / ROWTAB_DWORDS);
+    const int d = (int)(e % ROWTAB_DWORDS), h = d & 1, c = (d >> 1) % HMK_ALPHABET, k = d / (2 * HMK_ALPHABET);
+    const int k0 = rows_key_pos(X, L, 0), k1 = rows_key_pos(X, L, 1);
+    int i = k;
+    if (row_shared && k == k0 && h == 1 && 8 * g + 8 <= n) {
+        const uint8_t *first = res_sorted + (size_t)(8 * g) * lpad;
+        bool same = true;
+        for (int r = 1; r < 8; r++) same = same && first[(size_t)r * lpad + k0] == first[k0] && first[(size_t)r * lpad + k1] == first[k1];
+        if (same) i = k1;
+    }
+    uint32_t v = 0;
+    if (i < L) {
+        for (int t = 0; t < 4; t++) {
+            const uint32_t r = 8 * g + 4 * h + t;
+            if (r < n) {
+                const int a = res_sorted[(size_t)r * lpad + i];
+                v |= (uint32_t)(case_b ? mb[c * HMK_ALPHABET + a] : mb[a * HMK_ALPHABET + c]) << (8 * t);
+            }
+        }
+    }
+    keytab[(size_t)g * KEYGROUP_DWORDS + KEYGROUP_KEY_DWORDS + d] = v;
 }
 
 hipError_t launch_rows_keytab(const uint8_t *res_sorted, uint32_t lpad, uint32_t n, const uint8_t *mb, int case_b, int X, int L,
@@ -84,6 +116,16 @@ hipError_t launch_rows_keytab(const uint8_t *res_sorted, uint32_t lpad, uint32_t
     for (int k = 0; k < 8; k++) ci.w[k] = cinit[k];
     hipLaunchKernelGGL(k_rows_keytab, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, res_sorted, lpad, n, mb, case_b, X, L, ci,
                        keytab, n_groups);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_rowtab(const uint8_t *res_sorted, uint32_t lpad, uint32_t n, const uint8_t *mb, int case_b, int X, int L,
+                              bool row_shared, uint32_t *keytab, uint32_t n_groups) {
+    const uint64_t total = (uint64_t)n_groups * ROWTAB_DWORDS;
+    if (total == 0) return hipSuccess;
+    if (L != ROWTAB_POSITIONS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rows_rowtab, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, res_sorted, lpad, n, mb, case_b, X, L,
+                       row_shared ? 1 : 0, keytab, n_groups);
     return hipGetLastError();
 }
 

@@ -217,6 +217,9 @@ int hmk_neighbors_last_plan(hmk_ctx *ctx, hmk_neighbor_stats *stats);
 /* ... of that plan: its 16-row tiles (0: the plan is not paired) and those of them whose second row group takes the merged cells of
  * the two key positions from the first (both groups row-shared with the same two key residues; HMK_NO_ROW_RUN_SHARE=1: none) */
 int hmk_neighbors_last_plan_shared(hmk_ctx *ctx, uint32_t *paired_tiles, uint32_t *run_shared_tiles);
+/* ... of that plan: the tiles that copy their row groups' tables from the plan instead of building them (a key-sorted plan: all of
+ * its tiles; any other plan, or HMK_NO_TILE_TABLES=1: 0) and the bytes of device memory those tables take (0 with no such tile) */
+int hmk_neighbors_last_plan_tables(hmk_ctx *ctx, uint32_t *table_tiles, uint64_t *table_bytes);
 
 /* ---- query-vs-reference search ---------------------------------------------- */
 
