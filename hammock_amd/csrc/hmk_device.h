@@ -136,25 +136,6 @@ __device__ __forceinline__ int global_score_literal(const int *M, const uint8_t 
     return (int)(int16_t)row[len2 * stride];
 }
 
-// query profiles of R rows into LDS: entry (r, c, iq) = four int8 (score * scale) for lines 4 iq .. 4 iq + 3;
-// -128 for the pad residue (c == 24) and for lines beyond the row's length
-template <int R>
-__device__ __forceinline__ void build_profiles(uint32_t *q, const int8_t *m8, const uint8_t *rowres, const int *row_len,
-                                               uint32_t nrows, int scale, int tid) {
-    for (int e = tid; e < R * 25 * 8; e += 256) {
-        const int r = e / 200, rem = e - r * 200, c = rem >> 3, iq = rem & 7;
-        const int l1 = (uint32_t)r < nrows ? row_len[r] : 0;
-        uint32_t dw = 0;
-        for (int k = 0; k < 4; k++) {
-            const int i = iq * 4 + k;
-            int v = -128;
-            if (i < l1 && c < 24) v = m8[rowres[r * 32 + i] * 24 + c] * scale;
-            dw |= ((uint32_t)v & 0xFFu) << (8 * k);
-        }
-        q[e] = dw;
-    }
-}
-
 // per-lane LDS staging of one sequence: 9-dword stride keeps the byte reads of
 // the 64 lanes on different banks
 constexpr int SEQ_STRIDE_DW = 9;
@@ -208,56 +189,56 @@ __device__ __forceinline__ void place_edge(const NeighborParams &P, uint32_t x, 
 // from 256 CUs are served one after the other, ~100 ns each).
 __device__ __forceinline__ uint32_t tile_shard(uint32_t tile) { return tile % HMK_EDGE_SHARDS; }
 
-// Drains one wave's staged records to its output segment.  REC_DW dwords per
-// record: [0] column (sorted position), [1] row within the tile, [2..] the NW
-// accumulator dwords (SWAR) or the score itself (direct, NW == 0).
-template <int NW, bool DEG = true>
-__device__ __forceinline__ void flush_stage(const HMK_LDS uint32_t *stage, uint32_t cnt, const NeighborParams &P,
-                                            const Tile &T, int g, bool lane16, uint32_t shard) {
-    constexpr int REC_DW = (NW == 0) ? 3 : NW + 2;
-    if (cnt == 0) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // staged ds_writes land before the reads below
+// -----------------------------------------------------------------------------
+// the edge tail: what every drain does with a decoded record
+// -----------------------------------------------------------------------------
+// the 64-bit edge word: x << 40 | m << 16 | the score's low 16 bits (HMK_EDGE_*)
+__device__ __forceinline__ uint64_t pack_edge(uint32_t x, uint32_t m, int score) {
+    return ((uint64_t)x << 40) | ((uint64_t)m << 16) | (uint64_t)((uint32_t)score & 0xFFFFu);
+}
+
+// `cnt` (wave-uniform) consecutive places in the shard's segment -> the first of them, in every lane
+__device__ __forceinline__ unsigned long long claim_edges(const NeighborParams &P, uint32_t shard, uint32_t cnt) {
     // threadIdx.x lives in v0 for the whole kernel; an mbcnt-derived lane id is hoisted out of the tile loop by the
-    // compiler and then SPILLED to scratch there (8 bytes per lane and tile: +45 MB of HBM writes on the 10^5 pass)
-    const uint32_t lane = threadIdx.x & 63u;
+    // compiler and then SPILLED to scratch there (8 bytes per lane and tile: +45 MB of HBM writes on the 10^5 pass).
+    // readfirstlane(cnt): a count that arrives through a reference (HitStage, stage_slot's drain) is not proven uniform any more, and
+    // the atomic optimiser then builds its per-lane scan loop around the atomic instead of one multiply
     unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(&P.counts[shard], (unsigned long long)cnt);
+    if ((threadIdx.x & 63u) == 0) base = atomicAdd(&P.counts[shard], (unsigned long long)__builtin_amdgcn_readfirstlane(cnt));
     const uint32_t blo = __builtin_amdgcn_readfirstlane((uint32_t)base);
     const uint32_t bhi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-    base = ((unsigned long long)bhi << 32) | blo;
-    for (uint32_t k = lane; k < cnt; k += 64) {
-        const HMK_LDS uint32_t *rec = stage + k * REC_DW;
-        const uint32_t col = rec[0], r = rec[1];
-        int score;
-        if (NW == 0) {
-            score = (int)rec[2];
-        } else {
-            uint32_t mx = 0;
-#pragma unroll
-            for (int w = 0; w < NW; w++) {
-                const uint32_t dw = rec[2 + w];
-                if (lane16) {
-                    mx = max(mx, max(dw & 0xFFFFu, dw >> 16));
-                } else {
-                    mx = max(mx, max(max(dw & 0xFFu, (dw >> 8) & 0xFFu), max((dw >> 16) & 0xFFu, dw >> 24)));
-                }
-            }
-            score = (int)mx - g;
-        }
-        uint32_t x = T.row0 + r, m = col;
-        if (!P.perm_identity) { x = P.perm[x]; m = P.perm[m]; }   // wave-uniform branch
-        if (P.row_is_m || (P.symmetric && x > m)) { const uint32_t t = x; x = m; m = t; }
-        const unsigned long long pos = base + k;
-        if (pos < P.cap_per_shard) {
-            P.edges[(unsigned long long)shard * P.cap_per_shard + pos] =
-                ((unsigned long long)x << 40) | ((unsigned long long)m << 16) | (unsigned long long)((uint32_t)score & 0xFFFFu);
-            // degrees of STORED edges only: an edge dropped by a segment overflow must not be counted, or the CSR built
-            // from the counters (its scatter is enqueued before the host notices the overflow) would be sized for edges that
-            // are not there and overrun the adjacency buffer
-            if (DEG) place_edge<EDGES_RUNTIME>(P, x, m);   // stored edges only
-        }
+    return ((unsigned long long)bhi << 32) | blo;
+}
+
+// The pair (x = tile row, m = tile column, both sorted positions) to place `pos` of the shard's segment: caller order, orientation
+// (P.row_is_m: the row is m; a symmetric pass stores (min, max)), capacity check, store, degrees.  ROW_IS_M = false: a kernel none of
+// whose plans sets P.row_is_m leaves its test out.
+template <int MODE, bool ROW_IS_M = true>
+__device__ __forceinline__ void store_edge(const NeighborParams &P, uint32_t shard, unsigned long long pos, uint32_t x, uint32_t m,
+                                           int score) {
+    if (!P.perm_identity) { x = P.perm[x]; m = P.perm[m]; }   // wave-uniform branch
+    if ((ROW_IS_M && P.row_is_m) || (P.symmetric && x > m)) { const uint32_t t = x; x = m; m = t; }
+    if (pos < P.cap_per_shard) {
+        P.edges[(unsigned long long)shard * P.cap_per_shard + pos] = pack_edge(x, m, score);
+        place_edge<MODE>(P, x, m);   // stored edges only (see EDGES_*)
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // reads done before the stage is reused
+}
+
+// The three drains of one wave's staged records to its output segment: each is its record's decode between claim_edges and
+// store_edge, inside two fences (staged ds_writes land before the reads; reads are done before the stage is reused).
+//
+// flush_stage: three dwords per record, {column (sorted position), row within the tile, score}.  (No wave priority: its kernels
+// are bound by their DP, not by the LDS queue.)
+__device__ __forceinline__ void flush_stage(const HMK_LDS uint32_t *stage, uint32_t cnt, const NeighborParams &P, const Tile &T,
+                                            uint32_t shard) {
+    if (cnt == 0) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    const unsigned long long base = claim_edges(P, shard, cnt);
+    for (uint32_t k = threadIdx.x & 63u; k < cnt; k += 64) {
+        const HMK_LDS uint32_t *rec = stage + k * 3;
+        store_edge<EDGES_RUNTIME>(P, shard, base + k, T.row0 + rec[1], rec[0], (int)rec[2]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
 }
 
 // Compact staging (the exact 8-bit lane kernel): one dword per hit, (column - tile's first column) | row << 16 |
@@ -265,32 +246,19 @@ __device__ __forceinline__ void flush_stage(const HMK_LDS uint32_t *stage, uint3
 // tile has at most 65,536 columns and 16 rows, so the record is exact; staging it is a ds_write_b32 (2 LDS-array cycles per
 // wave-instruction) where the 16-byte {column, row, accumulators} record was a ds_write_b128 (8): with a hit in ~15 % of the
 // wave iterations that was 5 % of the kernel's LDS cycles (SQ_LDS_IDX_ACTIVE against 2 x the lookups).
+// The kernel's plans (shift-packed classes of one length) never set P.row_is_m: store_edge<MODE, false>.
 template <int MODE>
 __device__ __forceinline__ void flush_stage_compact(const HMK_LDS uint32_t *stage, uint32_t cnt, const NeighborParams &P,
                                                     const Tile &T, int threshold, uint32_t shard) {
     if (cnt == 0) return;
     drain_begin();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // staged ds_writes land before the reads below
-    const uint32_t lane = threadIdx.x & 63u;                // (not mbcnt: see flush_stage)
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(&P.counts[shard], (unsigned long long)cnt);
-    const uint32_t blo = __builtin_amdgcn_readfirstlane((uint32_t)base);
-    const uint32_t bhi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-    base = ((unsigned long long)bhi << 32) | blo;
-    for (uint32_t k = lane; k < cnt; k += 64) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    const unsigned long long base = claim_edges(P, shard, cnt);
+    for (uint32_t k = threadIdx.x & 63u; k < cnt; k += 64) {
         const uint32_t rec = stage[k];
-        const int score = (int)(rec >> 20) + threshold;
-        uint32_t x = T.row0 + ((rec >> 16) & 0xFu), m = T.col0 + (rec & 0xFFFFu);
-        if (!P.perm_identity) { x = P.perm[x]; m = P.perm[m]; }   // wave-uniform branch
-        if (P.symmetric && x > m) { const uint32_t t = x; x = m; m = t; }
-        const unsigned long long pos = base + k;
-        if (pos < P.cap_per_shard) {
-            P.edges[(unsigned long long)shard * P.cap_per_shard + pos] =
-                ((unsigned long long)x << 40) | ((unsigned long long)m << 16) | (unsigned long long)((uint32_t)score & 0xFFFFu);
-            if (MODE != EDGES_PLAIN) place_edge<MODE>(P, x, m);   // stored edges only
-        }
+        store_edge<MODE, false>(P, shard, base + k, T.row0 + ((rec >> 16) & 0xFu), T.col0 + (rec & 0xFFFFu), (int)(rec >> 20) + threshold);
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // reads done before the stage is reused
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     drain_end();
 }
 
@@ -302,28 +270,70 @@ __device__ __forceinline__ void flush_stage_packed(const HMK_LDS uint32_t *stage
                                                    const Tile &T, int base_score, uint32_t rec_dw, uint32_t shard) {
     if (cnt == 0) return;
     drain_begin();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // staged ds_writes land before the reads below
-    const uint32_t lane = threadIdx.x & 63u;                // (not mbcnt: see flush_stage)
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(&P.counts[shard], (unsigned long long)cnt);
-    const uint32_t blo = __builtin_amdgcn_readfirstlane((uint32_t)base);
-    const uint32_t bhi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-    base = ((unsigned long long)bhi << 32) | blo;
-    for (uint32_t k = lane; k < cnt; k += 64) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    const unsigned long long base = claim_edges(P, shard, cnt);
+    for (uint32_t k = threadIdx.x & 63u; k < cnt; k += 64) {
         const uint32_t rec = stage[k * rec_dw];
         const int score = rec_dw == 1 ? (int)(rec >> 20) + base_score : (int)stage[k * 2 + 1];
-        uint32_t x = T.row0 + ((rec >> 16) & 0xFu), m = T.col0 + (rec & 0xFFFFu);
-        if (!P.perm_identity) { x = P.perm[x]; m = P.perm[m]; }   // wave-uniform branch
-        if (P.row_is_m || (P.symmetric && x > m)) { const uint32_t t = x; x = m; m = t; }
-        const unsigned long long pos = base + k;
-        if (pos < P.cap_per_shard) {
-            P.edges[(unsigned long long)shard * P.cap_per_shard + pos] =
-                ((unsigned long long)x << 40) | ((unsigned long long)m << 16) | (unsigned long long)((uint32_t)score & 0xFFFFu);
-            if (DEG) place_edge<EDGES_RUNTIME>(P, x, m);   // stored edges only
+        store_edge<DEG ? EDGES_RUNTIME : EDGES_PLAIN>(P, shard, base + k, T.row0 + ((rec >> 16) & 0xFu), T.col0 + (rec & 0xFFFFu), score);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    drain_end();
+}
+
+// -----------------------------------------------------------------------------
+// the hit stage: a wave's hits of one (row, 64 columns) step appended behind those it holds
+// -----------------------------------------------------------------------------
+// The append every staging kernel shares, whatever its record: `mask` = the ballot of the lanes with a hit, `cnt` =
+// the records the wave's stage holds (wave-uniform), `cap` = the records it has room for.  The stage keeps room for one wave of
+// hits: where fewer than 64 places are free, drain() empties it first (and cnt restarts at 0, whether or not drain() zeroed it).
+// A caller may pass an empty mask (k_neighbors_swar does, when its keep filter drops every hit of the step): the stage may then
+// drain one step early, nothing else.  -> this lane's place (lanes of `mask` only).
+template <class Drain>
+__device__ __forceinline__ uint32_t stage_slot(uint32_t &cnt, uint64_t mask, uint32_t cap, Drain drain) {
+    if (cnt + 64u > cap) {
+        drain();
+        cnt = 0;
+    }
+    const uint32_t slot = cnt + mbcnt64(mask);
+    cnt += (uint32_t)__popcll(mask);
+    return slot;
+}
+
+// A wave's stage of CAP {column, row, score} records (flush_stage), of the four a 256-thread workgroup keeps at `stage_all`.
+template <int CAP>
+struct HitStage {
+    static constexpr int BYTES = 4 * CAP * 3 * 4;   // the workgroup's four stages
+    HMK_LDS uint32_t *stage;   // 32-bit LDS pointer: no 64-bit flat pointer held (and spilled) across the tile
+    uint32_t cnt = 0;          // staged records (wave-uniform)
+    const NeighborParams &P;
+    const Tile &T;
+    const uint32_t shard;
+
+    __device__ __forceinline__ HitStage(uint32_t *stage_all, const NeighborParams &P_, const Tile &T_, uint32_t shard_)
+        : stage((HMK_LDS uint32_t *)stage_all + (threadIdx.x >> 6) * (CAP * 3)), P(P_), T(T_), shard(shard_) {}
+    __device__ __forceinline__ void drain() {
+        flush_stage(stage, cnt, P, T, shard);
+        cnt = 0;
+    }
+    // all 64 lanes call it (wave-uniform control flow); the lanes with `keep` stage {col, row, score}
+    __device__ __forceinline__ void put(bool keep, uint32_t col, uint32_t row, int score) {
+        const uint64_t mask = __ballot(keep);
+        if (mask == 0) return;
+        const uint32_t slot = stage_slot(cnt, mask, CAP, [&] { drain(); });
+        if (keep) {
+            HMK_LDS uint32_t *rec = stage + slot * 3;
+            rec[0] = col;
+            rec[1] = row;
+            rec[2] = (uint32_t)score;
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // reads done before the stage is reused
-    drain_end();
+};
+
+// What a tile keeps of (row, column), both sorted positions: everything (diag == 0: two sets, or a tile off the diagonal),
+// column > row (1: the triangle of one class) or column != row (2: all ordered pairs of one class); hmk_plan.cpp, emit_tiles.
+__device__ __forceinline__ bool tile_keeps(uint32_t diag, uint32_t row, uint32_t col) {
+    return diag == 0 || (diag == 1 ? col > row : col != row);
 }
 
 // largest of the eight byte lanes of two accumulator dwords

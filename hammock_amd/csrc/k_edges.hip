@@ -566,7 +566,7 @@ k_rows_unpack(const uint32_t *__restrict__ start, const uint32_t *__restrict__ a
         for (uint32_t k = b + lane; k < e; k += 64) {
             const uint32_t a = adj[k];
             const int32_t sc = (int32_t)(a & 0xFF) + threshold;
-            if (k < out_capacity) out[k] = ((uint64_t)x << 40) | ((uint64_t)(a >> 8) << 16) | (uint64_t)(uint16_t)(int16_t)sc;
+            if (k < out_capacity) out[k] = pack_edge(x, a >> 8, sc);
         }
     }
 }

@@ -1,6 +1,6 @@
 // k_local.hip -- LocalAlignmentScorer (LocalAlignmentScorer.java:27-86, direction-matrix Smith-Waterman):
 // register-resident striped DP, tagged-max and packed-int16 forms; dense blocks and thresholded ordered pairs.
-#include "hmk_device.h"
+#include "hmk_tile_device.h"
 
 namespace hmk {
 
@@ -126,7 +126,7 @@ __global__ void __launch_bounds__(256)
 k_local_block(const uint8_t *__restrict__ res32, const uint8_t *__restrict__ len, const int32_t *__restrict__ Mg,
               uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1, int gap_open, int gap_extend,
               int32_t *__restrict__ out) {
-    constexpr int R = 16;                 // rows per workgroup pass
+    constexpr int R = TILE_ROWS;          // rows per workgroup pass
     constexpr int QROW = 25 * 8 * 4;      // profile bytes per row: 25 residues (24 + pad) x 8 dwords
     __shared__ __attribute__((aligned(16))) uint8_t smem[R * QROW + 576 + R * 32];
     int8_t *m8 = reinterpret_cast<int8_t *>(smem + R * QROW);
@@ -138,12 +138,7 @@ k_local_block(const uint8_t *__restrict__ res32, const uint8_t *__restrict__ len
     const uint32_t row_base = r0 + blockIdx.y * R;
     const uint32_t nrows = min((uint32_t)R, r1 - row_base);
 
-    for (int e = tid; e < 576; e += 256) m8[e] = (int8_t)Mg[e];
-    for (int e = tid; e < R * 32; e += 256) {
-        const uint32_t r = (uint32_t)e >> 5;
-        rowres[e] = r < nrows ? res32[(size_t)(row_base + r) * 32 + (e & 31)] : 0;
-    }
-    __syncthreads();
+    load_tile_rows(m8, rowres, Mg, res32, 32, row_base, nrows, tid);
     __shared__ int row_len[R];
     if (tid < R) row_len[tid] = (uint32_t)tid < nrows ? len[row_base + tid] : 0;
     __syncthreads();
@@ -152,24 +147,8 @@ k_local_block(const uint8_t *__restrict__ res32, const uint8_t *__restrict__ len
 
     // this lane's column sequence -> profile byte offsets (pad residue 24 beyond its length)
     uint32_t boff[LBMAX];
-    int len2 = 0;
-    {
-        uint32_t words[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) words[q] = 0;
-        if (col_ok) {
-            const u32x4 *src = reinterpret_cast<const u32x4 *>(res32 + (size_t)col * 32);
-            const u32x4 v0 = src[0], v1 = src[1];
-            words[0] = v0.x; words[1] = v0.y; words[2] = v0.z; words[3] = v0.w;
-            words[4] = v1.x; words[5] = v1.y; words[6] = v1.z; words[7] = v1.w;
-            len2 = len[col];
-        }
-#pragma unroll
-        for (int j = 0; j < LBMAX; j++) {
-            const uint32_t c = j < len2 ? ((words[j >> 2] >> ((j & 3) * 8)) & 0xFFu) : 24u;
-            boff[j] = c * 32u;
-        }
-    }
+    const int len2 = col_ok ? len[col] : 0;
+    column_offsets<LBMAX, 32>(res32, 32, col, col_ok, len2, boff);
     // widest column of the wave: columns beyond it are skipped wave-uniformly
     int wmax = len2;
 #pragma unroll
@@ -195,26 +174,19 @@ template <int LBMAX, bool ENC>
 __global__ void __launch_bounds__(256)
 k_neighbors_local(const NeighborParams P, const uint32_t tile_base, const int32_t *__restrict__ Mg, int gap_open,
                   int gap_extend, int threshold) {
-    constexpr int R = 16;
+    constexpr int R = TILE_ROWS;
     constexpr int QROW = 25 * 8 * 4;
     constexpr int STAGE_CAP = 128;
-    constexpr int REC_DW = 3;
-    __shared__ __attribute__((aligned(16))) uint8_t smem[R * QROW + 576 + R * 32 + 4 * STAGE_CAP * REC_DW * 4];
+    __shared__ __attribute__((aligned(16))) uint8_t smem[R * QROW + 576 + R * 32 + HitStage<STAGE_CAP>::BYTES];
     int8_t *m8 = reinterpret_cast<int8_t *>(smem + R * QROW);
     uint8_t *rowres = smem + R * QROW + 576;
-    uint32_t *stage_all = reinterpret_cast<uint32_t *>(smem + R * QROW + 576 + R * 32);
     const Tile T = P.tiles[tile_base + blockIdx.x];
     const TileClass *Cp = P.classes + T.cls;
     const int la = Cp->la, lb = Cp->lb;   // la: row (seq1) length, lb: column (seq2) length
-    const uint32_t shard = tile_shard(tile_base + blockIdx.x);
     const int tid = threadIdx.x;
-    HMK_LDS uint32_t *stage = (HMK_LDS uint32_t *)stage_all + (tid >> 6) * (STAGE_CAP * REC_DW);   // 32-bit LDS pointer: no 64-bit flat pointer held (and spilled) across the tile
+    HitStage<STAGE_CAP> hits(reinterpret_cast<uint32_t *>(smem + R * QROW + 576 + R * 32), P, T, tile_shard(tile_base + blockIdx.x));
 
-    for (int e = tid; e < 576; e += 256) m8[e] = (int8_t)Mg[e];
-    for (int e = tid; e < R * 32; e += 256) {
-        const uint32_t r = (uint32_t)e >> 5, k = e & 31;
-        rowres[e] = (r < T.nrows && k < P.lpad) ? P.res_sorted[(size_t)(T.row0 + r) * P.lpad + k] : 0;
-    }
+    load_tile_rows(m8, rowres, Mg, P.res_sorted, P.lpad, T.row0, T.nrows, tid);
     __syncthreads();
     __shared__ int row_len[R];
     if (tid < R) row_len[tid] = (uint32_t)tid < T.nrows ? la : 0;
@@ -225,51 +197,18 @@ k_neighbors_local(const NeighborParams P, const uint32_t tile_base, const int32_
     const uint32_t q_addr = lds_addr(smem);
     const uint32_t col_end = T.col0 + T.ncols;
     const int strips = (la + 3) >> 2;
-    uint32_t cnt = 0;
     for (uint32_t c0 = T.col0; c0 < col_end; c0 += 256) {
         const uint32_t col = c0 + tid;
         const bool col_ok = col < col_end;
         uint32_t boff[LBMAX];
-        {
-            uint32_t words[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) words[q] = 0;
-            if (col_ok) {
-                const u32x4 *src = reinterpret_cast<const u32x4 *>(P.res_sorted + (size_t)col * P.lpad);
-                const u32x4 v0 = src[0];
-                words[0] = v0.x; words[1] = v0.y; words[2] = v0.z; words[3] = v0.w;
-                if (LBMAX > 16) {
-                    const u32x4 v1 = src[1];
-                    words[4] = v1.x; words[5] = v1.y; words[6] = v1.z; words[7] = v1.w;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < LBMAX; j++) {
-                const uint32_t c = (col_ok && j < lb) ? ((words[j >> 2] >> ((j & 3) * 8)) & 0xFFu) : 24u;
-                boff[j] = c * 32u;
-            }
-        }
+        column_offsets<LBMAX, 32>(P.res_sorted, P.lpad, col, col_ok, lb, boff);
         for (uint32_t r = 0; r < T.nrows; r++) {
             const int gmax = sw_row<LBMAX, ENC>(q_addr + r * QROW, strips, lb, boff, gap_open, gap_extend);
-            bool keep = col_ok && gmax >= threshold;
-            if (T.diag) keep = keep && col != T.row0 + r;   // a sequence is never paired with itself
-            const uint64_t mask = __ballot(keep);
-            if (mask != 0) {
-                if (cnt > (uint32_t)(STAGE_CAP - 64)) {
-                    flush_stage<0>(stage, cnt, P, T, 0, false, shard);
-                    cnt = 0;
-                }
-                if (keep) {
-                    HMK_LDS uint32_t *rec = stage + (cnt + mbcnt64(mask)) * REC_DW;
-                    rec[0] = col;
-                    rec[1] = r;
-                    rec[2] = (uint32_t)gmax;
-                }
-                cnt += (uint32_t)__popcll(mask);
-            }
+            // (a local plan's tiles have diag 0 or 2 -- finish_plan_local with self = 2 or 0 -- so this is "a sequence is never paired with itself")
+            hits.put(col_ok && gmax >= threshold && tile_keeps(T.diag, T.row0 + r, col), col, r, gmax);
         }
     }
-    flush_stage<0>(stage, cnt, P, T, 0, false, shard);
+    hits.drain();
 }
 
 // -----------------------------------------------------------------------------
@@ -402,45 +341,26 @@ template <int LBMAX, bool SAT>
 __global__ void __launch_bounds__(256)
 k_neighbors_local_pk(const NeighborParams P, const uint32_t tile_base, const int32_t *__restrict__ Mg, int gap_open,
                      int gap_extend, int threshold) {
-    constexpr int R = 16;
+    constexpr int R = TILE_ROWS;
     constexpr int QROW = 25 * 8 * 8;      // 25 residues x 8 strips x (4 lines x int16)
     constexpr int STAGE_CAP = 192;        // room for two flush-free appends (lo and hi halves)
-    constexpr int REC_DW = 3;
-    __shared__ __attribute__((aligned(16))) uint8_t smem[R * QROW + 576 + R * 32 + 4 * STAGE_CAP * REC_DW * 4];
+    __shared__ __attribute__((aligned(16))) uint8_t smem[R * QROW + 576 + R * 32 + HitStage<STAGE_CAP>::BYTES];
     int8_t *m8 = reinterpret_cast<int8_t *>(smem + R * QROW);
     uint8_t *rowres = smem + R * QROW + 576;
-    uint32_t *stage_all = reinterpret_cast<uint32_t *>(smem + R * QROW + 576 + R * 32);
     const Tile T = P.tiles[tile_base + blockIdx.x];
     const TileClass *Cp = P.classes + T.cls;
     const int la = Cp->la, lb = Cp->lb;
-    const uint32_t shard = tile_shard(tile_base + blockIdx.x);
     const int tid = threadIdx.x;
-    HMK_LDS uint32_t *stage = (HMK_LDS uint32_t *)stage_all + (tid >> 6) * (STAGE_CAP * REC_DW);   // 32-bit LDS pointer: no 64-bit flat pointer held (and spilled) across the tile
+    HitStage<STAGE_CAP> hits(reinterpret_cast<uint32_t *>(smem + R * QROW + 576 + R * 32), P, T, tile_shard(tile_base + blockIdx.x));
 
-    for (int e = tid; e < 576; e += 256) m8[e] = (int8_t)Mg[e];
-    for (int e = tid; e < R * 32; e += 256) {
-        const uint32_t r = (uint32_t)e >> 5, k = e & 31;
-        rowres[e] = (r < T.nrows && k < P.lpad) ? P.res_sorted[(size_t)(T.row0 + r) * P.lpad + k] : 0;
-    }
+    load_tile_rows(m8, rowres, Mg, P.res_sorted, P.lpad, T.row0, T.nrows, tid);
     __syncthreads();
-    // profiles: entry (r, c, strip) = four int16 (4 * score; -128 for padding lines / the pad residue)
-    for (int e = tid; e < R * 25 * 8; e += 256) {
-        const int r = e / 200, rem = e - r * 200, c = rem >> 3, iq = rem & 7;
-        uint32_t w[2] = {0, 0};
-        for (int k = 0; k < 4; k++) {
-            const int i = iq * 4 + k;
-            int v = -128;
-            if ((uint32_t)r < T.nrows && i < la && c < 24) v = m8[rowres[r * 32 + i] * 24 + c] * 4;
-            w[k >> 1] |= ((uint32_t)v & 0xFFFFu) << (16 * (k & 1));
-        }
-        reinterpret_cast<u32x2 *>(smem)[e] = u32x2{w[0], w[1]};
-    }
+    build_profiles_i16<R>(reinterpret_cast<u32x2 *>(smem), m8, rowres, T.nrows, tid, [&](int) { return la; });
     __syncthreads();
 
     const uint32_t q_addr = lds_addr(smem);
     const uint32_t col_end = T.col0 + T.ncols;
     const int strips = (la + 3) >> 2;
-    uint32_t cnt = 0;
     for (uint32_t c0 = T.col0; c0 < col_end; c0 += 512) {
         uint32_t colv[2];
         bool okv[2];
@@ -449,49 +369,18 @@ k_neighbors_local_pk(const NeighborParams P, const uint32_t tile_base, const int
         for (int h = 0; h < 2; h++) {
             colv[h] = c0 + h * 256 + tid;
             okv[h] = colv[h] < col_end;
-            uint32_t words[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) words[q] = 0;
-            if (okv[h]) {
-                const u32x4 *src = reinterpret_cast<const u32x4 *>(P.res_sorted + (size_t)colv[h] * P.lpad);
-                const u32x4 v0 = src[0];
-                words[0] = v0.x; words[1] = v0.y; words[2] = v0.z; words[3] = v0.w;
-                if (LBMAX > 16) {
-                    const u32x4 v1 = src[1];
-                    words[4] = v1.x; words[5] = v1.y; words[6] = v1.z; words[7] = v1.w;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < LBMAX; j++) {
-                const uint32_t c = (okv[h] && j < lb) ? ((words[j >> 2] >> ((j & 3) * 8)) & 0xFFu) : 24u;
-                boff[h][j] = c * 64u;   // 8 strips x 8 bytes per residue
-            }
+            column_offsets<LBMAX, 64>(P.res_sorted, P.lpad, colv[h], okv[h], lb, boff[h]);   // 8 strips x 8 bytes per residue
         }
         for (uint32_t r = 0; r < T.nrows; r++) {
             const uint32_t g2 = sw_row_pk<LBMAX, SAT>(q_addr + r * QROW, strips, la, lb, boff[0], boff[1], gap_open, gap_extend);
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 const int gmax = (int)((g2 >> (16 * h)) & 0xFFFFu);
-                bool keep = okv[h] && gmax >= threshold;
-                if (T.diag) keep = keep && colv[h] != T.row0 + r;
-                const uint64_t mask = __ballot(keep);
-                if (mask != 0) {
-                    if (cnt > (uint32_t)(STAGE_CAP - 64)) {
-                        flush_stage<0>(stage, cnt, P, T, 0, false, shard);
-                        cnt = 0;
-                    }
-                    if (keep) {
-                        HMK_LDS uint32_t *rec = stage + (cnt + mbcnt64(mask)) * REC_DW;
-                        rec[0] = colv[h];
-                        rec[1] = r;
-                        rec[2] = (uint32_t)gmax;
-                    }
-                    cnt += (uint32_t)__popcll(mask);
-                }
+                hits.put(okv[h] && gmax >= threshold && tile_keeps(T.diag, T.row0 + r, colv[h]), colv[h], r, gmax);   // (diag 0 or 2: see k_neighbors_local)
             }
         }
     }
-    flush_stage<0>(stage, cnt, P, T, 0, false, shard);
+    hits.drain();
 }
 
 // -----------------------------------------------------------------------------
@@ -505,7 +394,7 @@ template <int LBMAX, bool SAT>
 __global__ void __launch_bounds__(256)
 k_local_block_pk(const uint8_t *__restrict__ res32, const uint8_t *__restrict__ len, const int32_t *__restrict__ Mg,
                  uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1, int gap_open, int gap_extend, int32_t *__restrict__ out) {
-    constexpr int R = 16;
+    constexpr int R = TILE_ROWS;
     constexpr int QROW = 25 * 8 * 8;      // 25 residues x 8 strips x (4 lines x int16)
     __shared__ __attribute__((aligned(16))) uint8_t smem[R * QROW + 576 + R * 32];
     __shared__ int row_len[R];
@@ -516,24 +405,10 @@ k_local_block_pk(const uint8_t *__restrict__ res32, const uint8_t *__restrict__ 
     const uint32_t row_base = r0 + blockIdx.y * R;
     const uint32_t nrows = min((uint32_t)R, r1 - row_base);
 
-    for (int e = tid; e < 576; e += 256) m8[e] = (int8_t)Mg[e];
-    for (int e = tid; e < R * 32; e += 256) {
-        const uint32_t r = (uint32_t)e >> 5;
-        rowres[e] = r < nrows ? res32[(size_t)(row_base + r) * 32 + (e & 31)] : 0;
-    }
+    load_tile_rows(m8, rowres, Mg, res32, 32, row_base, nrows, tid);
     if (tid < R) row_len[tid] = (uint32_t)tid < nrows ? len[row_base + tid] : 0;
     __syncthreads();
-    for (int e = tid; e < R * 25 * 8; e += 256) {
-        const int r = e / 200, rem = e - r * 200, c = rem >> 3, iq = rem & 7;
-        uint32_t w[2] = {0, 0};
-        for (int k = 0; k < 4; k++) {
-            const int i = iq * 4 + k;
-            int v = -128;
-            if (i < row_len[r] && c < 24) v = m8[rowres[r * 32 + i] * 24 + c] * 4;
-            w[k >> 1] |= ((uint32_t)v & 0xFFFFu) << (16 * (k & 1));
-        }
-        reinterpret_cast<u32x2 *>(smem)[e] = u32x2{w[0], w[1]};
-    }
+    build_profiles_i16<R>(reinterpret_cast<u32x2 *>(smem), m8, rowres, nrows, tid, [&](int r) { return row_len[r]; });
     __syncthreads();
 
     uint32_t colv[2];
@@ -544,22 +419,8 @@ k_local_block_pk(const uint8_t *__restrict__ res32, const uint8_t *__restrict__ 
     for (int h = 0; h < 2; h++) {
         colv[h] = c0 + blockIdx.x * 512 + h * 256 + tid;
         okv[h] = colv[h] < c1;
-        uint32_t words[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) words[q] = 0;
-        int len2 = 0;
-        if (okv[h]) {
-            const u32x4 *src = reinterpret_cast<const u32x4 *>(res32 + (size_t)colv[h] * 32);
-            const u32x4 v0 = src[0], v1 = src[1];
-            words[0] = v0.x; words[1] = v0.y; words[2] = v0.z; words[3] = v0.w;
-            words[4] = v1.x; words[5] = v1.y; words[6] = v1.z; words[7] = v1.w;
-            len2 = len[colv[h]];
-        }
-#pragma unroll
-        for (int j = 0; j < LBMAX; j++) {
-            const uint32_t c = j < len2 ? ((words[j >> 2] >> ((j & 3) * 8)) & 0xFFu) : 24u;
-            boff[h][j] = c * 64u;
-        }
+        const int len2 = okv[h] ? len[colv[h]] : 0;
+        column_offsets<LBMAX, 64>(res32, 32, colv[h], okv[h], len2, boff[h]);
         wmax = max(wmax, len2);
     }
 #pragma unroll
@@ -581,75 +442,27 @@ k_local_block_pk(const uint8_t *__restrict__ res32, const uint8_t *__restrict__ 
 // k_neighbors_local_literal: the same pass with the literal DP (LocalAlignmentScorer.java:31-86 line by line)
 // -----------------------------------------------------------------------------
 // For what the striped kernels do not take: positive gap penalties (the reference imposes no sign, :43-55) and matrix
-// entries beyond int8.  Same tiles, same edge orientation (row = seq1 = m, column = seq2 = x), one column per lane.
+// entries beyond int8.  Same tiles, same edge orientation (row = seq1 = m, column = seq2 = x), one column per lane: the literal
+// tile kernel of hmk_tile_device.h.
+struct LocalLiteral {
+    static constexpr bool DP_LINE = true;
+    int gap_open, gap_extend;
+    __device__ __forceinline__ int score(const int *M, const uint8_t *row, int la, const uint8_t *col, int lb, uint32_t *dp) const {
+        return local_score_literal(M, row, la, col, lb, gap_open, gap_extend, dp, 256);
+    }
+};
+
 __global__ void __launch_bounds__(256)
 k_neighbors_local_literal(const NeighborParams P, const uint32_t tile_base, const int32_t *__restrict__ Mg, int gap_open,
                           int gap_extend, int threshold) {
-    constexpr int R = 16, STAGE_CAP = 128, REC_DW = 3;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    int *M = reinterpret_cast<int *>(smem);                                   // 576 dwords
-    uint32_t *colseq = reinterpret_cast<uint32_t *>(smem + 2304);             // 256 x 9 dwords
-    uint32_t *rowseq = colseq + 256 * SEQ_STRIDE_DW;                          // R x 8 dwords
-    uint32_t *dp = rowseq + R * 8;                                            // 33 x 256 dwords: one DP line per lane
-    uint32_t *stage_all = dp + 33 * 256;
-    const Tile T = P.tiles[tile_base + blockIdx.x];
-    const TileClass *Cp = P.classes + T.cls;
-    const int la = Cp->la, lb = Cp->lb;
-    const uint32_t shard = tile_shard(tile_base + blockIdx.x);
-    const int tid = threadIdx.x;
-    HMK_LDS uint32_t *stage = (HMK_LDS uint32_t *)stage_all + (tid >> 6) * (STAGE_CAP * REC_DW);
-    for (int e = tid; e < 576; e += 256) M[e] = Mg[e];
-    for (int e = tid; e < R * 8; e += 256) {
-        const int r = e >> 3, q = e & 7;
-        uint32_t v = 0;
-        if ((uint32_t)r < T.nrows && (uint32_t)(q * 4) < P.lpad)
-            v = reinterpret_cast<const uint32_t *>(P.res_sorted + (size_t)(T.row0 + r) * P.lpad)[q];
-        rowseq[e] = v;
-    }
-    __syncthreads();
-    uint32_t cnt = 0;
-    const uint32_t col_end = T.col0 + T.ncols;
-    uint32_t *mine = colseq + tid * SEQ_STRIDE_DW;
-    for (uint32_t c0 = T.col0; c0 < col_end; c0 += 256) {
-        const uint32_t col = c0 + tid;
-        if (col < col_end) {
-            const uint32_t *src = reinterpret_cast<const uint32_t *>(P.res_sorted + (size_t)col * P.lpad);
-            for (uint32_t q = 0; q < P.lpad / 4; q++) mine[q] = src[q];
-        }
-        for (uint32_t r = 0; r < T.nrows; r++) {
-            if (cnt > (uint32_t)(STAGE_CAP - 64)) {
-                flush_stage<0>(stage, cnt, P, T, 0, false, shard);
-                cnt = 0;
-            }
-            bool keep = col < col_end;
-            if (T.diag) keep = keep && col != T.row0 + r;
-            int score = 0;
-            if (keep) {
-                score = local_score_literal(M, reinterpret_cast<const uint8_t *>(rowseq + r * 8), la,
-                                            reinterpret_cast<const uint8_t *>(mine), lb, gap_open, gap_extend, dp + tid, 256);
-                keep = score >= threshold;
-            }
-            const uint64_t mask = __ballot(keep);
-            if (mask != 0) {
-                if (keep) {
-                    HMK_LDS uint32_t *rec = stage + (cnt + mbcnt64(mask)) * REC_DW;
-                    rec[0] = col;
-                    rec[1] = r;
-                    rec[2] = (uint32_t)score;
-                }
-                cnt += (uint32_t)__popcll(mask);
-            }
-        }
-    }
-    flush_stage<0>(stage, cnt, P, T, 0, false, shard);
+    literal_tile(P, tile_base + blockIdx.x, Mg, LocalLiteral{gap_open, gap_extend}, threshold);
 }
 
 hipError_t launch_neighbors_local_literal(const NeighborParams &P, uint32_t tile_base, uint32_t n_tiles, const int32_t *d_matrix,
                                           int gap_open, int gap_extend, int threshold, hipStream_t s) {
     if (n_tiles == 0) return hipSuccess;
-    const size_t lds = 2304 + 256 * SEQ_STRIDE_DW * 4 + 16 * 8 * 4 + 33 * 256 * 4 + 4 * 128 * 3 * 4;
-    hipLaunchKernelGGL(k_neighbors_local_literal, dim3(n_tiles), dim3(256), lds, s, P, tile_base, d_matrix, gap_open, gap_extend,
-                       threshold);
+    hipLaunchKernelGGL(k_neighbors_local_literal, dim3(n_tiles), dim3(256), LiteralTile<LocalLiteral::DP_LINE>::BYTES, s, P, tile_base, d_matrix,
+                       gap_open, gap_extend, threshold);
     return hipGetLastError();
 }
 

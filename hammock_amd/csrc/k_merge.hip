@@ -189,7 +189,7 @@ k_merge_compact(uint32_t ncl, const uint32_t *__restrict__ cl_start, const uint3
             const uint64_t r = src[i];
             const int32_t score = (int32_t)(uint32_t)r + thr;
             if (dst + i < out_capacity)
-                out[dst + i] = ((uint64_t)a << 40) | ((uint64_t)(uint32_t)(r >> 32) << 16) | (uint64_t)((uint32_t)score & 0xFFFFu);
+                out[dst + i] = pack_edge(a, (uint32_t)(r >> 32), score);
         }
     }
 }

@@ -9,7 +9,7 @@
 //                       lanes, so one ds_read_b64 + one v_add3 per dword advance all 7 shift sums of a pair
 //   k_neighbors_planes  the same scheme for arbitrary lengths (conflict-free plane layout of the tables)
 //   k_neighbors_direct  literal tier for length classes whose sums fit neither 8- nor 16-bit lanes
-#include "hmk_device.h"
+#include "hmk_tile_device.h"
 
 namespace hmk {
 
@@ -175,21 +175,12 @@ k_neighbors_swar(const NeighborParams P, const uint32_t tile_base) {
                     for (int w = 1; w < NW; w++) any |= W[p][w];
                     const bool hit = (any & himask) != 0;  // some shift reached score >= threshold
                     if (__ballot(hit) != 0) {              // wave-uniform, rare
-                        if (cnt > (uint32_t)(STAGE_CAP - 64)) {  // keep room for one wave of hits
-                            flush_stage_compact<DEG>(stage, cnt, P, T, threshold, shard);
-                            cnt = 0;
-                        }
                         const uint32_t col = colpos[p];
                         bool keep = hit;
-                        if (!interior) {  // wave-uniform: only edge tiles filter
-                            keep = keep && col < col_end;
-                            if (T.diag == 1) keep = keep && col > T.row0 + r;   // triangle: column after row
-                            if (T.diag == 2) keep = keep && col != T.row0 + r;  // full square minus the diagonal
-                        }
-                        const uint64_t mask = __ballot(keep);
+                        if (!interior) keep = keep && col < col_end && tile_keeps(T.diag, T.row0 + r, col);   // wave-uniform: only edge tiles filter
+                        const uint32_t slot = stage_slot(cnt, __ballot(keep), STAGE_CAP, [&] { flush_stage_compact<DEG>(stage, cnt, P, T, threshold, shard); });
                         if (keep)   // score - threshold = best lane - 128, in 0..127
-                            stage[cnt + mbcnt64(mask)] = (col - T.col0) | ((uint32_t)r << 16) | ((max_byte_lane(W[p][0], W[p][1]) - 128u) << 20);
-                        cnt += (uint32_t)__popcll(mask);
+                            stage[slot] = (col - T.col0) | ((uint32_t)r << 16) | ((max_byte_lane(W[p][0], W[p][1]) - 128u) << 20);
                     }
                 }
             }
@@ -473,6 +464,8 @@ __global__ void __launch_bounds__(256, (NW == 2 && 2 * R + LBMAX <= 30) ? 6 : 1)
 #pragma unroll
                 for (int w = 1; w < NW; w++) any |= W[r][w];
                 const bool hit = (any & himask) != 0 && (uint32_t)r < T.nrows;
+                // This site stays as it was, byte for byte: on stage_slot 12 of the 32 instantiations took 1-2 more VGPRs
+                // (<6, 2, 12>: 8 -> 7 waves per SIMD), and tile_keeps' select form added up to 4 % instructions to its R unrolled copies.
                 if (__ballot(hit) != 0) {  // wave-uniform, rare
                     if ((cnt + 64) * rec_dw > (uint32_t)STAGE_DW) {
                         flush_stage_packed<true>(stage, cnt, P, T, base_score, rec_dw, shard);
@@ -507,75 +500,21 @@ __global__ void __launch_bounds__(256, (NW == 2 && 2 * R + LBMAX <= 30) ? 6 : 1)
 }
 
 // -----------------------------------------------------------------------------
-// k_neighbors_direct: generic tier (same tiles, literal scorer, one column per lane)
+// k_neighbors_direct: generic tier (same tiles, the literal tile kernel of hmk_tile_device.h with the shifted scorer)
 // -----------------------------------------------------------------------------
+struct ShiftedLiteral {
+    static constexpr bool DP_LINE = false;
+    int max_shift, shift_penalty;
+    // edge (x = row, m = column) carries sequenceScore(seq1 = m, seq2 = x)
+    __device__ __forceinline__ int score(const int *M, const uint8_t *row, int la, const uint8_t *col, int lb, uint32_t *) const {
+        return shifted_score_literal(M, col, lb, row, la, max_shift, shift_penalty);
+    }
+};
+
 __global__ void __launch_bounds__(256)
 k_neighbors_direct(const NeighborParams P, const uint32_t tile_base, const int32_t *__restrict__ Mg,
                    int max_shift, int shift_penalty, int threshold) {
-    constexpr int R = 16;
-    constexpr int STAGE_CAP = 128;
-    constexpr int REC_DW = 3;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    int *M = reinterpret_cast<int *>(smem);                                   // 2304 B
-    uint32_t *colseq = reinterpret_cast<uint32_t *>(smem + 2304);             // 256 * 9 dwords
-    uint32_t *rowseq = colseq + 256 * SEQ_STRIDE_DW;                          // R * 8 dwords
-    uint32_t *stage_all = rowseq + R * 8;
-
-    const Tile T = P.tiles[tile_base + blockIdx.x];
-    const TileClass *Cp = P.classes + T.cls;
-    const int la = Cp->la, lb = Cp->lb;
-    const uint32_t shard = tile_shard(tile_base + blockIdx.x);
-    const int tid = threadIdx.x;
-    HMK_LDS uint32_t *stage = (HMK_LDS uint32_t *)stage_all + (tid >> 6) * (STAGE_CAP * REC_DW);   // 32-bit LDS pointer: no 64-bit flat pointer held (and spilled) across the tile
-
-    for (int e = tid; e < 576; e += 256) M[e] = Mg[e];
-    for (int e = tid; e < R * 8; e += 256) {
-        const int r = e >> 3, q = e & 7;
-        uint32_t v = 0;
-        if ((uint32_t)r < T.nrows && (uint32_t)(q * 4) < P.lpad)
-            v = reinterpret_cast<const uint32_t *>(P.res_sorted + (size_t)(T.row0 + r) * P.lpad)[q];
-        rowseq[e] = v;
-    }
-    __syncthreads();
-
-    uint32_t cnt = 0;
-    const uint32_t col_end = T.col0 + T.ncols;
-    uint32_t *mine = colseq + tid * SEQ_STRIDE_DW;
-    for (uint32_t c0 = T.col0; c0 < col_end; c0 += 256) {
-        const uint32_t col = c0 + tid;
-        if (col < col_end) {
-            const uint32_t *src = reinterpret_cast<const uint32_t *>(P.res_sorted + (size_t)col * P.lpad);
-            for (uint32_t q = 0; q < P.lpad / 4; q++) mine[q] = src[q];
-        }
-        for (uint32_t r = 0; r < T.nrows; r++) {
-            if (cnt > (uint32_t)(STAGE_CAP - 64)) {
-                flush_stage<0>(stage, cnt, P, T, 0, false, shard);
-                cnt = 0;
-            }
-            bool keep = col < col_end;
-            if (T.diag == 1) keep = keep && col > T.row0 + r;
-            if (T.diag == 2) keep = keep && col != T.row0 + r;
-            int score = 0;
-            if (keep) {
-                // edge (x = row, m = column) carries sequenceScore(seq1 = m, seq2 = x)
-                score = shifted_score_literal(M, reinterpret_cast<const uint8_t *>(mine), lb,
-                                              reinterpret_cast<const uint8_t *>(rowseq + r * 8), la,
-                                              max_shift, shift_penalty);
-                keep = score >= threshold;
-            }
-            const uint64_t mask = __ballot(keep);
-            if (mask != 0) {
-                if (keep) {
-                    HMK_LDS uint32_t *rec = stage + (cnt + mbcnt64(mask)) * REC_DW;
-                    rec[0] = col;
-                    rec[1] = r;
-                    rec[2] = (uint32_t)score;
-                }
-                cnt += (uint32_t)__popcll(mask);
-            }
-        }
-    }
-    flush_stage<0>(stage, cnt, P, T, 0, false, shard);
+    literal_tile(P, tile_base + blockIdx.x, Mg, ShiftedLiteral{max_shift, shift_penalty}, threshold);
 }
 
 // -----------------------------------------------------------------------------
@@ -627,9 +566,8 @@ hipError_t launch_neighbors_direct(const NeighborParams &P, uint32_t tile_base, 
                                    const int32_t *d_matrix, int max_shift, int shift_penalty, int threshold,
                                    hipStream_t s) {
     if (n_tiles == 0) return hipSuccess;
-    const size_t lds = 2304 + 256 * SEQ_STRIDE_DW * 4 + 16 * 8 * 4 + 4 * 128 * 3 * 4;
-    hipLaunchKernelGGL(k_neighbors_direct, dim3(n_tiles), dim3(256), lds, s, P, tile_base, d_matrix, max_shift,
-                       shift_penalty, threshold);
+    hipLaunchKernelGGL(k_neighbors_direct, dim3(n_tiles), dim3(256), LiteralTile<ShiftedLiteral::DP_LINE>::BYTES, s, P, tile_base, d_matrix,
+                       max_shift, shift_penalty, threshold);
     return hipGetLastError();
 }
 

@@ -13,7 +13,7 @@ namespace {
 __device__ __forceinline__ uint64_t orient_to_query(uint64_t e, uint32_t q0, uint32_t nq) {
     const uint32_t x = (uint32_t)(e >> 40), m = (uint32_t)(e >> 16) & 0xFFFFFFu;
     if (m - q0 < nq) return e;
-    return ((uint64_t)m << 40) | ((uint64_t)x << 16) | (e & 0xFFFFull);
+    return pack_edge(m, x, (int)(uint32_t)e);
 }
 
 // selection key of a query's hit: larger = better, i.e. score descending, then reference index ascending.  Scores are >= the
