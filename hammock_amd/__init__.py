@@ -5,9 +5,9 @@ include/hammock_hip.h.  See DESIGN.md and INTEGRATION.md."""
 from .api import (AMINO_ACIDS, Cluster, Context, DataException, DeviceError, FileFormatException,
                   HammockException, HipClinkageSequenceClusterer, HipGreedySequenceClusterer, LocalAlignmentScorer, ProfileResult,
                   ReferenceWouldCrash, ShiftedScorer, UniqueSequence, aligned_rows, edge_fields, encode, load_background,
-                  load_frequency_matrix, pack_edges, pack_sequences, profile_params)
+                  load_frequency_matrix, pack_edges, pack_sequences, profile_params, gapped_rows, star_rows)
 
 __all__ = ["AMINO_ACIDS", "Cluster", "Context", "DataException", "DeviceError", "FileFormatException",
            "HammockException", "HipClinkageSequenceClusterer", "HipGreedySequenceClusterer", "LocalAlignmentScorer", "ProfileResult",
            "ReferenceWouldCrash", "ShiftedScorer", "UniqueSequence", "aligned_rows", "edge_fields", "encode", "load_background",
-           "load_frequency_matrix", "pack_edges", "pack_sequences", "profile_params"]
+           "load_frequency_matrix", "pack_edges", "pack_sequences", "profile_params", "gapped_rows", "star_rows"]

@@ -32,7 +32,7 @@ HMK_SCAN_ALL_WINDOWS = 1
 SYMBOLS = [
     "hmk_abi_version", "hmk_last_kernel_ms", "hmk_create", "hmk_create_multi", "hmk_device_count", "hmk_destroy", "hmk_last_error", "hmk_set_sequences",
     "hmk_score_pairs_shifted", "hmk_score_with_shift", "hmk_score_pairs_local", "hmk_score_block_shifted", "hmk_score_block_local",
-    "hmk_score_pairs_global", "hmk_score_block_global", "hmk_neighbors_global", "hmk_search_global",
+    "hmk_score_pairs_global", "hmk_score_block_global", "hmk_neighbors_global", "hmk_search_global", "hmk_align_pairs_global",
     "hmk_neighbors_shifted", "hmk_neighbors_local", "hmk_neighbors_shifted_dev", "hmk_compact_edges_dev", "hmk_pack_rows_dev", "hmk_unpack_rows_dev",
     "hmk_neighbors_last_plan", "hmk_neighbors_last_plan_shared", "hmk_neighbors_last_plan_tables", "hmk_search_shifted", "hmk_search_local", "hmk_search_best_shifted",
     "hmk_assign_shifted", "hmk_assign_local", "hmk_match_clusters_shifted", "hmk_match_clusters_local", "hmk_greedy_continue",
@@ -253,6 +253,7 @@ def _load():
     L.hmk_score_pairs_shifted.argtypes = [vp, p_u32, p_u32, u64, i32, i32, p_i32]
     L.hmk_score_pairs_local.argtypes = [vp, p_u32, p_u32, u64, i32, i32, p_i32]
     L.hmk_score_pairs_global.argtypes = [vp, p_u32, p_u32, u64, i32, i32, p_i32]
+    L.hmk_align_pairs_global.argtypes = [vp, p_u32, p_u32, u64, i32, i32, p_i32, p_u8, p_u64, p_u64]
     L.hmk_score_with_shift.argtypes = [vp, p_u32, p_u32, u64, i32, i32, p_i32, p_i32]
     L.hmk_score_block_shifted.argtypes = [vp, u32, u32, u32, u32, i32, i32, p_i32]
     L.hmk_score_block_local.argtypes = [vp, u32, u32, u32, u32, i32, i32, p_i32]

@@ -106,6 +106,53 @@ def aligned_rows(seqs, column, width_of_slot):
     return rows
 
 
+def gapped_rows(s1, s2, n_cols, gap1, gap2):
+    """The two aligned strings of one record of Context.align_pairs_global (seq1 = s1, seq2 = s2): column c (0 = leftmost) shows
+    '-' in the first row where bit c of gap1 is set, '-' in the second where bit c of gap2 is set, else the next residue."""
+    n_cols, gap1, gap2 = int(n_cols), int(gap1), int(gap2)
+    if gap1 & gap2 or (gap1 | gap2) >> n_cols:
+        raise ValueError("gap1 and gap2 share a column, or have a bit at or above n_cols")
+    if n_cols - bin(gap1).count("1") != len(s1) or n_cols - bin(gap2).count("1") != len(s2):
+        raise ValueError(f"a record of {n_cols} columns does not hold sequences of {len(s1)} and {len(s2)} residues")
+    it1, it2 = iter(s1), iter(s2)
+    row1 = "".join("-" if gap1 >> c & 1 else next(it1) for c in range(n_cols))
+    row2 = "".join("-" if gap2 >> c & 1 else next(it2) for c in range(n_cols))
+    return row1, row2
+
+
+def star_rows(center, members, records):
+    """The centre-star merge of gapped pair alignments: center a string of L residues, members strings, records[k] = (n_cols, gap1,
+    gap2) of align_pairs_global(seq1 = center, seq2 = members[k]) -> (the centre's row, the members' rows), all of one width.
+    With ins[k][p] = the columns of record k with a gap in the centre that stand before centre residue p (p = L: after the last)
+    and W[p] = max over k of ins[k][p], the width is L + sum W.  A member's row is, for each p, a block of W[p] columns with its
+    ins[k][p] inserted residues (right-justified for p = 0, left-justified otherwise, the rest '-'), then its residue under centre
+    residue p or '-'.  The centre's row has '-' in every block."""
+    L = len(center)
+    blocks, under = [], []   # per member: the inserted residues before each p (L + 1 strings); the residue under each p (L)
+    for s, (n_cols, gap1, gap2) in zip(members, records):
+        r1, r2 = gapped_rows(center, s, n_cols, gap1, gap2)
+        ins, und = [""] * (L + 1), []
+        for a, b in zip(r1, r2):
+            if a == "-":
+                ins[len(und)] += b
+            else:
+                und.append(b)
+        blocks.append(ins)
+        under.append(und)
+    W = [max([len(ins[p]) for ins in blocks], default=0) for p in range(L + 1)]
+
+    def row(ins, und):
+        out = []
+        for p in range(L + 1):
+            pad = "-" * (W[p] - len(ins[p]))
+            out.append(pad + ins[p] if p == 0 else ins[p] + pad)
+            if p < L:
+                out.append(und[p])
+        return "".join(out)
+
+    return row([""] * (L + 1), list(center)), [row(i, u) for i, u in zip(blocks, under)]
+
+
 def load_frequency_matrix(path):
     """A frequency matrix in the text format FileIOManager.loadFrequencyMatrix reads (FileIOManager.java:90-118): lines starting
     with '#' are comments, one header line of letters, then one tab-separated row of numbers per letter, in the header's order ->
@@ -323,6 +370,37 @@ class Context:
         """GlobalAlignmentScorer: out[k] = global(seq1 = i[k], seq2 = j[k]), Gotoh's global alignment score with the affine gap
         gap_open + (k - 1) gap_extend (penalties added; -127 <= gap_open <= gap_extend <= 0), end gaps charged."""
         return self._pairs(N.lib.hmk_score_pairs_global, i, j, gap_open, gap_extend)
+
+    def align_pairs_global(self, i, j, gap_open, gap_extend):
+        """The gapped alignments behind score_pairs_global (hmk_align_pairs_global; seq1 = i[k], seq2 = j[k]) -> (score int32,
+        n_cols uint8, gap1 uint64, gap2 uint64), one entry per pair: bit c of gap1 / gap2 marks a gap in seq1 / seq2 in column c,
+        column 0 the leftmost (gapped_rows builds the strings)."""
+        i = np.ascontiguousarray(i, dtype=np.uint32)
+        j = np.ascontiguousarray(j, dtype=np.uint32)
+        if i.shape != j.shape:
+            raise ValueError("i and j must have the same shape")
+        score = np.empty(i.size, dtype=np.int32)
+        n_cols = np.empty(i.size, dtype=np.uint8)
+        gap1 = np.empty(i.size, dtype=np.uint64)
+        gap2 = np.empty(i.size, dtype=np.uint64)
+        st = N.lib.hmk_align_pairs_global(self._h, _ptr(i, C.c_uint32), _ptr(j, C.c_uint32), i.size, int(gap_open), int(gap_extend),
+                                          _ptr(score, C.c_int32), _ptr(n_cols, C.c_uint8), _ptr(gap1, C.c_uint64), _ptr(gap2, C.c_uint64))
+        if st:
+            self._raise(st)
+        return score.reshape(i.shape), n_cols.reshape(i.shape), gap1.reshape(i.shape), gap2.reshape(i.shape)
+
+    def align_edges_global(self, edges, gap_open, gap_extend):
+        """The alignments of the edges of neighbors_global / search_global: seq1 = the edge's m, seq2 = its x (the orientation of
+        both calls' scores) -> (score, n_cols, gap1, gap2) in the edges' order.  Raises if a score differs from its edge's: the
+        edges were made with other penalties, another matrix or other sequences."""
+        x, m, s = edge_fields(edges)
+        score, n_cols, gap1, gap2 = self.align_pairs_global(m, x, gap_open, gap_extend)
+        bad = np.nonzero(score != s)[0]
+        if bad.size:
+            k = int(bad[0])
+            raise ValueError(f"{bad.size} edge(s) carry another score than their alignment: edge {k} (m = {int(m[k])}, x = {int(x[k])}) "
+                             f"has {int(s[k])}, the alignment scores {int(score[k])}")
+        return score, n_cols, gap1, gap2
 
     def _block(self, fn, r0, r1, c0, c1, a, b):
         out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), dtype=np.int32)

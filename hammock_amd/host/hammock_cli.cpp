@@ -66,6 +66,7 @@ struct Options {
     // search, greedy: --scorer shifted|global (parseScorerArgs); global: GlobalAlignmentScorer with --gap_open / --gap_extend
     bool haveScorer = false, globalScorer = false;
     int gapOpen = -5, gapExtend = -1;
+    bool alignments = false;   // search --scorer global --alignments: the hits' gapped rows (hmk_align_pairs_global)
 };
 
 void parseCommonArgs(const std::vector<std::string> &args, Options &o) {  // Hammock.java:824-908
@@ -149,8 +150,10 @@ void parseScorerArgs(const std::vector<std::string> &args, Options &o) {
             o.globalScorer = name == "global";
         } else if (a == "--gap_open" && more) o.gapOpen = javaIntegerDecode(args[++i]);
         else if (a == "--gap_extend" && more) o.gapExtend = javaIntegerDecode(args[++i]);
+        else if (a == "--alignments") o.alignments = true;
         else if (a == "-x" || a == "--max_shift" || a == "-p" || a == "--gap_penalty") shiftArgs = true;
     }
+    if (o.alignments && !o.globalScorer) throw CLIException("Error. --alignments needs --scorer global (the gapped rows are that scorer's alignments).");
     if (!o.globalScorer) return;
     if (shiftArgs) throw CLIException("Error. -x (--max_shift) and -p (--gap_penalty) have no meaning with --scorer global (--gap_open, --gap_extend).");
     if (o.gapOpen < -127 || o.gapOpen > o.gapExtend || o.gapExtend > 0)
@@ -171,7 +174,7 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "          hammock-hip greedy ... [--scorer shifted|global] [--gap_open <int>] [--gap_extend <int>]\n"
               << "          hammock-hip search -i <queries> --database <references> -d <directory> [-f fasta|tab] [-m <file>] [-x <int>]\n"
               << "                      [-p <int>] [-g <int>] [--best <int>] [--scorer shifted|global] [--gap_open <int>] [--gap_extend <int>]\n"
-              << "                      [--device <int>]\n"
+              << "                      [--alignments] [--device <int>]\n"
               << "          hammock-hip assign -i <new sequences> --clusters <initial_clusters_sequences.tsv> -d <directory> [--best <int>]\n"
               << "                      [--skip_singletons] [-f fasta|tab] [-m <file>] [-x <int>] [-p <int>] [-g <int>] [--device <int>]\n"
               << "          hammock-hip continue -i <new sequences> --clusters <initial_clusters_sequences.tsv> -d <directory> [-f fasta|tab]\n"
@@ -185,6 +188,8 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "          hammock-hip split -i <clusters.tsv> -d <directory> [-m <file>] [-x <int>] [-p <int>] [-g <int>] [--java_hashset <int>]\n"
               << "                      [--device <int>]\n"
               << "          hammock-hip align -i <clusters.tsv> -d <directory> [--skip_singletons] [-m <file>] [-x <int>] [-p <int>] [--device <int>]\n"
+              << "          hammock-hip align -i <clusters.tsv> -d <directory> --scorer global [--gap_open <int>] [--gap_extend <int>] [--skip_singletons]\n"
+              << "                      [-m <file>] [--device <int>]\n"
               << "          hammock-hip profile -i <clusters.tsv> -d <directory> --frequency_matrix <file> [--background <file>] [--min_ic <float>]\n"
               << "                      [--max_gap_proportion <float>] [--min_conserved_positions <int>] [--max_inner_gaps <int>] [--skip_singletons]\n"
               << "                      [-m <file>] [-x <int>] [-p <int>] [--device <int>]\n"
@@ -217,7 +222,8 @@ void printHelp() {  // Hammock.java:295-320 (greedy-relevant part)
               << "-S, --seed <int>\n\tA seed to make random processes deterministic (if -R random is in use)\n\n"
               << "--initial_clusters_limit <int>\n\tThe max. number of clusters resulting from gredy clustering\n\n"
               << "-L, --cache_size_limit <int>\n\t(clinkage) accepted and logged; has no effect, as in the reference\n\n"
-              << "--scorer <[shifted,global]>\n\t(search, greedy) the pair score: shifted (default) = ShiftedScorer with -x and -p; global = the optimal global\n\talignment score of the two whole sequences under the matrix with an affine gap (end gaps charged); -x and -p are errors with it.\n\tsearch then writes the columns query, target, score\n\n"
+              << "--scorer <[shifted,global]>\n\t(search, greedy) the pair score: shifted (default) = ShiftedScorer with -x and -p; global = the optimal global\n\talignment score of the two whole sequences under the matrix with an affine gap (end gaps charged); -x and -p are errors with it.\n\tsearch then writes the columns query, target, score;\n\t(align) global: gapped rows, a centre-star merge of the members' global alignments with their cluster's centre\n\n"
+              << "--alignments\n\t(search --scorer global) two more columns behind score, query_row and target_row: the hit's gapped alignment\n\n"
               << "--gap_open <int>\n\t(--scorer global) the penalty added for the first position of a gap (default -5); -127 <= --gap_open <= --gap_extend <= 0\n\n"
               << "--gap_extend <int>\n\t(--scorer global) the penalty added for every further position of a gap (default -1)\n\n"
               << "--device <int>\n\tHIP device ordinal (default 0)\n\n"
@@ -473,7 +479,11 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
     Options o;
     parseCommonArgs(args, o);
     if (clinkage) parseClinkageArgs(args, o);
-    else { parseGreedyArgs(args, o); parseScorerArgs(args, o); }
+    else {
+        parseGreedyArgs(args, o);
+        parseScorerArgs(args, o);
+        if (o.alignments) throw CLIException("Error. --alignments belongs to mode search.");
+    }
     requireInput(o);
     makeOutputDirectory(o, o.parentDir);
     Logger logger(o.workingDirectory + "/run.log", false);
@@ -623,7 +633,8 @@ int runSequenceClustering(const std::vector<std::string> &args, bool clinkage) {
 // both sides.  Defaults: -x as greedy's over the union of both files (Hammock.java:803-811,1421-1434), -g = round(1.7 x the mean
 // query length) (:394-397), -p 0.  --best K: only the best K hits of each query (hmk_search_best_shifted).
 // --scorer global: GlobalAlignmentScorer(--gap_open, --gap_extend) through hmk_search_global instead; no -x / -p, the columns are
-// query, target, score, and --best K cuts each query's sorted hits to K.
+// query, target, score, and --best K cuts each query's sorted hits to K.  --alignments (with --scorer global only) adds the columns
+// query_row and target_row: the gapped alignment of every kept hit (hmk_align_pairs_global, seq1 = query, seq2 = target).
 int runSearch(const std::vector<std::string> &args) {
     Options o;
     parseCommonArgs(args, o);
@@ -715,6 +726,15 @@ int runSearch(const std::vector<std::string> &args) {
             const int st = hmk_score_with_shift(c, pi.data(), pj.data(), pi.size(), o.maxShift, o.shiftPenalty, sc.data(), shift.data());
             if (st) nc->raise(st, nullptr);
         }
+        // --alignments: the gapped alignment of every kept hit (seq1 = query, seq2 = target)
+        std::vector<GappedAlignment> aligned;
+        if (o.alignments && !pi.empty()) {
+            aligned = GlobalAlignmentScorer(nc, o.gapOpen, o.gapExtend).alignUploaded(pi, pj);
+            size_t k = 0;
+            for (uint32_t q = 0; q < nq; q++)
+                for (auto &h : hits[q])
+                    if (aligned[k++].score != h.first) throw HammockException("an alignment's score differs from its hit's");
+        }
         logger.logAndStderr("Ready. Search time: " + std::to_string(millisSince(time0)));
         logger.logAndStderr("Pairs scored: " + std::to_string(stats.pairs_scored) + ", hits reported: " + std::to_string(pi.size()) +
                             ", GPU kernels: " + std::to_string(stats.kernel_ms) + " ms");
@@ -722,12 +742,16 @@ int runSearch(const std::vector<std::string> &args) {
         {
             std::ofstream out(hitsFile);
             if (!out) throw HammockException("cannot write " + hitsFile);
-            out << (o.globalScorer ? "query\ttarget\tscore\n" : "query\ttarget\tscore\tshift\n");
+            out << (o.alignments ? "query\ttarget\tscore\tquery_row\ttarget_row\n" : o.globalScorer ? "query\ttarget\tscore\n" : "query\ttarget\tscore\tshift\n");
             size_t k = 0;
             for (uint32_t q = 0; q < nq; q++)
                 for (auto &h : hits[q]) {
                     out << queries[q]->getSequenceString() << '\t' << references[h.second]->getSequenceString() << '\t' << h.first;
                     if (!o.globalScorer) out << '\t' << shift[k];
+                    if (o.alignments) {
+                        const auto rows = gappedRows(queries[q]->getSequenceString(), references[h.second]->getSequenceString(), aligned[k]);
+                        out << '\t' << rows.first << '\t' << rows.second;
+                    }
                     out << '\n';
                     k++;
                 }
@@ -1458,6 +1482,9 @@ int runSplit(const std::vector<std::string> &args) {
 //   cluster_centers.tsv              cluster_id, size (unique sequences), center (the medoid's string), center_sum, width; clusters
 //                                    in file order (--skip_singletons leaves clusters of one unique sequence out)
 // Exit codes as check: a cluster file the loader rejects is 2.
+// `align --scorer global [--gap_open --gap_extend]` writes the same three files with GAPPED rows (alignGlobal below): the centre by
+// the sums of GlobalAlignmentScorer scores, the rows a centre-star merge of the members' global alignments with it; -x and -p are
+// errors with it, as in search.  No file of align carries a shift, so no column loses its meaning; `profile` does not take it.
 //
 // `hammock-hip profile -i clusters.tsv -d dir --frequency_matrix F [--background B] [-k/--min_ic 1.2] [-y/--max_gap_proportion 0.2]
 // [-h/--min_conserved_positions n] [-u/--max_inner_gaps 0] [--skip_singletons]` aligns as align does, with the same scorer options,
@@ -1561,11 +1588,79 @@ std::string g17(double v) {
     return buf;
 }
 
+// `align --scorer global`: the same files with gapped rows.  Per slot (its members follow each other in `upload`) the centre is the
+// member with the largest sum of global(seq1 = the pair's larger index, seq2 = its smaller index) over the slot's other members, the
+// smallest index among equal sums (the orientation and tie rule of hmk_cluster_align_shifted); the sums come from
+// hmk_score_pairs_global over the enumerated inside pairs, chunk by chunk, added up in int64 here.  Every other member is aligned
+// with seq1 = the centre, seq2 = the member (hmk_align_pairs_global), and starRows merges a slot's records into rows of one width.
+// A slot of one member is its own row.  The shift / column of the ungapped model have no counterpart: a row IS the placement.
+void alignGlobal(const std::shared_ptr<NativeContext> &nc, const Options &o, const std::vector<UniqueSequencePtr> &upload, const Candidates &cand,
+                 std::vector<uint32_t> &center, std::vector<int64_t> &centerSum, std::vector<uint32_t> &width,
+                 std::unordered_map<const UniqueSequence *, std::string> &rows, hmk_align_stats &stats) {
+    const uint32_t n = (uint32_t)upload.size(), ncl = (uint32_t)cand.slots.size();
+    std::vector<uint32_t> first(ncl + 1, 0);   // slot c's members: upload[first[c] .. first[c + 1])
+    for (uint32_t k = 0; k < n; k++) first[cand.memberCluster[k] + 1]++;
+    for (uint32_t c = 0; c < ncl; c++) first[c + 1] += first[c];
+    std::vector<int64_t> sum(n, 0);
+    constexpr size_t CHUNK = (size_t)1 << 22;
+    std::vector<uint32_t> pi, pj;
+    std::vector<int32_t> sc;
+    auto flush = [&]() {
+        if (pi.empty()) return;
+        sc.resize(pi.size());
+        const int st = hmk_score_pairs_global(nc->get(), pi.data(), pj.data(), pi.size(), o.gapOpen, o.gapExtend, sc.data());
+        if (st) nc->raise(st, nullptr);
+        stats.kernel_ms += hmk_last_kernel_ms(nc->get());
+        stats.launches++;
+        for (size_t k = 0; k < pi.size(); k++) { sum[pi[k]] += sc[k]; sum[pj[k]] += sc[k]; }
+        stats.pairs_scored += pi.size();
+        pi.clear();
+        pj.clear();
+    };
+    for (uint32_t c = 0; c < ncl; c++)
+        for (uint32_t b = first[c] + 1; b < first[c + 1]; b++)
+            for (uint32_t a = first[c]; a < b; a++) {
+                pi.push_back(b);   // seq1 = the larger index
+                pj.push_back(a);
+                if (pi.size() == CHUNK) flush();
+            }
+    flush();
+    for (uint32_t c = 0; c < ncl; c++) {
+        uint32_t z = first[c];
+        for (uint32_t k = first[c] + 1; k < first[c + 1]; k++)
+            if (sum[k] > sum[z]) z = k;
+        center[c] = z;
+        centerSum[c] = sum[z];
+        for (uint32_t k = first[c]; k < first[c + 1]; k++)
+            if (k != z) { pi.push_back(z); pj.push_back(k); }
+    }
+    const std::vector<GappedAlignment> records = GlobalAlignmentScorer(nc, o.gapOpen, o.gapExtend).alignUploaded(pi, pj);
+    if (!pi.empty()) { stats.kernel_ms += hmk_last_kernel_ms(nc->get()); stats.launches++; }
+    size_t r = 0;
+    for (uint32_t c = 0; c < ncl; c++) {
+        const uint32_t s = first[c + 1] - first[c];
+        const std::string &z = upload[center[c]]->getSequenceString();
+        std::vector<std::string> members;
+        for (uint32_t k = first[c]; k < first[c + 1]; k++)
+            if (k != center[c]) members.push_back(upload[k]->getSequenceString());
+        const auto star = starRows(z, members, std::vector<GappedAlignment>(records.begin() + r, records.begin() + r + members.size()));
+        r += members.size();
+        size_t t = 0;
+        for (uint32_t k = first[c]; k < first[c + 1]; k++) rows.emplace(upload[k].get(), k == center[c] ? star.first : star.second[t++]);
+        width[c] = (uint32_t)star.first.size();
+        stats.max_width = std::max(stats.max_width, width[c]);
+        if (s > 1) stats.n_multi++;
+    }
+}
+
 int runAlign(const std::vector<std::string> &args, bool profile = false) {
     Options o;
     parseCommonArgs(args, o);
     parseModeArgs(args, o, -1);
+    parseScorerArgs(args, o);
     const std::string mode = profile ? "profile" : "align";
+    if (profile && o.globalScorer) throw CLIException("Error. --scorer global is not available in mode profile (its rows carry gaps inside peptides; use align).");
+    if (o.alignments) throw CLIException("Error. --alignments belongs to mode search.");
     requireOneDevice(o, mode, profile ? "a profile" : "an alignment");
     requireInput(o);
     ProfileOptions po;
@@ -1591,7 +1686,9 @@ int runAlign(const std::vector<std::string> &args, bool profile = false) {
         const std::vector<UniqueSequencePtr> all = sequencesOf(clusters);
         logger.logAndStderr(std::to_string(clusters.size()) + " clusters of " + std::to_string(all.size()) + " sequences loaded.");
         const SequenceListSummary summary = summariseSequences(all);
-        settleShiftAndThreshold(o, logger, summary, summary, summary, "Align");
+        if (o.globalScorer) requireKernelLengths(summary);   // (no shift, and nothing is thresholded)
+        else settleShiftAndThreshold(o, logger, summary, summary, summary, "Align");
+        logScorer(o, logger);
 
         std::vector<UniqueSequencePtr> upload;
         const Candidates cand = appendCandidates(clusters, false, 0, upload);
@@ -1620,7 +1717,13 @@ int runAlign(const std::vector<std::string> &args, bool profile = false) {
         }
         logger.logAndStderr(profile ? "Aligning and profiling..." : "Aligning...");
         const auto time0 = std::chrono::steady_clock::now();
-        {
+        std::unordered_map<const UniqueSequence *, std::string> rows;
+        rows.reserve(n);
+        if (o.globalScorer) {
+            const std::shared_ptr<NativeContext> nc = contextReady.get();
+            nc->setSequences(upload, true);
+            alignGlobal(nc, o, upload, cand, center, centerSum, width, rows, stats);
+        } else {
             const std::shared_ptr<NativeContext> nc = contextReady.get();
             nc->setSequences(upload, true);
             const int st = hmk_cluster_align_shifted(nc->get(), 0, n, cand.memberCluster.data(), ncl, o.maxShift, o.shiftPenalty, center.data(),
@@ -1653,14 +1756,13 @@ int runAlign(const std::vector<std::string> &args, bool profile = false) {
             logger.logAndStderr("Final system KLD over all MSA positions: " + g17(pstats.system_kld_all));
         }
         logger.logAndStderr("Saving results to output files...");
-        std::unordered_map<const UniqueSequence *, std::string> rows;
-        rows.reserve(n);
         auto rowOf = [&](uint32_t k) {
             const std::string &s = upload[k]->getSequenceString();
             const uint32_t w = width[cand.memberCluster[k]];
             return std::string(column[k], '-') + s + std::string(w - column[k] - (uint32_t)s.size(), '-');
         };
-        for (uint32_t k = 0; k < n; k++) rows.emplace(upload[k].get(), rowOf(k));
+        if (!o.globalScorer)
+            for (uint32_t k = 0; k < n; k++) rows.emplace(upload[k].get(), rowOf(k));
         const std::string seqCsv = o.workingDirectory + "/initial_clusters_sequences.tsv", msaDir = o.workingDirectory + "/alignments_initial",
                           centersCsv = o.workingDirectory + "/cluster_centers.tsv";
         FileIOManager::writeClusterSequencesToCsv(in.lineOrder, FileIOManager::SequenceClusterIndex(clusters), seqCsv, in.labels, &rows);

@@ -503,6 +503,62 @@ public:
 // ---- GlobalAlignmentScorer: no counterpart in the reference (hammock_hip.h, hmk_score_pairs_global) ------------------
 // The optimal score of a global alignment of two whole sequences with the affine gap gapOpen + (k - 1) gapExtend (penalties
 // added, -127 <= gapOpen <= gapExtend <= 0), end gaps charged; seq1 = lines, seq2 = columns of the matrix.
+// One record of hmk_align_pairs_global: the alignment behind a score.  Bit c of gap1 / gap2: column c (0 = leftmost) has a gap in
+// seq1 / seq2.
+struct GappedAlignment {
+    int score = 0, nCols = 0;
+    uint64_t gap1 = 0, gap2 = 0;
+};
+
+// the two aligned strings of a record (seq1 = s1, seq2 = s2)
+inline std::pair<std::string, std::string> gappedRows(const std::string &s1, const std::string &s2, const GappedAlignment &a) {
+    std::string r1, r2;
+    size_t i = 0, j = 0;
+    for (int c = 0; c < a.nCols; c++) {
+        const bool g1 = a.gap1 >> c & 1, g2 = a.gap2 >> c & 1;
+        if ((g1 && g2) || (!g1 && i >= s1.size()) || (!g2 && j >= s2.size())) throw HammockException("a gapped alignment does not fit its sequences");
+        r1.push_back(g1 ? '-' : s1[i++]);
+        r2.push_back(g2 ? '-' : s2[j++]);
+    }
+    if (i != s1.size() || j != s2.size() || (a.nCols < 64 && ((a.gap1 | a.gap2) >> a.nCols)))
+        throw HammockException("a gapped alignment does not fit its sequences");
+    return {r1, r2};
+}
+
+// The centre-star merge of gapped pair alignments: records[k] aligns seq1 = center (L residues) with seq2 = members[k] -> the centre's
+// row, then the members' rows, all of one width.  ins[k][p] = the columns of record k with a gap in the centre before centre residue p
+// (p = L: behind the last), W[p] their maximum over k: the width is L + sum W.  A member's row is, per p, a block of W[p] columns with
+// its ins[k][p] inserted residues (right-justified for p = 0, left-justified otherwise, the rest '-'), then its residue under centre
+// residue p or '-'; the centre's row has '-' in every block.
+inline std::pair<std::string, std::vector<std::string>> starRows(const std::string &center, const std::vector<std::string> &members,
+                                                                 const std::vector<GappedAlignment> &records) {
+    const size_t L = center.size();
+    std::vector<std::vector<std::string>> ins(members.size(), std::vector<std::string>(L + 1));
+    std::vector<std::string> under(members.size());
+    std::vector<size_t> W(L + 1, 0);
+    for (size_t k = 0; k < members.size(); k++) {
+        const auto rows = gappedRows(center, members[k], records[k]);
+        for (size_t c = 0; c < rows.first.size(); c++) {
+            if (rows.first[c] == '-') ins[k][under[k].size()].push_back(rows.second[c]);
+            else under[k].push_back(rows.second[c]);
+        }
+        for (size_t p = 0; p <= L; p++) W[p] = std::max(W[p], ins[k][p].size());
+    }
+    auto row = [&](const std::vector<std::string> *blocks, const std::string &und) {
+        std::string out;
+        for (size_t p = 0; p <= L; p++) {
+            const std::string block = blocks ? (*blocks)[p] : std::string();
+            const std::string pad(W[p] - block.size(), '-');
+            out += p == 0 ? pad + block : block + pad;
+            if (p < L) out.push_back(und[p]);
+        }
+        return out;
+    };
+    std::vector<std::string> out;
+    for (size_t k = 0; k < members.size(); k++) out.push_back(row(&ins[k], under[k]));
+    return {row(nullptr, center), out};
+}
+
 class GlobalAlignmentScorer : public SequenceScorer {
     std::shared_ptr<NativeContext> ctx_;
     int gapOpenPenalty_, gapExtendPenalty_;
@@ -520,6 +576,33 @@ public:
         const int st = hmk_score_pairs_global(ctx_->get(), &i, &j, 1, gapOpenPenalty_, gapExtendPenalty_, &score);
         if (st) ctx_->raise(st, nullptr);
         return score;
+    }
+    // the alignments behind the scores of (seq1, seq2) pairs, in one call (hmk_align_pairs_global)
+    std::vector<GappedAlignment> align(const std::vector<std::pair<UniqueSequencePtr, UniqueSequencePtr>> &pairs) {
+        std::vector<UniqueSequencePtr> seqs;
+        std::vector<uint32_t> i, j;
+        for (const auto &p : pairs) {
+            i.push_back((uint32_t)seqs.size());
+            seqs.push_back(p.first);
+            j.push_back((uint32_t)seqs.size());
+            seqs.push_back(p.second);
+        }
+        if (pairs.empty()) return {};
+        ctx_->setSequences(seqs, false);
+        return alignUploaded(i, j);
+    }
+    // ... of index pairs into the sequences the context already holds (NativeContext::setSequences)
+    std::vector<GappedAlignment> alignUploaded(const std::vector<uint32_t> &i, const std::vector<uint32_t> &j) {
+        if (i.size() != j.size()) throw HammockException("align: index lists of different lengths");
+        std::vector<int32_t> score(i.size());
+        std::vector<uint8_t> nCols(i.size());
+        std::vector<uint64_t> gap1(i.size()), gap2(i.size());
+        const int st = hmk_align_pairs_global(ctx_->get(), i.data(), j.data(), i.size(), gapOpenPenalty_, gapExtendPenalty_, score.data(),
+                                              nCols.data(), gap1.data(), gap2.data());
+        if (st) ctx_->raise(st, nullptr);
+        std::vector<GappedAlignment> out(i.size());
+        for (size_t k = 0; k < i.size(); k++) out[k] = GappedAlignment{score[k], nCols[k], gap1[k], gap2[k]};
+        return out;
     }
     int getGapOpenPenalty() const { return gapOpenPenalty_; }
     int getGapExtendPenalty() const { return gapExtendPenalty_; }

@@ -126,11 +126,27 @@ int hmk_score_pairs_local(hmk_ctx *ctx, const uint32_t *i, const uint32_t *j, ui
  * answered before the device is looked at (a host-only context answers them too), as are the thresholds' [-30000, 30000]
  * in the two edge calls below.  The lowest score, the all-gap alignment, is >= -8,128.  A symmetric matrix gives a symmetric
  * score; a 0 / -1 matrix with penalties -1 / -1 gives minus the Levenshtein distance.
- * Out of scope: assign, match and best-k forms with this scorer; multi-device sharding beyond part / n_parts; the
- * alignments themselves (traceback).
+ * Out of scope: assign, match and best-k forms with this scorer; multi-device sharding beyond part / n_parts.
  * out[k] = global(seq1 = i[k], seq2 = j[k]). */
 int hmk_score_pairs_global(hmk_ctx *ctx, const uint32_t *i, const uint32_t *j, uint64_t n_pairs,
                            int gap_open, int gap_extend, int32_t *out);
+/* The alignment behind that score (traceback): H, E, F are exactly the tables above, seq1 = i[k] (n residues), seq2 = j[k] (m).
+ * ONE deterministic walk from (n, m) in state H to (0, 0) emits the alignment's columns right to left:
+ *     i = 0            every remaining residue of seq2 is a column with a gap in seq1
+ *     j = 0            every remaining residue of seq1 is a column with a gap in seq2
+ *     H at (i, j)      the first that holds:  H[i][j] == H[i-1][j-1] + M[seq1[i-1]][seq2[j-1]] -> a pair column, H at (i-1, j-1);
+ *                      H[i][j] == E[i][j] -> state E at (i, j);  otherwise state F at (i, j)
+ *     E at (i, j)      a column seq2[j-1] against a gap in seq1; E at (i, j-1) if E[i][j] == E[i][j-1] + gap_extend (an optimal
+ *                      extension is preferred over an opening), otherwise H at (i, j-1)
+ *     F at (i, j)      the mirror: seq1[i-1] against a gap in seq2; F at (i-1, j) if F[i][j] == F[i-1][j] + gap_extend, else H at (i-1, j)
+ * The emitted alignment, rescored column by column, scores H[n][m].  Per pair:
+ *     score[k]  = H[n][m] (= hmk_score_pairs_global)         n_cols[k] = the alignment's width, max(n, m) <= n_cols <= n + m <= 64
+ *     gap1[k]   bit c set: column c has a gap in seq1        gap2[k]   bit c set: column c has a gap in seq2
+ * with column 0 the LEFTMOST: gap1 & gap2 == 0, popcount(gap1) = n_cols - n, popcount(gap2) = n_cols - m, bits at and above n_cols
+ * are zero.  Arguments, checks and their order as hmk_score_pairs_global (i[k] == j[k] is allowed; n_pairs = 0 writes nothing);
+ * hmk_last_kernel_ms covers the kernel.  One kernel for every matrix a context admits (int32 throughout). */
+int hmk_align_pairs_global(hmk_ctx *ctx, const uint32_t *i, const uint32_t *j, uint64_t n_pairs,
+                           int gap_open, int gap_extend, int32_t *score, uint8_t *n_cols, uint64_t *gap1, uint64_t *gap2);
 /* Dense block: out[(r - r0) * (c1 - c0) + (c - c0)] = score(r, c), r0<=r<r1, c0<=c<c1. */
 int hmk_score_block_shifted(hmk_ctx *ctx, uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1,
                             int max_shift, int shift_penalty, int32_t *out);
