@@ -1,6 +1,6 @@
 // hmk_components.cpp -- connected components of the thresholded neighbour graph, at one threshold or a range (hmk_components_*).
-//   pass      hmk_neighbors_shifted's (neighbors_internal: the all-vs-all plan slot, the same kernels) at `threshold` into the context's
-//             edge buffer, grown until it fits;
+//   pass      pass_edge_runs (hmk_levels.cpp): hmk_neighbors_shifted's (neighbors_internal: the all-vs-all plan slot, the same kernels) at
+//             `threshold` into the context's edge buffer, grown until it fits;
 //   levels    k_cc_hist, k_cc_scan, k_cc_partition: the edges' (x, m) in one run per level min(score, threshold_hi) - threshold (SB_CC_RUNS);
 //             a single-level call that wants no `levels` skips them and unites straight from the pass's segments;
 //   union     one k_cc_union launch per level from threshold_hi down, k_cc_flatten and k_cc_sizes behind each: no host
@@ -8,7 +8,7 @@
 //   copy      that block and parent[] (= component at `threshold`) at the end.
 // hmk_components_from_edges is the same answer by a sequential union-find on the host: the second implementation the device path is
 // tested against, and what a host-only context runs.
-#include "hmk_ctx.h"
+#include "hmk_levels.h"
 #include "hmk_components.h"
 
 namespace hmk { namespace impl {
@@ -17,8 +17,9 @@ namespace {
 
 // the argument checks all three entry points make before the device is looked at
 int check_components(hmk_ctx *ctx, int thr, int thr_hi, const uint32_t *component, const hmk_component_level *levels) {
-    if (thr_hi < thr) return fail(ctx, HMK_ERR_BAD_ARG, "threshold_hi is below threshold");
-    if ((long long)thr_hi - thr > (long long)CC_MAX_LEVELS - 1) return fail(ctx, HMK_ERR_BAD_ARG, "at most 256 levels per call: threshold_hi - threshold <= 255");
+    static_assert(CC_MAX_LEVELS == SWEEP_MAX_LEVELS, "check_level_range checks the levels of both");
+    const int st = check_level_range(ctx, thr, thr_hi, false);   // (no edge is dealt whole here: threshold_hi may lie above every score)
+    if (st) return st;
     if (ctx->n && !component && !levels) return fail(ctx, HMK_ERR_BAD_ARG, "null outputs (component and levels)");
     return HMK_OK;
 }
@@ -32,7 +33,7 @@ void fill_stats(hmk_components_stats *S, const hmk_component_level *lv, uint32_t
 }
 
 // The device side behind the edges: E names them (packed, on this context's device), total = their number.
-int components_on_device(hmk_ctx *ctx, const CcEdges &E, uint64_t total, int thr, int thr_hi, uint32_t *component, hmk_component_level *levels,
+int components_on_device(hmk_ctx *ctx, const EdgeRuns &E, uint64_t total, int thr, int thr_hi, uint32_t *component, hmk_component_level *levels,
                          hmk_components_stats *S) {
     const uint32_t n = ctx->n, nl = (uint32_t)(thr_hi - thr) + 1;
     const bool direct = nl == 1 && !levels;   // one level and only its labels wanted: no histogram, no partition
@@ -44,10 +45,9 @@ int components_on_device(hmk_ctx *ctx, const CcEdges &E, uint64_t total, int thr
     CcState *st = buf<CcState>(ctx, SB_CC_STATE);
     uint64_t *runs = buf<uint64_t>(ctx, SB_CC_RUNS);
     hipStream_t Q = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, Q);
+    EventPair ev;
+    HIPCHK(ctx, ev.create());
+    hipError_t e = ev.start(Q);
     if (e == hipSuccess) e = hipMemsetAsync(st, 0, sizeof(CcState), Q);
     if (e == hipSuccess) e = launch_cc_init(parent, size, n, Q);
     if (e == hipSuccess && !direct && total) {
@@ -60,15 +60,13 @@ int components_on_device(hmk_ctx *ctx, const CcEdges &E, uint64_t total, int thr
         if (e == hipSuccess) e = launch_cc_flatten(parent, size, n, Q);
         if (e == hipSuccess) e = launch_cc_sizes(size, n, l, st, Q);
     }
-    if (e == hipSuccess) e = hipEventRecord(e1, Q);
+    if (e == hipSuccess) e = ev.stop(Q);
     std::vector<hmk_component_level> lv(nl);
     if (e == hipSuccess) e = hipMemcpy(lv.data(), st->levels, nl * sizeof(hmk_component_level), hipMemcpyDeviceToHost);
     const bool bad = e == hipSuccess && lv[0].reserved != 0;
     if (e == hipSuccess && !bad && component) e = hipMemcpy(component, parent, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
     float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    if (e == hipSuccess) e = ev.elapsed(&ms);
     if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("components: ") + hipGetErrorString(e));
     if (bad) return fail(ctx, HMK_ERR_BAD_ARG, "edge list references a sequence outside [0, n) or a self pair");
     // the device counted each level's hooks: components at t = n - the hooks of the levels >= t
@@ -82,17 +80,6 @@ int components_on_device(hmk_ctx *ctx, const CcEdges &E, uint64_t total, int thr
     fill_stats(S, lv.data(), nl);
     if (levels) std::copy(lv.begin(), lv.end(), levels);
     return HMK_OK;
-}
-
-void set_runs(CcEdges &E, const uint64_t *base, uint64_t stride, uint32_t n_runs, const unsigned long long *count) {
-    E = CcEdges{};
-    E.base = base;
-    E.stride = stride;
-    E.n_runs = n_runs;
-    for (uint32_t s = 0; s < n_runs; s++) {
-        E.count[s] = count[s];
-        E.chunk_start[s + 1] = E.chunk_start[s] + (uint32_t)((count[s] + CC_CHUNK - 1) / CC_CHUNK);
-    }
 }
 
 int components_shifted(hmk_ctx *ctx, int X, int p, int thr, int thr_hi, uint32_t *component, hmk_component_level *levels,
@@ -114,15 +101,12 @@ int components_shifted(hmk_ctx *ctx, int X, int p, int thr, int thr_hi, uint32_t
         if (stats) *stats = S;
         return HMK_OK;
     }
-    unsigned long long counts[HMK_EDGE_SHARDS];
-    double ms = 0;
-    st = neighbors_internal(ctx, X, p, thr, 0, 1, sizing::edge_capacity_guess(true, n, 1, ctx->sw.edge_guess, ctx->edges.cap), counts, &ms);
+    PassRuns P;
+    st = pass_edge_runs(ctx, X, p, thr, true, &P);
     if (st) return st;
-    S.kernel_ms = ms;
-    S.pairs_scored = ctx->plan.stats.pairs_scored;
-    CcEdges E;
-    set_runs(E, ctx->edges.d, ctx->edges.seg_cap(), HMK_EDGE_SHARDS, counts);
-    st = components_on_device(ctx, E, total_of(counts), thr, thr_hi, component, levels, &S);
+    S.kernel_ms = P.kernel_ms;
+    S.pairs_scored = P.pairs_scored;
+    st = components_on_device(ctx, P.E, P.total, thr, thr_hi, component, levels, &S);
     if (st == HMK_OK && stats) *stats = S;
     return st;
 }
@@ -135,8 +119,8 @@ int components_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n_edge
     hmk_components_stats S{};
     int st = check_components(ctx, thr, thr_hi, component, levels);
     if (st) return st;
-    if (n_edges && !d_edges) return fail(ctx, HMK_ERR_BAD_ARG, "null edge buffer");
-    if (n_edges > ((uint64_t)1 << 41)) return fail(ctx, HMK_ERR_BAD_ARG, "more than 2^41 edges");   // (chunks are counted in 32 bits)
+    st = check_edges_dev(ctx, d_edges, n_edges);
+    if (st) return st;
     st = need_device(ctx);
     if (st) return st;
     const uint32_t nl = (uint32_t)(thr_hi - thr) + 1;
@@ -148,10 +132,8 @@ int components_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n_edge
     }
     // the caller's block may have been written on any stream of its own: wait for the device
     HIPCHK(ctx, hipDeviceSynchronize());
-    CcEdges E;
     const unsigned long long cnt = n_edges;
-    set_runs(E, (const uint64_t *)d_edges, 0, 1, &cnt);
-    st = components_on_device(ctx, E, n_edges, thr, thr_hi, component, levels, &S);
+    st = components_on_device(ctx, edge_runs((const uint64_t *)d_edges, 0, 1, &cnt), n_edges, thr, thr_hi, component, levels, &S);
     if (st == HMK_OK && stats) *stats = S;
     return st;
 }

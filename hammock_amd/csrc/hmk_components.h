@@ -10,18 +10,6 @@
 namespace hmk {
 
 constexpr uint32_t CC_MAX_LEVELS = 256;   // threshold_hi - threshold <= 255
-constexpr uint32_t CC_CHUNK = 1024;       // edges a workgroup takes at a time from the edge runs (4 per lane)
-
-// Where a call's packed edges lie: n_runs runs, run s = count[s] entries at base + s * stride -- the HMK_EDGE_SHARDS segments of a
-// neighbour pass (the host has read their counts), or one run (a caller's block).  A chunk is CC_CHUNK consecutive entries of one
-// run; chunk_start[s] = the chunks before run s.  Passed to the kernels by value.
-struct CcEdges {
-    const uint64_t *base;
-    uint64_t stride;
-    uint32_t n_runs;
-    uint32_t chunk_start[HMK_EDGE_SHARDS + 1];
-    unsigned long long count[HMK_EDGE_SHARDS];
-};
 
 // The per-call device block behind the levels' results (SB_CC_STATE): zeroed at the start of a call.
 //   levels   as the ABI's, except n_components = the hooks of that level's launch (the host turns them into counts) and
@@ -38,15 +26,15 @@ struct CcState {
 // parent[i] = i, size[i] = 0
 hipError_t launch_cc_init(uint32_t *parent, uint32_t *size, uint32_t n, hipStream_t s);
 // level of an edge = min(score, thr_hi) - thr; edges below thr are left out, invalid ones (index >= n, self pair) flagged and left out
-hipError_t launch_cc_hist(const CcEdges &E, uint32_t n, int thr, int thr_hi, CcState *st, hipStream_t s);
+hipError_t launch_cc_hist(const EdgeRuns &E, uint32_t n, int thr, int thr_hi, CcState *st, hipStream_t s);
 // start / cursor from hist, levels[l].n_edges = edges of the levels >= l (one workgroup)
 hipError_t launch_cc_scan(uint32_t n_levels, CcState *st, hipStream_t s);
 // every counted edge's (x, m), as x << 32 | m, into its level's run of `runs`
-hipError_t launch_cc_partition(const CcEdges &E, uint32_t n, int thr, int thr_hi, CcState *st, uint64_t *runs, hipStream_t s);
+hipError_t launch_cc_partition(const EdgeRuns &E, uint32_t n, int thr, int thr_hi, CcState *st, uint64_t *runs, hipStream_t s);
 // the union of one level's run (total_edges: the edges of all levels, which sizes the grid -- the level's own count stays on the device)
 hipError_t launch_cc_union(const uint64_t *runs, unsigned long long total_edges, uint32_t level, uint32_t *parent, CcState *st, hipStream_t s);
 // the union straight from the edge runs (a single level): counts the edges >= thr into levels[0].n_edges
-hipError_t launch_cc_union_edges(const CcEdges &E, uint32_t n, int thr, uint32_t *parent, CcState *st, hipStream_t s);
+hipError_t launch_cc_union_edges(const EdgeRuns &E, uint32_t n, int thr, uint32_t *parent, CcState *st, hipStream_t s);
 // parent[v] = v's root, size[root] += 1
 hipError_t launch_cc_flatten(uint32_t *parent, uint32_t *size, uint32_t n, hipStream_t s);
 // levels[level].n_singletons / largest from size[], which is cleared

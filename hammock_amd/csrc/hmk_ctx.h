@@ -3,7 +3,7 @@
 // buffers and their owners, streams), hmk_sizing.h (the sizing rules, pure functions), hmk_plan.cpp (the neighbour passes' planner),
 // hmk_pass.cpp (launching the passes; the pair and block probes), hmk_cluster.cpp (the single-device clustering calls, CSR pipeline,
 // row hand-over, second-loop driver), hmk_multi.cpp (the same calls on several devices), and one file per further call
-// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp, hmk_separation.cpp, hmk_sweep.cpp, hmk_representatives.cpp, hmk_density.cpp, hmk_profile.cpp, hmk_scan.cpp, hmk_orders.cpp).  Not part of the public ABI.
+// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp, hmk_separation.cpp, hmk_sweep.cpp, hmk_representatives.cpp, hmk_density.cpp, hmk_profile.cpp, hmk_scan.cpp, hmk_orders.cpp; hmk_levels.cpp: what the threshold-range calls among them share).  Not part of the public ABI.
 #ifndef HMK_CTX_H
 #define HMK_CTX_H
 #include <hip/hip_runtime_api.h>
@@ -351,6 +351,44 @@ struct EdgeSource {
     //   before_full  blocks until every device's piece of the adjacency is complete (its size in the device's h_counts[HC_TOTAL]);
     //                HMK_OK, ST_RETRY_OVERFLOW or an error code (the text is in the context)
     std::function<int()> before_band, before_full;
+};
+
+// The source of one segment: the first `total` entries of `edges`, d_count = that number in device memory (a buffer without an edge:
+// a count of 0 in a segment of room 1).  packed: null, or -- where the caller knows the adjacency format without looking at the
+// edges -- whether an entry fits 4 bytes over `base`.
+inline EdgeSource one_segment_source(const uint64_t *edges, const unsigned long long *d_count, uint64_t total, bool symmetric,
+                                     const bool *packed = nullptr, int base = 0) {
+    EdgeSource src;
+    src.symmetric = symmetric;
+    src.segs.n = 1;
+    src.segs.s[0] = EdgeSeg{edges, d_count, std::max<uint64_t>(total, 1)};
+    src.total_known = total;
+    if (packed) {
+        src.format_known = true;
+        src.packed = *packed;
+        src.base = base;
+        src.adj_bound = (symmetric ? 2 : 1) * total;
+    }
+    return src;
+}
+
+// Two events that time a stretch of a stream, destroyed with the pair.
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    EventPair() = default;
+    EventPair(const EventPair &) = delete;
+    EventPair &operator=(const EventPair &) = delete;
+    ~EventPair() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+    hipError_t create() {
+        const hipError_t e = hipEventCreate(&a);
+        return e == hipSuccess ? hipEventCreate(&b) : e;
+    }
+    hipError_t start(hipStream_t s) { return hipEventRecord(a, s); }
+    hipError_t stop(hipStream_t s) { return hipEventRecord(b, s); }
+    hipError_t elapsed(float *ms) const { return hipEventElapsedTime(ms, a, b); }   // (once b has passed)
 };
 
 // Cluster.size() per row as the clustering tail reads it: the context's sizes, or the permuted view of the order whose tail is

@@ -3,9 +3,9 @@
 // clusters are the connected components of the core vertices under core-core edges, named by their smallest core index; a non-core
 // vertex next to a core one is border and joins the cluster of its anchor, the core neighbour with the largest score (among equal
 // scores the smallest index); everything else is noise.
-//   pass      hmk_neighbors_shifted's (neighbors_internal: the all-vs-all plan slot, the same kernels) at `threshold` into the context's
-//             edge buffer, grown until it fits;
-//   deal      a range only: k_sweep_hist, k_sweep_scan, k_sweep_deal as hmk_sweep.cpp runs them (SB_SWEEP_STATE, SB_SWEEP_RUNS): the edges
+//   pass      pass_edge_runs (hmk_levels.cpp): hmk_neighbors_shifted's (neighbors_internal: the all-vs-all plan slot, the same kernels) at
+//             `threshold` into the context's edge buffer, grown until it fits;
+//   deal      a range only: k_sweep_hist, k_sweep_scan, k_sweep_deal through deal_by_level (hmk_levels.cpp; SB_SWEEP_STATE, SB_SWEEP_RUNS): the edges
 //             with score >= t are the prefix [0, prefix[t - threshold]) of one buffer, and level l's own run is [prefix[l + 1], prefix[l]).
 //             A single level reads the pass's segments directly;
 //   levels    from the top down, k_den_degree, k_den_core, k_den_link, k_den_labels, k_den_sizes per level (k_density.hip), every level
@@ -14,7 +14,7 @@
 //             a batch comes back with one copy per requested array.  The levels' block comes back last.
 // hmk_density_from_edges is the definition written plainly on the host: the second implementation the device path is tested against,
 // and what a host-only context runs.
-#include "hmk_ctx.h"
+#include "hmk_levels.h"
 #include "hmk_density.h"
 
 namespace hmk { namespace impl {
@@ -30,9 +30,8 @@ struct DenOut {
 // the argument checks all three entry points make before the device is looked at
 int check_density(hmk_ctx *ctx, int thr, int thr_hi, int min_neighbors, const DenOut &o) {
     if (min_neighbors < 0) return fail(ctx, HMK_ERR_BAD_ARG, "min_neighbors is negative");
-    if (thr_hi < thr) return fail(ctx, HMK_ERR_BAD_ARG, "threshold_hi is below threshold");
-    if ((long long)thr_hi - thr > (long long)SWEEP_MAX_LEVELS - 1) return fail(ctx, HMK_ERR_BAD_ARG, "at most 256 levels per call: threshold_hi - threshold <= 255");
-    if (thr_hi > 32767) return fail(ctx, HMK_ERR_BAD_ARG, "threshold_hi is above 32767, the highest score an edge holds");
+    const int st = check_level_range(ctx, thr, thr_hi, true);
+    if (st) return st;
     if (ctx->n && !o.levels && !o.cluster && !o.anchor && !o.degree) return fail(ctx, HMK_ERR_BAD_ARG, "null outputs (levels, cluster, anchor and degree)");
     return HMK_OK;
 }
@@ -58,51 +57,21 @@ void fill_stats(hmk_density_stats &S, const std::vector<hmk_density_level> &lv, 
     S.largest = lv[0].largest;
 }
 
-void set_runs(SweepEdges &E, const uint64_t *base, uint64_t stride, uint32_t n_runs, const unsigned long long *count) {
-    E = SweepEdges{};
-    E.base = base;
-    E.stride = stride;
-    E.n_runs = n_runs;
-    for (uint32_t s = 0; s < n_runs; s++) {
-        E.count[s] = count[s];
-        E.chunk_start[s + 1] = E.chunk_start[s] + (uint32_t)((count[s] + SWEEP_CHUNK - 1) / SWEEP_CHUNK);
-    }
-}
-
 // The device side behind the edges: src names them (packed, on this context's device), total = their number.
-int density_on_device(hmk_ctx *ctx, const SweepEdges &src, uint64_t total, int thr, int thr_hi, int min_neighbors, const DenOut &o, hmk_density_stats &S) {
+int density_on_device(hmk_ctx *ctx, const EdgeRuns &src, uint64_t total, int thr, int thr_hi, int min_neighbors, const DenOut &o, hmk_density_stats &S) {
     const uint32_t n = ctx->n, nl = (uint32_t)(thr_hi - thr) + 1;
     int st = greedy_streams(ctx);
     if (st) return st;
     hipStream_t Q = ctx->gstream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    struct Events {
-        hipEvent_t &a, &b;
-        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } events{e0, e1};
-    if (e == hipSuccess) e = hipEventRecord(e0, Q);
-    HIPCHK(ctx, e);
+    EventPair ev;
+    HIPCHK(ctx, ev.create());
+    HIPCHK(ctx, ev.start(Q));
     // a range: the whole edges by level, the top level first (the sweep's kernels and buffers)
-    struct { unsigned long long prefix[SWEEP_MAX_LEVELS], flag; } back{};
-    static_assert(offsetof(SweepState, flag) == offsetof(SweepState, prefix) + sizeof(back.prefix), "prefix and flag are read in one copy");
+    LevelPrefix back{};
     const uint64_t *dealt = nullptr;
     if (nl > 1) {
-        HIPCHK(ctx, ensure_buf(ctx, SB_SWEEP_STATE, sizeof(SweepState)));
-        HIPCHK(ctx, ensure_buf(ctx, SB_SWEEP_RUNS, std::max<uint64_t>(total, 1) * sizeof(uint64_t)));
-        SweepState *state = buf<SweepState>(ctx, SB_SWEEP_STATE);
-        uint64_t *runs = buf<uint64_t>(ctx, SB_SWEEP_RUNS);
-        e = hipMemsetAsync(state, 0, sizeof(SweepState), Q);
-        if (e == hipSuccess) e = launch_sweep_hist(src, n, thr, thr_hi, state, Q);
-        if (e == hipSuccess) e = launch_sweep_scan(nl, state, Q);
-        if (e == hipSuccess) e = launch_sweep_deal(src, n, thr, thr_hi, state, runs, Q);
-        if (e == hipSuccess) e = hipMemcpyAsync(&back, state->prefix, sizeof(back), hipMemcpyDeviceToHost, Q);
-        if (e == hipSuccess) e = hipStreamSynchronize(Q);
-        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("density: ") + hipGetErrorString(e));
-        if (back.flag) return fail(ctx, HMK_ERR_BAD_ARG, "edge list references a sequence outside [0, n) or a self pair");
-        if (back.prefix[0] > total) return fail(ctx, HMK_ERR_DEVICE, "density: more edges dealt than given");
-        dealt = runs;
+        st = deal_by_level(ctx, "density", Q, src, total, thr, thr_hi, nullptr, &back, &dealt);
+        if (st) return st;
     }
     uint32_t *const host_rows[3] = {o.cluster, o.anchor, o.degree};
     const uint32_t n_arrays = (o.cluster ? 1u : 0u) + (o.anchor ? 1u : 0u) + (o.degree ? 1u : 0u);
@@ -117,18 +86,14 @@ int density_on_device(hmk_ctx *ctx, const SweepEdges &src, uint64_t total, int t
     for (uint32_t a = 0, k = 0; a < 3; a++)
         if (host_rows[a]) dev_rows[a] = rows + (size_t)k++ * per_batch * n;
     const size_t state_bytes = offsetof(DenState, level) + (size_t)nl * sizeof(DenLevel);
-    e = hipMemsetAsync(dst, 0, state_bytes, Q);
+    hipError_t e = hipMemsetAsync(dst, 0, state_bytes, Q);
     if (e == hipSuccess) e = launch_den_init(V, n, Q);
     uint32_t batch_hi = nl - 1;   // the batch at hand holds the levels batch_lo ... batch_hi, level l in slot l - batch_lo
     for (uint32_t l = nl; e == hipSuccess && l-- > 0;) {
         const uint32_t batch_lo = batch_hi + 1 >= per_batch ? batch_hi + 1 - per_batch : 0, slot = l - batch_lo;
         DenEdges D;
-        D.E = src;
-        D.own_start = 0;
-        if (nl > 1) {
-            set_runs(D.E, dealt, 0, 1, &back.prefix[l]);
-            D.own_start = l + 1 < nl ? back.prefix[l + 1] : 0;
-        }
+        D.E = nl > 1 ? edge_runs(dealt, 0, 1, &back.prefix[l]) : src;
+        D.own_start = nl > 1 && l + 1 < nl ? back.prefix[l + 1] : 0;
         e = launch_den_degree(D, n, thr, V, dst, l, Q);
         if (e == hipSuccess) e = launch_den_core(n, (uint32_t)min_neighbors, V, dst, l, Q);
         if (e == hipSuccess) e = launch_den_link(D, n, thr, V, dst, l, Q);
@@ -162,11 +127,10 @@ int density_on_device(hmk_ctx *ctx, const SweepEdges &src, uint64_t total, int t
             std::fprintf(stderr, "[hmk density] threshold %d: %u vertices turned core, the link step looked at %llu of %llu edges\n", thr + (int)l, d.new_core,
                          d.looked, (unsigned long long)lv[l].n_edges);
     }
-    e = hipEventRecord(e1, Q);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    HIPCHK(ctx, ev.stop(Q));
+    HIPCHK(ctx, hipEventSynchronize(ev.b));
     float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    HIPCHK(ctx, e);
+    HIPCHK(ctx, ev.elapsed(&ms));
     S.density_ms = ms;
     fill_stats(S, lv, min_neighbors);
     if (o.levels) std::copy(lv.begin(), lv.end(), o.levels);
@@ -186,15 +150,12 @@ int density_shifted(hmk_ctx *ctx, int X, int p, int thr, int thr_hi, int min_nei
     st = need_device(ctx);
     if (st) return st;
     hmk_density_stats S{};
-    unsigned long long counts[HMK_EDGE_SHARDS];
-    double ms = 0;
-    st = neighbors_internal(ctx, X, p, thr, 0, 1, sizing::edge_capacity_guess(true, n, 1, ctx->sw.edge_guess, ctx->edges.cap), counts, &ms);
+    PassRuns P;
+    st = pass_edge_runs(ctx, X, p, thr, true, &P);
     if (st) return st;
-    S.kernel_ms = ms;
-    S.pairs_scored = ctx->plan.stats.pairs_scored;
-    SweepEdges E;
-    set_runs(E, ctx->edges.d, ctx->edges.seg_cap(), HMK_EDGE_SHARDS, counts);
-    st = density_on_device(ctx, E, total_of(counts), thr, thr_hi, min_neighbors, o, S);
+    S.kernel_ms = P.kernel_ms;
+    S.pairs_scored = P.pairs_scored;
+    st = density_on_device(ctx, P.E, P.total, thr, thr_hi, min_neighbors, o, S);
     if (st == HMK_OK && o.stats) *o.stats = S;
     return st;
 }
@@ -205,8 +166,8 @@ int density_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n_edges, 
     refresh_switches(ctx);
     int st = check_density(ctx, thr, thr_hi, min_neighbors, o);
     if (st) return st;
-    if (n_edges && !d_edges) return fail(ctx, HMK_ERR_BAD_ARG, "null edge buffer");
-    if (n_edges > ((uint64_t)1 << 41)) return fail(ctx, HMK_ERR_BAD_ARG, "more than 2^41 edges");   // (chunks are counted in 32 bits)
+    st = check_edges_dev(ctx, d_edges, n_edges);
+    if (st) return st;
     const uint32_t nl = (uint32_t)(thr_hi - thr) + 1;
     if (ctx->n == 0) return empty_set(nl, min_neighbors, o);
     st = need_device(ctx);
@@ -214,10 +175,8 @@ int density_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n_edges, 
     // the caller's block may have been written on any stream of its own: wait for the device
     HIPCHK(ctx, hipDeviceSynchronize());
     hmk_density_stats S{};
-    SweepEdges E;
     const unsigned long long cnt = n_edges;
-    set_runs(E, (const uint64_t *)d_edges, 0, 1, &cnt);
-    st = density_on_device(ctx, E, n_edges, thr, thr_hi, min_neighbors, o, S);
+    st = density_on_device(ctx, edge_runs((const uint64_t *)d_edges, 0, 1, &cnt), n_edges, thr, thr_hi, min_neighbors, o, S);
     if (st == HMK_OK && o.stats) *o.stats = S;
     return st;
 }

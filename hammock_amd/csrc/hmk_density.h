@@ -9,7 +9,7 @@
 
 namespace hmk {
 
-constexpr uint32_t DEN_CHUNK = SWEEP_CHUNK;   // edges a workgroup takes at a time (4 per lane): the chunks of a SweepEdges
+constexpr uint32_t DEN_CHUNK = EDGE_RUN_CHUNK;   // edges a workgroup takes at a time (4 per lane): the chunks of an EdgeRuns
 constexpr uint32_t DEN_MAX_GRID = 2048;       // workgroups of a launch over edges or vertices (8 per compute unit of 256)
 constexpr int DEN_COMBINE = 4;                // distinct values a wave combines by ballot before its lanes add one by one
 
@@ -55,7 +55,7 @@ inline DenVertex den_vertex_arrays(void *block, uint32_t n) {
 // edges where they lie, those below thr and the invalid ones left out by every kernel); the level's own run, the edges that are not
 // edges of the level above, begins at entry own_start of run 0 (0: every edge is the level's own).
 struct DenEdges {
-    SweepEdges E;
+    EdgeRuns E;
     unsigned long long own_start;
 };
 

@@ -120,6 +120,19 @@ struct EdgeSeg { const uint64_t *edges; const unsigned long long *count; uint64_
 constexpr uint32_t HMK_MAX_SEGS = HMK_EDGE_SHARDS + 16;
 struct EdgeSegs { EdgeSeg s[HMK_MAX_SEGS]; uint32_t n; };
 
+// Where a call's packed edges lie: n_runs runs, run s = count[s] entries at base + s * stride -- the HMK_EDGE_SHARDS segments of a
+// neighbour pass (the host has read their counts), or one run (a caller's block, a level's prefix of a dealt buffer).  A chunk is
+// EDGE_RUN_CHUNK consecutive entries of one run; chunk_start[s] = the chunks before run s.  Passed to the kernels by value; the host
+// fills it with edge_runs (hmk_levels.h).
+constexpr uint32_t EDGE_RUN_CHUNK = 1024;   // edges a workgroup takes at a time (4 per lane)
+struct EdgeRuns {
+    const uint64_t *base;
+    uint64_t stride;
+    uint32_t n_runs;
+    uint32_t chunk_start[HMK_EDGE_SHARDS + 1];
+    unsigned long long count[HMK_EDGE_SHARDS];
+};
+
 // Where the adjacency rows of a clustering call live on the device side: one piece (this device's CSR), or -- a multi-device call --
 // one piece per device, device d holding the rows [d * rows_per, (d + 1) * rows_per) (its start[] / up[] are indexed by the row itself,
 // rows it does not own are empty).  The second loop's kernels run on the root and read a joiner's row where it lives.

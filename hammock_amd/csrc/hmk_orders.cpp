@@ -3,8 +3,8 @@
 // clusters (hmk_greedy_orders*).  Replaces one LimitedGreedySequenceClusterer(scorer, threshold, maxClusters).cluster(list k)
 // (LimitedGreedySequenceClusterer.java:22,39-69) per order k, list k = the set as UniqueSequence.sortSequences would hand it over
 // under another -R: the scores do not depend on the order, only the tail does.
-//   pass      hmk_neighbors_shifted's (neighbors_internal: the all-vs-all plan slot, the same kernels) at `threshold` into the context's
-//             edge buffer, grown until it fits;
+//   pass      pass_edge_runs (hmk_levels.cpp): hmk_neighbors_shifted's (neighbors_internal: the all-vs-all plan slot, the same kernels) at
+//             `threshold` into the context's edge buffer, grown until it fits;
 //   relabel   per order k_orders_relabel: the edges renamed to the order's positions (SB_ORD_EDGES), the 16 score bits copied;
 //   tail      per order the clustering tail as it is (cluster_on_device) on an EdgeSource of one segment, with Cluster.size() read
 //             through the order's permuted view (hmk_ctx::sizes_view); the rows mapped back to uploaded indices on the host;
@@ -12,7 +12,7 @@
 //   consensus k_components.hip's union-find (hmk_cc_device.h) straight over the support edges at min_support, flatten, count.
 // hmk_greedy_orders_from_edges is the same answer on the host: relabel, hmk_greedy_from_edges's merge per order, supports by a loop,
 // a sequential union-find -- the second implementation the device path is tested against, and what a host-only context runs.
-#include "hmk_ctx.h"
+#include "hmk_levels.h"
 #include "hmk_components.h"
 #include "hmk_orders.h"
 
@@ -181,21 +181,6 @@ struct SizesView {
     ~SizesView() { ctx->sizes_view = nullptr; }
 };
 
-void set_runs(SweepEdges &E, OrderRuns &R, const uint64_t *base, uint64_t stride, uint32_t n_runs, const unsigned long long *count) {
-    E = SweepEdges{};
-    R = OrderRuns{};
-    E.base = base;
-    E.stride = stride;
-    E.n_runs = n_runs;
-    unsigned long long off = 0;
-    for (uint32_t s = 0; s < n_runs; s++) {
-        E.count[s] = count[s];
-        E.chunk_start[s + 1] = E.chunk_start[s] + (uint32_t)((count[s] + SWEEP_CHUNK - 1) / SWEEP_CHUNK);
-        R.off[s] = off;
-        off += count[s];
-    }
-}
-
 int greedy_orders(hmk_ctx *ctx, int X, int p, int thr, int max_clusters, const uint32_t *orders, uint32_t n_orders, uint32_t min_support,
                   const OrdersOut &o) {
     if (!ctx) return fail(nullptr, HMK_ERR_BAD_ARG, "null context");
@@ -209,17 +194,16 @@ int greedy_orders(hmk_ctx *ctx, int X, int p, int thr, int max_clusters, const u
     if (st) return st;
     hmk_greedy_orders_stats S{};
     S.n_orders = n_orders;
-    unsigned long long counts[HMK_EDGE_SHARDS];
-    double pass_ms = 0;
-    st = neighbors_internal(ctx, X, p, thr, 0, 1, sizing::edge_capacity_guess(true, n, 1, ctx->sw.edge_guess, ctx->edges.cap), counts, &pass_ms);
+    PassRuns P;
+    st = pass_edge_runs(ctx, X, p, thr, true, &P);
     if (st) return st;
-    S.kernel_ms = pass_ms;
-    S.pairs_scored = ctx->plan.stats.pairs_scored;
-    const uint64_t total = total_of(counts);
+    S.kernel_ms = P.kernel_ms;
+    S.pairs_scored = P.pairs_scored;
+    const EdgeRuns &E = P.E;
+    const uint64_t total = P.total;
     S.n_edges = total;
-    SweepEdges E;
-    OrderRuns runs;
-    set_runs(E, runs, ctx->edges.d, ctx->edges.seg_cap(), HMK_EDGE_SHARDS, counts);
+    OrderRuns runs{};   // the runs back to back in the renamed buffer
+    for (uint32_t s = 1; s < E.n_runs; s++) runs.off[s] = runs.off[s - 1] + E.count[s - 1];
     st = greedy_streams(ctx);
     if (st) return st;
     hipStream_t Q = ctx->gstream;
@@ -233,15 +217,8 @@ int greedy_orders(hmk_ctx *ctx, int X, int p, int thr, int max_clusters, const u
     HIPCHK(ctx, hipMemsetAsync(state, 0, sizeof(OrdersState), Q));
     HIPCHK(ctx, hipMemcpyAsync(&state->total, &total_word, sizeof(total_word), hipMemcpyHostToDevice, Q));
     HIPCHK(ctx, hipStreamSynchronize(Q));
-    struct Events {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~Events() {
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-        }
-    } ev;
-    HIPCHK(ctx, hipEventCreate(&ev.a));
-    HIPCHK(ctx, hipEventCreate(&ev.b));
+    EventPair ev;
+    HIPCHK(ctx, ev.create());
 
     OrdersRun R;
     R.init(ctx, n_orders, o);
@@ -251,19 +228,12 @@ int greedy_orders(hmk_ctx *ctx, int X, int p, int thr, int max_clusters, const u
         const uint32_t *order = orders + (size_t)k * n;
         R.begin(ctx, order);
         HIPCHK(ctx, hipMemcpyAsync(d_pos, R.pos.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, Q));
-        HIPCHK(ctx, hipEventRecord(ev.a, Q));
+        HIPCHK(ctx, ev.start(Q));
         HIPCHK(ctx, launch_orders_relabel(E, runs, n, d_pos, renamed, state, Q));
-        HIPCHK(ctx, hipEventRecord(ev.b, Q));
+        HIPCHK(ctx, ev.stop(Q));
         // the tail takes the renamed edges as one segment whose count is the state's `total`, in device memory
-        EdgeSource src;
-        src.symmetric = true;
-        src.segs.n = 1;
-        src.segs.s[0] = EdgeSeg{renamed, &state->total, std::max<uint64_t>(total, 1)};
-        src.total_known = total;
-        src.format_known = true;
-        src.packed = adjacency_packed(ctx, X, p, thr);
-        src.base = thr;
-        src.adj_bound = 2 * total;
+        const bool packed = adjacency_packed(ctx, X, p, thr);
+        const EdgeSource src = one_segment_source(renamed, &state->total, total, true, &packed, thr);
         ctx->phases = hmk_greedy_phases{};
         HIPCHK(ctx, hipEventRecord(ctx->ev_t0, Q));
         HIPCHK(ctx, hipEventRecord(ctx->ev_edges, Q));
@@ -275,7 +245,7 @@ int greedy_orders(hmk_ctx *ctx, int X, int p, int thr, int max_clusters, const u
         if (st != HMK_OK && st != HMK_ERR_REFERENCE_WOULD_CRASH) return st;
         float ms = 0;
         HIPCHK(ctx, hipEventSynchronize(ev.b));
-        HIPCHK(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
+        HIPCHK(ctx, ev.elapsed(&ms));
         S.relabel_ms += ms;
         R.finish(k, order, o, st, gs, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     }
@@ -305,7 +275,7 @@ int greedy_orders(hmk_ctx *ctx, int X, int p, int thr, int max_clusters, const u
     struct { unsigned long long n_support, n_always, total, flag; } back;
     static_assert(offsetof(OrdersState, flag) == offsetof(OrdersState, n_support) + 3 * sizeof(unsigned long long), "the counters and the flag are read in one copy");
     HIPCHK(ctx, hipMemcpyAsync(d_ids, idsT.data(), idsT.size() * sizeof(int32_t), hipMemcpyHostToDevice, Q));
-    HIPCHK(ctx, hipEventRecord(ev.a, Q));
+    HIPCHK(ctx, ev.start(Q));
     HIPCHK(ctx, hipMemsetAsync(d_ever, 0, (size_t)n * 2 * sizeof(uint32_t), Q));
     HIPCHK(ctx, hipMemsetAsync(cc, 0, sizeof(CcState), Q));
     HIPCHK(ctx, launch_cc_init(parent, size, n, Q));
@@ -316,15 +286,11 @@ int greedy_orders(hmk_ctx *ctx, int X, int p, int thr, int max_clusters, const u
     if (back.n_support > room) return fail(ctx, HMK_ERR_DEVICE, "greedy orders: more support edges than pairs inside clusters");
     // the consensus: the support edges are HMK_EDGE_* edges with the support as their score -- k_components.hip's single-level union at
     // `level`, flatten, count (the host knows their number now)
-    CcEdges C{};
-    C.base = d_support;
-    C.n_runs = 1;
-    C.count[0] = unreachable ? 0 : back.n_support;
-    C.chunk_start[1] = (uint32_t)((C.count[0] + CC_CHUNK - 1) / CC_CHUNK);
-    HIPCHK(ctx, launch_cc_union_edges(C, n, (int)level, parent, cc, Q));
+    const unsigned long long n_united = unreachable ? 0 : back.n_support;
+    HIPCHK(ctx, launch_cc_union_edges(edge_runs(d_support, 0, 1, &n_united), n, (int)level, parent, cc, Q));
     HIPCHK(ctx, launch_cc_flatten(parent, size, n, Q));
     HIPCHK(ctx, launch_cc_sizes(size, n, 0, cc, Q));
-    HIPCHK(ctx, hipEventRecord(ev.b, Q));
+    HIPCHK(ctx, ev.stop(Q));
     hmk_component_level lv{};
     std::vector<unsigned long long> sums((size_t)2 * ORDERS_MAX);
     HIPCHK(ctx, hipMemcpyAsync(&lv, &cc->levels[0], sizeof(lv), hipMemcpyDeviceToHost, Q));
@@ -337,7 +303,7 @@ int greedy_orders(hmk_ctx *ctx, int X, int p, int thr, int max_clusters, const u
         HIPCHK(ctx, hipMemcpyAsync(o.support_edges, d_support, back.n_support * sizeof(uint64_t), hipMemcpyDeviceToHost, Q));
     HIPCHK(ctx, hipStreamSynchronize(Q));
     float ms = 0;
-    HIPCHK(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
+    HIPCHK(ctx, ev.elapsed(&ms));
     S.support_ms = ms;
     if (lv.reserved) return fail(ctx, HMK_ERR_DEVICE, "greedy orders: a support edge outside [0, n) or a self pair");
     for (uint32_t v = 0; v < nv; v++) {

@@ -1,6 +1,6 @@
 // hmk_orders.h -- launchers of k_orders.hip (the packed edges of one neighbour pass renamed into another order of the set; the
 // co-clustering support of every edge over the orders' clusterings), used by hmk_orders.cpp (hmk_greedy_orders*).  The edges are
-// named as hmk_sweep.h's SweepEdges names them.
+// named by an EdgeRuns (hmk_internal.h).
 #ifndef HMK_ORDERS_H
 #define HMK_ORDERS_H
 
@@ -16,7 +16,7 @@ constexpr uint32_t ORDERS_MAX_GRID = 2048;       // workgroups of the two kernel
 constexpr uint32_t ORDERS_FLUSH_CHUNKS = 1u << 21;   // k_orders_support adds its LDS counters to the global ones after that many chunks:
                                                      // 2^31 edges at most in one 32-bit counter
 
-// where run s of the edges begins in the renamed buffer: the runs back to back (passed by value beside SweepEdges)
+// where run s of the edges begins in the renamed buffer: the runs back to back (passed by value beside EdgeRuns)
 struct OrderRuns {
     unsigned long long off[HMK_EDGE_SHARDS];
 };
@@ -35,12 +35,12 @@ struct OrdersState {
 
 // every edge (x, m, score) as (min(pos[x], pos[m]), max(...), score) at the same place of the runs laid back to back; the 16 score
 // bits are copied.  pos[n]: the order's inverse permutation.
-hipError_t launch_orders_relabel(const SweepEdges &E, const OrderRuns &R, uint32_t n, const uint32_t *pos, uint64_t *out, OrdersState *st,
+hipError_t launch_orders_relabel(const EdgeRuns &E, const OrderRuns &R, uint32_t n, const uint32_t *pos, uint64_t *out, OrdersState *st,
                                  hipStream_t s);
 // support of every edge = the valid orders v with ids[x][v] == ids[m][v] (ids: [n][n_valid], the transposed cluster ids).  An edge
 // with support >= 1 goes to out[] (x < m, support in the score field) while there is room (cap entries; out may be null), counts
 // towards ever[x], ever[m] and, at support == n_valid, always[x], always[m]; the per-order sums go to st.
-hipError_t launch_orders_support(const SweepEdges &E, uint32_t n, const int32_t *ids, uint32_t n_valid, uint64_t *out, unsigned long long cap,
+hipError_t launch_orders_support(const EdgeRuns &E, uint32_t n, const int32_t *ids, uint32_t n_valid, uint64_t *out, unsigned long long cap,
                                  uint32_t *ever, uint32_t *always, OrdersState *st, hipStream_t s);
 
 }  // namespace hmk

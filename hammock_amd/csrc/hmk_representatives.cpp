@@ -2,9 +2,9 @@
 // representative iff no representative r < i is its neighbour in {score >= t} -- the greedy incremental selection of CD-HIT and
 // UCLUST, on the graph the lexicographically first maximal independent set -- and for every other sequence the representatives next
 // to it (covered_by: the smallest index, nearest: the largest score).
-//   pass      hmk_neighbors_shifted's (neighbors_internal: the all-vs-all plan slot, the same kernels) at `threshold` into the context's
-//             edge buffer, grown until it fits;
-//   deal      a range only: k_sweep_hist, k_sweep_scan, k_sweep_deal as hmk_sweep.cpp runs them (SB_SWEEP_STATE, SB_SWEEP_RUNS): the edges
+//   pass      pass_edge_runs (hmk_levels.cpp): hmk_neighbors_shifted's (neighbors_internal: the all-vs-all plan slot, the same kernels) at
+//             `threshold` into the context's edge buffer, grown until it fits;
+//   deal      a range only: k_sweep_hist, k_sweep_scan, k_sweep_deal through deal_by_level (hmk_levels.cpp; SB_SWEEP_STATE, SB_SWEEP_RUNS): the edges
 //             with score >= t are the prefix [0, prefix[t - threshold]) of one buffer.  A single level reads the pass's segments directly;
 //   rounds    per level k_rep_mark* / k_rep_decide until a round leaves no vertex undecided: the host watches the progress word the
 //             decision kernel stores into pinned memory and keeps one round in the queue beside the running one (the pattern of
@@ -13,7 +13,7 @@
 //             groups' sizes are counted on the host from `nearest`.
 // hmk_representatives_from_edges is the definition written plainly on the host: the second implementation the device path is tested
 // against, and what a host-only context runs.
-#include "hmk_ctx.h"
+#include "hmk_levels.h"
 #include "hmk_representatives.h"
 
 namespace hmk { namespace impl {
@@ -29,9 +29,8 @@ struct RepOut {
 
 // the argument checks all three entry points make before the device is looked at
 int check_representatives(hmk_ctx *ctx, int thr, int thr_hi, const RepOut &o) {
-    if (thr_hi < thr) return fail(ctx, HMK_ERR_BAD_ARG, "threshold_hi is below threshold");
-    if ((long long)thr_hi - thr > (long long)SWEEP_MAX_LEVELS - 1) return fail(ctx, HMK_ERR_BAD_ARG, "at most 256 levels per call: threshold_hi - threshold <= 255");
-    if (thr_hi > 32767) return fail(ctx, HMK_ERR_BAD_ARG, "threshold_hi is above 32767, the highest score an edge holds");
+    const int st = check_level_range(ctx, thr, thr_hi, true);
+    if (st) return st;
     if (ctx->n && !o.levels && !o.covered_by && !o.nearest && !o.nearest_score)
         return fail(ctx, HMK_ERR_BAD_ARG, "null outputs (levels, covered_by, nearest and nearest_score)");
     return HMK_OK;
@@ -70,24 +69,13 @@ void fill_stats(hmk_representatives_stats &S, const std::vector<hmk_representati
     for (const hmk_representative_level &L : lv) S.rounds_total += L.n_rounds;
 }
 
-void set_runs(SweepEdges &E, const uint64_t *base, uint64_t stride, uint32_t n_runs, const unsigned long long *count) {
-    E = SweepEdges{};
-    E.base = base;
-    E.stride = stride;
-    E.n_runs = n_runs;
-    for (uint32_t s = 0; s < n_runs; s++) {
-        E.count[s] = count[s];
-        E.chunk_start[s + 1] = E.chunk_start[s] + (uint32_t)((count[s] + SWEEP_CHUNK - 1) / SWEEP_CHUNK);
-    }
-}
-
 double ms_since(std::chrono::steady_clock::time_point a) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
 }
 
 // One level on the device: E = its edges (those with score >= t count), room = an upper bound of their number.  -> the level's block
 // in *back, its arrays in the caller's rows (nearest_row is never null).
-int level_on_device(hmk_ctx *ctx, hipStream_t Q, const SweepEdges &E, uint64_t room, int t, const RepVertex &V, RepState *st, uint64_t *live0,
+int level_on_device(hmk_ctx *ctx, hipStream_t Q, const EdgeRuns &E, uint64_t room, int t, const RepVertex &V, RepState *st, uint64_t *live0,
                     uint64_t *live1, uint64_t cap, uint32_t *covered_row, uint32_t *nearest_row, int32_t *score_row, RepState *back) {
     const uint32_t n = ctx->n;
     volatile unsigned long long *word = ctx->h_loop;
@@ -149,41 +137,21 @@ int level_on_device(hmk_ctx *ctx, hipStream_t Q, const SweepEdges &E, uint64_t r
 }
 
 // The device side behind the edges: src names them (packed, on this context's device), total = their number.
-int select_on_device(hmk_ctx *ctx, const SweepEdges &src, uint64_t total, int thr, int thr_hi, const RepOut &o, hmk_representatives_stats &S) {
+int select_on_device(hmk_ctx *ctx, const EdgeRuns &src, uint64_t total, int thr, int thr_hi, const RepOut &o, hmk_representatives_stats &S) {
     const uint32_t n = ctx->n, nl = (uint32_t)(thr_hi - thr) + 1;
     int st = greedy_streams(ctx);
     if (st) return st;
     if (!ctx->h_loop) return fail(ctx, HMK_ERR_DEVICE, "no coherent pinned block for the rounds' progress word");
     hipStream_t Q = ctx->gstream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    struct Events {
-        hipEvent_t &a, &b;
-        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } events{e0, e1};
-    if (e == hipSuccess) e = hipEventRecord(e0, Q);
-    HIPCHK(ctx, e);
+    EventPair ev;
+    HIPCHK(ctx, ev.create());
+    HIPCHK(ctx, ev.start(Q));
     // a range: the whole edges by level, the top level first (the sweep's kernels and buffers)
-    struct { unsigned long long prefix[SWEEP_MAX_LEVELS], flag; } back{};
-    static_assert(offsetof(SweepState, flag) == offsetof(SweepState, prefix) + sizeof(back.prefix), "prefix and flag are read in one copy");
+    LevelPrefix back{};
     const uint64_t *dealt = nullptr;
-    SweepState *state = nullptr;
     if (nl > 1) {
-        HIPCHK(ctx, ensure_buf(ctx, SB_SWEEP_STATE, sizeof(SweepState)));
-        HIPCHK(ctx, ensure_buf(ctx, SB_SWEEP_RUNS, std::max<uint64_t>(total, 1) * sizeof(uint64_t)));
-        state = buf<SweepState>(ctx, SB_SWEEP_STATE);
-        uint64_t *runs = buf<uint64_t>(ctx, SB_SWEEP_RUNS);
-        e = hipMemsetAsync(state, 0, sizeof(SweepState), Q);
-        if (e == hipSuccess) e = launch_sweep_hist(src, n, thr, thr_hi, state, Q);
-        if (e == hipSuccess) e = launch_sweep_scan(nl, state, Q);
-        if (e == hipSuccess) e = launch_sweep_deal(src, n, thr, thr_hi, state, runs, Q);
-        if (e == hipSuccess) e = hipMemcpyAsync(&back, state->prefix, sizeof(back), hipMemcpyDeviceToHost, Q);
-        if (e == hipSuccess) e = hipStreamSynchronize(Q);
-        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("representatives: ") + hipGetErrorString(e));
-        if (back.flag) return fail(ctx, HMK_ERR_BAD_ARG, "edge list references a sequence outside [0, n) or a self pair");
-        if (back.prefix[0] > total) return fail(ctx, HMK_ERR_DEVICE, "representatives: more edges dealt than given");
-        dealt = runs;
+        st = deal_by_level(ctx, "representatives", Q, src, total, thr, thr_hi, nullptr, &back, &dealt);
+        if (st) return st;
     }
     const uint64_t cap = std::max<uint64_t>(nl > 1 ? back.prefix[0] : total, 1);   // no level has more edges, no round keeps more
     HIPCHK(ctx, ensure_buf(ctx, SB_REP_STATE, sizeof(RepState)));
@@ -195,12 +163,8 @@ int select_on_device(hmk_ctx *ctx, const SweepEdges &src, uint64_t total, int th
     std::vector<hmk_representative_level> lv(nl);
     std::vector<uint32_t> near_scratch(o.nearest ? 0 : n), members;
     for (uint32_t l = nl; l-- > 0;) {
-        SweepEdges E = src;
-        uint64_t room = total;
-        if (nl > 1) {
-            set_runs(E, dealt, 0, 1, &back.prefix[l]);
-            room = back.prefix[l];
-        }
+        const EdgeRuns E = nl > 1 ? edge_runs(dealt, 0, 1, &back.prefix[l]) : src;
+        const uint64_t room = nl > 1 ? back.prefix[l] : total;
         uint32_t *near_row = o.nearest ? o.nearest + (size_t)l * n : near_scratch.data();
         RepState rb{};
         st = level_on_device(ctx, Q, E, room, thr + (int)l, V, rst, live0, live1, cap, o.covered_by ? o.covered_by + (size_t)l * n : nullptr, near_row,
@@ -208,11 +172,10 @@ int select_on_device(hmk_ctx *ctx, const SweepEdges &src, uint64_t total, int th
         if (st) return st;
         lv[l] = level_record(n, nl > 1 ? back.prefix[l] : rb.n_edges, rb.n_rep, rb.n_isolated, rb.rounds, near_row, members);
     }
-    e = hipEventRecord(e1, Q);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    HIPCHK(ctx, ev.stop(Q));
+    HIPCHK(ctx, hipEventSynchronize(ev.b));
     float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    HIPCHK(ctx, e);
+    HIPCHK(ctx, ev.elapsed(&ms));
     S.select_ms = ms;
     fill_stats(S, lv);
     if (o.levels) std::copy(lv.begin(), lv.end(), o.levels);
@@ -232,15 +195,12 @@ int representatives_shifted(hmk_ctx *ctx, int X, int p, int thr, int thr_hi, con
     st = need_device(ctx);
     if (st) return st;
     hmk_representatives_stats S{};
-    unsigned long long counts[HMK_EDGE_SHARDS];
-    double ms = 0;
-    st = neighbors_internal(ctx, X, p, thr, 0, 1, sizing::edge_capacity_guess(true, n, 1, ctx->sw.edge_guess, ctx->edges.cap), counts, &ms);
+    PassRuns P;
+    st = pass_edge_runs(ctx, X, p, thr, true, &P);
     if (st) return st;
-    S.kernel_ms = ms;
-    S.pairs_scored = ctx->plan.stats.pairs_scored;
-    SweepEdges E;
-    set_runs(E, ctx->edges.d, ctx->edges.seg_cap(), HMK_EDGE_SHARDS, counts);
-    st = select_on_device(ctx, E, total_of(counts), thr, thr_hi, o, S);
+    S.kernel_ms = P.kernel_ms;
+    S.pairs_scored = P.pairs_scored;
+    st = select_on_device(ctx, P.E, P.total, thr, thr_hi, o, S);
     if (st == HMK_OK && o.stats) *o.stats = S;
     return st;
 }
@@ -251,8 +211,8 @@ int representatives_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n
     refresh_switches(ctx);
     int st = check_representatives(ctx, thr, thr_hi, o);
     if (st) return st;
-    if (n_edges && !d_edges) return fail(ctx, HMK_ERR_BAD_ARG, "null edge buffer");
-    if (n_edges > ((uint64_t)1 << 41)) return fail(ctx, HMK_ERR_BAD_ARG, "more than 2^41 edges");   // (chunks are counted in 32 bits)
+    st = check_edges_dev(ctx, d_edges, n_edges);
+    if (st) return st;
     const uint32_t nl = (uint32_t)(thr_hi - thr) + 1;
     if (ctx->n == 0) return empty_set(nl, o);
     st = need_device(ctx);
@@ -260,10 +220,8 @@ int representatives_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n
     // the caller's block may have been written on any stream of its own: wait for the device
     HIPCHK(ctx, hipDeviceSynchronize());
     hmk_representatives_stats S{};
-    SweepEdges E;
     const unsigned long long cnt = n_edges;
-    set_runs(E, (const uint64_t *)d_edges, 0, 1, &cnt);
-    st = select_on_device(ctx, E, n_edges, thr, thr_hi, o, S);
+    st = select_on_device(ctx, edge_runs((const uint64_t *)d_edges, 0, 1, &cnt), n_edges, thr, thr_hi, o, S);
     if (st == HMK_OK && o.stats) *o.stats = S;
     return st;
 }

@@ -9,7 +9,7 @@
 
 namespace hmk {
 
-constexpr uint32_t REP_CHUNK = SWEEP_CHUNK;   // edges a workgroup takes at a time (4 per lane): the chunks of a SweepEdges
+constexpr uint32_t REP_CHUNK = EDGE_RUN_CHUNK;   // edges a workgroup takes at a time (4 per lane): the chunks of an EdgeRuns
 constexpr uint32_t REP_MAX_GRID = 2048;       // workgroups of a launch over edges or vertices (8 per compute unit of 256)
 
 enum : uint8_t { REP_UNDECIDED = 0, REP_REP = 1, REP_REDUNDANT = 2 };
@@ -19,7 +19,7 @@ enum : uint8_t { REP_UNDECIDED = 0, REP_REP = 1, REP_REDUNDANT = 2 };
 //             the decision kernel of round r clears live[(r + 1) & 1] for the round behind it
 //   tally     the decision kernel's workgroups that are through << 32 | the vertices they leave undecided: 0 again when the kernel ends
 //   rounds    the first round that left no vertex undecided (0: none yet)
-//   n_edges   the edges >= thr a round-1 launch over a SweepEdges counted
+//   n_edges   the edges >= thr a round-1 launch over an EdgeRuns counted
 //   n_rep, n_isolated   the finish kernel's counts
 //   flag      non-zero once an edge named an index >= n or a self pair
 //   trace     the live edges behind each of the first REP_TRACE rounds (HMK_GREEDY_TIMING prints them)
@@ -60,7 +60,7 @@ hipError_t launch_rep_init(const RepVertex &v, uint32_t n, hipStream_t s);
 // Rounds 1 and 2 over the level's edges E where they lie (those with score >= thr; invalid ones flagged and left out).  Round 1
 // counts them into st->n_edges and appends nothing: every vertex is undecided, every edge stays live.  Round 2 reads them again and
 // appends the undecided-undecided ones as lo << 32 | hi to live0 (room for `cap` entries).
-hipError_t launch_rep_mark_first(uint32_t round, const SweepEdges &E, uint32_t n, int thr, const RepVertex &v, RepState *st, uint64_t *live0,
+hipError_t launch_rep_mark_first(uint32_t round, const EdgeRuns &E, uint32_t n, int thr, const RepVertex &v, RepState *st, uint64_t *live0,
                                  uint64_t cap, hipStream_t s);
 // Round r >= 3 over the live buffer the round before wrote (its length is st->live[(r - 1) & 1]; total_edges, the level's, sizes the
 // grid) into the other one
@@ -69,7 +69,7 @@ hipError_t launch_rep_mark(uint32_t round, uint64_t total_edges, const RepVertex
 // The decisions of round r; the last workgroup stores round << 32 | undecided into host_word[0] and the live count into host_word[1]
 hipError_t launch_rep_decide(uint32_t round, uint32_t n, const RepVertex &v, RepState *st, unsigned long long *host_word, hipStream_t s);
 // covered_by (minimum) and key (maximum) from every edge of the level
-hipError_t launch_rep_assign(const SweepEdges &E, uint32_t n, int thr, const RepVertex &v, hipStream_t s);
+hipError_t launch_rep_assign(const EdgeRuns &E, uint32_t n, int thr, const RepVertex &v, hipStream_t s);
 // nearest, nearest_score from the keys, the representatives' own entries, st->n_rep and st->n_isolated
 hipError_t launch_rep_finish(uint32_t n, const RepVertex &v, RepState *st, hipStream_t s);
 

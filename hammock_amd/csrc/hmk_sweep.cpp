@@ -1,16 +1,15 @@
 // hmk_sweep.cpp -- the greedy clusterings at every threshold of a range from ONE scoring pass (hmk_greedy_sweep*).
 // Replaces one LimitedGreedySequenceClusterer(scorer, t, maxClusters).cluster(sequences) per threshold t
 // (LimitedGreedySequenceClusterer.java:22,39-69), each of which scores the whole pair space again.
-//   pass      hmk_neighbors_shifted's (neighbors_internal: the all-vs-all plan slot, the same kernels) at `threshold` into the context's
-//             edge buffer, grown until it fits;
-//   deal      k_sweep_hist, k_sweep_scan, k_sweep_deal: the whole edges in one run per level min(score, threshold_hi) - threshold,
-//             the top level first (SB_SWEEP_RUNS), so that the edges with score >= t are the prefix [0, prefix[t - threshold]);
-//             no host synchronisation between the three, prefix[] and the flag come back in one copy;
+//   pass      pass_edge_runs (hmk_levels.cpp): hmk_neighbors_shifted's (neighbors_internal: the all-vs-all plan slot, the same kernels) at
+//             `threshold` into the context's edge buffer, grown until it fits;
+//   deal      deal_by_level (hmk_levels.cpp): k_sweep_hist, k_sweep_scan, k_sweep_deal put the whole edges in one run per level
+//             min(score, threshold_hi) - threshold, the top level first (SB_SWEEP_RUNS), so that the edges with score >= t are the
+//             prefix [0, prefix[t - threshold]);
 //   tails     per level the clustering tail as it is (cluster_on_device) on an EdgeSource of one segment: that prefix.
 // hmk_greedy_sweep_from_edges is the same answer on the host: the edges sorted by level by counting, hmk_greedy_from_edges's merge per
 // prefix -- the second implementation the device path is tested against, and what a host-only context runs.
-#include "hmk_ctx.h"
-#include "hmk_sweep.h"
+#include "hmk_levels.h"
 
 namespace hmk { namespace impl {
 
@@ -24,9 +23,8 @@ struct SweepOut {
 
 // the argument checks all three entry points make before the device is looked at
 int check_sweep(hmk_ctx *ctx, int thr, int thr_hi, const SweepOut &o) {
-    if (thr_hi < thr) return fail(ctx, HMK_ERR_BAD_ARG, "threshold_hi is below threshold");
-    if ((long long)thr_hi - thr > (long long)SWEEP_MAX_LEVELS - 1) return fail(ctx, HMK_ERR_BAD_ARG, "at most 256 levels per call: threshold_hi - threshold <= 255");
-    if (thr_hi > 32767) return fail(ctx, HMK_ERR_BAD_ARG, "threshold_hi is above 32767, the highest score an edge holds");
+    const int st = check_level_range(ctx, thr, thr_hi, true);
+    if (st) return st;
     if (ctx->n && !o.levels && !o.cluster_id && !o.result_order && !o.member_rank)
         return fail(ctx, HMK_ERR_BAD_ARG, "null outputs (levels, cluster_id, result_order and member_rank)");
     return HMK_OK;
@@ -80,49 +78,23 @@ int32_t *level_row(int32_t *rows, uint32_t l, uint32_t n) {
     return rows + (size_t)l * n;
 }
 
-void set_runs(SweepEdges &E, const uint64_t *base, uint64_t stride, uint32_t n_runs, const unsigned long long *count) {
-    E = SweepEdges{};
-    E.base = base;
-    E.stride = stride;
-    E.n_runs = n_runs;
-    for (uint32_t s = 0; s < n_runs; s++) {
-        E.count[s] = count[s];
-        E.chunk_start[s + 1] = E.chunk_start[s] + (uint32_t)((count[s] + SWEEP_CHUNK - 1) / SWEEP_CHUNK);
-    }
-}
-
 // The device side behind the edges: E names them (packed, on this context's device), total = their number.  X, p: the scoring
 // parameters the adjacency format follows from (scored = true), else the tail reads the format off each level's scores.
-int sweep_on_device(hmk_ctx *ctx, const SweepEdges &E, uint64_t total, bool symmetric, bool scored, int X, int p, int thr, int thr_hi, int max_clusters,
+int sweep_on_device(hmk_ctx *ctx, const EdgeRuns &E, uint64_t total, bool symmetric, bool scored, int X, int p, int thr, int thr_hi, int max_clusters,
                     const SweepOut &o, hmk_greedy_sweep_stats &S) {
     const uint32_t n = ctx->n, nl = (uint32_t)(thr_hi - thr) + 1;
     int st = greedy_streams(ctx);
     if (st) return st;
     hipStream_t Q = ctx->gstream;
-    HIPCHK(ctx, ensure_buf(ctx, SB_SWEEP_STATE, sizeof(SweepState)));
-    HIPCHK(ctx, ensure_buf(ctx, SB_SWEEP_RUNS, std::max<uint64_t>(total, 1) * sizeof(uint64_t)));
-    SweepState *state = buf<SweepState>(ctx, SB_SWEEP_STATE);
-    uint64_t *dealt = buf<uint64_t>(ctx, SB_SWEEP_RUNS);
-    struct { unsigned long long prefix[SWEEP_MAX_LEVELS], flag; } back;
-    static_assert(offsetof(SweepState, flag) == offsetof(SweepState, prefix) + sizeof(back.prefix), "prefix and flag are read in one copy");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, Q);
-    if (e == hipSuccess) e = hipMemsetAsync(state, 0, sizeof(SweepState), Q);
-    if (e == hipSuccess) e = launch_sweep_hist(E, n, thr, thr_hi, state, Q);
-    if (e == hipSuccess) e = launch_sweep_scan(nl, state, Q);
-    if (e == hipSuccess) e = launch_sweep_deal(E, n, thr, thr_hi, state, dealt, Q);
-    if (e == hipSuccess) e = hipEventRecord(e1, Q);
-    if (e == hipSuccess) e = hipMemcpyAsync(&back, state->prefix, sizeof(back), hipMemcpyDeviceToHost, Q);
-    if (e == hipSuccess) e = hipStreamSynchronize(Q);
+    EventPair ev;   // around the deal's kernels
+    HIPCHK(ctx, ev.create());
+    LevelPrefix back;
+    const uint64_t *dealt = nullptr;
+    SweepState *state = nullptr;
+    st = deal_by_level(ctx, "greedy sweep", Q, E, total, thr, thr_hi, &ev, &back, &dealt, &state);
+    if (st) return st;
     float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("greedy sweep: ") + hipGetErrorString(e));
-    if (back.flag) return fail(ctx, HMK_ERR_BAD_ARG, "edge list references a sequence outside [0, n) or a self pair");
-    if (back.prefix[0] > total) return fail(ctx, HMK_ERR_DEVICE, "greedy sweep: more edges dealt than given");
+    HIPCHK(ctx, ev.elapsed(&ms));
     S.deal_ms = ms;
     S.n_edges = back.prefix[0];
     S.n_levels = nl;
@@ -134,17 +106,8 @@ int sweep_on_device(hmk_ctx *ctx, const SweepEdges &E, uint64_t total, bool symm
         const auto t0 = std::chrono::steady_clock::now();
         const int t = thr + (int)l;
         const uint64_t m = back.prefix[l];
-        EdgeSource src;
-        src.symmetric = symmetric;
-        src.segs.n = 1;
-        src.segs.s[0] = EdgeSeg{dealt, &state->prefix[l], std::max<uint64_t>(m, 1)};   // (a level without an edge: a count of 0 in a segment of room 1)
-        src.total_known = m;
-        if (scored) {
-            src.format_known = true;
-            src.packed = adjacency_packed(ctx, X, p, t);
-            src.base = t;
-            src.adj_bound = (symmetric ? 2 : 1) * m;
-        }
+        const bool packed = scored && adjacency_packed(ctx, X, p, t);
+        const EdgeSource src = one_segment_source(dealt, &state->prefix[l], m, symmetric, scored ? &packed : nullptr, t);
         ctx->phases = hmk_greedy_phases{};
         HIPCHK(ctx, hipEventRecord(ctx->ev_t0, Q));
         HIPCHK(ctx, hipEventRecord(ctx->ev_edges, Q));
@@ -169,15 +132,12 @@ int greedy_sweep(hmk_ctx *ctx, int X, int p, int thr, int thr_hi, int max_cluste
     st = need_device(ctx);
     if (st) return st;
     hmk_greedy_sweep_stats S{};
-    unsigned long long counts[HMK_EDGE_SHARDS];
-    double ms = 0;
-    st = neighbors_internal(ctx, X, p, thr, 0, 1, sizing::edge_capacity_guess(ctx->symmetric, n, 1, ctx->sw.edge_guess, ctx->edges.cap), counts, &ms);
+    PassRuns P;
+    st = pass_edge_runs(ctx, X, p, thr, ctx->symmetric, &P);
     if (st) return st;
-    S.kernel_ms = ms;
-    S.pairs_scored = ctx->plan.stats.pairs_scored;
-    SweepEdges E;
-    set_runs(E, ctx->edges.d, ctx->edges.seg_cap(), HMK_EDGE_SHARDS, counts);
-    st = sweep_on_device(ctx, E, total_of(counts), ctx->symmetric, true, X, p, thr, thr_hi, max_clusters, o, S);
+    S.kernel_ms = P.kernel_ms;
+    S.pairs_scored = P.pairs_scored;
+    st = sweep_on_device(ctx, P.E, P.total, ctx->symmetric, true, X, p, thr, thr_hi, max_clusters, o, S);
     if (st == HMK_OK && o.stats) *o.stats = S;
     return st;
 }
@@ -189,8 +149,8 @@ int greedy_sweep_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n_ed
     refresh_switches(ctx);
     int st = check_sweep(ctx, thr, thr_hi, o);
     if (st) return st;
-    if (n_edges && !d_edges) return fail(ctx, HMK_ERR_BAD_ARG, "null edge buffer");
-    if (n_edges > ((uint64_t)1 << 41)) return fail(ctx, HMK_ERR_BAD_ARG, "more than 2^41 edges");   // (chunks are counted in 32 bits)
+    st = check_edges_dev(ctx, d_edges, n_edges);
+    if (st) return st;
     const uint32_t nl = (uint32_t)(thr_hi - thr) + 1;
     if (ctx->n == 0) return empty_set(nl, o);
     st = need_device(ctx);
@@ -198,10 +158,8 @@ int greedy_sweep_from_edges_dev(hmk_ctx *ctx, const void *d_edges, uint64_t n_ed
     // the caller's block may have been written on any stream of its own: wait for the device
     HIPCHK(ctx, hipDeviceSynchronize());
     hmk_greedy_sweep_stats S{};
-    SweepEdges E;
     const unsigned long long cnt = n_edges;
-    set_runs(E, (const uint64_t *)d_edges, 0, 1, &cnt);
-    st = sweep_on_device(ctx, E, n_edges, symmetric, false, 0, 0, thr, thr_hi, max_clusters, o, S);
+    st = sweep_on_device(ctx, edge_runs((const uint64_t *)d_edges, 0, 1, &cnt), n_edges, symmetric, false, 0, 0, thr, thr_hi, max_clusters, o, S);
     if (st == HMK_OK && o.stats) *o.stats = S;
     return st;
 }

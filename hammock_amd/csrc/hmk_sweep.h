@@ -10,21 +10,9 @@
 namespace hmk {
 
 constexpr uint32_t SWEEP_MAX_LEVELS = 256;     // threshold_hi - threshold <= 255
-constexpr uint32_t SWEEP_CHUNK = 1024;         // edges a workgroup takes at a time (4 per lane)
 constexpr uint32_t SWEEP_MAX_GRID = 2048;      // workgroups of k_sweep_hist / k_sweep_deal (8 per compute unit of 256)
 constexpr uint32_t SWEEP_FLUSH_CHUNKS = 1u << 21;   // k_sweep_hist adds its LDS counters to the global ones after that many chunks:
                                                     // 2^31 edges at most in one 32-bit counter
-
-// Where a call's packed edges lie: n_runs runs, run s = count[s] entries at base + s * stride -- the HMK_EDGE_SHARDS segments of a
-// neighbour pass (the host has read their counts), or one run (a caller's block).  A chunk is SWEEP_CHUNK consecutive entries of
-// one run; chunk_start[s] = the chunks before run s.  Passed to the kernels by value.
-struct SweepEdges {
-    const uint64_t *base;
-    uint64_t stride;
-    uint32_t n_runs;
-    uint32_t chunk_start[HMK_EDGE_SHARDS + 1];
-    unsigned long long count[HMK_EDGE_SHARDS];
-};
 
 // The per-call device block (SB_SWEEP_STATE), zeroed at the start of a call.  Level l = min(score, threshold_hi) - threshold.
 //   hist     edges per level
@@ -43,11 +31,11 @@ struct SweepState {
 
 // level of an edge = min(score, thr_hi) - thr into st->hist; edges below thr are left out, invalid ones (index >= n, self pair)
 // flagged and left out
-hipError_t launch_sweep_hist(const SweepEdges &E, uint32_t n, int thr, int thr_hi, SweepState *st, hipStream_t s);
+hipError_t launch_sweep_hist(const EdgeRuns &E, uint32_t n, int thr, int thr_hi, SweepState *st, hipStream_t s);
 // start, cursor and prefix from hist (one workgroup)
 hipError_t launch_sweep_scan(uint32_t n_levels, SweepState *st, hipStream_t s);
 // every counted edge, all 8 bytes of it, into its level's run of `dealt`
-hipError_t launch_sweep_deal(const SweepEdges &E, uint32_t n, int thr, int thr_hi, SweepState *st, uint64_t *dealt, hipStream_t s);
+hipError_t launch_sweep_deal(const EdgeRuns &E, uint32_t n, int thr, int thr_hi, SweepState *st, uint64_t *dealt, hipStream_t s);
 
 }  // namespace hmk
 #endif

@@ -35,7 +35,7 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 }
 
 // the run that holds chunk c (workgroup-uniform)
-__device__ __forceinline__ uint32_t cc_run_of(const CcEdges &E, uint32_t c) {
+__device__ __forceinline__ uint32_t cc_run_of(const EdgeRuns &E, uint32_t c) {
     uint32_t lo = 0, hi = E.n_runs;   // chunk_start[lo] <= c < chunk_start[hi]
     while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;
@@ -48,9 +48,9 @@ __device__ __forceinline__ uint32_t cc_run_of(const CcEdges &E, uint32_t c) {
 struct CcEdge { uint32_t x, m; int level; };   // level < 0: not an edge of this call
 
 // entry j of the lane in chunk c: tested before any array is touched with its indices (bad: where an invalid one is flagged, or null)
-__device__ __forceinline__ CcEdge cc_edge(const CcEdges &E, uint32_t run, uint32_t c, int j, uint32_t n, int thr, int thr_hi, uint32_t *bad) {
+__device__ __forceinline__ CcEdge cc_edge(const EdgeRuns &E, uint32_t run, uint32_t c, int j, uint32_t n, int thr, int thr_hi, uint32_t *bad) {
     CcEdge e{0, 0, -1};
-    const unsigned long long k = (unsigned long long)(c - E.chunk_start[run]) * CC_CHUNK + (unsigned)j * 256u + threadIdx.x;
+    const unsigned long long k = (unsigned long long)(c - E.chunk_start[run]) * EDGE_RUN_CHUNK + (unsigned)j * 256u + threadIdx.x;
     if (k >= E.count[run]) return e;
     const uint64_t w = E.base[(unsigned long long)run * E.stride + k];
     e.x = HMK_EDGE_X(w);
@@ -73,12 +73,12 @@ __global__ void __launch_bounds__(256) k_cc_init(uint32_t *__restrict__ parent, 
     }
 }
 
-__global__ void __launch_bounds__(256) k_cc_hist(const CcEdges E, uint32_t n, int thr, int thr_hi, CcState *__restrict__ st) {
+__global__ void __launch_bounds__(256) k_cc_hist(const EdgeRuns E, uint32_t n, int thr, int thr_hi, CcState *__restrict__ st) {
     __shared__ uint32_t cnt[CC_MAX_LEVELS];
     cnt[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t n_chunks = E.chunk_start[E.n_runs];
-    uint32_t in_lds = 0;   // chunks counted since the last flush (workgroup-uniform): CC_CHUNK each, far from 2^32
+    uint32_t in_lds = 0;   // chunks counted since the last flush (workgroup-uniform): EDGE_RUN_CHUNK each, far from 2^32
     for (uint32_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const uint32_t run = cc_run_of(E, c);
 #pragma unroll
@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(256) k_cc_scan(uint32_t n_levels, CcState *__r
     if (l == 0) st->start[n_levels] = total;
 }
 
-__global__ void __launch_bounds__(256) k_cc_partition(const CcEdges E, uint32_t n, int thr, int thr_hi, CcState *st,
+__global__ void __launch_bounds__(256) k_cc_partition(const EdgeRuns E, uint32_t n, int thr, int thr_hi, CcState *st,
                                                       uint64_t *__restrict__ runs) {
     __shared__ uint32_t cnt[CC_MAX_LEVELS];
     __shared__ unsigned long long base[CC_MAX_LEVELS];
@@ -152,7 +152,7 @@ __global__ void __launch_bounds__(256) k_cc_union(const uint64_t *__restrict__ r
     if ((threadIdx.x & 63) == 0 && hooks) atomicAdd(&st->levels[level].n_components, hooks);
 }
 
-__global__ void __launch_bounds__(256) k_cc_union_edges(const CcEdges E, uint32_t n, int thr, uint32_t *parent, CcState *__restrict__ st) {
+__global__ void __launch_bounds__(256) k_cc_union_edges(const EdgeRuns E, uint32_t n, int thr, uint32_t *parent, CcState *__restrict__ st) {
     const uint32_t n_chunks = E.chunk_start[E.n_runs];
     uint32_t hooks = 0, edges = 0;
     for (uint32_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
@@ -219,7 +219,7 @@ __global__ void __launch_bounds__(256) k_cc_sizes(uint32_t *__restrict__ size, u
 // -----------------------------------------------------------------------------
 namespace {
 uint32_t vertex_grid(const char *kernel, uint32_t n) { return capped_grid(kernel, std::min<uint32_t>((n + 255) / 256, 2048)); }
-uint32_t chunk_grid(const char *kernel, const CcEdges &E) { return capped_grid(kernel, std::min<uint32_t>(E.chunk_start[E.n_runs], 4096)); }
+uint32_t chunk_grid(const char *kernel, const EdgeRuns &E) { return capped_grid(kernel, std::min<uint32_t>(E.chunk_start[E.n_runs], 4096)); }
 }  // namespace
 
 hipError_t launch_cc_init(uint32_t *parent, uint32_t *size, uint32_t n, hipStream_t s) {
@@ -228,7 +228,7 @@ hipError_t launch_cc_init(uint32_t *parent, uint32_t *size, uint32_t n, hipStrea
     return hipGetLastError();
 }
 
-hipError_t launch_cc_hist(const CcEdges &E, uint32_t n, int thr, int thr_hi, CcState *st, hipStream_t s) {
+hipError_t launch_cc_hist(const EdgeRuns &E, uint32_t n, int thr, int thr_hi, CcState *st, hipStream_t s) {
     if (E.chunk_start[E.n_runs] == 0) return hipSuccess;
     hipLaunchKernelGGL(k_cc_hist, dim3(chunk_grid("k_cc_hist", E)), dim3(256), 0, s, E, n, thr, thr_hi, st);
     return hipGetLastError();
@@ -239,7 +239,7 @@ hipError_t launch_cc_scan(uint32_t n_levels, CcState *st, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_cc_partition(const CcEdges &E, uint32_t n, int thr, int thr_hi, CcState *st, uint64_t *runs, hipStream_t s) {
+hipError_t launch_cc_partition(const EdgeRuns &E, uint32_t n, int thr, int thr_hi, CcState *st, uint64_t *runs, hipStream_t s) {
     if (E.chunk_start[E.n_runs] == 0) return hipSuccess;
     hipLaunchKernelGGL(k_cc_partition, dim3(chunk_grid("k_cc_partition", E)), dim3(256), 0, s, E, n, thr, thr_hi, st, runs);
     return hipGetLastError();
@@ -252,7 +252,7 @@ hipError_t launch_cc_union(const uint64_t *runs, unsigned long long total_edges,
     return hipGetLastError();
 }
 
-hipError_t launch_cc_union_edges(const CcEdges &E, uint32_t n, int thr, uint32_t *parent, CcState *st, hipStream_t s) {
+hipError_t launch_cc_union_edges(const EdgeRuns &E, uint32_t n, int thr, uint32_t *parent, CcState *st, hipStream_t s) {
     if (E.chunk_start[E.n_runs] == 0) return hipSuccess;
     hipLaunchKernelGGL(k_cc_union_edges, dim3(chunk_grid("k_cc_union_edges", E)), dim3(256), 0, s, E, n, thr, parent, st);
     return hipGetLastError();

@@ -41,7 +41,7 @@ __device__ __forceinline__ uint32_t den_wave_max(uint32_t v) {
 }
 
 // the run that holds chunk c (workgroup-uniform)
-__device__ __forceinline__ uint32_t den_run_of(const SweepEdges &E, uint32_t c) {
+__device__ __forceinline__ uint32_t den_run_of(const EdgeRuns &E, uint32_t c) {
     uint32_t lo = 0, hi = E.n_runs;   // chunk_start[lo] <= c < chunk_start[hi]
     while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;

@@ -25,7 +25,7 @@ namespace hmk {
 namespace {
 
 // the run that holds chunk c (workgroup-uniform)
-__device__ __forceinline__ uint32_t orders_run_of(const SweepEdges &E, uint32_t c) {
+__device__ __forceinline__ uint32_t orders_run_of(const EdgeRuns &E, uint32_t c) {
     uint32_t lo = 0, hi = E.n_runs;   // chunk_start[lo] <= c < chunk_start[hi]
     while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;
@@ -36,8 +36,8 @@ __device__ __forceinline__ uint32_t orders_run_of(const SweepEdges &E, uint32_t 
 }
 
 // entry j of the lane in chunk c: its place k in the run (false: past the run's end) and the edge as stored
-__device__ __forceinline__ bool orders_edge(const SweepEdges &E, uint32_t run, uint32_t c, int j, unsigned long long &k, uint64_t &w) {
-    k = (unsigned long long)(c - E.chunk_start[run]) * SWEEP_CHUNK + (unsigned)j * 256u + threadIdx.x;
+__device__ __forceinline__ bool orders_edge(const EdgeRuns &E, uint32_t run, uint32_t c, int j, unsigned long long &k, uint64_t &w) {
+    k = (unsigned long long)(c - E.chunk_start[run]) * EDGE_RUN_CHUNK + (unsigned)j * 256u + threadIdx.x;
     if (k >= E.count[run]) return false;
     w = E.base[(unsigned long long)run * E.stride + k];
     return true;
@@ -45,7 +45,7 @@ __device__ __forceinline__ bool orders_edge(const SweepEdges &E, uint32_t run, u
 
 }  // namespace
 
-__global__ void __launch_bounds__(256) k_orders_relabel(const SweepEdges E, const OrderRuns R, uint32_t n, const uint32_t *__restrict__ pos,
+__global__ void __launch_bounds__(256) k_orders_relabel(const EdgeRuns E, const OrderRuns R, uint32_t n, const uint32_t *__restrict__ pos,
                                                         uint64_t *__restrict__ out, OrdersState *__restrict__ st) {
     const uint32_t n_chunks = E.chunk_start[E.n_runs];
     for (uint32_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
@@ -67,7 +67,7 @@ __global__ void __launch_bounds__(256) k_orders_relabel(const SweepEdges E, cons
     }
 }
 
-__global__ void __launch_bounds__(256) k_orders_support(const SweepEdges E, uint32_t n, const int32_t *__restrict__ ids, uint32_t nv,
+__global__ void __launch_bounds__(256) k_orders_support(const EdgeRuns E, uint32_t n, const int32_t *__restrict__ ids, uint32_t nv,
                                                         uint64_t *__restrict__ out, unsigned long long cap, uint32_t *__restrict__ ever,
                                                         uint32_t *__restrict__ always, OrdersState *__restrict__ st) {
     __shared__ uint32_t tog[ORDERS_MAX], first[ORDERS_MAX];
@@ -143,17 +143,17 @@ __global__ void __launch_bounds__(256) k_orders_support(const SweepEdges E, uint
 // launchers
 // -----------------------------------------------------------------------------
 namespace {
-uint32_t orders_grid(const char *kernel, const SweepEdges &E) { return capped_grid(kernel, std::min<uint32_t>(E.chunk_start[E.n_runs], ORDERS_MAX_GRID)); }
+uint32_t orders_grid(const char *kernel, const EdgeRuns &E) { return capped_grid(kernel, std::min<uint32_t>(E.chunk_start[E.n_runs], ORDERS_MAX_GRID)); }
 }  // namespace
 
-hipError_t launch_orders_relabel(const SweepEdges &E, const OrderRuns &R, uint32_t n, const uint32_t *pos, uint64_t *out, OrdersState *st,
+hipError_t launch_orders_relabel(const EdgeRuns &E, const OrderRuns &R, uint32_t n, const uint32_t *pos, uint64_t *out, OrdersState *st,
                                  hipStream_t s) {
     if (E.chunk_start[E.n_runs] == 0) return hipSuccess;
     hipLaunchKernelGGL(k_orders_relabel, dim3(orders_grid("k_orders_relabel", E)), dim3(256), 0, s, E, R, n, pos, out, st);
     return hipGetLastError();
 }
 
-hipError_t launch_orders_support(const SweepEdges &E, uint32_t n, const int32_t *ids, uint32_t n_valid, uint64_t *out, unsigned long long cap,
+hipError_t launch_orders_support(const EdgeRuns &E, uint32_t n, const int32_t *ids, uint32_t n_valid, uint64_t *out, unsigned long long cap,
                                  uint32_t *ever, uint32_t *always, OrdersState *st, hipStream_t s) {
     if (E.chunk_start[E.n_runs] == 0 || n_valid == 0) return hipSuccess;
     hipLaunchKernelGGL(k_orders_support, dim3(orders_grid("k_orders_support", E)), dim3(256), 0, s, E, n, ids, n_valid, out, cap, ever, always, st);

@@ -48,7 +48,7 @@ __device__ __forceinline__ uint32_t rep_wave_sum(uint32_t v) {
 template <class T> __device__ __forceinline__ T rep_look(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 
 // the run that holds chunk c (workgroup-uniform)
-__device__ __forceinline__ uint32_t rep_run_of(const SweepEdges &E, uint32_t c) {
+__device__ __forceinline__ uint32_t rep_run_of(const EdgeRuns &E, uint32_t c) {
     uint32_t lo = 0, hi = E.n_runs;   // chunk_start[lo] <= c < chunk_start[hi]
     while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;
@@ -59,7 +59,7 @@ __device__ __forceinline__ uint32_t rep_run_of(const SweepEdges &E, uint32_t c) 
 }
 
 // entry j of the lane in chunk c: true = an edge of this level, x != m both below n, score >= thr.  An invalid one raises *bad, if given.
-__device__ __forceinline__ bool rep_edge(const SweepEdges &E, uint32_t run, uint32_t c, int j, uint32_t n, int thr, uint32_t *bad, uint32_t &x,
+__device__ __forceinline__ bool rep_edge(const EdgeRuns &E, uint32_t run, uint32_t c, int j, uint32_t n, int thr, uint32_t *bad, uint32_t &x,
                                          uint32_t &m, int &score) {
     const unsigned long long k = (unsigned long long)(c - E.chunk_start[run]) * REP_CHUNK + (unsigned)j * 256u + threadIdx.x;
     if (k >= E.count[run]) return false;
@@ -126,7 +126,7 @@ __global__ void __launch_bounds__(256) k_rep_init(const RepVertex v, uint32_t n)
     }
 }
 
-__global__ void __launch_bounds__(256) k_rep_mark_first(uint32_t round, const SweepEdges E, uint32_t n, int thr, const RepVertex v, RepState *st,
+__global__ void __launch_bounds__(256) k_rep_mark_first(uint32_t round, const EdgeRuns E, uint32_t n, int thr, const RepVertex v, RepState *st,
                                                         uint64_t *__restrict__ live0, uint64_t cap) {
     __shared__ uint32_t wave_tot[4];
     __shared__ unsigned long long chunk_base;
@@ -218,7 +218,7 @@ __global__ void __launch_bounds__(256) k_rep_decide(uint32_t round, uint32_t n, 
     }
 }
 
-__global__ void __launch_bounds__(256) k_rep_assign(const SweepEdges E, uint32_t n, int thr, const RepVertex v) {
+__global__ void __launch_bounds__(256) k_rep_assign(const EdgeRuns E, uint32_t n, int thr, const RepVertex v) {
     const uint32_t n_chunks = E.chunk_start[E.n_runs];
     for (uint32_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const uint32_t run = rep_run_of(E, c);
@@ -268,7 +268,7 @@ __global__ void __launch_bounds__(256) k_rep_finish(uint32_t n, const RepVertex 
 // -----------------------------------------------------------------------------
 namespace {
 uint32_t vertex_grid(const char *kernel, uint32_t n) { return capped_grid(kernel, std::min<uint32_t>((n + 255) / 256, REP_MAX_GRID)); }
-uint32_t chunk_grid(const char *kernel, const SweepEdges &E) { return capped_grid(kernel, std::min<uint32_t>(E.chunk_start[E.n_runs], REP_MAX_GRID)); }
+uint32_t chunk_grid(const char *kernel, const EdgeRuns &E) { return capped_grid(kernel, std::min<uint32_t>(E.chunk_start[E.n_runs], REP_MAX_GRID)); }
 }  // namespace
 
 hipError_t launch_rep_init(const RepVertex &v, uint32_t n, hipStream_t s) {
@@ -277,7 +277,7 @@ hipError_t launch_rep_init(const RepVertex &v, uint32_t n, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_rep_mark_first(uint32_t round, const SweepEdges &E, uint32_t n, int thr, const RepVertex &v, RepState *st, uint64_t *live0,
+hipError_t launch_rep_mark_first(uint32_t round, const EdgeRuns &E, uint32_t n, int thr, const RepVertex &v, RepState *st, uint64_t *live0,
                                  uint64_t cap, hipStream_t s) {
     if (E.chunk_start[E.n_runs] == 0) return hipSuccess;
     hipLaunchKernelGGL(k_rep_mark_first, dim3(chunk_grid("k_rep_mark_first", E)), dim3(256), 0, s, round, E, n, thr, v, st, live0, cap);
@@ -299,7 +299,7 @@ hipError_t launch_rep_decide(uint32_t round, uint32_t n, const RepVertex &v, Rep
     return hipGetLastError();
 }
 
-hipError_t launch_rep_assign(const SweepEdges &E, uint32_t n, int thr, const RepVertex &v, hipStream_t s) {
+hipError_t launch_rep_assign(const EdgeRuns &E, uint32_t n, int thr, const RepVertex &v, hipStream_t s) {
     if (E.chunk_start[E.n_runs] == 0) return hipSuccess;
     hipLaunchKernelGGL(k_rep_assign, dim3(chunk_grid("k_rep_assign", E)), dim3(256), 0, s, E, n, thr, v);
     return hipGetLastError();

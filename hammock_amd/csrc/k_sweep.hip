@@ -20,7 +20,7 @@ namespace hmk {
 namespace {
 
 // the run that holds chunk c (workgroup-uniform)
-__device__ __forceinline__ uint32_t sweep_run_of(const SweepEdges &E, uint32_t c) {
+__device__ __forceinline__ uint32_t sweep_run_of(const EdgeRuns &E, uint32_t c) {
     uint32_t lo = 0, hi = E.n_runs;   // chunk_start[lo] <= c < chunk_start[hi]
     while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;
@@ -32,9 +32,9 @@ __device__ __forceinline__ uint32_t sweep_run_of(const SweepEdges &E, uint32_t c
 
 // entry j of the lane in chunk c -> its level, or -1: past the run's end, invalid (then *bad is raised, if given) or below thr.
 // w = the edge as stored.
-__device__ __forceinline__ int sweep_level(const SweepEdges &E, uint32_t run, uint32_t c, int j, uint32_t n, int thr, int thr_hi,
+__device__ __forceinline__ int sweep_level(const EdgeRuns &E, uint32_t run, uint32_t c, int j, uint32_t n, int thr, int thr_hi,
                                            unsigned long long *bad, uint64_t &w) {
-    const unsigned long long k = (unsigned long long)(c - E.chunk_start[run]) * SWEEP_CHUNK + (unsigned)j * 256u + threadIdx.x;
+    const unsigned long long k = (unsigned long long)(c - E.chunk_start[run]) * EDGE_RUN_CHUNK + (unsigned)j * 256u + threadIdx.x;
     w = 0;
     if (k >= E.count[run]) return -1;
     w = E.base[(unsigned long long)run * E.stride + k];
@@ -49,7 +49,7 @@ __device__ __forceinline__ int sweep_level(const SweepEdges &E, uint32_t run, ui
 
 }  // namespace
 
-__global__ void __launch_bounds__(256) k_sweep_hist(const SweepEdges E, uint32_t n, int thr, int thr_hi, SweepState *__restrict__ st) {
+__global__ void __launch_bounds__(256) k_sweep_hist(const EdgeRuns E, uint32_t n, int thr, int thr_hi, SweepState *__restrict__ st) {
     __shared__ uint32_t cnt[SWEEP_MAX_LEVELS];
     cnt[threadIdx.x] = 0;
     __syncthreads();
@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(256) k_sweep_scan(uint32_t n_levels, SweepStat
     st->prefix[l] = above + h[l];
 }
 
-__global__ void __launch_bounds__(256) k_sweep_deal(const SweepEdges E, uint32_t n, int thr, int thr_hi, SweepState *st,
+__global__ void __launch_bounds__(256) k_sweep_deal(const EdgeRuns E, uint32_t n, int thr, int thr_hi, SweepState *st,
                                                     uint64_t *__restrict__ dealt) {
     __shared__ uint32_t cnt[SWEEP_MAX_LEVELS];
     __shared__ unsigned long long base[SWEEP_MAX_LEVELS];
@@ -121,10 +121,10 @@ __global__ void __launch_bounds__(256) k_sweep_deal(const SweepEdges E, uint32_t
 // launchers
 // -----------------------------------------------------------------------------
 namespace {
-uint32_t sweep_grid(const char *kernel, const SweepEdges &E) { return capped_grid(kernel, std::min<uint32_t>(E.chunk_start[E.n_runs], SWEEP_MAX_GRID)); }
+uint32_t sweep_grid(const char *kernel, const EdgeRuns &E) { return capped_grid(kernel, std::min<uint32_t>(E.chunk_start[E.n_runs], SWEEP_MAX_GRID)); }
 }  // namespace
 
-hipError_t launch_sweep_hist(const SweepEdges &E, uint32_t n, int thr, int thr_hi, SweepState *st, hipStream_t s) {
+hipError_t launch_sweep_hist(const EdgeRuns &E, uint32_t n, int thr, int thr_hi, SweepState *st, hipStream_t s) {
     if (E.chunk_start[E.n_runs] == 0) return hipSuccess;
     hipLaunchKernelGGL(k_sweep_hist, dim3(sweep_grid("k_sweep_hist", E)), dim3(256), 0, s, E, n, thr, thr_hi, st);
     return hipGetLastError();
@@ -135,7 +135,7 @@ hipError_t launch_sweep_scan(uint32_t n_levels, SweepState *st, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_sweep_deal(const SweepEdges &E, uint32_t n, int thr, int thr_hi, SweepState *st, uint64_t *dealt, hipStream_t s) {
+hipError_t launch_sweep_deal(const EdgeRuns &E, uint32_t n, int thr, int thr_hi, SweepState *st, uint64_t *dealt, hipStream_t s) {
     if (E.chunk_start[E.n_runs] == 0) return hipSuccess;
     hipLaunchKernelGGL(k_sweep_deal, dim3(sweep_grid("k_sweep_deal", E)), dim3(256), 0, s, E, n, thr, thr_hi, st, dealt);
     return hipGetLastError();

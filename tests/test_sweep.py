@@ -475,6 +475,10 @@ def synthetic(name):
         return 10, hammock_amd.pack_edges(np.full(1000, 3), np.full(1000, 7), np.full(1000, 22)), 20, 24
     if name == "none":
         return 50, np.zeros(0, dtype=np.uint64), 20, 24
+    if name == "single_level":   # threshold_hi = threshold: one level, the scores below it left out, those above it clamped into it
+        a, b = np.triu_indices(50, 1)
+        pick = rng.choice(a.size, 600, replace=False)
+        return 50, hammock_amd.pack_edges(a[pick], b[pick], 20 + np.arange(600) % 5), 22, 22
     n = 3000
     x, m = np.triu_indices(n, 1)
     if name == "one_level":   # all scores in one level
@@ -504,7 +508,7 @@ def synthetic_expect(name):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("cap", [0, 1, 3])
-@pytest.mark.parametrize("name", ["repeated", "none", "one_level", "clamped", "long_level"])
+@pytest.mark.parametrize("name", ["repeated", "none", "single_level", "one_level", "clamped", "long_level"])
 def test_from_edges_dev_on_synthetic_edge_lists_at_every_grid(gpu, monkeypatch, capfd, name, cap):
     n, edges, thr, hi = synthetic(name)
     ctx = hammock_amd.Context(matrix(), device=0)
@@ -528,6 +532,8 @@ def test_from_edges_dev_on_synthetic_edge_lists_at_every_grid(gpu, monkeypatch, 
     assert {k: v for k, v in lines.items() if k.startswith("k_sweep_")} == cut
     if name == "long_level":
         assert -(-edges.size // 1024) > 2048 and got[0]["n_edges"][0] == edges.size
+    if name == "single_level":
+        assert hi == thr and s.n_levels == 1 and got[0]["n_edges"][0] == 360
     if name == "clamped":
         assert hi - thr == 255 and got[0]["n_edges"][0] < edges.size and got[0]["n_edges"][255] > edges.size // 259
 
