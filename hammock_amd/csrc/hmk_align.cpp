@@ -2,7 +2,7 @@
 // per slot the member with the largest sum of ShiftedScorer scores against the others (the centre), per member scoreWithShift against
 // that centre (ShiftedScorer.java:48-95), from whose shifts the aligned rows follow.  Not Clustal Omega's alignment
 // (ClustalRunner.java:34-66): no gap ever stands inside a peptide.
-//   tables   hmk_linkage.cpp's (build_link_tables), O(members + clusters), one upload;
+//   tables   hmk_slots.cpp's (build_link_tables), O(members + clusters), one upload;
 //   kernels  k_align.hip on the clustering stream: accumulators cleared, the members' sums (small slots flat, large slots tiled), the
 //            slots' centres, every member against its centre; the centres stay on the device between the last two;
 //   results  one copy of the per-slot block and one of the per-member block; keys decoded, columns and widths formed on the host,
@@ -10,7 +10,6 @@
 // Nothing proportional to the number of pairs exists anywhere.
 #include "hmk_ctx.h"
 #include "hmk_align.h"
-#include "hmk_linkage.h"
 
 namespace hmk { namespace impl {
 
@@ -23,20 +22,15 @@ int cluster_align(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member
     std::lock_guard<std::mutex> lock(ctx->mu);
     refresh_switches(ctx);
     std::vector<uint32_t> members;
-    std::vector<int64_t> size;
-    {
-        std::vector<int32_t> ids(n_clusters);
-        for (uint32_t c = 0; c < n_clusters; c++) ids[c] = (int32_t)c + 1;
-        const int st = check_clusters(ctx, "align", 0, 0, r0, r1, member_cluster, ids.data(), n_clusters, members, size);
-        if (st) return st;
-    }
+    int st = check_slots(ctx, "align", r0, r1, member_cluster, n_clusters, members);
+    if (st) return st;
     const uint32_t nm = r1 - r0;
     if (n_clusters && (!center || !center_sum || !width)) return fail(ctx, HMK_ERR_BAD_ARG, "null output (center, center_sum, width)");
     if (nm && (!center_score || !shift || !column)) return fail(ctx, HMK_ERR_BAD_ARG, "null output (center_score, shift, column)");
     if (!ctx->symmetric)
         return fail(ctx, HMK_ERR_BAD_ARG, "the alignment of a cluster needs a symmetric scoring matrix: a member's sum of scores must not "
                                           "depend on which sequence of a pair comes first");
-    int st = need_device(ctx);
+    st = need_device(ctx);
     if (st) return st;
     hmk_align_stats S{};
     if (nm == 0) {   // (check_clusters: then there is no slot either) nothing is written
@@ -60,11 +54,10 @@ int cluster_align(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member
             S.max_width = std::max<uint32_t>(S.max_width, width[c]);
         }
     }
-    for (uint32_t c = 0; c < n_clusters; c++)
-        if (members[c] >= 2) {
-            S.n_multi++;
-            S.pairs_scored += (uint64_t)members[c] * (members[c] - 1) / 2 + (members[c] - 1);
-        }
+    const SlotCounts counts = count_slots(members);
+    S.n_multi = counts.n_multi;
+    S.pairs_scored = counts.pairs;
+    for (const uint32_t s : members) S.pairs_scored += s >= 2 ? s - 1 : 0;   // (every member of such a slot but its centre, against the centre)
     if (S.n_multi == 0) {
         if (stats) *stats = S;
         return HMK_OK;
@@ -72,8 +65,6 @@ int cluster_align(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member
 
     LinkTables T;
     build_link_tables(r0, nm, member_cluster, n_clusters, members, T);
-    const std::vector<uint32_t> &h = T.h;
-    const size_t words = h.size();
 
     st = ensure_res32(ctx);
     if (st) return st;
@@ -82,11 +73,12 @@ int cluster_align(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member
     // per slot: key uint64[ncl] | min_shift int32[ncl] | max_end int32[ncl]; per member: sum int64[nm] | score int32[nm] | shift int32[nm]
     const size_t slot_bytes = (size_t)n_clusters * 16, memb_bytes = (size_t)nm * 16;
     const size_t memb_from = member_sum ? 0 : (size_t)nm * 8;   // (sums not wanted: they stay on the device)
-    HIPCHK(ctx, ensure_buf(ctx, SB_LINK_TAB, words * 4));
+    LinkView V;
+    st = reserve_link_tables(ctx, T, &V);
+    if (st) return st;
     HIPCHK(ctx, ensure_buf(ctx, SB_ALIGN_SLOT, slot_bytes));
     HIPCHK(ctx, ensure_buf(ctx, SB_ALIGN_MEMB, memb_bytes));
     HIPCHK(ctx, ctx->h_merge.ensure(slot_bytes + memb_bytes + 64, 0));
-    const uint32_t *d_tab = buf<uint32_t>(ctx, SB_LINK_TAB);
     AlignOut out;
     out.key = buf<uint64_t>(ctx, SB_ALIGN_SLOT);
     out.min_shift = reinterpret_cast<int32_t *>(out.key + n_clusters);
@@ -94,41 +86,28 @@ int cluster_align(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member
     out.sum = buf<long long>(ctx, SB_ALIGN_MEMB);
     out.score = reinterpret_cast<int32_t *>(out.sum + nm);
     out.shift = out.score + nm;
-    AlignSlots slots;
-    slots.tab = d_tab + T.o_tab;
-    slots.fslot = d_tab + T.o_fslot;
-    slots.fmstart = d_tab + T.o_fmstart;
-    slots.bslot = d_tab + T.o_bslot;
-    slots.bmstart = d_tab + T.o_bmstart;
-    slots.nf = T.nf;
-    slots.nb = T.nb;
-    slots.nt = h[T.o_bmstart + T.nb];
+    const AlignSlots slots{V.tab, V.fslot, V.fmstart, V.bslot, V.bmstart, V.nf, V.nb, V.nt};
     const uint8_t *res32 = ctx->d_res32.as<uint8_t>(), *len = ctx->d_len.as<uint8_t>();
     const int32_t *d_M = ctx->d_M.as<int32_t>();
     char *h_slot = (char *)ctx->h_merge.p, *h_memb = h_slot + slot_bytes;
     hipStream_t Q = ctx->gstream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint32_t *>(d_tab), h.data(), words * 4, hipMemcpyHostToDevice, Q);
-    if (e == hipSuccess) e = hipEventRecord(e0, Q);
+    EventPair ev;
+    HIPCHK(ctx, ev.create());
+    hipError_t e = upload_link_tables(ctx, T, Q);
+    if (e == hipSuccess) e = ev.start(Q);
     if (e == hipSuccess) e = launch_align_init(out, n_clusters, nm, Q);
-    if (e == hipSuccess)
-        e = launch_align_sums_flat(res32, len, d_M, slots.tab, slots.fmstart, reinterpret_cast<const unsigned long long *>(d_tab + T.o_fpstart), T.nf,
-                                   T.flat_pairs, r0, X, p, out.sum, Q);
-    if (e == hipSuccess) e = launch_align_sums_tiled(res32, len, d_M, slots.tab, slots.bmstart, d_tab + T.o_btstart, T.nb, T.n_tiles, r0, X, p, out.sum, Q);
+    if (e == hipSuccess) e = launch_align_sums_flat(res32, len, d_M, V, r0, X, p, out.sum, Q);
+    if (e == hipSuccess) e = launch_align_sums_tiled(res32, len, d_M, V, r0, X, p, out.sum, Q);
     if (e == hipSuccess) e = launch_align_center(slots, r0, out.sum, out.key, Q);
     if (e == hipSuccess) e = launch_align_shift(res32, len, d_M, slots, r0, r1, X, p, out, Q);
-    S.launches = 3 + (T.flat_pairs ? 1 : 0) + (T.n_tiles ? 1 : 0);
-    if (e == hipSuccess) e = hipEventRecord(e1, Q);
+    S.launches = 3 + (V.flat_pairs ? 1 : 0) + (V.n_tiles ? 1 : 0);
+    if (e == hipSuccess) e = ev.stop(Q);
     if (e == hipSuccess) e = hipMemcpyAsync(h_slot, out.key, slot_bytes, hipMemcpyDeviceToHost, Q);
     if (e == hipSuccess) e = hipMemcpyAsync(h_memb + memb_from, (const char *)out.sum + memb_from, memb_bytes - memb_from, hipMemcpyDeviceToHost, Q);
     if (e == hipSuccess) e = hipStreamSynchronize(Q);
     float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("cluster align: ") + hipGetErrorString(e));
+    if (e == hipSuccess) e = ev.elapsed(&ms);
+    if (e != hipSuccess) return fail_hip(ctx, "cluster align", e);
     S.kernel_ms = ms;
 
     const uint64_t *h_key = (const uint64_t *)h_slot;

@@ -1,10 +1,9 @@
 // hmk_align.h -- launchers of k_align.hip (centre-star alignment of given clusters around their medoids), used by hmk_align.cpp.
-// The work is decoded from the host tables of the pairs inside given clusters (hmk_linkage.h: LinkTables).
+// The work is decoded from the host tables of the pairs inside given clusters (hmk_slots.h: LinkTables, LinkView).
 #ifndef HMK_ALIGN_H
 #define HMK_ALIGN_H
 
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
+#include "hmk_slots.h"
 
 namespace hmk {
 
@@ -21,14 +20,12 @@ struct AlignOut {
 
 // key = 0, min_shift = INT32_MAX, max_end = INT32_MIN; sum = 0, score = INT32_MAX, shift = 0 (what a centre and a slot of one keep)
 hipError_t launch_align_init(const AlignOut &out, uint32_t n_clusters, uint32_t nm, hipStream_t s);
-// the sums of the flat slots' members (tables as launch_linkage_flat takes them)
-hipError_t launch_align_sums_flat(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const uint32_t *tab, const uint32_t *fmstart,
-                                  const unsigned long long *fpstart, uint32_t nf, unsigned long long n_pairs, uint32_t r0, int X, int p,
-                                  long long *sum, hipStream_t s);
-// the sums of the big slots' members (tables as launch_linkage_tiled takes them)
-hipError_t launch_align_sums_tiled(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const uint32_t *tab, const uint32_t *bmstart,
-                                   const uint32_t *btstart, uint32_t nb, uint32_t n_tiles, uint32_t r0, int X, int p, long long *sum,
-                                   hipStream_t s);
+// the sums of the flat slots' members (V: the uploaded tables, as launch_linkage_flat takes them)
+hipError_t launch_align_sums_flat(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const impl::LinkView &V, uint32_t r0, int X,
+                                  int p, long long *sum, hipStream_t s);
+// the sums of the big slots' members (as launch_linkage_tiled takes them)
+hipError_t launch_align_sums_tiled(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const impl::LinkView &V, uint32_t r0, int X,
+                                   int p, long long *sum, hipStream_t s);
 // The tables' slots as both member kernels walk them: place t of tab (nt places: the flat slots' members, then the big slots') lies in
 // flat slot run_of(fmstart, t) or big slot run_of(bmstart, t).
 struct AlignSlots {

@@ -142,22 +142,19 @@ int assign(hmk_ctx *ctx, int scorer, uint32_t q0, uint32_t q1, uint32_t r0, uint
     uint32_t *d_best = buf<uint32_t>(ctx, SB_SEARCH_HITS);
     int32_t *d_score = (int32_t *)(d_best + nk);
     uint32_t *d_nfeas = d_best + 2 * nk;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
+    EventPair ev;
+    HIPCHK(ctx, ev.create());
+    hipError_t e = ev.start(nullptr);
     if (e == hipSuccess)
         e = launch_assign(ctx->edges.d, ctx->edges.seg_cap(), ctx->edges.counts, max_of(counts), total, q0, nq, r0, nm, k, d_cl,
                           d_cl + nm, d_cl + nm + n_clusters, buf<uint32_t>(ctx, SB_SEARCH_CNT), buf<uint32_t>(ctx, SB_SEARCH_START),
                           buf<uint64_t>(ctx, SB_SEARCH_SCAN), buf<uint64_t>(ctx, SB_SEARCH_OUT), std::max<uint64_t>(total, 1), d_best, d_score,
                           d_nfeas, nullptr);
-    if (e == hipSuccess) e = hipEventRecord(e1, nullptr);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    if (e == hipSuccess) e = ev.stop(nullptr);
+    if (e == hipSuccess) e = hipEventSynchronize(ev.b);
     float sel_ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&sel_ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("assignment: ") + hipGetErrorString(e));
+    if (e == hipSuccess) e = ev.elapsed(&sel_ms);
+    if (e != hipSuccess) return fail_hip(ctx, "assignment", e);
     HIPCHK(ctx, hipMemcpy(best_cluster, d_best, nk * 4, hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(best_score, d_score, nk * 4, hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(n_feasible, d_nfeas, (size_t)nq * 4, hipMemcpyDeviceToHost));

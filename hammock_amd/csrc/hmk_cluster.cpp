@@ -431,7 +431,7 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
             const int r = src.before_full ? src.before_full() : HMK_OK;
             if (r != HMK_OK) { hook_fail(r, ctx->err.empty() ? "gathering the peers' edges failed" : ctx->err); return false; }
             const hipError_t e0 = enqueue_full();
-            if (e0 != hipSuccess) { hook_fail(e0 == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("CSR build: ") + hipGetErrorString(e0)); return false; }
+            if (e0 != hipSuccess) { hook_fail(hip_status(e0), std::string("CSR build: ") + hipGetErrorString(e0)); return false; }
         }
         hipError_t e = hipEventSynchronize(ctx->ev_edges);
         if (e == hipSuccess && src.check_overflow) {
@@ -454,7 +454,7 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
             if (e == hipSuccess) e = enqueue_scatter();
         }
         if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_csr);
-        if (e != hipSuccess) { hook_fail(e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("CSR build: ") + hipGetErrorString(e)); return false; }
+        if (e != hipSuccess) { hook_fail(hip_status(e), std::string("CSR build: ") + hipGetErrorString(e)); return false; }
         if (h_range[2] != 0) { hook_fail(HMK_ERR_BAD_ARG, "edge list references a sequence outside [0, n) or a self pair"); return false; }
         const uint64_t want = src.total_known ? (symmetric ? 2 * src.total_known : src.total_known) : h_start[n];
         if (h_start[n] != want) { hook_fail(HMK_ERR_DEVICE, "CSR build: adjacency size mismatch"); return false; }
@@ -480,7 +480,7 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
         if (e == hipSuccess)
             e = launch_csr_scatter(src.band_segs, symmetric, buf<uint64_t>(ctx, SB_BSTART), buf<uint32_t>(ctx, SB_BCURSOR),
                                    buf<void>(ctx, SB_BADJ), packed, base, R1, C, n);
-        if (e != hipSuccess) { hook_fail(e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("band hand-over: ") + hipGetErrorString(e)); return -1; }
+        if (e != hipSuccess) { hook_fail(hip_status(e), std::string("band hand-over: ") + hipGetErrorString(e)); return -1; }
         return (int64_t)entries;
     };
     // ---- the band, prepared for phase 1 (BandPack, hmk_internal.h) ---------------------------------------------------------
@@ -515,7 +515,7 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
                                         (uint32_t *)(db + o_trstart), (uint32_t *)(db + o_tr), BandPack::NEAR_T, buf<uint32_t>(ctx, SB_BFTOP) + (size_t)R1 * FAR_T,
                                         (uint32_t *)(db + o_ntop), C);
             if (e == hipSuccess) e = hipStreamSynchronize(C);
-            if (e != hipSuccess) { hook_fail(e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("band hand-over: ") + hipGetErrorString(e)); return nullptr; }
+            if (e != hipSuccess) { hook_fail(hip_status(e), std::string("band hand-over: ") + hipGetErrorString(e)); return nullptr; }
             const uint64_t n_near = ((const uint32_t *)(hb + o_nstart))[R1];
             uint64_t n_tr = 0;   // what was written of the intersections (their room, tr_start, is an upper bound)
             for (uint32_t u = 0; u < TRN; u++) { const uint32_t c = ((const uint32_t *)(hb + o_trowner))[u]; if (c != ~0u) n_tr += c; }
@@ -627,7 +627,7 @@ int cluster_on_device(hmk_ctx *ctx, const EdgeSource &src, int max_clusters, int
             if (piece_base[d]) for (uint32_t x = a; x <= b; x++) h_start[x] += piece_base[d];
         }
         if (multi) (void)hipSetDevice(ctx->device);
-        if (e != hipSuccess) { hook_fail(e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("adjacency copy: ") + hipGetErrorString(e)); return 0; }
+        if (e != hipSuccess) { hook_fail(hip_status(e), std::string("adjacency copy: ") + hipGetErrorString(e)); return 0; }
         rows_here = r_end;
         t_rows += ms_since(tw);
         return rows_here;

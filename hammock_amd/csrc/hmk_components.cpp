@@ -67,7 +67,7 @@ int components_on_device(hmk_ctx *ctx, const EdgeRuns &E, uint64_t total, int th
     if (e == hipSuccess && !bad && component) e = hipMemcpy(component, parent, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
     float ms = 0;
     if (e == hipSuccess) e = ev.elapsed(&ms);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("components: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail_hip(ctx, "components", e);
     if (bad) return fail(ctx, HMK_ERR_BAD_ARG, "edge list references a sequence outside [0, n) or a self pair");
     // the device counted each level's hooks: components at t = n - the hooks of the levels >= t
     uint32_t hooks = 0;

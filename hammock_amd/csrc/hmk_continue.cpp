@@ -107,7 +107,7 @@ int greedy_continue(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_
     const bool packed = adjacency_packed(ctx, X, p, thr);   // (4-byte entries m << 8 | score - threshold, as hmk_greedy_cluster)
     hipError_t e = piece_enqueue_csr(ctx, ctx->edges.segs(), true, packed, thr, n, q0, q1, false, false, Q);
     if (e == hipSuccess) e = hipStreamSynchronize(Q);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("continuation CSR: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail_hip(ctx, "continuation CSR", e);
     if (((const int *)(ctx->h_counts + HC_RANGE))[2] != 0) return fail(ctx, HMK_ERR_DEVICE, "continuation CSR: an edge names a sequence outside [0, n)");
     const uint64_t entries = ctx->h_counts[HC_TOTAL];
 

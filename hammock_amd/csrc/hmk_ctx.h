@@ -3,7 +3,7 @@
 // buffers and their owners, streams), hmk_sizing.h (the sizing rules, pure functions), hmk_plan.cpp (the neighbour passes' planner),
 // hmk_pass.cpp (launching the passes; the pair and block probes), hmk_cluster.cpp (the single-device clustering calls, CSR pipeline,
 // row hand-over, second-loop driver), hmk_multi.cpp (the same calls on several devices), and one file per further call
-// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp, hmk_separation.cpp, hmk_sweep.cpp, hmk_representatives.cpp, hmk_density.cpp, hmk_profile.cpp, hmk_scan.cpp, hmk_orders.cpp; hmk_levels.cpp: what the threshold-range calls among them share).  Not part of the public ABI.
+// (hmk_search.cpp ... hmk_components.cpp, hmk_align.cpp, hmk_survey.cpp, hmk_separation.cpp, hmk_sweep.cpp, hmk_representatives.cpp, hmk_density.cpp, hmk_profile.cpp, hmk_scan.cpp, hmk_orders.cpp; hmk_levels.cpp: what the threshold-range calls among them share; hmk_slots.cpp: what the calls over given clusters share).  Not part of the public ABI.
 #ifndef HMK_CTX_H
 #define HMK_CTX_H
 #include <hip/hip_runtime_api.h>
@@ -282,13 +282,14 @@ namespace hmk { namespace impl {
 
 extern thread_local std::string g_last_error;
 int fail(hmk_ctx *ctx, int code, const std::string &msg);
+// what a failed HIP call becomes: its status, and fail() with that status and "<what>: <HIP's text>"
+inline int hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE; }
+inline int fail_hip(hmk_ctx *ctx, const std::string &what, hipError_t e) { return fail(ctx, hip_status(e), what + ": " + hipGetErrorString(e)); }
 
-#define HIPCHK(ctx, expr)                                                                       \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return fail(ctx, e_ == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE,          \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                     \
+#define HIPCHK(ctx, expr)                                        \
+    do {                                                         \
+        hipError_t e_ = (expr);                                  \
+        if (e_ != hipSuccess) return fail_hip(ctx, #expr, e_);   \
     } while (0)
 
 // a HIP call whose failure is not this call's business (teardown): the error must not stay behind as the thread's last one
@@ -433,10 +434,6 @@ int build_plan_local_search(hmk_ctx *ctx, PlanLocal &pl, uint32_t q0, uint32_t q
 int build_plan_triangle(hmk_ctx *ctx, Plan &pl, int X, int p, int thr, uint32_t q0, uint32_t q1);
 // the parameter checks of a shifted rectangle (the shift against both ranges, threshold and int16 limits)
 int check_shifted(hmk_ctx *ctx, int X, int p, int thr, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r1);
-// ---- hmk_linkage.cpp
-// the parameter checks of a call that scores the pairs inside slots of the members [r0, r1): check_shifted over the range, and the
-// lowest possible score fits int16, the indices 24 bits
-int check_link_scores(hmk_ctx *ctx, int X, int p, int thr, uint32_t r0, uint32_t r1);
 // ---- hmk_assign.cpp
 // the clusters' argument checks of the assignment and the continuation (`what` names the call in the range message):
 // members[c] = slot c's members, size[c] = its Cluster.size()
@@ -538,19 +535,18 @@ int neighbors_grow(hmk_ctx *ctx, uint64_t want_cap, unsigned long long counts[HM
     if (st) return st;
     uint64_t cap = std::max<uint64_t>(want_cap, (uint64_t)1 << 20);
     cap = (cap + HMK_EDGE_SHARDS - 1) / HMK_EDGE_SHARDS * HMK_EDGE_SHARDS;
-    hipEvent_t e0, e1;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    HIPCHK(ctx, hipEventCreate(&e1));
+    EventPair ev;
+    HIPCHK(ctx, ev.create());
     auto attempt = [&]() -> int {
         int r = ctx->edges.reserve(ctx, cap);
         if (r) return r;
-        HIPCHK(ctx, hipEventRecord(e0, nullptr));
+        HIPCHK(ctx, ev.start(nullptr));
         r = launch(ctx->edges.d, ctx->edges.cap, ctx->edges.counts);
         if (r) return r;
-        HIPCHK(ctx, hipEventRecord(e1, nullptr));
-        HIPCHK(ctx, hipEventSynchronize(e1));
+        HIPCHK(ctx, ev.stop(nullptr));
+        HIPCHK(ctx, hipEventSynchronize(ev.b));
         float ms = 0;
-        HIPCHK(ctx, hipEventElapsedTime(&ms, e0, e1));
+        HIPCHK(ctx, ev.elapsed(&ms));
         if (kernel_ms) *kernel_ms = ms;
         HIPCHK(ctx, hipMemcpy(counts, ctx->edges.counts, HMK_EDGE_SHARDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         if (max_of(counts) <= ctx->edges.seg_cap()) return HMK_OK;
@@ -562,8 +558,6 @@ int neighbors_grow(hmk_ctx *ctx, uint64_t want_cap, unsigned long long counts[HM
     };
     st = ST_RETRY_OVERFLOW;
     for (int k = 0; k < 4 && st == ST_RETRY_OVERFLOW; k++) st = attempt();
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (st == ST_RETRY_OVERFLOW) return fail(ctx, HMK_ERR_DEVICE, "internal edge buffer kept overflowing");
     return st;
 }

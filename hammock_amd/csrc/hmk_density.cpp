@@ -111,7 +111,7 @@ int density_on_device(hmk_ctx *ctx, const EdgeRuns &src, uint64_t total, int thr
     std::vector<unsigned char> block(state_bytes);
     if (e == hipSuccess) e = hipMemcpyAsync(block.data(), dst, state_bytes, hipMemcpyDeviceToHost, Q);
     if (e == hipSuccess) e = hipStreamSynchronize(Q);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("density: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail_hip(ctx, "density", e);
     const DenState *hb = (const DenState *)block.data();
     if (hb->flag) return fail(ctx, HMK_ERR_BAD_ARG, "edge list references a sequence outside [0, n) or a self pair");
     std::vector<hmk_density_level> lv(nl);

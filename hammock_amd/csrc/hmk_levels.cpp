@@ -56,7 +56,7 @@ int deal_by_level(hmk_ctx *ctx, const char *what, hipStream_t Q, const EdgeRuns 
     if (e == hipSuccess && timed) e = timed->stop(Q);
     if (e == hipSuccess) e = hipMemcpyAsync(back, st->prefix, sizeof(LevelPrefix), hipMemcpyDeviceToHost, Q);
     if (e == hipSuccess) e = hipStreamSynchronize(Q);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+    if (e != hipSuccess) return fail_hip(ctx, what, e);
     if (back->flag) return fail(ctx, HMK_ERR_BAD_ARG, "edge list references a sequence outside [0, n) or a self pair");
     if (back->prefix[0] > total) return fail(ctx, HMK_ERR_DEVICE, std::string(what) + ": more edges dealt than given");
     *dealt = runs;

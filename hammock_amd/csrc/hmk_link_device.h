@@ -1,5 +1,5 @@
 // hmk_link_device.h -- device code shared by the kernels that walk the pairs INSIDE given clusters: k_linkage.hip (minimum and counts
-// per slot and member) and k_split.hip (every score, as dense triangles).  Both decode the same host tables (hmk_linkage.h:
+// per slot and member) and k_split.hip (every score, as dense triangles).  Both decode the same host tables (hmk_slots.h:
 // LinkTables) and score a pair the same way: the literal scorer with seq1 = the pair's larger index.
 #ifndef HMK_LINK_DEVICE_H
 #define HMK_LINK_DEVICE_H

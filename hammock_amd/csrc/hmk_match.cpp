@@ -86,23 +86,20 @@ int match(hmk_ctx *ctx, int scorer, uint32_t q0, uint32_t q1, const uint32_t *qu
     int32_t *d_score = (int32_t *)(d_best + nk);
     uint32_t *d_nfeas = d_best + 2 * nk;
     uint32_t *d_scr2 = buf<uint32_t>(ctx, SB_MATCH_SCR);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
+    EventPair ev;
+    HIPCHK(ctx, ev.create());
+    hipError_t e = ev.start(nullptr);
     if (e == hipSuccess)
         e = launch_match(ctx->edges.d, ctx->edges.seg_cap(), ctx->edges.counts, max_of(counts), total, q0, nq, r0, nm, nb, k, d_cl, d_cl + nm,
                          d_cl + nm + n_clusters, d_cl + nm + 2 * (size_t)n_clusters, d_cl + nm + 2 * (size_t)n_clusters + nq,
                          buf<uint32_t>(ctx, SB_SEARCH_CNT), buf<uint32_t>(ctx, SB_SEARCH_START), buf<uint64_t>(ctx, SB_SEARCH_SCAN),
                          buf<uint64_t>(ctx, SB_SEARCH_OUT), buf<uint64_t>(ctx, SB_MATCH_REC), cap, d_scr2, d_scr2 + nq + 3 * (size_t)nb + 1,
                          d_best, d_score, d_nfeas, nullptr);
-    if (e == hipSuccess) e = hipEventRecord(e1, nullptr);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    if (e == hipSuccess) e = ev.stop(nullptr);
+    if (e == hipSuccess) e = hipEventSynchronize(ev.b);
     float sel_ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&sel_ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("match: ") + hipGetErrorString(e));
+    if (e == hipSuccess) e = ev.elapsed(&sel_ms);
+    if (e != hipSuccess) return fail_hip(ctx, "match", e);
     HIPCHK(ctx, hipMemcpy(best_cluster, d_best, nk * 4, hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(best_score, d_score, nk * 4, hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(n_feasible, d_nfeas, (size_t)nb * 4, hipMemcpyDeviceToHost));

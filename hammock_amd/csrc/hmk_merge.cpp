@@ -10,6 +10,7 @@
 // Only the cluster-level lists cross to the host.  hmk_clinkage_merge_from_edges builds the same lists on the host from a
 // sequence-level edge list: the second implementation the device graph is tested against, and what a host-only context runs.
 #include "hmk_ctx.h"
+#include "hmk_slots.h"
 
 #include <unordered_map>
 
@@ -20,15 +21,11 @@ namespace {
 constexpr int32_t MAX_CLUSTER_ID = 1 << 30;
 
 // the checks both entry points make before the device is looked at; members[c] / size[c] as check_clusters'.  cluster_id may be
-// null (hmk_cluster_pairs_shifted has no ids)
+// null (hmk_cluster_pairs_shifted has no ids, and reads no size)
 int check_merge(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_cluster, const int32_t *cluster_id, uint32_t n_clusters,
                 std::vector<uint32_t> &members, std::vector<int64_t> &size) {
-    std::vector<int32_t> own_ids;
-    if (!cluster_id) {
-        own_ids.resize(n_clusters);
-        for (uint32_t c = 0; c < n_clusters; c++) own_ids[c] = (int32_t)c + 1;
-    }
-    int st = check_clusters(ctx, "merge", 0, 0, r0, r1, member_cluster, cluster_id ? cluster_id : own_ids.data(), n_clusters, members, size);
+    int st = cluster_id ? check_clusters(ctx, "merge", 0, 0, r0, r1, member_cluster, cluster_id, n_clusters, members, size)
+                        : check_slots(ctx, "merge", r0, r1, member_cluster, n_clusters, members);
     if (st) return st;
     if (cluster_id)
         for (uint32_t c = 0; c < n_clusters; c++)
@@ -160,10 +157,9 @@ int device_graph(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_
 
     const bool packed = adjacency_packed(ctx, X, p, thr);   // (4-byte entries m << 8 | score - threshold, as hmk_greedy_cluster)
     const EdgeSegs segs = ctx->edges.segs();
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, Q);
+    EventPair ev;
+    HIPCHK(ctx, ev.create());
+    hipError_t e = ev.start(Q);
     if (e == hipSuccess) e = piece_enqueue_csr(ctx, segs, true, packed, thr, n, r0, r1, false, false, Q);
     if (e == hipSuccess)
         e = launch_merge_graph(packed, buf<uint64_t>(ctx, SB_START), buf<void>(ctx, SB_ADJ), thr, r0, nm, n_clusters, d_cl, d_cl + n_clusters + 1,
@@ -188,13 +184,11 @@ int device_graph(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_
             e = launch_merge_compact(n_clusters, d_cl, buf<uint32_t>(ctx, SB_MERGE_MSTART), buf<uint64_t>(ctx, SB_MERGE_TMP), buf<uint32_t>(ctx, SB_MERGE_CNT),
                                      buf<uint32_t>(ctx, SB_MERGE_OSTART), thr, d_out, total, Q);
     }
-    if (e == hipSuccess) e = hipEventRecord(e1, Q);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    if (e == hipSuccess) e = ev.stop(Q);
+    if (e == hipSuccess) e = hipEventSynchronize(ev.b);
     float gms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&gms, e0, e1);
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("merge graph: ") + hipGetErrorString(e));
+    if (e == hipSuccess) e = ev.elapsed(&gms);
+    if (e != hipSuccess) return fail_hip(ctx, "merge graph", e);
     if (bad_edge) return fail(ctx, HMK_ERR_DEVICE, "merge CSR: an edge names a sequence outside the range, or the rows do not add up to the edges");
     S->graph_ms = gms;
     *n_rec = total;

@@ -137,7 +137,7 @@ int greedy_cluster_multi(hmk_ctx *ctx, int max_shift, int shift_penalty, int thr
             hmk_ctx *c = J.c;
             const uint32_t d = J.d;
             auto hip_fail = [&](const char *what, hipError_t e) {
-                fail_job(J, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+                fail_job(J, hip_status(e), std::string(what) + ": " + hipGetErrorString(e));
             };
             int r = need_device(c);
             if (r) { fail_job(J, r, c->err); return; }

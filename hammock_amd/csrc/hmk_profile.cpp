@@ -4,7 +4,7 @@
 // Statistics.java:207-300; the system means of Hammock.java:681-697), for every slot at once.
 //   checks   on the host, before the device is looked at: the placement against HMK_PROFILE_MAX_WIDTH, the parameters, the residues;
 //            the widths and the slots' column offsets are formed there too (O(members + clusters));
-//   tables   hmk_linkage.cpp's (build_link_tables) for the multi-member slots, and one block of the call's own: the frequency table,
+//   tables   hmk_slots.cpp's (build_link_tables) for the multi-member slots, and one block of the call's own: the frequency table,
 //            per member slot and column, per slot size and column offset, the large slots' chunks; two uploads;
 //   kernels  k_profile.hip on the clustering stream: accumulators cleared, counts (small slots, large slots), columns, match states,
 //            KLDs; the masks stay on the device between them;
@@ -13,7 +13,6 @@
 #include <cmath>
 
 #include "hmk_ctx.h"
-#include "hmk_linkage.h"
 #include "hmk_profile.h"
 
 static_assert(HMK_PROFILE_SYMBOLS == hmk::PROFILE_SYMBOLS && HMK_PROFILE_MAX_WIDTH == hmk::PROFILE_MAX_WIDTH, "hmk_profile.h restates the ABI's constants");
@@ -32,13 +31,8 @@ int cluster_profile(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *memb
     std::lock_guard<std::mutex> lock(ctx->mu);
     refresh_switches(ctx);
     std::vector<uint32_t> members;
-    std::vector<int64_t> size;
-    {
-        std::vector<int32_t> ids(n_clusters);
-        for (uint32_t c = 0; c < n_clusters; c++) ids[c] = (int32_t)c + 1;
-        const int st = check_clusters(ctx, "profile", 0, 0, r0, r1, member_cluster, ids.data(), n_clusters, members, size);
-        if (st) return st;
-    }
+    int st = check_slots(ctx, "profile", r0, r1, member_cluster, n_clusters, members);
+    if (st) return st;
     const uint32_t nm = r1 - r0;
     if (!params || !stats || !col_start) return fail(ctx, HMK_ERR_BAD_ARG, "null params, stats or col_start");
     if (n_clusters && (!width || !n_conserved || !n_match || !passes || !kld_match_mean || !kld_all_mean))
@@ -74,10 +68,9 @@ int cluster_profile(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *memb
         w = std::max<uint32_t>(w, column[i] + ctx->len[r0 + i]);
     }
     col_start[0] = 0;
-    for (uint32_t c = 0; c < n_clusters; c++) {
-        col_start[c + 1] = col_start[c] + width[c];
-        if (members[c] >= 2) S.n_multi++; else S.omitted++;
-    }
+    for (uint32_t c = 0; c < n_clusters; c++) col_start[c + 1] = col_start[c] + width[c];
+    S.n_multi = count_slots(members).n_multi;
+    S.omitted = n_clusters - S.n_multi;
     S.columns = col_start[n_clusters];
     S.system_kld_match = S.system_kld_all = std::nan("");
     if ((counts || ic || col_flags) && col_capacity < S.columns) {
@@ -85,7 +78,7 @@ int cluster_profile(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *memb
         return fail(ctx, HMK_ERR_CAPACITY, "the per-column arrays hold " + std::to_string(col_capacity) + " columns, the slots have " +
                                            std::to_string(S.columns));
     }
-    int st = need_device(ctx);
+    st = need_device(ctx);
     if (st) return st;
     if (nm == 0) {
         *stats = S;
@@ -96,7 +89,7 @@ int cluster_profile(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *memb
     LinkTables T;
     build_link_tables(r0, nm, member_cluster, n_clusters, members, T);
     const std::vector<uint32_t> &h = T.h;
-    const uint32_t nt = h[T.o_bmstart + T.nb], n_cols = (uint32_t)S.columns;
+    const uint32_t n_cols = (uint32_t)S.columns;
 
     // the call's own block: frequency | background (doubles), then mslot[nm] | column[nm] | size[ncl] | cstart[ncl + 1] | chunk[3 n_chunks]
     const uint32_t large_min = ctx->sw.profile_large_min >= 2 ? (uint32_t)ctx->sw.profile_large_min : PROFILE_LARGE_MIN;
@@ -135,12 +128,14 @@ int cluster_profile(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *memb
     // per column: ic double[n_cols] | counts uint32[21 n_cols] | flags uint8[n_cols]
     // per member and slot: kld_match double[nm] | kld_all double[nm] | n_conserved uint32[ncl] | first uint32[ncl] | last uint32[ncl]
     const size_t col_bytes = (size_t)n_cols * (8 + 4 * PROFILE_SYMBOLS + 1), res_bytes = (size_t)nm * 16 + (size_t)n_clusters * 12;
-    HIPCHK(ctx, ensure_buf(ctx, SB_LINK_TAB, h.size() * 4));
+    LinkView V;
+    st = reserve_link_tables(ctx, T, &V);
+    if (st) return st;
     HIPCHK(ctx, ensure_buf(ctx, SB_PROF_IN, in_words * 4));
     HIPCHK(ctx, ensure_buf(ctx, SB_PROF_COLS, col_bytes));
     HIPCHK(ctx, ensure_buf(ctx, SB_PROF_OUT, res_bytes));
     HIPCHK(ctx, ctx->h_merge.ensure(res_bytes + 64, 0));
-    uint32_t *d_tab = buf<uint32_t>(ctx, SB_LINK_TAB), *d_in = buf<uint32_t>(ctx, SB_PROF_IN);
+    uint32_t *d_in = buf<uint32_t>(ctx, SB_PROF_IN);
     ProfileIn in;
     in.mslot = d_in + o_mslot;
     in.column = d_in + o_column;
@@ -172,30 +167,27 @@ int cluster_profile(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *memb
     const uint8_t *res32 = ctx->d_res32.as<uint8_t>(), *len = ctx->d_len.as<uint8_t>();
     char *h_res = (char *)ctx->h_merge.p;
     hipStream_t Q = ctx->gstream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tab, h.data(), h.size() * 4, hipMemcpyHostToDevice, Q);
+    EventPair ev;
+    HIPCHK(ctx, ev.create());
+    hipError_t e = upload_link_tables(ctx, T, Q);
     if (e == hipSuccess) e = hipMemcpyAsync(d_in, hin.data(), in_words * 4, hipMemcpyHostToDevice, Q);
-    if (e == hipSuccess) e = hipEventRecord(e0, Q);
+    if (e == hipSuccess) e = ev.start(Q);
     if (e == hipSuccess) e = launch_profile_init(in, out, Q);
     if (e == hipSuccess) e = launch_profile_counts_small(res32, len, r0, in, out.counts, Q);
-    if (e == hipSuccess) e = launch_profile_counts_large(res32, len, d_tab + T.o_tab, r0, in, out.counts, Q);
+    if (e == hipSuccess) e = launch_profile_counts_large(res32, len, V, r0, in, out.counts, Q);
     if (e == hipSuccess) e = launch_profile_columns(in, K, out, Q);
     if (e == hipSuccess) e = launch_profile_match(in, K, out, Q);
-    if (e == hipSuccess) e = launch_profile_kld(res32, len, d_tab + T.o_tab, nt, r0, in, K, out, Q);
-    S.launches = 4 + (n_chunks ? 1 : 0) + (nt ? 1 : 0);
-    if (e == hipSuccess) e = hipEventRecord(e1, Q);
+    if (e == hipSuccess) e = launch_profile_kld(res32, len, V, r0, in, K, out, Q);
+    S.launches = 4 + (n_chunks ? 1 : 0) + (V.nt ? 1 : 0);
+    if (e == hipSuccess) e = ev.stop(Q);
     if (e == hipSuccess) e = hipMemcpyAsync(h_res, out.kld_match, res_bytes, hipMemcpyDeviceToHost, Q);
     if (e == hipSuccess && ic) e = hipMemcpyAsync(ic, out.ic, (size_t)n_cols * 8, hipMemcpyDeviceToHost, Q);
     if (e == hipSuccess && counts) e = hipMemcpyAsync(counts, out.counts, (size_t)n_cols * PROFILE_SYMBOLS * 4, hipMemcpyDeviceToHost, Q);
     if (e == hipSuccess && col_flags) e = hipMemcpyAsync(col_flags, out.flags, n_cols, hipMemcpyDeviceToHost, Q);
     if (e == hipSuccess) e = hipStreamSynchronize(Q);
     float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("cluster profile: ") + hipGetErrorString(e));
+    if (e == hipSuccess) e = ev.elapsed(&ms);
+    if (e != hipSuccess) return fail_hip(ctx, "cluster profile", e);
     S.kernel_ms = ms;
 
     const double *h_match = (const double *)h_res, *h_all = h_match + nm;

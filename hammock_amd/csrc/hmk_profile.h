@@ -1,11 +1,10 @@
 // hmk_profile.h -- launchers of k_profile.hip (column counts, information content, match states and leave-one-out KLD of given
 // clusters under a given placement), used by hmk_profile.cpp.  The multi-member slots are walked through the host tables of the
-// pairs inside given clusters (hmk_linkage.h: LinkTables); what the profile adds to them is ProfileIn.
+// pairs inside given clusters (hmk_slots.h: LinkTables, LinkView); what the profile adds to them is ProfileIn.
 #ifndef HMK_PROFILE_H
 #define HMK_PROFILE_H
 
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
+#include "hmk_slots.h"
 
 namespace hmk {
 
@@ -47,14 +46,14 @@ hipError_t launch_profile_init(const ProfileIn &in, const ProfileOut &out, hipSt
 hipError_t launch_profile_counts_small(const uint8_t *res32, const uint8_t *len, uint32_t r0, const ProfileIn &in, uint32_t *counts,
                                        hipStream_t s);
 // the residues of the larger slots: a chunk of a slot's places in tab per workgroup step, counted in LDS, non-zero words flushed
-hipError_t launch_profile_counts_large(const uint8_t *res32, const uint8_t *len, const uint32_t *tab, uint32_t r0, const ProfileIn &in,
+hipError_t launch_profile_counts_large(const uint8_t *res32, const uint8_t *len, const impl::LinkView &V, uint32_t r0, const ProfileIn &in,
                                        uint32_t *counts, hipStream_t s);
 // a lane per column: the gap count, ic, the conserved bit; per slot the conserved columns' number, first and last
 hipError_t launch_profile_columns(const ProfileIn &in, const ProfileParams &P, const ProfileOut &out, hipStream_t s);
 // a lane per column: the match-state bit from the slot's finished first / last
 hipError_t launch_profile_match(const ProfileIn &in, const ProfileParams &P, const ProfileOut &out, hipStream_t s);
-// a lane per place of tab (nt places, the multi-member slots' members by slot): both KLDs of the member
-hipError_t launch_profile_kld(const uint8_t *res32, const uint8_t *len, const uint32_t *tab, uint32_t nt, uint32_t r0, const ProfileIn &in,
+// a lane per place of V.tab (V.nt places, the multi-member slots' members by slot): both KLDs of the member
+hipError_t launch_profile_kld(const uint8_t *res32, const uint8_t *len, const impl::LinkView &V, uint32_t r0, const ProfileIn &in,
                               const ProfileParams &P, const ProfileOut &out, hipStream_t s);
 
 }  // namespace hmk

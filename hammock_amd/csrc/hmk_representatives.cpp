@@ -125,7 +125,7 @@ int level_on_device(hmk_ctx *ctx, hipStream_t Q, const EdgeRuns &E, uint64_t roo
     if (r == hipSuccess) r = hipMemcpyAsync(nearest_row, V.nearest, (size_t)n * 4, hipMemcpyDeviceToHost, Q);
     if (r == hipSuccess && score_row) r = hipMemcpyAsync(score_row, V.nearest_score, (size_t)n * 4, hipMemcpyDeviceToHost, Q);
     if (r == hipSuccess) r = hipStreamSynchronize(Q);
-    if (r != hipSuccess) return fail(ctx, r == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("representatives: ") + hipGetErrorString(r));
+    if (r != hipSuccess) return fail_hip(ctx, "representatives", r);
     if (back->flag) return fail(ctx, HMK_ERR_BAD_ARG, "edge list references a sequence outside [0, n) or a self pair");
     if (back->rounds == 0) return fail(ctx, HMK_ERR_DEVICE, "representatives: the rounds did not come to an end");
     if (ctx->sw.greedy_timing) {

@@ -78,24 +78,19 @@ void build_work(const hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t t0, uint3
 }
 
 struct EventTimer {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair ev;   // (made at the first begin)
     double ms = 0;
     hipError_t begin() {
-        hipError_t e = e0 ? hipSuccess : hipEventCreate(&e0);
-        if (e == hipSuccess && !e1) e = hipEventCreate(&e1);
-        return e == hipSuccess ? hipEventRecord(e0, nullptr) : e;
+        const hipError_t e = ev.b ? hipSuccess : ev.create();
+        return e == hipSuccess ? ev.start(nullptr) : e;
     }
     hipError_t end(bool add) {   // waits for the work; add: its time counts
-        hipError_t e = hipEventRecord(e1, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        hipError_t e = ev.stop(nullptr);
+        if (e == hipSuccess) e = hipEventSynchronize(ev.b);
         float t = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
+        if (e == hipSuccess) e = ev.elapsed(&t);
         if (add) ms += t;
         return e;
-    }
-    ~EventTimer() {
-        if (e0) HMK_QUIET(hipEventDestroy(e0));
-        if (e1) HMK_QUIET(hipEventDestroy(e1));
     }
 };
 

@@ -10,6 +10,7 @@
 // (sizing::separation_segments), so no clustering ends in HMK_ERR_CAPACITY.
 #include "hmk_ctx.h"
 #include "hmk_separation.h"
+#include "hmk_slots.h"
 
 namespace hmk { namespace impl {
 
@@ -22,20 +23,15 @@ int cluster_separation(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *m
     std::lock_guard<std::mutex> lock(ctx->mu);
     refresh_switches(ctx);
     std::vector<uint32_t> members;
-    std::vector<int64_t> size;
-    {
-        std::vector<int32_t> ids(n_clusters);
-        for (uint32_t c = 0; c < n_clusters; c++) ids[c] = (int32_t)c + 1;
-        const int st = check_clusters(ctx, "separation", 0, 0, r0, r1, member_cluster, ids.data(), n_clusters, members, size);
-        if (st) return st;
-    }
+    int st = check_slots(ctx, "separation", r0, r1, member_cluster, n_clusters, members);
+    if (st) return st;
     const uint32_t nm = r1 - r0;
     if (nm && (!own_sum || !near_sum || !near_cluster)) return fail(ctx, HMK_ERR_BAD_ARG, "null output (own_sum, near_sum, near_cluster)");
     if (!stats) return fail(ctx, HMK_ERR_BAD_ARG, "stats must not be null");
     if (!ctx->symmetric)
         return fail(ctx, HMK_ERR_BAD_ARG, "the separation of clusters needs a symmetric scoring matrix: a member's sum of scores must not "
                                           "depend on which sequence of a pair comes first");
-    int st = need_device(ctx);
+    st = need_device(ctx);
     if (st) return st;
     hmk_separation_stats S{};
     if (nm == 0) {   // (check_clusters: then there is no slot either) nothing is written
@@ -44,7 +40,7 @@ int cluster_separation(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *m
     }
     st = check_link_scores(ctx, X, p, 0, r0, r1);   // (nothing is thresholded: 0 passes the threshold's own range check)
     if (st) return st;
-    for (uint32_t c = 0; c < n_clusters; c++) S.n_multi += members[c] >= 2;
+    S.n_multi = count_slots(members).n_multi;
     S.pairs_scored = (uint64_t)nm * (nm - 1);
     const sizing::SeparationSegments segs = sizing::separation_segments(nm, (uint32_t)ctx->sw.test_separation_segment);
     S.n_segments = segs.count;
@@ -53,12 +49,10 @@ int cluster_separation(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *m
     const size_t o_ord = 0, o_pslot = nm, o_mslot = 2 * (size_t)nm, o_cstart = 3 * (size_t)nm, words = o_cstart + n_clusters + 1;
     std::vector<uint32_t> h(words);
     {
-        uint32_t at = 0;
-        for (uint32_t c = 0; c < n_clusters; c++) { h[o_cstart + c] = at; at += members[c]; }
-        h[o_cstart + n_clusters] = at;
-        std::vector<uint32_t> place(h.begin() + o_cstart, h.begin() + o_cstart + n_clusters);   // where the slot's next member goes
-        for (uint32_t i = 0; i < nm; i++) {
-            const uint32_t c = member_cluster[i], k = place[c]++;   // (index order inside every slot)
+        const SlotMembers M(nm, member_cluster, n_clusters, members);   // (index order inside every slot)
+        std::copy(M.start.begin(), M.start.end(), h.begin() + o_cstart);
+        for (uint32_t k = 0; k < nm; k++) {
+            const uint32_t i = M.list[k], c = member_cluster[i];
             h[o_ord + k] = r0 + i;
             h[o_pslot + k] = c;
             h[o_mslot + i] = c;
@@ -102,22 +96,19 @@ int cluster_separation(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *m
     const int32_t *d_M = ctx->d_M.as<int32_t>();
     char *h_out = (char *)ctx->h_merge.p;
     hipStream_t Q = ctx->gstream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint32_t *>(d_tab), h.data(), words * 4, hipMemcpyHostToDevice, Q);
-    if (e == hipSuccess) e = hipEventRecord(e0, Q);
+    EventPair ev;
+    HIPCHK(ctx, ev.create());
+    hipError_t e = hipMemcpyAsync(const_cast<uint32_t *>(d_tab), h.data(), words * 4, hipMemcpyHostToDevice, Q);
+    if (e == hipSuccess) e = ev.start(Q);
     if (e == hipSuccess) e = launch_separation_walk(res32, len, d_M, T, r0, X, p, rec, Q);
     if (e == hipSuccess) e = launch_separation_merge(T, rec, out, Q);
     S.launches = 2;
-    if (e == hipSuccess) e = hipEventRecord(e1, Q);
+    if (e == hipSuccess) e = ev.stop(Q);
     if (e == hipSuccess) e = hipMemcpyAsync(h_out, out.own_sum, out_bytes, hipMemcpyDeviceToHost, Q);
     if (e == hipSuccess) e = hipStreamSynchronize(Q);
     float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("cluster separation: ") + hipGetErrorString(e));
+    if (e == hipSuccess) e = ev.elapsed(&ms);
+    if (e != hipSuccess) return fail_hip(ctx, "cluster separation", e);
     S.kernel_ms = ms;
 
     const int64_t *h_own = (const int64_t *)h_out, *h_near = h_own + nm;

@@ -1,7 +1,7 @@
 // hmk_split.cpp -- splitting given clusters by complete linkage: per slot ClinkageSequenceClusterer.cluster
 // (ClinkageSequenceClusterer.java:43-124) on that slot's members alone, in index order.  The reverse of hmk_merge.cpp: that call runs
 // the chain BETWEEN given clusters and never looks inside one, this one runs it INSIDE each given cluster and never looks between two.
-//   tables   hmk_linkage.cpp's (build_link_tables): the block-diagonal pair space, sum of s (s - 1) / 2 over the slots;
+//   tables   hmk_slots.cpp's (build_link_tables): the block-diagonal pair space, sum of s (s - 1) / 2 over the slots;
 //   kernels  k_split.hip on the clustering stream: every score inside a slot as int16, a dense strict lower triangle per slot;
 //   copy     the triangles to a pinned block in one piece;
 //   chains   per slot its seeds -- one cluster per member, ids 1 ... s, the candidate lists read off the triangle row by row, which
@@ -23,17 +23,6 @@ struct SplitOut {
     uint32_t *split_cluster, *n_parts;
     int32_t *part_id, *member_rank, *part_order;
     uint32_t *part_start;
-};
-
-// The slots' members: slot c = list[start[c] .. start[c + 1]), places in [0, nm), ascending (start = the call's part_start).
-struct SlotMembers {
-    std::vector<uint32_t> start, list;
-    SlotMembers(uint32_t nm, const uint32_t *member_cluster, uint32_t n_clusters, const std::vector<uint32_t> &members)
-        : start((size_t)n_clusters + 1, 0), list(nm) {
-        for (uint32_t c = 0; c < n_clusters; c++) start[c + 1] = start[c] + members[c];
-        std::vector<uint32_t> at(start.begin(), start.end() - 1);
-        for (uint32_t i = 0; i < nm; i++) list[at[member_cluster[i]]++] = i;
-    }
 };
 
 // fills the candidate lists of slot c (s >= 2 members, numbered by their place in the slot; each list sorted by place) -> its edges
@@ -135,27 +124,20 @@ int run_slots(hmk_ctx *ctx, uint32_t r0, uint32_t nm, const uint32_t *member_clu
     return HMK_OK;
 }
 
-// the checks both entry points make before the device is looked at; members[c] / size[c] as check_clusters'
+// the checks both entry points make before the device is looked at; members[c] as check_slots'
 int check_split(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_cluster, uint32_t n_clusters, const SplitOut &out,
                 std::vector<uint32_t> &members, hmk_split_stats *S) {
-    std::vector<int64_t> size;
-    {
-        std::vector<int32_t> ids(n_clusters);
-        for (uint32_t c = 0; c < n_clusters; c++) ids[c] = (int32_t)c + 1;
-        const int st = check_clusters(ctx, "split", 0, 0, r0, r1, member_cluster, ids.data(), n_clusters, members, size);
-        if (st) return st;
-    }
+    const int st = check_slots(ctx, "split", r0, r1, member_cluster, n_clusters, members);
+    if (st) return st;
     if (r1 > r0 && (!out.split_cluster || !out.n_parts)) return fail(ctx, HMK_ERR_BAD_ARG, "null output (split_cluster, n_parts)");
     if ((out.part_order == nullptr) != (out.part_start == nullptr))
         return fail(ctx, HMK_ERR_BAD_ARG, "part_order and part_start are given together or not at all");
     if (!ctx->symmetric)
         return fail(ctx, HMK_ERR_BAD_ARG, "clinkage needs a symmetric scoring matrix: the reference caches cluster scores by unordered "
                                           "pair (CachedClusterScorer.java:43-53), so its result depends on the evaluation order otherwise");
-    for (uint32_t c = 0; c < n_clusters; c++) {
-        if (members[c] < 2) continue;
-        S->n_multi++;
-        S->pairs_scored += (uint64_t)members[c] * (members[c] - 1) / 2;
-    }
+    const SlotCounts counts = count_slots(members);
+    S->n_multi = counts.n_multi;
+    S->pairs_scored = counts.pairs;
     if (S->pairs_scored > SPLIT_MAX_PAIRS)
         return fail(ctx, HMK_ERR_BAD_ARG, std::to_string(S->pairs_scored) + " pairs inside the slots of this call, more than 2^30: pass fewer slots "
                                           "per call (slots are split independently of each other)");
@@ -195,38 +177,32 @@ int split(hmk_ctx *ctx, uint32_t r0, uint32_t r1, const uint32_t *member_cluster
         if (st) return st;
         st = greedy_streams(ctx);
         if (st) return st;
-        const size_t words = T.h.size(), score_bytes = (size_t)T.total_pairs * sizeof(int16_t);
-        HIPCHK(ctx, ensure_buf(ctx, SB_LINK_TAB, words * 4));
+        const size_t score_bytes = (size_t)T.total_pairs * sizeof(int16_t);
+        LinkView V;
+        st = reserve_link_tables(ctx, T, &V);
+        if (st) return st;
         HIPCHK(ctx, ensure_buf(ctx, SB_SPLIT_SCORES, score_bytes));
         HIPCHK(ctx, ctx->h_split.ensure(score_bytes + 64, 0));
-        const uint32_t *d_tab = buf<uint32_t>(ctx, SB_LINK_TAB);
         int16_t *d_scores = buf<int16_t>(ctx, SB_SPLIT_SCORES);
         const uint8_t *res32 = ctx->d_res32.as<uint8_t>(), *len = ctx->d_len.as<uint8_t>();
         const int32_t *d_M = ctx->d_M.as<int32_t>();
         hipStream_t Q = ctx->gstream;
-        hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-        HIPCHK(ctx, hipEventCreate(&e0));
-        hipError_t e = hipEventCreate(&e1);
-        if (e == hipSuccess) e = hipEventCreate(&e2);
-        if (e == hipSuccess) e = hipMemcpyAsync((void *)d_tab, T.h.data(), words * 4, hipMemcpyHostToDevice, Q);
-        if (e == hipSuccess) e = hipEventRecord(e0, Q);
-        if (e == hipSuccess)
-            e = launch_split_flat(res32, len, d_M, d_tab + T.o_tab, d_tab + T.o_fmstart, reinterpret_cast<const unsigned long long *>(d_tab + T.o_fpstart),
-                                  T.nf, T.flat_pairs, X, p, d_scores, Q);
-        if (e == hipSuccess)
-            e = launch_split_tiled(res32, len, d_M, d_tab + T.o_tab, d_tab + T.o_bmstart, d_tab + T.o_btstart,
-                                   reinterpret_cast<const unsigned long long *>(d_tab + T.o_tbase), T.nb, T.n_tiles, X, p, d_scores, Q);
-        if (e == hipSuccess) e = hipEventRecord(e1, Q);
+        EventPair kernels, copy;   // (the copy's stretch begins where the kernels' ends)
+        HIPCHK(ctx, kernels.create());
+        HIPCHK(ctx, copy.create());
+        hipError_t e = upload_link_tables(ctx, T, Q);
+        if (e == hipSuccess) e = kernels.start(Q);
+        if (e == hipSuccess) e = launch_split_flat(res32, len, d_M, V, X, p, d_scores, Q);
+        if (e == hipSuccess) e = launch_split_tiled(res32, len, d_M, V, X, p, d_scores, Q);
+        if (e == hipSuccess) e = kernels.stop(Q);
+        if (e == hipSuccess) e = copy.start(Q);
         if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_split.p, d_scores, score_bytes, hipMemcpyDeviceToHost, Q);
-        if (e == hipSuccess) e = hipEventRecord(e2, Q);
+        if (e == hipSuccess) e = copy.stop(Q);
         if (e == hipSuccess) e = hipStreamSynchronize(Q);
         float ms = 0, copy_ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&copy_ms, e1, e2);
-        (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (e2) (void)hipEventDestroy(e2);
-        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("clinkage split: ") + hipGetErrorString(e));
+        if (e == hipSuccess) e = kernels.elapsed(&ms);
+        if (e == hipSuccess) e = copy.elapsed(&copy_ms);
+        if (e != hipSuccess) return fail_hip(ctx, "clinkage split", e);
         S.kernel_ms = ms;
         S.copy_ms = copy_ms;
         scores = (const int16_t *)ctx->h_split.p;

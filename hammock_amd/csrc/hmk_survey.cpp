@@ -9,6 +9,7 @@
 #include <atomic>
 
 #include "hmk_ctx.h"
+#include "hmk_slots.h"
 #include "hmk_survey.h"
 
 namespace hmk { namespace impl {
@@ -82,23 +83,20 @@ int score_survey(hmk_ctx *ctx, uint32_t q0, uint32_t q1, uint32_t r0, uint32_t r
     const int32_t *d_M = ctx->d_M.as<int32_t>();
     char *h_fixed = (char *)ctx->h_merge.p, *h_rows = h_fixed + fixed_bytes;
     hipStream_t Q = ctx->gstream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, Q);
+    EventPair ev;
+    HIPCHK(ctx, ev.create());
+    hipError_t e = ev.start(Q);
     if (e == hipSuccess) e = launch_survey_init(acc, n_bins, nq, Q);
     if (e == hipSuccess) e = launch_survey_tiled(res32, len, d_M, triangle, q0, nq, r0, nr, X, p, thr_dev, lo_dev, n_bins, g_hist_form.load(), acc, Q);
     if (e == hipSuccess) e = launch_survey_decode(acc, nq, Q);
     S.launches = rows ? 3 : 2;
-    if (e == hipSuccess) e = hipEventRecord(e1, Q);
+    if (e == hipSuccess) e = ev.stop(Q);
     if (e == hipSuccess) e = hipMemcpyAsync(h_fixed, acc.hist, fixed_bytes, hipMemcpyDeviceToHost, Q);
     if (e == hipSuccess && rows) e = hipMemcpyAsync(h_rows, acc.best_score, (size_t)nq * 12, hipMemcpyDeviceToHost, Q);
     if (e == hipSuccess) e = hipStreamSynchronize(Q);
     float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? HMK_ERR_OOM : HMK_ERR_DEVICE, std::string("score survey: ") + hipGetErrorString(e));
+    if (e == hipSuccess) e = ev.elapsed(&ms);
+    if (e != hipSuccess) return fail_hip(ctx, "score survey", e);
     S.kernel_ms = ms;
 
     const uint64_t *h_hist = (const uint64_t *)h_fixed, *h_counts = h_hist + HMK_SURVEY_MAX_BINS;

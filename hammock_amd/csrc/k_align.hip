@@ -301,22 +301,22 @@ hipError_t launch_align_init(const AlignOut &out, uint32_t n_clusters, uint32_t 
     return hipGetLastError();
 }
 
-hipError_t launch_align_sums_flat(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const uint32_t *tab, const uint32_t *fmstart,
-                                  const unsigned long long *fpstart, uint32_t nf, unsigned long long n_pairs, uint32_t r0, int X, int p,
-                                  long long *sum, hipStream_t s) {
-    if (n_pairs == 0 || nf == 0) return hipSuccess;
-    const unsigned long long chunks = (n_pairs + 255) / 256;
+hipError_t launch_align_sums_flat(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const impl::LinkView &V, uint32_t r0, int X,
+                                  int p, long long *sum, hipStream_t s) {
+    if (V.flat_pairs == 0 || V.nf == 0) return hipSuccess;
+    const unsigned long long chunks = (V.flat_pairs + 255) / 256;
     const uint32_t blocks = capped_grid("k_align_sums_flat", (uint32_t)std::min<unsigned long long>(chunks, 65536));
-    hipLaunchKernelGGL(k_align_sums_flat, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, tab, fmstart, fpstart, nf, n_pairs, r0, X, p, sum);
+    hipLaunchKernelGGL(k_align_sums_flat, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, V.tab, V.fmstart, V.fpstart, V.nf, V.flat_pairs, r0, X,
+                       p, sum);
     return hipGetLastError();
 }
 
-hipError_t launch_align_sums_tiled(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const uint32_t *tab, const uint32_t *bmstart,
-                                   const uint32_t *btstart, uint32_t nb, uint32_t n_tiles, uint32_t r0, int X, int p, long long *sum,
-                                   hipStream_t s) {
-    if (n_tiles == 0 || nb == 0) return hipSuccess;
-    const uint32_t blocks = capped_grid("k_align_sums_tiled", std::min<uint32_t>(n_tiles, 65536));
-    hipLaunchKernelGGL(k_align_sums_tiled, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, tab, bmstart, btstart, nb, n_tiles, r0, X, p, sum);
+hipError_t launch_align_sums_tiled(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const impl::LinkView &V, uint32_t r0, int X,
+                                   int p, long long *sum, hipStream_t s) {
+    if (V.n_tiles == 0 || V.nb == 0) return hipSuccess;
+    const uint32_t blocks = capped_grid("k_align_sums_tiled", std::min<uint32_t>(V.n_tiles, 65536));
+    hipLaunchKernelGGL(k_align_sums_tiled, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, V.tab, V.bmstart, V.btstart, V.nb, V.n_tiles, r0, X,
+                       p, sum);
     return hipGetLastError();
 }
 

@@ -266,25 +266,22 @@ hipError_t launch_linkage_init(uint64_t *key, unsigned long long *below, uint32_
     return hipGetLastError();
 }
 
-hipError_t launch_linkage_flat(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const uint32_t *tab, const uint32_t *fslot,
-                               const uint32_t *fmstart, const unsigned long long *fpstart, uint32_t nf, unsigned long long n_pairs, uint32_t r0,
-                               int X, int p, int thr, uint64_t *key, unsigned long long *below, int32_t *member_min, uint32_t *member_below,
-                               hipStream_t s) {
-    if (n_pairs == 0 || nf == 0) return hipSuccess;
-    const unsigned long long chunks = (n_pairs + 255) / 256;
+hipError_t launch_linkage_flat(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const impl::LinkView &V, uint32_t r0, int X, int p,
+                               int thr, uint64_t *key, unsigned long long *below, int32_t *member_min, uint32_t *member_below, hipStream_t s) {
+    if (V.flat_pairs == 0 || V.nf == 0) return hipSuccess;
+    const unsigned long long chunks = (V.flat_pairs + 255) / 256;
     const uint32_t blocks = capped_grid("k_linkage_flat", (uint32_t)std::min<unsigned long long>(chunks, 65536));
-    hipLaunchKernelGGL(k_linkage_flat, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, tab, fslot, fmstart, fpstart, nf, n_pairs, r0, X, p,
-                       thr, key, below, member_min, member_below);
+    hipLaunchKernelGGL(k_linkage_flat, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, V.tab, V.fslot, V.fmstart, V.fpstart, V.nf, V.flat_pairs,
+                       r0, X, p, thr, key, below, member_min, member_below);
     return hipGetLastError();
 }
 
-hipError_t launch_linkage_tiled(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const uint32_t *tab, const uint32_t *bslot,
-                                const uint32_t *bmstart, const uint32_t *btstart, uint32_t nb, uint32_t n_tiles, uint32_t r0, int X, int p,
+hipError_t launch_linkage_tiled(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const impl::LinkView &V, uint32_t r0, int X, int p,
                                 int thr, uint64_t *key, unsigned long long *below, int32_t *member_min, uint32_t *member_below, hipStream_t s) {
-    if (n_tiles == 0 || nb == 0) return hipSuccess;
-    const uint32_t blocks = capped_grid("k_linkage_tiled", std::min<uint32_t>(n_tiles, 65536));
-    hipLaunchKernelGGL(k_linkage_tiled, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, tab, bslot, bmstart, btstart, nb, n_tiles, r0, X, p,
-                       thr, key, below, member_min, member_below);
+    if (V.n_tiles == 0 || V.nb == 0) return hipSuccess;
+    const uint32_t blocks = capped_grid("k_linkage_tiled", std::min<uint32_t>(V.n_tiles, 65536));
+    hipLaunchKernelGGL(k_linkage_tiled, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, V.tab, V.bslot, V.bmstart, V.btstart, V.nb, V.n_tiles,
+                       r0, X, p, thr, key, below, member_min, member_below);
     return hipGetLastError();
 }
 

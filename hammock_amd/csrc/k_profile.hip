@@ -240,11 +240,11 @@ hipError_t launch_profile_counts_small(const uint8_t *res32, const uint8_t *len,
     return hipGetLastError();
 }
 
-hipError_t launch_profile_counts_large(const uint8_t *res32, const uint8_t *len, const uint32_t *tab, uint32_t r0, const ProfileIn &in,
+hipError_t launch_profile_counts_large(const uint8_t *res32, const uint8_t *len, const impl::LinkView &V, uint32_t r0, const ProfileIn &in,
                                        uint32_t *counts, hipStream_t s) {
     if (in.n_chunks == 0) return hipSuccess;
     const uint32_t blocks = capped_grid("k_profile_counts_large", std::min<uint32_t>(in.n_chunks, 65536));
-    hipLaunchKernelGGL(k_profile_counts_large, dim3(blocks), dim3(256), 0, s, res32, len, tab, r0, in, counts);
+    hipLaunchKernelGGL(k_profile_counts_large, dim3(blocks), dim3(256), 0, s, res32, len, V.tab, r0, in, counts);
     return hipGetLastError();
 }
 
@@ -262,11 +262,11 @@ hipError_t launch_profile_match(const ProfileIn &in, const ProfileParams &P, con
     return hipGetLastError();
 }
 
-hipError_t launch_profile_kld(const uint8_t *res32, const uint8_t *len, const uint32_t *tab, uint32_t nt, uint32_t r0, const ProfileIn &in,
+hipError_t launch_profile_kld(const uint8_t *res32, const uint8_t *len, const impl::LinkView &V, uint32_t r0, const ProfileIn &in,
                               const ProfileParams &P, const ProfileOut &out, hipStream_t s) {
-    if (nt == 0) return hipSuccess;
-    const uint32_t blocks = capped_grid("k_profile_kld", std::min<uint32_t>((nt + 255) / 256, 65536));
-    hipLaunchKernelGGL(k_profile_kld, dim3(blocks), dim3(256), 0, s, res32, len, tab, nt, r0, in, P, out);
+    if (V.nt == 0) return hipSuccess;
+    const uint32_t blocks = capped_grid("k_profile_kld", std::min<uint32_t>((V.nt + 255) / 256, 65536));
+    hipLaunchKernelGGL(k_profile_kld, dim3(blocks), dim3(256), 0, s, res32, len, V.tab, V.nt, r0, in, P, out);
     return hipGetLastError();
 }
 

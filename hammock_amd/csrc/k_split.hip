@@ -100,23 +100,23 @@ k_split_tiled(const uint8_t *__restrict__ res32, const uint8_t *__restrict__ len
 // -----------------------------------------------------------------------------
 // launchers
 // -----------------------------------------------------------------------------
-hipError_t launch_split_flat(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const uint32_t *tab, const uint32_t *fmstart,
-                             const unsigned long long *fpstart, uint32_t nf, unsigned long long n_pairs, int X, int p, int16_t *scores,
-                             hipStream_t s) {
-    if (n_pairs == 0 || nf == 0) return hipSuccess;
-    const unsigned long long chunks = (n_pairs + 255) / 256;
+hipError_t launch_split_flat(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const impl::LinkView &V, int X, int p,
+                             int16_t *scores, hipStream_t s) {
+    if (V.flat_pairs == 0 || V.nf == 0) return hipSuccess;
+    const unsigned long long chunks = (V.flat_pairs + 255) / 256;
     const uint32_t blocks = capped_grid("k_split_flat", (uint32_t)std::min<unsigned long long>(chunks, 65536));
-    hipLaunchKernelGGL(k_split_flat, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, tab, fmstart, fpstart, nf, n_pairs, X, p, scores);
+    hipLaunchKernelGGL(k_split_flat, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, V.tab, V.fmstart, V.fpstart, V.nf, V.flat_pairs, X, p,
+                       scores);
     return hipGetLastError();
 }
 
-hipError_t launch_split_tiled(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const uint32_t *tab, const uint32_t *bmstart,
-                              const uint32_t *btstart, const unsigned long long *tbase, uint32_t nb, uint32_t n_tiles, int X, int p,
+hipError_t launch_split_tiled(const uint8_t *res32, const uint8_t *len, const int32_t *d_matrix, const impl::LinkView &V, int X, int p,
                               int16_t *scores, hipStream_t s) {
-    if (n_tiles == 0 || nb == 0) return hipSuccess;
+    if (V.n_tiles == 0 || V.nb == 0) return hipSuccess;
     const uint32_t blocks =
-        capped_grid("k_split_tiled", (uint32_t)std::min<unsigned long long>((unsigned long long)n_tiles * (LINK_TILE / SPLIT_ROWS), 65536));
-    hipLaunchKernelGGL(k_split_tiled, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, tab, bmstart, btstart, tbase, nb, n_tiles, X, p, scores);
+        capped_grid("k_split_tiled", (uint32_t)std::min<unsigned long long>((unsigned long long)V.n_tiles * (LINK_TILE / SPLIT_ROWS), 65536));
+    hipLaunchKernelGGL(k_split_tiled, dim3(blocks), dim3(256), 0, s, res32, len, d_matrix, V.tab, V.bmstart, V.btstart, V.tbase, V.nb, V.n_tiles, X,
+                       p, scores);
     return hipGetLastError();
 }
 
